@@ -33,7 +33,12 @@ launch stream during the timed steps, bound = "valu" (the path sit
 HBM ridge), frac = max(B_alg / 8 TB/s, F_alg / 157.3 TFLOP/s) / t, the HBM view beside it, and --
 at N = 1 -- PMC counters of THIS build collected live by rocprofv3 child runs of this script
 (FETCH_SIZE, WRITE_SIZE, SQ_* in separate passes; --pmc file reads profiles/r05/pmc_counters.json
-instead, --pmc off skips).  `cpu_baseline` (N = 1): the CPU oracle on the host cores.
+instead, --pmc off skips).  `cpu_baseline` (N = 1): the CPU oracle on the host cores.  The printed line is the
+record without its notes and its per-kernel, per-rank and per-case detail; --record FILE writes the whole record.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step (u, v, invalid of rank 0's pairs, a seeded
+sample of them beyond 60 MiB) as DIR/<name>.npy.  The frames are rendered deterministically, so the same arguments give
+the same inputs in every run and two builds can be compared output for output.
 """
 import argparse
 import csv
@@ -100,10 +105,19 @@ def parse_args():
     ap.add_argument("--e2e-pairs", type=int, default=256)
     ap.add_argument("--e2e-block-pairs", type=int, default=128, help="pairs per case of the end_to_end block of the default run")
     ap.add_argument("--fill-workers", type=int, default=8)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed for rank 0's pairs to DIR/<name>.npy: u, v "
+                         "(float64), invalid (float32 0 / 1) and pair_id (float64); a fixed seeded sample of the pairs when "
+                         "all of them exceed 60 MiB")
+    ap.add_argument("--record", metavar="FILE", default=None,
+                    help="also write the whole record as one JSON line to FILE (the printed line leaves out the notes and the "
+                         "per-kernel, per-rank and per-case detail)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not all(p_ in ("exact", "f64", "fast", "reference") for p_ in a.precision.split(",")):
         ap.error("--precision must be exact, f64, fast or reference")
+    if a.e2e and (a.dump_outputs or a.record):
+        ap.error("--dump-outputs and --record belong to the kernel-path bench, not to --e2e")
     if a.mode is None:
         a.mode = "CWS" if a.config == 1 else "DWS"
     if a.batch is None:
@@ -112,6 +126,8 @@ def parse_args():
         a.steps = 200 if a.config == 1 else 10
     if a.warmup is None:
         a.warmup = 5 if a.config == 1 else 1
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return a
 
 
@@ -499,6 +515,40 @@ class GpuSampler:
         return out
 
 
+DUMP_BYTES = 60 * 2**20        # --dump-outputs writes at most this much array data
+
+
+def dump_outputs(d, pair_ids, u, v, inv):
+    """--dump-outputs: what the timed path hands its caller after the last timed step -- u, v (float64) and invalid (as
+    float32 0 / 1) of every pair with the pairs' ids, or of a fixed seeded sample of the pairs when all of them exceed
+    DUMP_BYTES.  The sample depends on the arguments alone, so two builds run with the same arguments dump the same pairs."""
+    import numpy as np
+    import torch
+    n = u.shape[0]
+    k = min(n, DUMP_BYTES // (u.shape[1] * u.shape[2] * (8 + 8 + 4) + 8))
+    pick = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    sel = torch.from_numpy(pick).to(u.device)
+    os.makedirs(d, exist_ok=True)
+    for name, t, dt in (("pair_id", pair_ids, torch.float64), ("u", u, torch.float64), ("v", v, torch.float64),
+                        ("invalid", inv, torch.float32)):
+        np.save(os.path.join(d, name + ".npy"), t.index_select(0, sel).to(dt).cpu().numpy())
+
+
+# what the printed line leaves out of the record (--record FILE keeps all of it): the prose notes and the per-kernel,
+# per-rank and per-case detail.  The whole record outgrew what a reader of stdout takes in as one line (21 kB in round 5).
+LINE_OMITS = {"note", "log", "what", "sample", "source", "kernels", "counters_per_launch", "hbm", "valu_issue", "ranks",
+              "post_validation", "trials", "host"}
+
+
+def result_line(rec):
+    """The printed line: the record without LINE_OMITS at any depth, and without the roofline blocks of the side runs."""
+    def trim(d, top):
+        if not isinstance(d, dict):
+            return d
+        return {k: trim(v, False) for k, v in d.items() if k not in LINE_OMITS and (top or k != "roofline")}
+    return trim(rec, True)
+
+
 def main():
     args = parse_args()
     if args.e2e:
@@ -531,9 +581,15 @@ def main():
     ws, ov = args.ws, args.ws // 2
     batch = args.batch
 
-    # ---- synthetic frames rendered on the device (seed = 1234 + global pair index), resident in HBM
+    # ---- synthetic frames rendered on the device (seed = 1234 + global pair index), resident in HBM.  Deterministic
+    # algorithms sum the particles into each pixel (index_add_) in one order, so the frames are the same in every run.
     distinct = batch if args.distinct <= 0 else min(args.distinct, batch)
-    A0, B0 = synth.make_batch(distinct, H, W, first_index=rank * batch, device=dev)
+    det = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        A0, B0 = synth.make_batch(distinct, H, W, first_index=rank * batch, device=dev)
+    finally:
+        torch.use_deterministic_algorithms(det)
     reps = (batch + distinct - 1) // distinct
     A = A0.repeat(reps, 1, 1)[:batch].contiguous()
     B = B0.repeat(reps, 1, 1)[:batch].contiguous()
@@ -554,10 +610,10 @@ def main():
         scaling = "strong"
     gather_every_step = args.config == 2
 
-    def measure(precision, steps, warmup, timed=True):
+    def measure(precision, steps, warmup, timed=True, dump=None):
         """W warm-up steps, then exactly `steps` timed steps between barrier + synchronize pairs; returns the
         elapsed wall time (max over ranks), the per-step event times, the per-kernel event times and the plan's
-        geometry / kernel names."""
+        geometry / kernel names.  `dump`: a directory for dump_outputs() of the last timed step."""
         plan = engine.Plan(H, W, ws, ov, n_pass=args.passes, mode=args.mode, max_batch=batch, device=dev,
                            precision=precision)
         nr, nc = plan.out_shape
@@ -618,6 +674,8 @@ def main():
         step_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(steps)]
         timing, n_runs = plan.get_timing()
         plan.set_timing(False)
+        if dump:
+            dump_outputs(dump, pair_ids[:n_local], u_all[:n_local], v_all[:n_local], i_all[:n_local])
         res = {"precision": precision, "elapsed": elapsed, "step_ms": step_ms, "timing": timing, "n_runs": n_runs,
                "geometry": list(plan.geometry), "names": [plan.kernel_name(p_) for p_ in range(plan.n_pass)],
                "n_pass": plan.n_pass, "elapsed_local": elapsed_local,
@@ -660,7 +718,7 @@ def main():
     if "," in args.precision:
         raise SystemExit("bench.py: one --precision (the comma form is the profiled child's)")
 
-    head = measure(args.precision, args.steps, args.warmup)
+    head = measure(args.precision, args.steps, args.warmup, dump=args.dump_outputs if rank == 0 else None)
     also_fast = world == 1 and args.config == 1 and not args.no_fast and args.precision != "fast"
     also_f64 = also_fast and args.precision == "exact"
     f64_run = measure("f64", args.steps, args.warmup) if also_f64 else None
@@ -891,7 +949,10 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(H, W, ws, ov, args.passes, args.mode)
         assert rec["n_gpus"] == args.gpus
-        print(json.dumps(rec), flush=True)
+        if args.record:
+            with open(args.record, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        print(json.dumps(result_line(rec)), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

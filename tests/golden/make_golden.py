@@ -14,8 +14,11 @@ import os
 import sys
 import tempfile
 
-import numpy as np
-import torch
+# MKL's processor-independent FFT path, as in tests/conftest.py: the goldens then hold on any x86 host
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np                             # noqa: E402
+import torch                                   # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
@@ -43,7 +46,20 @@ def special_regions(a, b):
     return a, b
 
 
+# fixtures whose uint8 input frames alone are too large to rewrite (over 1 MiB): <name>.npz keeps the frames as first
+# committed (checked equal here), and every other array -- the outputs, which follow the FFT path -- goes to
+# <name>_out.npz, whose arrays tests/conftest.py's load_golden puts in place of <name>.npz's own
+SPLIT = ("g4_multipass", "g8_round2")
+
+
 def save(name, **arrs):
+    if name in SPLIT:
+        with np.load(os.path.join(HERE, name + ".npz"), allow_pickle=False) as base:
+            for k, a in arrs.items():
+                if a.dtype == np.uint8:
+                    assert np.array_equal(base[k], a), f"{name}: input {k} differs from the committed one"
+        arrs = {k: a for k, a in arrs.items() if a.dtype != np.uint8}
+        name += "_out"
     path = os.path.join(HERE, name + ".npz")
     np.savez_compressed(path, **arrs)
     print(f"{name}: {os.path.getsize(path) / 1024:.1f} KiB")

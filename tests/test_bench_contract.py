@@ -99,3 +99,57 @@ def test_committed_lines_carry_what_a_scaling_run_needs():
     assert d["per_rank_ms_per_step"]["max"] <= two["ms_per_step"] * 1.001
     for r_ in d["ranks"]:
         assert {"rank", "device", "step_ms_median", "ms_per_step_own_clock", "gather_ms", "gather_payload_bytes"} <= set(r_)
+
+
+def test_printed_line_summarises_the_record():
+    """The printed line is the whole record (--record) without its notes and per-kernel / per-rank / per-case detail: short
+    enough to be read back as one line, and it keeps every field a reader of the headline takes from it."""
+    import bench
+    for name in ("bench_n1.json", "bench_gloo4_config1.json"):
+        path = os.path.join(ROOT, "profiles", "r05", name)
+        if not os.path.exists(path):
+            pytest.skip("no round-5 profile run committed yet")
+        rec = json.loads(open(path).read().strip().splitlines()[-1])
+        line = bench.result_line(rec)
+        assert len(json.dumps(line)) < 6000, name
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                    "vs_baseline", "dtype", "data", "config", "roofline", "kernel_ms"):
+            assert line[key] == bench.result_line({key: rec[key]})[key], key
+        assert line["value"] == rec["value"] and line["ms_per_step"] == rec["ms_per_step"]
+        assert {"bound", "kernel", "achieved", "peak", "frac"} <= set(line["roofline"]) and "kernels" not in line
+        assert "ranks" not in line["distributed"] and line["distributed"]["per_rank_ms_per_step"]
+    n1 = bench.result_line(json.loads(open(os.path.join(ROOT, "profiles", "r05", "bench_n1.json")).read().strip().splitlines()[-1]))
+    for side in ("f64_transform", "fast"):
+        assert n1[side]["value"] > 0 and n1[side]["ms_per_step"] > 0 and "roofline" not in n1[side]
+    assert n1["end_to_end"]["resident_isolated_spots"] > 0 and n1["cpu_baseline"]["value"] > 0
+
+
+def test_dump_outputs_writes_the_fields_or_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    n, nr, nc = 40, 7, 9
+    g = torch.Generator().manual_seed(5)
+    u = torch.randn(n, nr, nc, dtype=torch.float64, generator=g)
+    v = torch.randn(n, nr, nc, dtype=torch.float64, generator=g)
+    inv = (torch.rand(n, nr, nc, generator=g) < 0.1).to(torch.uint8)
+    ids = torch.arange(100, 100 + n)
+    per_pair = nr * nc * (8 + 8 + 4) + 8
+    for budget, k in ((n * per_pair, n), (12 * per_pair + 5, 12)):
+        monkeypatch.setattr(bench, "DUMP_BYTES", budget)
+        dumps = []
+        for rep in range(2):
+            d = tmp_path / f"b{budget}_{rep}"
+            bench.dump_outputs(str(d), ids, u, v, inv)
+            got = {f: np.load(d / f"{f}.npy") for f in ("pair_id", "u", "v", "invalid")}
+            assert sum(os.path.getsize(d / f"{f}.npy") for f in got) <= budget + 4 * 128      # (+ the .npy headers)
+            dumps.append(got)
+        got = dumps[0]
+        assert {f: a.dtype for f, a in got.items()} == {"pair_id": np.float64, "u": np.float64, "v": np.float64,
+                                                          "invalid": np.float32}
+        pick = got["pair_id"].astype(np.int64) - 100
+        assert len(pick) == k and np.all(np.diff(pick) > 0) and pick.min() >= 0 and pick.max() < n
+        assert np.array_equal(got["u"], u.numpy()[pick]) and np.array_equal(got["v"], v.numpy()[pick])
+        assert np.array_equal(got["invalid"], inv.numpy()[pick].astype(np.float32))
+        # the sample depends on the sizes alone: a second dump holds the same pairs
+        assert all(np.array_equal(got[f], dumps[1][f]) for f in got)

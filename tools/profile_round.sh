@@ -28,12 +28,12 @@ export TMPDIR=/tmp
 R="--kernel-include-regex xcorr|predict|finalize|postval"
 PART=${2:-ab}
 if [[ $PART == *a* ]]; then
-python3 bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err || { tail $OUT/bench_n1.err; exit 1; }
-python3 bench.py --precision reference --no-cpu-baseline --no-fast --no-e2e > $OUT/bench_n1_reference.json 2> $OUT/bench_ref.err || exit 1
-python3 bench.py --config 2 --no-cpu-baseline --no-e2e > $OUT/bench_n1_config2.json 2> $OUT/bench_c2.err || exit 1
-TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 2 --steps 20 --warmup 2 --batch 64 --pmc off > $OUT/bench_gloo2_config1.json 2> $OUT/g2.err || exit 1
-TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 2 --config 2 --steps 3 --stream 1000 --batch 250 --pmc off > $OUT/bench_gloo2_config2.json 2> $OUT/g2c2.err || exit 1
-TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 4 --steps 10 --warmup 2 --batch 32 --pmc off > $OUT/bench_gloo4_config1.json 2> $OUT/g4.err || exit 1
+python3 bench.py --record $OUT/bench_n1.json > /dev/null 2> $OUT/bench_n1.err || { tail $OUT/bench_n1.err; exit 1; }
+python3 bench.py --precision reference --no-cpu-baseline --no-fast --no-e2e --record $OUT/bench_n1_reference.json > /dev/null 2> $OUT/bench_ref.err || exit 1
+python3 bench.py --config 2 --no-cpu-baseline --no-e2e --record $OUT/bench_n1_config2.json > /dev/null 2> $OUT/bench_c2.err || exit 1
+TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 2 --steps 20 --warmup 2 --batch 64 --pmc off --record $OUT/bench_gloo2_config1.json > /dev/null 2> $OUT/g2.err || exit 1
+TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 2 --config 2 --steps 3 --stream 1000 --batch 250 --pmc off --record $OUT/bench_gloo2_config2.json > /dev/null 2> $OUT/g2c2.err || exit 1
+TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 4 --steps 10 --warmup 2 --batch 32 --pmc off --record $OUT/bench_gloo4_config1.json > /dev/null 2> $OUT/g4.err || exit 1
 # soak: 2000 timed steps of the headline workload (stability of the rate; no counters, no side measurements)
 python3 bench.py --steps 2000 --warmup 5 --pmc off --no-cpu-baseline --no-e2e --no-fast > $OUT/bench_soak2000.json 2> $OUT/soak.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv $R -d $OUT/stats -- python3 bench.py --steps 50 --warmup 5 --pmc off --no-cpu-baseline --no-e2e > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
