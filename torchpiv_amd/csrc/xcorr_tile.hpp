@@ -18,7 +18,9 @@
 //     v_permlane32_swap of the off-diagonal blocks.  The last transform is a c2r one: only spectrum
 //     columns 0..WS/2 cross the LDS the second time (transpose_half).  Kernels at three wavefronts per SIMD move one
 //     float plane at a time (8.4 KB per wavefront), the others complex elements (16.9 KB).
-//   * the k <-> -k partner of the packed spectrum is fetched with ds_bpermute (no LDS memory).
+//   * the k <-> -k partner of the packed spectrum is fetched with ds_bpermute (no LDS memory).  The planar 32x32 / 64x64
+//     kernels split each spectrum column between the lanes of columns c and -c: half the cross-spectrum products, one
+//     radix-2 level and a WS/2-point inverse column transform per lane (TPIV_HALF_INV*, transpose_half_pairs).
 //   * peak search: plain max scans per lane, DPP / permlane reductions, one LDS row lookup for the
 //     arg-max position, sign-bit exclusion for the second peak (compares and selects cost twice a
 //     plain fp32 instruction on MI355X); an 8-float record per window goes to finalize_kernel.
@@ -482,6 +484,70 @@ __device__ __forceinline__ void transpose_half(const cf (&a)[WS], cf (&g)[WS / 2
         wave_sync();
 #pragma unroll
         for (int r = 0; r <= M; ++r) g[r] = t[r * P + i];
+    }
+}
+
+// ---- half transposition after the paired inverse column transform (TPIV_HALF_INV, planar tiles, WS = 32 / 64) ----------------
+// in:  lane (w, r) holds the WS/2-point inverse column result h[FFT_POS<m, WS/2>] (see the body):
+//        r = c in 1 .. WS/2-1:   column c, rows 2m;
+//        r = WS - c:             column c, rows 2m + 1, conjugated (it is the inverse of column -c);
+//        r = 0 or WS/2:          column r as h[m] = t(2m) + i t(2m + 1) (the column is real)
+// out: lane (w, y) holds g[kx] = element (row y, column kx) for kx = 0 .. WS/2; for kx = 0 and WS/2 only g.x is set (the
+//      c2r last transform ignores the imaginary parts of its DC and Nyquist bins).
+// Layout per window: element (y, kx) at y * Q + kx, Q = WS/2 + 1.  Every lane writes (no lane is idle) with a per-lane base
+// and the common offset 2Q m; the readers read with stride Q.  The conjugation of the odd rows is the sign of one multiply.
+// The two self-mirrored lanes store t(2m) and t(2m + 1) in the same slot of the two planes, in the even or the odd row of
+// the pair, whichever keeps each 32-lane group of a ds_write_b32 on 32 distinct banks (64x64: lanes 0..31 are column 0 and
+// the even-row lanes, lanes 32..63 column WS/2 and the odd-row lanes; 32x32: one window per group); the readers of a row
+// pair fetch that slot together (a broadcast) and take the plane by their row's parity.
+template <int WS, bool PLANAR>
+__device__ __forceinline__ void transpose_half_pairs(const cf (&h)[WS / 2], cf (&g)[WS / 2 + 1], float* lds, int lane) {
+    static_assert(PLANAR && (WS == 32 || WS == 64), "planar tiles of 32 and 64");
+    using G = TileGeo<WS, PLANAR>;
+    constexpr int M = WS / 2, Q = M + 1;
+    static_assert(64 * Q <= G::LDS_FLOATS, "the half-spectrum plane fits the tile");
+    const int r = lane % WS;
+    float* t = lds + (lane / WS) * (WS * Q);
+    const bool odd = r > M;                                   // holds column WS - r: odd rows, conjugated
+    constexpr bool ZERO_ODD = WS == 32;                       // column 0 in the odd row of a pair, column WS/2 in the even one
+    const bool up = odd || (r == 0 && ZERO_ODD) || (r == M && !ZERO_ODD);
+    float* wp = t + (odd ? WS - r : r) + (up ? Q : 0);
+    const float sy = odd ? -1.0f : 1.0f;
+    // (pinned: the stores take the transform's results as they come, instead of the compiler sinking its tail into them)
+    cf b[M];
+    static_for<0, M>([&](auto mc) TPIV_LAMBDA_INLINE {
+        constexpr int m = decltype(mc)::value;
+        b[m] = h[FFT_POS<m, M>];
+        asm volatile("" : "+v"(b[m].x), "+v"(b[m].y));
+    });
+    const int y = lane % WS;
+    const float* rd = t + y * Q;
+    const float* r0 = t + ((y & ~1) + (ZERO_ODD ? 1 : 0)) * Q;            // column 0 of the row pair
+    const float* rm = t + ((y & ~1) + (ZERO_ODD ? 0 : 1)) * Q + M;        // column WS/2 of the row pair
+    wave_sync();
+    static_for<0, M>([&](auto mc) TPIV_LAMBDA_INLINE {
+        constexpr int m = decltype(mc)::value;
+        wp[2 * Q * m] = b[m].x;
+    });
+    wave_sync();
+    g[0].x = r0[0];
+#pragma unroll
+    for (int k = 1; k < M; ++k) g[k].x = rd[k];
+    g[M].x = rm[0];
+    wave_sync();
+    static_for<0, M>([&](auto mc) TPIV_LAMBDA_INLINE {
+        constexpr int m = decltype(mc)::value;
+        wp[2 * Q * m] = b[m].y * sy;
+    });
+    wave_sync();
+    g[0].y = r0[0];
+#pragma unroll
+    for (int k = 1; k < M; ++k) g[k].y = rd[k];
+    g[M].y = rm[0];
+    // columns 0 and WS/2: t(y) is in the real plane for even y, in the imaginary plane for odd y
+    if (y & 1) {
+        g[0].x = g[0].y;
+        g[M].x = g[M].y;
     }
 }
 
@@ -1744,85 +1810,152 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
         fft_inreg<WS, 1>(x, tw);                          // over y; Z(ky, kx = lane) at x[FFT_POS<ky>]
         TPIV_STAMP(5);      // forward column FFT
 
-        // ---- cross-spectrum.  A = (Z(k) + conj Z(-k))/2, B = (Z(k) - conj Z(-k))/(2i),
-        //      P = conj(A) * B / n^2.  Z(-ky, -kx) sits in lane (-kx mod WS), register (-ky mod WS).
-        {
-            const int lane_c = fresh_lane();
-            const int r_c = lane_c % WS;
-            const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
-            // with zk = a + ib, zm = Z(-k) = c + id:  4 P = conj(2A) * (2B)
-            //   re = (a+c)(b+d) + (b-d)(c-a) = 2 (a d + b c),   im = (c^2 - a^2) + (d^2 - b^2)
-            // (the factor 0.25 / WS^2 is already in the inputs, see the normalisation above)
-            auto cross = [&](cf zk, cf zm) TPIV_LAMBDA_INLINE {
-                const float a_ = zk.x, b_ = zk.y, c_ = zm.x, d_ = zm.y;
-                cf pr;
-                pr.x = (a_ * d_ + b_ * c_) * 2.0f;
-                pr.y = (c_ * c_ - a_ * a_) + (d_ * d_ - b_ * b_);
-                return pr;
-            };
-            static_for<0, WS / 2 + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
-                constexpr int ky = decltype(kc)::value;
-                constexpr int nky = (WS - ky) % WS;
-                constexpr int p1 = FFT_POS<ky, WS>, p2 = FFT_POS<nky, WS>;
-                const cf z1 = x[p1];
-                if constexpr (ky == nky) {
-                    cf m1;
-                    m1.x = __shfl(z1.x, partner, 64);
-                    m1.y = __shfl(z1.y, partner, 64);
-                    x[p1] = cross(z1, m1);
-                } else {
-                    const cf z2 = x[p2];
-                    cf m1, m2;
-                    m1.x = __shfl(z2.x, partner, 64);     // Z(-ky, -kx)
-                    m1.y = __shfl(z2.y, partner, 64);
-                    m2.x = __shfl(z1.x, partner, 64);     // Z(+ky, -kx), the partner of bin -ky
-                    m2.y = __shfl(z1.y, partner, 64);
-                    x[p1] = cross(z1, m1);
-                    x[p2] = cross(z2, m2);
-                }
-            });
-        }
-
-        TPIV_STAMP(6);      // cross-spectrum incl. the bpermute exchange
-        // ---- inverse: columns (natural-order input: rename registers), transpose, rows
-        cf t[WS];
-        static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
-            constexpr int ky = decltype(kc)::value;
-            t[ky] = x[FFT_POS<ky, WS>];
-        });
-        fft_inreg<WS, -1>(t, tw);                         // over ky; row y at t[FFT_POS<y>]
-        TPIV_STAMP(7);      // inverse column FFT
+        // ---- paired half inverse (DESIGN.md 3.1 "Cross-spectrum and inverse columns in mirror pairs").  P(-ky, -kx) =
+        //      conj P(ky, kx): the lanes of columns c and -c hold one column's worth of information between them.  Each lane
+        //      forms its own products for ky = 0 .. WS/2 only and takes the partner's P(WS/2 - k) from the other lane, then
+        //      ONE radix-2 decimation-in-frequency level over ky splits the column's inverse into two WS/2-point transforms:
+        //        lane c (1 .. WS/2-1):  P(k) + P(k + WS/2)          -> rows 2m of column c
+        //        lane WS - c:           w^k (P(k) - P(k + WS/2))    -> rows 2m + 1 of column -c = conj of column c's
+        //        lanes 0, WS/2 (their own mirrors: real columns, partner = self): the c2r form of the column,
+        //          (P(k) + conj P(WS/2 - k)) + i w^k (P(k) - conj P(WS/2 - k))  -> t(2m) + i t(2m + 1)
+        //      with P(k + WS/2) = conj P_partner(WS/2 - k).  Half the products, half the column transform (w = exp(2 pi i / WS)).
 #ifndef TPIV_C2R
 #define TPIV_C2R 1
 #endif
-        float crow[WS];
-        // (64x64: the planar three-wavefront kernels take the c2r form too -- round 1 and the first try of round 2
-        //  ended in 32-42 spills at the 168-VGPR cap, which were the compiler sinking the tail of the column
-        //  transform into the conditional stores of transpose_half; with the values pinned in front of the branch
-        //  the kernel keeps its one spill and pass 1 went from 6.94 to 6.42 ms per 256 pairs.  The complex-tile
-        //  64x64 CWS kernel keeps the complex last transform.)
 #ifndef TPIV_C2R64
 #define TPIV_C2R64 1
 #endif
-        if constexpr (TPIV_C2R && (WS <= 32 || (TPIV_C2R64 && WS == 64))) {
-            // the map rows are real: only spectrum columns 0..WS/2 cross the LDS and a WS/2-point complex
-            // transform yields the row as z[m] = corr(y, 2m) + i corr(y, 2m + 1)  (c2r_inreg)
-            cf hs[WS / 2 + 1], z[WS / 2];
-            transpose_half<WS, PLANAR>(t, hs, tile, fresh_lane());
+#ifndef TPIV_HALF_INV64
+#define TPIV_HALF_INV64 1
+#endif
+#ifndef TPIV_HALF_INV32
+#define TPIV_HALF_INV32 1
+#endif
+        constexpr bool HALF_INV = PLANAR && TPIV_C2R &&
+                                  ((WS == 64 && TPIV_C2R64 && TPIV_HALF_INV64) || (WS == 32 && TPIV_HALF_INV32));
+        float crow[WS];
+        if constexpr (HALF_INV) {
+            constexpr int M = WS / 2;
+            cf h[M];
+            {
+                const int lane_c = fresh_lane();
+                const int r_c = lane_c % WS;
+                const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
+                auto cross = [&](cf zk, cf zm) TPIV_LAMBDA_INLINE {      // the formula of the full form below
+                    const float a_ = zk.x, b_ = zk.y, c_ = zm.x, d_ = zm.y;
+                    cf pr;
+                    pr.x = (a_ * d_ + b_ * c_) * 2.0f;
+                    pr.y = (c_ * c_ - a_ * a_) + (d_ * d_ - b_ * b_);
+                    return pr;
+                };
+                cf pc[M + 1];
+                static_for<0, M + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
+                    constexpr int ky = decltype(kc)::value;
+                    constexpr int nky = (WS - ky) % WS;
+                    const cf z2 = x[FFT_POS<nky, WS>];
+                    cf m1;
+                    m1.x = __shfl(z2.x, partner, 64);        // Z(-ky, -kx)
+                    m1.y = __shfl(z2.y, partner, 64);
+                    pc[ky] = cross(x[FFT_POS<ky, WS>], m1);
+                });
+                TPIV_STAMP(6);      // cross-spectrum incl. the bpermute exchange
+                const bool odd = r_c > M;
+                const float fs = (r_c == 0 || r_c == M) ? 1.0f : 0.0f;
+                static_for<0, M>([&](auto kc) TPIV_LAMBDA_INLINE {
+                    constexpr int k = decltype(kc)::value;
+                    cf pr;                                    // P_partner(M - k): conj of P(k + M)
+                    pr.x = __shfl(pc[M - k].x, partner, 64);
+                    pr.y = __shfl(pc[M - k].y, partner, 64);
+                    const cf s{pc[k].x + pr.x, pc[k].y - pr.y};
+                    const cf tt = twmul<k, WS, -1>(cf{pc[k].x - pr.x, pc[k].y + pr.y});
+                    h[k].x = odd ? tt.x : __builtin_fmaf(-fs, tt.y, s.x);
+                    h[k].y = odd ? tt.y : __builtin_fmaf(fs, tt.x, s.y);
+                });
+            }
+            fft_inreg<M, -1>(h, tw);                          // over k; row 2m (+1) at h[FFT_POS<m, M>]
+            TPIV_STAMP(7);      // inverse column FFT
+            cf hs[M + 1], z[M];
+            transpose_half_pairs<WS, PLANAR>(h, hs, tile, fresh_lane());
             TPIV_STAMP(8);      // transposition 2
             c2r_inreg<WS>(hs, z);
             static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
                 constexpr int x_ = decltype(xc)::value;
-                crow[x_] = (x_ & 1) ? z[FFT_POS<x_ / 2, WS / 2>].y : z[FFT_POS<x_ / 2, WS / 2>].x;
+                crow[x_] = (x_ & 1) ? z[FFT_POS<x_ / 2, M>].y : z[FFT_POS<x_ / 2, M>].x;
             });
         } else {
-            transpose_tile<WS, true, PLANAR>(t, tile, fresh_lane());  // lane = y, t[kx] natural
-            TPIV_STAMP(8);      // transposition 2
-            fft_inreg<WS, -1>(t, tw);                     // over kx; corr(y = lane, x) at t[FFT_POS<x>].x
-            static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
-                constexpr int x_ = decltype(xc)::value;
-                crow[x_] = t[FFT_POS<x_, WS>].x;
+            // ---- cross-spectrum.  A = (Z(k) + conj Z(-k))/2, B = (Z(k) - conj Z(-k))/(2i),
+            //      P = conj(A) * B / n^2.  Z(-ky, -kx) sits in lane (-kx mod WS), register (-ky mod WS).
+            {
+                const int lane_c = fresh_lane();
+                const int r_c = lane_c % WS;
+                const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
+                // with zk = a + ib, zm = Z(-k) = c + id:  4 P = conj(2A) * (2B)
+                //   re = (a+c)(b+d) + (b-d)(c-a) = 2 (a d + b c),   im = (c^2 - a^2) + (d^2 - b^2)
+                // (the factor 0.25 / WS^2 is already in the inputs, see the normalisation above)
+                auto cross = [&](cf zk, cf zm) TPIV_LAMBDA_INLINE {
+                    const float a_ = zk.x, b_ = zk.y, c_ = zm.x, d_ = zm.y;
+                    cf pr;
+                    pr.x = (a_ * d_ + b_ * c_) * 2.0f;
+                    pr.y = (c_ * c_ - a_ * a_) + (d_ * d_ - b_ * b_);
+                    return pr;
+                };
+                static_for<0, WS / 2 + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
+                    constexpr int ky = decltype(kc)::value;
+                    constexpr int nky = (WS - ky) % WS;
+                    constexpr int p1 = FFT_POS<ky, WS>, p2 = FFT_POS<nky, WS>;
+                    const cf z1 = x[p1];
+                    if constexpr (ky == nky) {
+                        cf m1;
+                        m1.x = __shfl(z1.x, partner, 64);
+                        m1.y = __shfl(z1.y, partner, 64);
+                        x[p1] = cross(z1, m1);
+                    } else {
+                        const cf z2 = x[p2];
+                        cf m1, m2;
+                        m1.x = __shfl(z2.x, partner, 64);     // Z(-ky, -kx)
+                        m1.y = __shfl(z2.y, partner, 64);
+                        m2.x = __shfl(z1.x, partner, 64);     // Z(+ky, -kx), the partner of bin -ky
+                        m2.y = __shfl(z1.y, partner, 64);
+                        x[p1] = cross(z1, m1);
+                        x[p2] = cross(z2, m2);
+                    }
+                });
+            }
+
+            TPIV_STAMP(6);      // cross-spectrum incl. the bpermute exchange
+            // ---- inverse: columns (natural-order input: rename registers), transpose, rows
+            cf t[WS];
+            static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
+                constexpr int ky = decltype(kc)::value;
+                t[ky] = x[FFT_POS<ky, WS>];
             });
+            fft_inreg<WS, -1>(t, tw);                         // over ky; row y at t[FFT_POS<y>]
+            TPIV_STAMP(7);      // inverse column FFT
+            // (64x64: the planar three-wavefront kernels take the c2r form too -- round 1 and the first try of round 2
+            //  ended in 32-42 spills at the 168-VGPR cap, which were the compiler sinking the tail of the column
+            //  transform into the conditional stores of transpose_half; with the values pinned in front of the branch
+            //  the kernel keeps its one spill and pass 1 went from 6.94 to 6.42 ms per 256 pairs.  The complex-tile
+            //  64x64 CWS kernel keeps the complex last transform.)
+            if constexpr (TPIV_C2R && (WS <= 32 || (TPIV_C2R64 && WS == 64))) {
+                // the map rows are real: only spectrum columns 0..WS/2 cross the LDS and a WS/2-point complex
+                // transform yields the row as z[m] = corr(y, 2m) + i corr(y, 2m + 1)  (c2r_inreg)
+                cf hs[WS / 2 + 1], z[WS / 2];
+                transpose_half<WS, PLANAR>(t, hs, tile, fresh_lane());
+                TPIV_STAMP(8);      // transposition 2
+                c2r_inreg<WS>(hs, z);
+                static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
+                    constexpr int x_ = decltype(xc)::value;
+                    crow[x_] = (x_ & 1) ? z[FFT_POS<x_ / 2, WS / 2>].y : z[FFT_POS<x_ / 2, WS / 2>].x;
+                });
+            } else {
+                transpose_tile<WS, true, PLANAR>(t, tile, fresh_lane());  // lane = y, t[kx] natural
+                TPIV_STAMP(8);      // transposition 2
+                fft_inreg<WS, -1>(t, tw);                     // over kx; corr(y = lane, x) at t[FFT_POS<x>].x
+                static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
+                    constexpr int x_ = decltype(xc)::value;
+                    crow[x_] = t[FFT_POS<x_, WS>].x;
+                });
+            }
         }
         wave_sync();                                  // tile reads done: it becomes the map
         TPIV_STAMP(9);      // inverse row FFT
