@@ -266,11 +266,13 @@ int tpiv_plan_exact_timing(const tpiv_plan* plan, double* ms4);
 
 /* ---- test hook ------------------------------------------------------------------ */
 
-/* Runs one pass like tpiv_pass1 (mode 0, float32) / tpiv_iter (mode DWS/CWS at `precision`; zero_dev =
- * [batch, n_rows, n_cols] float64 zeros, used as u0 = v0) and additionally writes the staged
- * windows win_dev [batch, N, 2, ws, ws] float32 (frame a, frame b, after the shift) and the
- * correlation maps corr_dev [batch, N, ws, ws] float32 (corr - min + 1e-7, fftshift layout).
- * Either may be NULL. */
+/* Runs one pass like tpiv_pass1 (mode 0: float32, or the exact first pass when precision is
+ * TPIV_PREC_EXACT) / tpiv_iter (mode DWS/CWS at `precision`; zero_dev = [batch, n_rows, n_cols]
+ * float64 zeros, used as u0 = v0) and additionally writes the staged windows win_dev
+ * [batch, N, 2, ws, ws] float32 (frame a, frame b, after the shift) and the correlation maps
+ * corr_dev [batch, N, ws, ws] float32 (corr - min + 1e-7, fftshift layout).  Mode 0 with
+ * TPIV_PREC_EXACT: the maps of the float32 locating kernel, the one whose decisions the exact
+ * pass takes (also for the windows it then sends to the float64 transform).  Either may be NULL. */
 int tpiv_debug_pass(int mode, int precision, const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H, int W,
                     int ws, int ov, const double* u2_dev, const double* v2_dev, const double* zero_dev,
                     double* u_dev, double* v_dev, uint8_t* invalid_dev,

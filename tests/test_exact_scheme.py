@@ -22,9 +22,49 @@ MAX_MIN = 4
 
 
 def band_coef(W):
-    """2 Gamma(W) (1 + 1/16): the proven bound on the float32 map's cell error, per unit of E+ (piv_kernels.h: exact_band_coef)."""
+    """2 Gamma(W) (1 + 1/16): the proven bound on the float32 map's cell error, per unit of E+ (piv_kernels.h: exact_band_coef),
+    for the radix-2 transforms of the power-of-two sizes (gamma_u below covers every kind)."""
     levels = 2 * int(np.ceil(np.log2(W)))
     return 2.0 * (3 * levels * ETA + 7) * (1 + 1 / 16) * U32
+
+
+# the transform a window size's locating kernel runs (piv_kernels.h: EXACT_FFT_RADIX2 / _MIXED / _PLAIN, in that order)
+KINDS = ("radix2", "mixed", "plain")
+
+
+def mixed_factors(n):
+    """n = n1 n2 with 2 <= n1 <= n2 <= 8, n1 as large as possible (xcorr_generic.hip: ct_factors), or None."""
+    n1 = 0
+    for a in range(2, int(np.sqrt(n)) + 1):
+        if n % a == 0 and n // a <= 8:
+            n1 = a
+    return (n1, n // n1) if n1 >= 2 and n // n1 <= 8 else None
+
+
+def kind_of(ws):
+    """piv_launch.hip's rule: the tile kernels (8, 16, 32, 64) and the 128x128 kernel run radix-2/4 codelets; even sizes
+    with a two-factor split run the mixed-radix kernel (xcorr_generic_ct_kernel, fft_mixed.hpp / radix_pass); the rest the
+    plain O(n^2) DFTs of the first-generation generic kernel."""
+    if ws in (8, 16, 32, 64, 128):
+        return "radix2"
+    if ws % 2 == 0 and 4 <= ws <= 96 and mixed_factors(ws) is not None:
+        return "mixed"
+    return "plain"
+
+
+def gamma_u(ws, kind):
+    """Gamma(ws, kind) in units of u = 2^-24 (piv_kernels.h: exact_gamma_u): 2 (2 F + 1) + 5 + 2 I with the per-transform
+    error constants F (forward, normwise) and I (inverse) of the kind."""
+    kind = KINDS[kind] if isinstance(kind, int) else kind
+    lg = int(np.ceil(np.log2(ws)))
+    rt = int(np.floor(np.sqrt(ws))) + 1                 # >= sqrt(ws)
+    if kind == "radix2":
+        f1 = i1 = lg * ETA
+    elif kind == "mixed":
+        f1 = i1 = 64.0
+    else:
+        f1, i1 = (ws + 3) * rt, float(ws + 3)
+    return 2.0 * (2.0 * f1 + 1.0) + 5.0 + 2.0 * i1
 
 
 def e_plus(a, b):

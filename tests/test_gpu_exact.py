@@ -208,8 +208,9 @@ def test_exact_random_geometries(eng):
 def test_exact_on_adversarial_windows(eng):
     """tests/golden/g12_adversarial.npz: the windows tools/research/exact_adversarial.py found by hill-climbing on the float32
     map's error relative to E+ (nine seed families, 64 x 64; worst ratio 8.0e-7 against the proven Gamma = 1.47e-5 the
-    band is built from, profiles/r05/exact_adversarial.txt).  (1) the float32 map of the tile kernel stays inside Gamma E+ on
-    every one of them, with an order of magnitude to spare; (2) precision "exact" gives the float64 kernels' fields."""
+    band is built from, profiles/r05/exact_adversarial.txt).  (1) the float32 maps of the tile kernel and of the locating
+    kernel of precision "exact" stay inside Gamma E+ on every one of them, with an order of magnitude to spare; (2) precision
+    "exact" gives the float64 kernels' fields."""
     import os
     from test_exact_scheme import band_coef, e_plus
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g12_adversarial.npz"))
@@ -218,19 +219,21 @@ def test_exact_on_adversarial_windows(eng):
         P = g[f"w{i}"]
         a, b = np.ascontiguousarray(P[:, 0]), np.ascontiguousarray(P[:, 1])
         A, B = dev(a), dev(b)
-        _, _, _, _, corr = eng.debug_pass(0, A, B, 64, 0, precision="fast")
-        c32 = corr.cpu().numpy().reshape(-1, 64, 64).astype(np.float64)
         af, bf = a.astype(np.float64), b.astype(np.float64)
         an = af / af.mean(axis=(1, 2), keepdims=True) - 1
         bn = bf / bf.mean(axis=(1, 2), keepdims=True) - 1
         c64 = np.fft.fftshift(np.fft.irfft2(np.conj(np.fft.rfft2(an)) * np.fft.rfft2(bn), s=(64, 64)), axes=(1, 2))
-        e = (c32 - (c64 - c64.min(axis=(1, 2), keepdims=True) + 1e-7)).reshape(len(a), -1)
-        err = 0.5 * (e.max(axis=1) - e.min(axis=1))            # (up to the common offset, which changes no decision)
         ep = np.array([e_plus(x, y) for x, y in zip(a, b)])
-        ratio = float((err / ep).max())
-        worst = max(worst, ratio)
         gamma = band_coef(64) / (2 * (1 + 1 / 16))
-        assert ratio < gamma / 8, (str(name), ratio, gamma)
+        # the "fast" kernel's map, and the map of the kernel that takes the decisions (xcorr_tile_cand_kernel<64>)
+        for precision in ("fast", "exact"):
+            _, _, _, _, corr = eng.debug_pass(0, A, B, 64, 0, precision=precision)
+            c32 = corr.cpu().numpy().reshape(-1, 64, 64).astype(np.float64)
+            e = (c32 - (c64 - c64.min(axis=(1, 2), keepdims=True) + 1e-7)).reshape(len(a), -1)
+            err = 0.5 * (e.max(axis=1) - e.min(axis=1))            # (up to the common offset, which changes no decision)
+            ratio = float((err / ep).max())
+            worst = max(worst, ratio)
+            assert 0 < ratio < gamma / 8, (str(name), precision, ratio, gamma)
         plan = eng.Plan(64, 64, 64, 0, n_pass=1, max_batch=len(a), precision="exact")
         ue, ve, ie = plan.run(A, B)
         n_fb = plan.exact_fallbacks()

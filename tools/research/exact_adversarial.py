@@ -1,31 +1,30 @@
 """Adversarial search for the float32 locating pass of precision="exact" (GPU): hill-climb on uint8 windows that MAXIMISES
 the float32 map's cell error relative to E+ = (|a'|^2 + |b'|^2) / 2, the quantity the decision band is proportional to
-(piv_kernels.h "The band": band = 2 Gamma (1 + 1/16) E+, Gamma the proven bound -- 247 u = 1.47e-5 at 64 x 64).
+(piv_kernels.h "The band": band = 2 Gamma (1 + 1/16) E+, Gamma the proven bound of the kind of transform the size's
+locating kernel runs -- radix-2, two-factor mixed radix or plain DFT; 247 u = 1.47e-5 at 64 x 64).
 
 A population of window pairs per seed family (particles, noise, two-level, sinusoids, checkerboards, impulses, saturated)
 is mutated -- single pixels, blocks, rows, copies between the frames, level shifts -- and a mutant replaces its parent
-when err / E+ grows.  err is the largest deviation of the float32 map (tile kernel, debug hook: the same transforms as the
-candidate kernels) from the float64 map, after removing the common offset (which changes no decision).  Output: the worst
-ratio per family and size against Gamma, and the worst windows as tests/golden/g12_adversarial.npz
-(tests/test_gpu_exact.py::test_exact_on_adversarial_windows runs precision="exact" against the float64 kernels on them).
+when err / E+ grows.  err is the largest deviation of the float32 map of the locating kernel itself (debug hook of
+precision="exact") from the float64 map, after removing the common offset (which changes no decision).  Output: the worst
+ratio per family and size against Gamma, and the worst windows: --save writes the 64 x 64 ones as
+tests/golden/g12_adversarial.npz (tests/test_gpu_exact.py::test_exact_on_adversarial_windows), --save-sizes the worst one or two
+pairs per family and size as tests/golden/g13_adversarial_sizes.npz (tests/test_gpu_exact_band.py).
 
-    python tools/research/exact_adversarial.py [--iters 400] [--pop 128] [--sizes 64 32 16 8 128] [--save]
+    python tools/research/exact_adversarial.py [--iters 400] [--pop 128] [--sizes 64 32 16 8 128] [--save] [--save-sizes]
 """
 import argparse
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
+from test_exact_scheme import U32, gamma_u, kind_of       # Gamma(ws, kind): the mirror of piv_kernels.h exact_gamma_u
 from torchpiv_amd import engine
-
-U32 = 2.0 ** -24
-
-
-def gamma_u(W):
-    return 2 * (2 * np.ceil(np.log2(W)) * 6.66 + 1) + 5 + 2 * np.ceil(np.log2(W)) * 6.66
 
 
 def seeds(W, pop, rng):
@@ -61,14 +60,15 @@ def seeds(W, pop, rng):
     sat = np.full((pop, 2, W, W), 255.0)
     sat[rng.random(sat.shape) < 0.01] = 0
     fam["saturated"] = sat
-    fam["all 255 / all 1 blocks"] = np.where(rng.random((pop, 2, W // 4, W // 4)).repeat(4, 2).repeat(4, 3) < 0.5, 255.0, 1.0)
+    nb = (W + 3) // 4
+    fam["all 255 / all 1 blocks"] = np.where(rng.random((pop, 2, nb, nb)).repeat(4, 2).repeat(4, 3)[:, :, :W, :W] < 0.5, 255.0, 1.0)
     return {k_: np.clip(np.rint(v), 0, 255).astype(np.uint8) for k_, v in fam.items()}
 
 
 def evaluate(P, W):
     """P: uint8 [n, 2, W, W] on the device -> (err / E+ offset-free, err / E+ plain, R / E+) per individual (float64, device)."""
     a, b = P[:, 0].contiguous(), P[:, 1].contiguous()
-    _, _, _, _, corr = engine.debug_pass(0, a, b, W, 0, precision="fast")
+    _, _, _, _, corr = engine.debug_pass(0, a, b, W, 0, precision="exact")
     c32 = corr.reshape(-1, W, W).double()
     af, bf = a.double(), b.double()
     ma, mb = af.mean(dim=(1, 2), keepdim=True), bf.mean(dim=(1, 2), keepdim=True)
@@ -121,13 +121,14 @@ def main():
     ap.add_argument("--pop", type=int, default=96)
     ap.add_argument("--sizes", type=int, nargs="*", default=[64, 32, 16, 8, 128])
     ap.add_argument("--save", action="store_true")
+    ap.add_argument("--save-sizes", action="store_true")
     args = ap.parse_args()
     rng = np.random.default_rng(20261)
-    keep = {}
-    print(f"{'W':>4s} {'family':30s} {'start err/E+':>13s} {'found err/E+':>13s} {'(plain)':>10s} {'R/E+ there':>11s} {'Gamma':>10s} {'Gamma / found':>13s}")
+    keep, keep_sizes = {}, {}
+    print(f"{'W':>4s} {'kind':6s} {'family':30s} {'start err/E+':>13s} {'found err/E+':>13s} {'(plain)':>10s} {'R/E+ there':>11s} {'Gamma':>10s} {'Gamma / found':>13s}")
     for W in args.sizes:
         pop = args.pop if W <= 64 else max(16, args.pop // 4)
-        G = gamma_u(W) * U32
+        G = gamma_u(W, kind_of(W)) * U32
         for name, s in seeds(W, pop, rng).items():
             P = s.copy()
             fit, plain, re = (t.cpu().numpy() for t in evaluate(torch.from_numpy(P).cuda(), W))
@@ -139,16 +140,22 @@ def main():
                 P[better] = Q[better]
                 fit, plain, re = np.where(better, fq, fit), np.where(better, pq, plain), np.where(better, rq, re)
             j = int(fit.argmax())
-            print(f"{W:4d} {name:30s} {start:13.3e} {float(fit[j]):13.3e} {float(plain[j]):10.2e} {float(re[j]):11.2e} {G:10.3e} {G / max(float(fit[j]), 1e-30):13.1f}",
+            print(f"{W:4d} {kind_of(W):6s} {name:30s} {start:13.3e} {float(fit[j]):13.3e} {float(plain[j]):10.2e} {float(re[j]):11.2e} {G:10.3e} {G / max(float(fit[j]), 1e-30):13.1f}",
                   flush=True)
             if W == 64:
                 keep[name] = P[np.argsort(-fit)[:4]].copy()
+            keep_sizes[(W, name)] = P[np.argsort(-fit)[:2 if W < 96 else 1]].copy()      # (the file stays below 1 MiB)
     if args.save and keep:
-        root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         names = sorted(keep)
-        np.savez_compressed(os.path.join(root, "tests", "golden", "g12_adversarial.npz"), names=np.array(names),
+        np.savez_compressed(os.path.join(ROOT, "tests", "golden", "g12_adversarial.npz"), names=np.array(names),
                             **{f"w{i}": keep[n_] for i, n_ in enumerate(names)})
         print("saved tests/golden/g12_adversarial.npz:", {n_: keep[n_].shape for n_ in names})
+    if args.save_sizes and keep_sizes:
+        items = sorted(keep_sizes)
+        path = os.path.join(ROOT, "tests", "golden", "g13_adversarial_sizes.npz")
+        np.savez_compressed(path, sizes=np.array([w for w, _ in items]), names=np.array([n_ for _, n_ in items]),
+                            **{f"w{i}": keep_sizes[k_] for i, k_ in enumerate(items)})
+        print(f"saved tests/golden/g13_adversarial_sizes.npz: {len(items)} sets, {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

@@ -12,6 +12,7 @@ few dark pixels) -- the float32 correlation maps of the tile kernel (debug hook)
 and the fields of precision="exact" with those of precision="f64" (any difference above 1e-9 px is a wrong decision that
 went unnoticed).
 """
+import functools
 import os
 import sys
 
@@ -22,20 +23,29 @@ import torch
 from torchpiv_amd import engine, synth
 
 
-def families(n=64, seed=0):
+@functools.lru_cache(maxsize=None)
+def _particle_frames(size, noise):
+    A, B = synth.make_batch(1, size, size, device="cpu", noise=noise, first_index=int(noise) + 3)
+    return A[0].numpy(), B[0].numpy()
+
+
+def families(n=64, seed=0, W=64, size=1024):
+    """Window-pair families of size W x W, n pairs each (the particle families are the first n W x W tiles of a size x size
+    synthetic pair: size // W >= ceil(n / (size // W)) rows of them are needed)."""
     rng = np.random.default_rng(seed)
-    W = 64
     yy, xx = np.mgrid[0:W, 0:W]
     fam = {}
+    k_ = size // W
+    assert k_ * k_ >= n, (size, W, n)
     for noise in (0.0, 2.0, 8.0, 24.0):
-        A, B = synth.make_batch(1, 1024, 1024, device="cpu", noise=noise, first_index=int(noise) + 3)
-        a = A[0].numpy().reshape(16, 64, 16, 64).transpose(0, 2, 1, 3).reshape(-1, 64, 64)[:n]
-        b = B[0].numpy().reshape(16, 64, 16, 64).transpose(0, 2, 1, 3).reshape(-1, 64, 64)[:n]
+        A, B = _particle_frames(size, noise)
+        a = A[:k_ * W, :k_ * W].reshape(k_, W, k_, W).transpose(0, 2, 1, 3).reshape(-1, W, W)[:n]
+        b = B[:k_ * W, :k_ * W].reshape(k_, W, k_, W).transpose(0, 2, 1, 3).reshape(-1, W, W)[:n]
         fam[f"particles noise {noise:g}"] = (a, b)
     fam["uniform noise"] = (rng.integers(0, 256, (n, W, W)), rng.integers(0, 256, (n, W, W)))
     fam["low-contrast noise 100..103"] = (rng.integers(100, 104, (n, W, W)), rng.integers(100, 104, (n, W, W)))
     fam["two levels 200/201"] = (200 + rng.integers(0, 2, (n, W, W)), 200 + rng.integers(0, 2, (n, W, W)))
-    k = rng.integers(1, 31, (n, 1, 1))
+    k = rng.integers(1, max(2, W // 2 - 1), (n, 1, 1))
     fam["orthogonal sinusoids"] = (np.rint(127 + 100 * np.sin(2 * np.pi * k * xx[None] / W)),
                                    np.rint(127 + 100 * np.sin(2 * np.pi * k * yy[None] / W)))
     fam["same sinusoid, other phase"] = (np.rint(127 + 100 * np.sin(2 * np.pi * k * xx[None] / W)),
@@ -53,11 +63,11 @@ def families(n=64, seed=0):
     fam["saturated, five dark pixels"] = (sat, sat2)
     fam["checkerboard vs stripes"] = (np.broadcast_to(255 * ((xx + yy) & 1), (n, W, W)) + rng.integers(0, 2, (n, W, W)) * 0,
                                       np.broadcast_to(255 * (xx & 1), (n, W, W)) + rng.integers(0, 3, (n, W, W)))
-    fam["ramp vs noise"] = (np.broadcast_to(xx * 4, (n, W, W)), rng.integers(0, 256, (n, W, W)))
+    fam["ramp vs noise"] = (np.broadcast_to(xx * (256 // W), (n, W, W)), rng.integers(0, 256, (n, W, W)))
     # background-subtracted recordings: 3x3 particle images on a TRUE zero, most map cells exactly 0
     za, zb = np.zeros((n, W + 8, W + 8)), None
     for i in range(n):
-        for _ in range(14):
+        for _ in range(max(2, round(14 * W * W / 4096))):
             y, x = rng.integers(3, W + 4), rng.integers(3, W + 4)
             za[i, y - 1:y + 2, x - 1:x + 2] += rng.uniform(80, 200)
     fam["particles on a true-zero background"] = (za[:, 2:2 + W, 2:2 + W], za[:, 4:4 + W, 1:1 + W])

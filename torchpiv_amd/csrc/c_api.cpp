@@ -520,9 +520,9 @@ int tpiv_iter(int mode, const uint8_t* a, const uint8_t* b, int batch, int H, in
 int tpiv_debug_pass(int mode, int precision, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws,
                     int ov, const double* u2, const double* v2, const double* zero, double* u, double* v,
                     uint8_t* invalid, float* win, float* corr, void* work, size_t work_bytes, void* stream) {
-    if (mode == 0)
-        return pass1_impl(a, b, batch, H, W, ws, ov, 1.2, 3, TPIV_PREC_FAST, u, v, invalid, work, work_bytes, win,
-                          corr, stream);
+    if (mode == 0)      // the float32 kernel; TPIV_PREC_EXACT: the exact pass, whose maps come from its locating kernel alone
+        return pass1_impl(a, b, batch, H, W, ws, ov, 1.2, 3, precision == TPIV_PREC_EXACT ? TPIV_PREC_EXACT : TPIV_PREC_FAST,
+                          u, v, invalid, work, work_bytes, win, corr, stream);
     if (!zero || !u2 || !v2) return fail(TPIV_EINVAL, "tpiv_debug_pass: shifted passes need u2, v2 and a zero field");
     return run_iter(mode, precision, a, b, batch, H, W, ws, ov, zero, zero, u2, v2, 1.2, 3, u, v, invalid, nullptr,
                     nullptr, win, corr, work, work_bytes, stream);

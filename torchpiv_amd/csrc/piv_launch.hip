@@ -179,6 +179,21 @@ hipError_t launch_peaks_from_maps(const PassParams& p, const float* maps, int n_
 static constexpr size_t WORK_CTR_BYTES = TILE_CTR_BYTES;
 static size_t work_ctr_offset(int batch, int n_windows) { return (peak_bytes(batch, n_windows) + 127) / 128 * 128; }
 
+// test hook of precision "exact" (tpiv_debug_pass): the tile candidate kernels store their maps raw (the store then costs
+// them no registers); one workgroup per window turns them into corr - min + 1e-7, the form of every other kernel's debug map
+// -- the same min and the same two roundings
+__global__ __launch_bounds__(256) void dbg_map_shift_kernel(float* maps, int nn) {
+    __shared__ float red[4];
+    float* const m = maps + (size_t)blockIdx.x * nn;
+    float mn = 3.4e38f;
+    for (int i = threadIdx.x; i < nn; i += 256) mn = fminf(mn, m[i]);
+    for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
+    __syncthreads();
+    mn = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    for (int i = threadIdx.x; i < nn; i += 256) m[i] = __fadd_rn(__fsub_rn(m[i], mn), 1e-7f);
+}
+
 // precision "exact": float64 records | candidate cells (16 B per window) | float64 list | its counter | tile work counters
 // | generic sizes: the DFT scratch tiles of the first-generation kernel (float32 locating pass and float64 list pass)
 struct ExactLayout {
@@ -308,7 +323,16 @@ hipError_t launch_xcorr(const PassParams& p_in, int mode, int n_cu, hipStream_t 
             default: e = launch_xcorr_generic(q, MODE_PASS1, 256, gscratch, stream); break;
         }
         if (e != hipSuccess) return e;
+        if (p.dbg_corr != nullptr && tile_size(p.ws)) {
+            hipLaunchKernelGGL(dbg_map_shift_kernel, dim3((unsigned)(p.batch * p.n_rows * p.n_cols)), dim3(256), 0, stream,
+                               p.dbg_corr, p.ws * p.ws);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
         mark(0);
+        // the debug maps (tpiv_debug_pass) are the locating kernel's: the float64 generic kernel would overwrite those of the
+        // listed windows, so the launches behind it get none
+        p.dbg_win = p.dbg_corr = q.dbg_win = q.dbg_corr = nullptr;
         e = launch_exact_refine(p, n_cu, stream);
         if (e != hipSuccess) return e;
         mark(1);

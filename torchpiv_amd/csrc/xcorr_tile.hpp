@@ -1428,6 +1428,15 @@ __device__ __forceinline__ void peak_candidates(const PassParams& p, const float
     };
     float* const my_row = tile + w * WS;              // one parked map row per window
     const int ys = (r + WS / 2) % WS;
+    if (p.dbg_corr != nullptr && active) {            // test hook: the RAW map the decisions below are taken on (launch_xcorr
+        int yy = ys;                                  // shifts it to corr - min + 1e-7 behind the pass); opaque row index:
+        asm volatile("" : "+v"(yy));                  // keeps the WS store addresses out of the item loop's registers
+        float* d = p.dbg_corr + fidx * WS * WS + yy * WS;
+        static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
+            constexpr int xsft = decltype(kc)::value;
+            d[xsft] = row[(xsft + WS / 2) % WS];
+        });
+    }
     float rmin = 3.4e38f, rmax = -3.4e38f;
 #pragma unroll
     for (int k = 0; k < WS; ++k) {

@@ -150,7 +150,10 @@ def iterate(mode, a, b, ws, ov, u0, v0, u2, v2, val_ratio=1.2, val_win=3, want_r
 
 def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference"):
     """Test hook: one pass plus the staged windows and the correlation maps (shifted passes at
-    `precision`: "reference" = the reference's operation order, bit-identical windows)."""
+    `precision`: "reference" = the reference's operation order, bit-identical windows).  Pass 1
+    (mode 0) runs the float32 kernel, or with precision="exact" the exact first pass, whose maps
+    are those of its float32 locating kernel -- the map every decision is taken on, also for the
+    windows that then go to the float64 transform."""
     prec = _precision(precision)
     a, b = _frames(a, b)
     B, H, W = a.shape
