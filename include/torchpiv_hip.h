@@ -267,10 +267,14 @@ int tpiv_plan_exact_timing(const tpiv_plan* plan, double* ms4);
 /* ---- test hook ------------------------------------------------------------------ */
 
 /* Runs one pass like tpiv_pass1 (mode 0: float32, or the exact first pass when precision is
- * TPIV_PREC_EXACT) / tpiv_iter (mode DWS/CWS at `precision`; zero_dev = [batch, n_rows, n_cols]
- * float64 zeros, used as u0 = v0) and additionally writes the staged windows win_dev
+ * TPIV_PREC_EXACT) / tpiv_iter (mode DWS/CWS/CWS_Fast at `precision`; zero_dev = [batch, n_rows, n_cols]
+ * float64 zeros) and additionally writes the staged windows win_dev
  * [batch, N, 2, ws, ws] float32 (frame a, frame b, after the shift) and the correlation maps
- * corr_dev [batch, N, ws, ws] float32 (corr - min + 1e-7, fftshift layout).  Mode 0 with
+ * corr_dev [batch, N, ws, ws] float32 (corr - min + 1e-7, fftshift layout; odd window sizes write none).
+ * DWS / CWS: u2_dev, v2_dev are the half shift as tpiv_iter takes it (DWS: integral values) and u0 = v0 = 0, so the
+ * outputs are u = 2 u2 + du, v = 2 v2 + dv with the pass's raw displacement du, dv where the window is valid, and 0
+ * where invalid_dev says it is not.  CWS_Fast: u2_dev, v2_dev are the predictor itself, passed as u0, v0 (the windows
+ * are resampled by -/+ u0 / 2 inside themselves) and the outputs are tpiv_iter's, u = u0 + du unless masked.  Mode 0 with
  * TPIV_PREC_EXACT: the maps of the float32 locating kernel, the one whose decisions the exact
  * pass takes (also for the windows it then sends to the float64 transform).  Either may be NULL. */
 int tpiv_debug_pass(int mode, int precision, const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H, int W,

@@ -524,8 +524,10 @@ int tpiv_debug_pass(int mode, int precision, const uint8_t* a, const uint8_t* b,
         return pass1_impl(a, b, batch, H, W, ws, ov, 1.2, 3, precision == TPIV_PREC_EXACT ? TPIV_PREC_EXACT : TPIV_PREC_FAST,
                           u, v, invalid, work, work_bytes, win, corr, stream);
     if (!zero || !u2 || !v2) return fail(TPIV_EINVAL, "tpiv_debug_pass: shifted passes need u2, v2 and a zero field");
-    return run_iter(mode, precision, a, b, batch, H, W, ws, ov, zero, zero, u2, v2, 1.2, 3, u, v, invalid, nullptr,
-                    nullptr, win, corr, work, work_bytes, stream);
+    // CWS_Fast takes its shift from u0, v0 (B:644-653): the given predictor goes there
+    const bool cwsf = mode == TPIV_MODE_CWS_FAST;
+    return run_iter(mode, precision, a, b, batch, H, W, ws, ov, cwsf ? u2 : zero, cwsf ? v2 : zero, u2, v2, 1.2, 3, u, v,
+                    invalid, nullptr, nullptr, win, corr, work, work_bytes, stream);
 }
 
 int tpiv_debug_peaks(const float* maps, int n_maps, int ws, int planar, double val_ratio, int val_win, double* u,

@@ -29,6 +29,23 @@ struct cf {
     float x, y;
 };
 
+// Test-only switch (tools/diag/libtorchpiv_hip_mutant_tw.so, tests/test_gpu_shifted_maps.py): -DTPIV_MUTANT_TWIDDLE=eps scales
+// the first non-trivial twiddle w_N^1 of every codelet (fft_inreg.hpp, fft_mixed.hpp, the run-time table of the mixed-radix
+// generic kernel) by 1 + eps, and the plain DFT's table entry w_n^1 by 1 + 100 eps (xcorr_generic.hip).  Values only: no
+// index, no branch changes.  The shipped library never defines it (the factor is then 1, and the code is the same
+// instruction for instruction).
+#ifdef TPIV_MUTANT_TWIDDLE
+constexpr bool MUT_TW_ON = true;
+constexpr float MUT_TW = (float)(1.0 + (double)(TPIV_MUTANT_TWIDDLE));
+constexpr float MUT_TW_PLAIN = (float)(1.0 + 100.0 * (double)(TPIV_MUTANT_TWIDDLE));     // xcorr_generic_kernel's table
+#else
+constexpr bool MUT_TW_ON = false;
+constexpr float MUT_TW = 1.0f;
+#endif
+// (the factor of twiddle w_N^K: MUT_TW for K = 1 mod N, else 1)
+template <int K, int N>
+constexpr float mut_tw() { return (((K % N) + N) % N == 1) ? MUT_TW : 1.0f; }
+
 TPIV_HD cf cadd(cf a, cf b) { return cf{a.x + b.x, a.y + b.y}; }
 TPIV_HD cf csub(cf a, cf b) { return cf{a.x - b.x, a.y - b.y}; }
 
@@ -67,8 +84,8 @@ TPIV_HD cf twmul(cf a) {
     } else if constexpr (idx == 96) {
         return DIR > 0 ? cf{-a.y, a.x} : cf{a.y, -a.x};
     } else {
-        constexpr float c = TW_COS[idx];
-        constexpr float s = DIR > 0 ? -TW_SIN[idx] : TW_SIN[idx];
+        constexpr float c = TW_COS[idx] * mut_tw<K, N>();
+        constexpr float s = (DIR > 0 ? -TW_SIN[idx] : TW_SIN[idx]) * mut_tw<K, N>();
         return cf{a.x * c - a.y * s, a.x * s + a.y * c};
     }
 }
@@ -115,9 +132,14 @@ TPIV_HD cf twmul_t(cf a, const TW& tw) {
         constexpr bool cneg = (q == 1 || q == 2);
         constexpr bool sneg0 = (q == 2 || q == 3);
         constexpr bool sneg = DIR > 0 ? !sneg0 : sneg0;   // multiply by exp(-DIR * i * theta)
-        const float C = tw.template m<rc, cneg>();
-        const float S = tw.template m<rs, sneg>();
-        const float nS = tw.template m<rs, !sneg>();
+        float C = tw.template m<rc, cneg>();
+        float S = tw.template m<rs, sneg>();
+        float nS = tw.template m<rs, !sneg>();
+        if constexpr (MUT_TW_ON && mut_tw<K, N>() != 1.0f) {
+            C *= MUT_TW;
+            S *= MUT_TW;
+            nS *= MUT_TW;
+        }
 #if defined(__HIP_DEVICE_COMPILE__)
         return cf{__builtin_fmaf(a.y, nS, a.x * C), __builtin_fmaf(a.y, C, a.x * S)};
 #else

@@ -75,8 +75,8 @@ TPIV_HD cf twm(cf a) {
         return DIR > 0 ? cf{-a.y, a.x} : cf{a.y, -a.x};
     } else {
         constexpr SinCos sc = sincos_2pi(k, N);
-        constexpr float c = (float)sc.c;
-        constexpr float s = DIR > 0 ? (float)(-sc.s) : (float)sc.s;
+        constexpr float c = (float)sc.c * mut_tw<K, N>();
+        constexpr float s = (DIR > 0 ? (float)(-sc.s) : (float)sc.s) * mut_tw<K, N>();
         return cf{a.x * c - a.y * s, a.x * s + a.y * c};
     }
 }

@@ -318,6 +318,11 @@ __global__ __launch_bounds__(GT) void xcorr_generic_kernel(PassParams p, cplx<R>
         double s, c;
         sincospi(2.0 * (double)k / (double)n, &s, &c);
         tw[k] = cf{(R)c, (R)(-s)};
+#ifdef TPIV_MUTANT_TWIDDLE
+        // (100 eps here: w_n^1 is one entry of the table that all n^2 products read, and the plain DFT's worst-case Gamma,
+        //  (n + 3) sqrt(n) u per transform, sits 20-50 x above what a 1e-4 error in it does to the map)
+        tw[k] = cf{tw[k].x * (k == 1 ? (R)MUT_TW_PLAIN : (R)1), tw[k].y * (k == 1 ? (R)MUT_TW_PLAIN : (R)1)};     // (fft_inreg.hpp)
+#endif
         if (n > 1) {
             sincospi(2.0 * (double)k / (double)(n - 1), &s, &c);
             tw2[k] = cf{(R)c, (R)(-s)};
@@ -807,6 +812,9 @@ __global__ __launch_bounds__(NC > 0 ? 64 : CT_T) void xcorr_generic_ct_kernel(Pa
             double s, c;
             sincospi(2.0 * (double)k / (double)n, &s, &c);
             tw[k] = cff{(float)c, (float)(-s)};
+#ifdef TPIV_MUTANT_TWIDDLE
+            tw[k] = cff{tw[k].x * (k == 1 ? MUT_TW : 1.f), tw[k].y * (k == 1 ? MUT_TW : 1.f)};     // (fft_inreg.hpp)
+#endif
         }
         __syncthreads();
     }

@@ -153,7 +153,8 @@ def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference"):
     `precision`: "reference" = the reference's operation order, bit-identical windows).  Pass 1
     (mode 0) runs the float32 kernel, or with precision="exact" the exact first pass, whose maps
     are those of its float32 locating kernel -- the map every decision is taken on, also for the
-    windows that then go to the float64 transform."""
+    windows that then go to the float64 transform.  "CWS_Fast" takes u2, v2 as its predictor u0, v0 (the windows are
+    resampled by -/+ u0 / 2 inside themselves); DWS / CWS return u = 2 u2 + du where valid, 0 where invalid."""
     prec = _precision(precision)
     a, b = _frames(a, b)
     B, H, W = a.shape
@@ -165,7 +166,7 @@ def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference"):
     inv = torch.empty(B, nr, nc, dtype=torch.uint8, device=dev)
     win = torch.empty(B, N, 2, ws, ws, dtype=torch.float32, device=dev)
     corr = torch.empty(B, N, ws, ws, dtype=torch.float32, device=dev)
-    m = 0 if mode in (0, None, "PASS1") else MODES[mode]
+    m = 0 if mode in (0, None, "PASS1") else ITER_MODES[mode]
     zero = torch.zeros(B, nr, nc, dtype=torch.float64, device=dev) if m else None
     with torch.cuda.device(dev):
         work, nbytes = _work(H, W, ws, ov, B, dev)
