@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the PIV cross-correlation hot path (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W [--config 1|2] [--precision exact|f64|fast|reference]
+    python bench.py --gpus N --steps K --warmup W [--config 1|2] [--precision exact|f64|fast|reference] [--full]
+
+A plain run does what the headline needs and no more: it renders the frames, warms up, times the K steps, writes
+--dump-outputs if asked and prints the line, whose roofline and per-kernel figures come from the events of those same
+steps.  --full adds what takes runs of its own (N = 1): the float64-FFT and all-float32 runs beside the headline, the exact
+pass 1 against the float64 FFT on the bench batch, live PMC counters, the end_to_end block and the CPU baseline.
 
 Metric (BASELINE.json): image-pairs/sec at 4 MP, wind=64 ov=32, 2-pass CWS x2.0.
 
@@ -23,17 +28,17 @@ Precision.  `value` is measured at --precision exact (the default of the library
 passes in the reference's types (float32 with the float64 epilogue, B:249-257, B:382), and pass 1 -- float64 in the
 reference, B:513-514 -- from EXACT integer correlation sums at the map cells that reach the result (a float32 FFT pass only
 locates them inside an error band; undecided windows run the float64 transform; csrc/xcorr_exact.hip).  The fields are
-within 1e-14 px of the float64 pass 1 (tests/test_gpu_exact.py) -- not a narrower type.  At N = 1 the same process then
-times the same workload with pass 1 through the float64 FFT kernel (`f64_transform`, the headline of rounds 2-3) and
+within 1e-14 px of the float64 pass 1 (tests/test_gpu_exact.py) -- not a narrower type.  With --full at N = 1 the same
+process then times the same workload with pass 1 through the float64 FFT kernel (`f64_transform`, the headline of rounds 2-3) and
 with pass 1 in float32 (`fast`), reported BESIDE the headline, never as `value`; then `end_to_end` (the generator through
 post-validation and yield, tools/e2e_generator.py) and `cpu_baseline`.
 
 Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel: HIP-event durations on the
 launch stream during the timed steps, bound = "valu" (the path sits ~10x above the
 HBM ridge), frac = max(B_alg / 8 TB/s, F_alg / 157.3 TFLOP/s) / t, the HBM view beside it, and --
-at N = 1 -- PMC counters of THIS build collected live by rocprofv3 child runs of this script
+with --full at N = 1 -- PMC counters of THIS build collected live by rocprofv3 child runs of this script
 (FETCH_SIZE, WRITE_SIZE, SQ_* in separate passes; --pmc file reads profiles/r05/pmc_counters.json
-instead, --pmc off skips).  `cpu_baseline` (N = 1): the CPU oracle on the host cores.  The printed line is the
+instead, --pmc off skips).  `cpu_baseline` (--full, N = 1): the CPU oracle on the host cores.  The printed line is the
 record without its notes and its per-kernel, per-rank and per-case detail; --record FILE writes the whole record.
 
 --dump-outputs DIR writes what the timed path computed in its last timed step (u, v, invalid of rank 0's pairs, a seeded
@@ -88,8 +93,11 @@ def parse_args():
                          "f64: pass 1 through a float64 FFT like the reference (PIVbackend.py:513-514); "
                          "reference: the same with the reference's operation order in the CWS sampling; fast: pass 1 in float32 too")
     ap.add_argument("--no-gpu-sampling", action="store_true", help="do not sample the GPU clock / power from sysfs during the timed steps")
-    ap.add_argument("--no-fast", action="store_true", help="N = 1: skip the float64-FFT and all-float32 runs reported beside the headline")
-    ap.add_argument("--no-e2e", action="store_true", help="N = 1: skip the end_to_end block (generator rates)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline, also the float64-FFT and all-float32 runs, the exact pass 1 against the "
+                         "float64 FFT, PMC counters (--pmc), the end_to_end block and cpu_baseline; the --no-* options trim these")
+    ap.add_argument("--no-fast", action="store_true", help="--full: skip the float64-FFT and all-float32 runs reported beside the headline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end_to_end block (generator rates)")
     ap.add_argument("--batch", type=int, default=None, help="pairs per GPU per launch (config 1: 256; config 2: shard 500)")
     ap.add_argument("--stream", type=int, default=4000, help="config 2: pairs in the stream (all ranks together)")
     ap.add_argument("--size", type=int, default=2048)
@@ -97,13 +105,14 @@ def parse_args():
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--mode", default=None, help="CWS (config 1) / DWS (config 2)")
     ap.add_argument("--distinct", type=int, default=0, help="distinct synthetic pairs to render (0 = a whole batch)")
-    ap.add_argument("--pmc", default="live", choices=("live", "file", "off"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--pmc", default="live", choices=("live", "file", "off"),
+                    help="--full: PMC counters of the roofline from rocprofv3 child runs (live), from the committed file, or none")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--e2e", action="store_true",
                     help="end-to-end generator mode instead of the kernel-path bench: ResidentPIV / OfflinePIV.batched incl. "
                          "device post-validation, counted host fallbacks, BMP ingest (one JSON line, N = 1)")
     ap.add_argument("--e2e-pairs", type=int, default=256)
-    ap.add_argument("--e2e-block-pairs", type=int, default=128, help="pairs per case of the end_to_end block of the default run")
+    ap.add_argument("--e2e-block-pairs", type=int, default=128, help="pairs per case of the end_to_end block of --full")
     ap.add_argument("--fill-workers", type=int, default=8)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed for rank 0's pairs to DIR/<name>.npy: u, v "
@@ -129,6 +138,18 @@ def parse_args():
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     return a
+
+
+def side_measurements(args, world):
+    """What the kernel-path bench measures beside the headline run.  Nothing without --full: a plain run's line comes from
+    the headline's own steps alone.  With --full at N = 1 (config 1 for the side runs and end_to_end) everything the --no-*
+    options leave ("f64": the float64-FFT run and the exact pass 1 against it); at N > 1 --full reads the committed PMC
+    counters."""
+    one = args.full and world == 1
+    fast = one and args.config == 1 and not args.no_fast and args.precision != "fast"
+    return {"fast": fast, "f64": fast and args.precision == "exact",
+            "pmc": args.pmc if args.full else "off", "pmc_live": one and args.pmc == "live",
+            "end_to_end": one and args.config == 1 and not args.no_e2e, "cpu_baseline": one and not args.no_cpu_baseline}
 
 
 def free_port():
@@ -719,12 +740,11 @@ def main():
         raise SystemExit("bench.py: one --precision (the comma form is the profiled child's)")
 
     head = measure(args.precision, args.steps, args.warmup, dump=args.dump_outputs if rank == 0 else None)
-    also_fast = world == 1 and args.config == 1 and not args.no_fast and args.precision != "fast"
-    also_f64 = also_fast and args.precision == "exact"
-    f64_run = measure("f64", args.steps, args.warmup) if also_f64 else None
-    fast = measure("fast", args.steps, args.warmup) if also_fast else None
+    side = side_measurements(args, world)
+    f64_run = measure("f64", args.steps, args.warmup) if side["f64"] else None
+    fast = measure("fast", args.steps, args.warmup) if side["fast"] else None
     parity = None
-    if also_f64 and "exact_timing" in head:
+    if side["f64"] and "exact_timing" in head:
         try:
             parity = exact_against_f64()
         except Exception as exc:                          # never let the side check break the bench line
@@ -747,10 +767,10 @@ def main():
 
     if rank == 0:
         # ---- PMC counters (N = 1): one set of child passes covers both precisions
-        pmc, pmc_src = None, "off"
-        if world == 1 and args.pmc == "live":
-            pmc, pmc_src = collect_pmc_live(args, [args.precision] + (["f64"] if also_f64 else []) + (["fast"] if also_fast else []))
-        if pmc is None and args.pmc in ("live", "file") and os.path.exists(PMC_FILE):
+        pmc, pmc_src = None, "off" if args.full else "off (--full collects them)"
+        if side["pmc_live"]:
+            pmc, pmc_src = collect_pmc_live(args, [args.precision] + (["f64"] if side["f64"] else []) + (["fast"] if side["fast"] else []))
+        if pmc is None and side["pmc"] in ("live", "file") and os.path.exists(PMC_FILE):
             try:
                 with open(PMC_FILE) as f:
                     blob = json.load(f)
@@ -938,7 +958,7 @@ def main():
                            "kernel_ms": fast["timing"], "roofline": froof, "kernels": fk,
                            "note": "the same workload, same process, timed right after the headline with pass 1 in float32 "
                                    "(narrower than the reference's float64 pass 1: reported beside `value`, never as it)"}
-        if world == 1 and args.config == 1 and not args.no_e2e:
+        if side["end_to_end"]:
             del A, B
             torch.cuda.empty_cache()
             try:
@@ -946,7 +966,7 @@ def main():
                 rec["end_to_end"] = e2e_block(r, log, args.e2e_block_pairs, args.fill_workers)
             except Exception as exc:                      # never let the side block break the bench line
                 rec["end_to_end"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if side["cpu_baseline"]:
             rec["cpu_baseline"] = cpu_baseline(H, W, ws, ov, args.passes, args.mode)
         assert rec["n_gpus"] == args.gpus
         if args.record:

@@ -9,7 +9,7 @@ timeout -k 10 900 python3 -m pytest tests -m gpu -x -q -s > $OUT/pytest.log 2>&1
 rc=$?
 tail -n 15 $OUT/pytest.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 400 python3 bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err || { tail -n 20 $OUT/bench_n1.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err || { tail -n 20 $OUT/bench_n1.err; exit 1; }
 python3 - $OUT/bench_n1.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

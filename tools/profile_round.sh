@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile on the GPU box.  Everything the bench line quotes can be re-derived from these outputs:
-#   bench_n1.json               the driver's command (configs[1] at the default precision "exact" = the headline, with the
+#   bench_n1.json               bench.py --full (configs[1] at the default precision "exact" = the headline, with the
 #                               float64-FFT and all-float32 runs beside it, the end_to_end block, live PMC counters and the
 #                               CPU baseline)
 #   bench_n1_reference.json     the same at precision "reference" (reference-order CWS staging)
@@ -28,15 +28,15 @@ export TMPDIR=/tmp
 R="--kernel-include-regex xcorr|predict|finalize|postval"
 PART=${2:-ab}
 if [[ $PART == *a* ]]; then
-python3 bench.py --record $OUT/bench_n1.json > /dev/null 2> $OUT/bench_n1.err || { tail $OUT/bench_n1.err; exit 1; }
-python3 bench.py --precision reference --no-cpu-baseline --no-fast --no-e2e --record $OUT/bench_n1_reference.json > /dev/null 2> $OUT/bench_ref.err || exit 1
-python3 bench.py --config 2 --no-cpu-baseline --no-e2e --record $OUT/bench_n1_config2.json > /dev/null 2> $OUT/bench_c2.err || exit 1
+python3 bench.py --full --record $OUT/bench_n1.json > /dev/null 2> $OUT/bench_n1.err || { tail $OUT/bench_n1.err; exit 1; }
+python3 bench.py --full --precision reference --no-cpu-baseline --no-fast --no-e2e --record $OUT/bench_n1_reference.json > /dev/null 2> $OUT/bench_ref.err || exit 1
+python3 bench.py --full --config 2 --no-cpu-baseline --no-e2e --record $OUT/bench_n1_config2.json > /dev/null 2> $OUT/bench_c2.err || exit 1
 TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 2 --steps 20 --warmup 2 --batch 64 --pmc off --record $OUT/bench_gloo2_config1.json > /dev/null 2> $OUT/g2.err || exit 1
 TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 2 --config 2 --steps 3 --stream 1000 --batch 250 --pmc off --record $OUT/bench_gloo2_config2.json > /dev/null 2> $OUT/g2c2.err || exit 1
 TPIV_DIST_BACKEND=gloo python3 bench.py --gpus 4 --steps 10 --warmup 2 --batch 32 --pmc off --record $OUT/bench_gloo4_config1.json > /dev/null 2> $OUT/g4.err || exit 1
 # soak: 2000 timed steps of the headline workload (stability of the rate; no counters, no side measurements)
 python3 bench.py --steps 2000 --warmup 5 --pmc off --no-cpu-baseline --no-e2e --no-fast > $OUT/bench_soak2000.json 2> $OUT/soak.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv $R -d $OUT/stats -- python3 bench.py --steps 50 --warmup 5 --pmc off --no-cpu-baseline --no-e2e > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv $R -d $OUT/stats -- python3 bench.py --full --steps 50 --warmup 5 --pmc off --no-cpu-baseline --no-e2e > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 cp $OUT/stats/*/*_kernel_stats.csv $OUT/rocprofv3_kernel_stats.csv && rm -rf $OUT/stats
 fi
 if [[ $PART == *b* ]]; then
