@@ -27,6 +27,12 @@
 #include "piv_kernels.h"
 #include "xcorr_tile.hpp"      // grp_reduce, wave_sync, load_dwords
 
+// wavefronts (= windows) per workgroup of the 64x64 refinement: 2 -> 16.9 KB of LDS per workgroup, 9 workgroups = 18
+// wavefronts per CU against 4 x 4 = 16 with 4 (1.10 -> 1.06 ms per 1 016 064 windows; profiles/exact_neighbourhood)
+#ifndef TPIV_REFINE_WAVES64
+#define TPIV_REFINE_WAVES64 2
+#endif
+
 namespace tpiv {
 
 namespace {
@@ -38,8 +44,8 @@ struct XGeo {
     static constexpr int GROUP = W < 64 ? W : 64;            // lanes of one window inside a wavefront
     static constexpr int WPW = 64 / GROUP;                   // windows per wavefront (32x32: two)
     static constexpr int PARTS = W / GROUP;                  // wavefronts per window (128x128: two)
-    static constexpr int WAVES = W == 128 ? 2 : 4;           // wavefronts per workgroup
-    static constexpr int WINS = WAVES * WPW / PARTS;         // windows per workgroup: 8 / 4 / 1
+    static constexpr int WAVES = W == 128 ? 2 : (W == 64 ? TPIV_REFINE_WAVES64 : 4);      // wavefronts per workgroup
+    static constexpr int WINS = WAVES * WPW / PARTS;         // windows per workgroup: 8 / 2 / 1
     static constexpr int KD = W * W;
     // rows are LOADED by the window's lanes together (W >= 32): 16-byte chunks, chunk ci = row * P16 + part, lane t of the
     // window takes chunks t, t + LW, ... -- consecutive lanes read consecutive pieces of a row
@@ -198,6 +204,17 @@ __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel
     if (m == -2 && r0 < 8 && writer) out[r0] = r0 == 6 ? 0.0 : 1.0;      // zero-mean window (B:513: NaN map): finalize_kernel looks at the flag [7] only
     const bool go = m >= 0;
     if (__ballot(go) == 0ull) return;                        // (128x128: the same decision in both wavefronts of the window)
+    // A REGULAR arg-max: none of the clamps below fires and m +- 1 stay in m's map row (fftshift column 1 ... W - 2).  Then
+    // the four neighbours are rotations dx +- 1 of m's frame-b row (one span of NDW + 2 dwords covers all three) and the rows
+    // dy +- 1, which are m's span against frame a moved by one row: S(dy +- 1, dx) = sum_y a[y -+ 1] . span_m[y].  A
+    // wavefront takes that path when every window of it that goes is regular (32x32: two windows; 128x128: both wavefronts
+    // see the same m), otherwise every cell goes through the per-cell path below.
+    bool nb_fast = false;
+    if constexpr (G::COOP) {
+        const bool regular = (m & (W - 1)) >= 1 && (m & (W - 1)) <= W - 2 && m + 1 < KD - 1 && m - 1 > 0 && m + W < KD - 1 &&
+                             m - W > 0;
+        nb_fast = __ballot(go && !regular) == 0ull;
+    }
 
     // ---- the cells: lane j of the window holds flat index q_j (fftshift layout) or -1
     int q = -1;
@@ -229,6 +246,7 @@ __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel
         if constexpr (G::PARTS == 2) __syncthreads();   // (128x128: both wavefronts of the window)
         else wave_sync();
     };
+    uint32_t au[NDW], ad[NDW];                               // frame-a rows (row - 1), (row + 1): the shared neighbourhood only
     if constexpr (G::COOP) {
         // frame a: chunks -> hand-over tile (pitch AP dwords: 16-byte reads of 16 lanes cover all banks) -> the lane's row
         uint4* const ta = reinterpret_cast<uint4*>(rows_b);
@@ -242,6 +260,15 @@ __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel
         for (int k = 0; k < NDW / 4; ++k) {
             const uint4 t = ta[row * (G::AP / 4) + k];
             a[4 * k] = t.x, a[4 * k + 1] = t.y, a[4 * k + 2] = t.z, a[4 * k + 3] = t.w;
+        }
+        if (nb_fast) {                                  // the rows above and below (circular) for the shared neighbourhood
+            const int ru = (row - 1) & (W - 1), rd = (row + 1) & (W - 1);
+#pragma unroll
+            for (int k = 0; k < NDW / 4; ++k) {
+                const uint4 t = ta[ru * (G::AP / 4) + k], s = ta[rd * (G::AP / 4) + k];
+                au[4 * k] = t.x, au[4 * k + 1] = t.y, au[4 * k + 2] = t.z, au[4 * k + 3] = t.w;
+                ad[4 * k] = s.x, ad[4 * k + 1] = s.y, ad[4 * k + 2] = s.z, ad[4 * k + 3] = s.w;
+            }
         }
         lds_sync();
         // frame b: every chunk twice into its parked row (odd pitch: single dwords)
@@ -268,9 +295,38 @@ __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel
     }
     lds_sync();                                         // the rows are parked
 
-    // ---- S at every requested cell
+    // ---- S at m and its four neighbours, shared (regular arg-max, see above): ONE span of NDW + 2 dwords from byte s =
+    //      (dx - 1) mod W of m's frame-b row, aligned to s once (u), then the rotations s / s + 1 / s + 2 (m - 1 / m / m + 1)
+    //      and m's span against the frame-a rows above and below (m + W / m - W)
+    if constexpr (G::COOP) {
+        if (nb_fast) {
+            const int mm = go ? m : KD / 2 + W / 2;     // (windows that do not go: any cell, discarded)
+            const int dy = mm / W - W / 2, s = (mm % W - W / 2 - 1) & (W - 1);
+            const int brow = (row + dy) & (W - 1);
+            uint32_t w[NDW + 2];
+            read_span<NDW + 2>(rows_b + brow * XP + (s >> 2), w);
+            // s = W - 1 reaches byte 2 W, the pad dword of the parked row (never written): that is the row's first dword
+            w[NDW + 1] = s == W - 1 ? w[1] : w[NDW + 1];
+            uint32_t u[NDW + 1];
+#pragma unroll
+            for (int i = 0; i <= NDW; ++i) u[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], (unsigned)(s & 3));
+            unsigned s_m = 0u, s_l = 0u, s_r = 0u, s_t = 0u, s_b = 0u;
+#pragma unroll
+            for (int i = 0; i < NDW; ++i) {
+                const uint32_t c = __builtin_amdgcn_alignbyte(u[i + 1], u[i], 1u);
+                s_r = __builtin_amdgcn_udot4(a[i], u[i], s_r, false);
+                s_m = __builtin_amdgcn_udot4(a[i], c, s_m, false);
+                s_l = __builtin_amdgcn_udot4(a[i], __builtin_amdgcn_alignbyte(u[i + 1], u[i], 2u), s_l, false);
+                s_t = __builtin_amdgcn_udot4(au[i], c, s_t, false);
+                s_b = __builtin_amdgcn_udot4(ad[i], c, s_b, false);
+            }
+            P[0] = go ? s_m : 0u, P[1] = go ? s_l : 0u, P[2] = go ? s_r : 0u, P[3] = go ? s_t : 0u, P[4] = go ? s_b : 0u;
+        }
+    }
+    // ---- S at every other requested cell (all of them when the wavefront does not take the shared neighbourhood)
     static_for<0, XCELLS>([&](auto cc) TPIV_LAMBDA_INLINE {
         constexpr int c = decltype(cc)::value;
+        if (c < 5 && nb_fast) return;                   // (done above)
         int qc = __builtin_amdgcn_readlane(q, c);
         bool any = qc >= 0;
         static_for<1, G::WPW>([&](auto wc) TPIV_LAMBDA_INLINE {          // (the other windows of the wavefront)
