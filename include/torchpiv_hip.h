@@ -222,6 +222,23 @@ int tpiv_ensemble_moments(const double* u_dev, const double* v_dev, int n, long 
 int tpiv_bmp_unpack(const uint8_t* raw_dev, const int64_t* desc_dev, const uint8_t* lut_dev, int n_files,
                     int H, int W, uint8_t* out_dev, void* stream);
 
+/* tpiv_bmp_unpack with the static background subtracted in the same pass: out = max(px, bg) - bg per pixel, where
+ * bg_dev [2, H, W] uint8 holds two backgrounds (frames a, frames b of a pair) and desc_dev[f][5] picks the one of file f
+ * (0: bg_dev[0], otherwise bg_dev[1]).  Bit-identical to tpiv_bmp_unpack followed by tpiv_subtract_background. */
+int tpiv_bmp_unpack_bg(const uint8_t* raw_dev, const int64_t* desc_dev, const uint8_t* lut_dev, int n_files,
+                       int H, int W, const uint8_t* bg_dev, uint8_t* out_dev, void* stream);
+
+/* ---- static background (ensemble minimum) --------------------------------------------- */
+
+/* acc_dev[p] = min(acc_dev[p], frames_dev[f][p]) over the n frames frames_dev [n, pixels] uint8: one call or several
+ * over parts of a recording give the per-pixel minimum of all of them (start from an acc of 255s). */
+int tpiv_frame_min(const uint8_t* frames_dev, int n, long long pixels, uint8_t* acc_dev, void* stream);
+
+/* out_dev[f][p] = max(frames_dev[f][p], bg_dev[p]) - bg_dev[p] (frame minus background, clamped at 0) for n frames
+ * [n, pixels] uint8.  out_dev may be frames_dev itself; other overlaps are not supported. */
+int tpiv_subtract_background(const uint8_t* frames_dev, int n, long long pixels, const uint8_t* bg_dev,
+                             uint8_t* out_dev, void* stream);
+
 /* Host side of the ingest (no GPU involved): reads n_files files into dst + i * slot_bytes (page-locked staging memory
  * of the caller, at most slot_bytes each) with up to n_threads native reader threads -- what PIVDataset.__getitem__
  * (B:129-144) does file by file with np.fromfile, here for a whole batch without the interpreter in the loop.

@@ -17,12 +17,18 @@ ap.add_argument("--noise", type=float, default=0.0)
 ap.add_argument("--width", type=int, default=0, help="frame width when it differs from --size (row-pitch experiments)")
 ap.add_argument("--precision", default="fast", choices=("fast", "f64", "reference", "exact"))
 ap.add_argument("--scale", type=float, default=2.0, help="multipass_scale (window size of pass p+1 = int(ws_p // scale))")
+ap.add_argument("--background", default="none", choices=("none", "min"),
+                help="min: subtract the per-pixel minimum of the batch's a / b frames first (static background removal)")
 a = ap.parse_args()
 H = a.size
 W = a.width or a.size
 A0, B0 = synth.make_batch(a.distinct, H, W, device="cuda", kind=a.kind, noise=a.noise)
 A = A0.repeat((a.batch + a.distinct - 1) // a.distinct, 1, 1)[:a.batch].contiguous()
 B = B0.repeat((a.batch + a.distinct - 1) // a.distinct, 1, 1)[:a.batch].contiguous()
+if a.background == "min":
+    A = engine.subtract_background(A, engine.frame_min(A))
+    B = engine.subtract_background(B, engine.frame_min(B))
+    print("background min: frames minus the per-pixel minimum of the batch")
 plan = engine.Plan(H, W, a.ws, a.ws // 2, n_pass=a.passes, mode=a.mode, pass_scale=a.scale, max_batch=a.batch, precision=a.precision)
 out = plan.run(A, B)
 torch.cuda.synchronize()

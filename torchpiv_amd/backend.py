@@ -325,6 +325,38 @@ def free_cuda_memory():
 # ----------------------------------------------------------------------------------------
 # the generator API (B:824-903)
 # ----------------------------------------------------------------------------------------
+def _background_arg(background, shape=None):
+    """The background= argument of OfflinePIV / ResidentPIV, checked: None, "min", or a pair of uint8 images [H, W] as
+    torch tensors (one image given for both frames of a pair, or a pair (bg_a, bg_b); numpy arrays or tensors).  shape:
+    the frame shape the images must have (None: not known, e.g. an empty folder).  Anything else raises ValueError."""
+    if background is None:
+        return None
+    if isinstance(background, str):
+        if background != "min":
+            raise ValueError(f"background: None, 'min', a uint8 image [H, W] or a pair of them, got {background!r}")
+        return "min"
+    imgs = list(background) if isinstance(background, (tuple, list)) else [background, background]
+    if len(imgs) != 2:
+        raise ValueError(f"background: a pair (bg_a, bg_b) holds two images, got {len(imgs)}")
+    out = []
+    for im in imgs:
+        if isinstance(im, np.ndarray):
+            if im.dtype != np.uint8:
+                raise ValueError(f"background: uint8 images, got {im.dtype}")
+            im = torch.from_numpy(np.ascontiguousarray(im))
+        elif not isinstance(im, torch.Tensor):
+            raise ValueError(f"background: a uint8 numpy array or tensor [H, W], got {type(im).__name__}")
+        elif im.dtype != torch.uint8:
+            raise ValueError(f"background: uint8 images, got {im.dtype}")
+        if im.dim() != 2:
+            raise ValueError(f"background: images [H, W], got shape {tuple(im.shape)}")
+        out.append(im)
+    if out[0].shape != out[1].shape or (shape is not None and tuple(out[0].shape) != tuple(shape)):
+        raise ValueError(f"background: images of the frame shape {None if shape is None else tuple(shape)}, got "
+                         f"{tuple(out[0].shape)} and {tuple(out[1].shape)}")
+    return out
+
+
 class OfflinePIV:
     """for x, y, u, v in OfflinePIV(folder, device, file_fmt, wind_size, overlap, ...)(): ...
 
@@ -339,7 +371,7 @@ class OfflinePIV:
     def __init__(self, folder: str, device: str, file_fmt: str, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
-                 validation_ratio: float = 1.2, validation_window: int = 3) -> None:
+                 validation_ratio: float = 1.2, validation_window: int = 3, background=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -349,6 +381,9 @@ class OfflinePIV:
         # windows).  "fast": pass 1 in float32 too (~1e-6 px from the float64 pass 1, about 1.9x the rate).
         # validation_ratio / validation_window (extensions): the constants the reference hides inside
         # correlation_to_displacement (B:364-365: val_ratio=1.2, validation_window=3), same defaults.
+        # background (extension): static background removal -- every frame enters the passes as max(f, bg) - bg.
+        # "min": bg_a / bg_b = the per-pixel minimum over the a / b frames of every pair of the dataset (compute_background,
+        # computed on first use); a uint8 image [H, W] (both frames) or a pair (bg_a, bg_b): given.  None: frames as read.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         self._precision = precision
@@ -365,9 +400,13 @@ class OfflinePIV:
         self._mode = multipass_mode
         self._plan = None
         self._single_plans = {}          # plans of the one-pair path, per frame shape
+        self._bg_arg = _background_arg(background)
+        self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
         self.reset_stats()
         if not self:
             return
+        if self._bg_arg is not None and self._bg_arg != "min":
+            _background_arg(background, self.frame_shape())
         _require_gpu(self._device)
 
     def __len__(self) -> int:
@@ -392,6 +431,108 @@ class OfflinePIV:
                                      val_ratio=self._val_ratio, val_win=self._val_win,
                                      device=self._device, precision=self._precision)
         return self._plan
+
+    def _background(self, shape, batch_size=None):
+        """The background the frames of shape (H, W) lose (uint8 [2, H, W] on the device: bg_a, bg_b), None without one.
+        "min" runs compute_background() here, once per object."""
+        if self._bg_arg is None:
+            return None
+        if self._bg is None:
+            if self._bg_arg == "min":
+                self._set_background(*self.compute_background(batch_size=batch_size))
+            else:
+                self._set_background(*self._bg_arg)
+        if tuple(self._bg.shape[1:]) != tuple(shape):
+            raise ValueError(f"background of shape {tuple(self._bg.shape[1:])} for frames of shape {tuple(shape)}")
+        return self._bg
+
+    def _set_background(self, bg_a, bg_b):
+        self._bg = torch.stack([bg_a.to(self._device), bg_b.to(self._device)]).contiguous()
+
+    bg_batch = 32            # pairs per upload of compute_background (default)
+
+    def compute_background(self, indices=None, batch_size=None):
+        """(bg_a, bg_b): the per-pixel minimum over the a frames and over the b frames of the pairs `indices` (None: every
+        pair of the dataset) as uint8 [H, W] tensors on the device -- what background="min" subtracts.  Pairs that cannot
+        be decoded or whose frame shape differs from the dataset's (frame_shape()) are left out; with none left both
+        images are 255 everywhere (the identity of the minimum: a rank's empty shard).  The files go through the native
+        read-ahead ring and the device unpack, like batched() (whose staging buffers they share when batch_size and the
+        file size agree), and each batch is folded in with tpiv_frame_min."""
+        from .io import ReadAhead, parse_bmp_headers, stage_raw
+        shape = self.frame_shape()
+        if shape is None:
+            raise ValueError("compute_background: the dataset holds no decodable pair")
+        H, W = shape
+        dev = self._device
+        acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=dev)
+        idx = list(range(len(self._dataset))) if indices is None else list(indices)
+        if not idx:
+            return acc[0], acc[1]
+        import os as _os
+        bs = int(batch_size or self.bg_batch)
+        pairs = self._dataset.img_pairs
+        paths = []
+        for i in idx:
+            paths += [pairs[i][0], pairs[i][-1]]
+        sizes = [H * W] + [_os.path.getsize(p_) for p_ in paths[:2] if _os.path.exists(p_)]
+        cap = (max(sizes) + 4095) // 4096 * 4096
+        prev = getattr(self, "_reader", None)            # an abandoned batched() run's reader still fills the buffers
+        if prev is not None:
+            prev.close()
+            self._reader = None
+            torch.cuda.synchronize(dev)
+        if getattr(self, "_stage_key", None) != (bs, cap):
+            self._stage = [torch.empty(2 * bs, cap, dtype=torch.uint8).pin_memory() for _ in range(3)]
+            self._stage_key = (bs, cap)
+        stage = self._stage
+        if getattr(self, "_raw_dev_key", None) != (bs, cap, str(dev)):
+            self._raw_dev = [torch.empty(2 * bs, cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self._raw_dev_key = (bs, cap, str(dev))
+        raw_d = self._raw_dev[0]
+        cur = torch.cuda.current_stream(dev)
+        rd = ReadAhead(paths, 2 * bs, [t.data_ptr() for t in stage], cap, threads=self.read_threads,
+                       read=str(paths[0]).lower().endswith(".bmp"))
+        decoders = None
+        try:
+            for s0 in range(0, len(idx), bs):
+                got = rd.next()
+                if got is None:
+                    break
+                buf, sizes = got
+                raw = stage[buf].numpy()
+                lays = parse_bmp_headers(raw[:len(sizes)], sizes, H, W)
+                rest = [j for j, lay in enumerate(lays) if lay is None]
+                if rest:
+                    if decoders is None:
+                        from concurrent.futures import ThreadPoolExecutor
+                        decoders = ThreadPoolExecutor(max_workers=self.read_threads)
+                    for j, lay in zip(rest, decoders.map(lambda j: stage_raw(paths[2 * s0 + j], raw[j], H, W), rest)):
+                        lays[j] = lay
+                desc_a, desc_b, luts_a, luts_b = [], [], [], []
+                for k in range(len(sizes) // 2):
+                    la, lb = lays[2 * k], lays[2 * k + 1]
+                    if la is None or lb is None:            # left out, as batched() leaves it to the one-pair path
+                        continue
+                    desc_a.append([2 * k * cap, la[0], la[1], la[2], la[3], 0])
+                    desc_b.append([(2 * k + 1) * cap, lb[0], lb[1], lb[2], lb[3], 1])
+                    luts_a.append(la[4])
+                    luts_b.append(lb[4])
+                if desc_a:
+                    n = len(desc_a)
+                    raw_d[:len(sizes)].copy_(stage[buf][:len(sizes)], non_blocking=True)
+                    desc_d = torch.tensor(desc_a + desc_b, dtype=torch.int64).to(dev, non_blocking=True)
+                    lut_d = torch.from_numpy(np.stack(luts_a + luts_b)).to(dev, non_blocking=True)
+                    frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W)      # [2n, H, W]: a_0..a_n-1, b_0..b_n-1
+                    engine.frame_min(frames[:n], acc[0])
+                    engine.frame_min(frames[n:], acc[1])
+                    cur.synchronize()           # the upload is through: the readers may refill the staging buffer
+                rd.release()
+        finally:
+            rd.close()
+            torch.cuda.synchronize(dev)
+            if decoders is not None:
+                decoders.shutdown(wait=False)
+        return acc[0], acc[1]
 
     def reset_stats(self):
         """Counters of the post-validation: pairs seen, dropped for 'no invalid vector' / 'too many
@@ -682,6 +823,10 @@ class OfflinePIV:
         a = a.to(self._device, non_blocking=True)
         b = b.to(self._device, non_blocking=True)
         shape = (int(a.shape[-2]), int(a.shape[-1]))
+        bg = self._background(shape)
+        if bg is not None:
+            a = engine.subtract_background(a, bg[0])
+            b = engine.subtract_background(b, bg[1])
         plans = self._single_plans
         plan = plans.get(shape)
         if plan is None:
@@ -734,6 +879,7 @@ class OfflinePIV:
         if first is None:
             return
         H, W = first[1]
+        bg = self._background((H, W), batch_size)     # (background="min": the prepass over the files runs here, once)
         plan = self._get_plan(H, W, max_batch=batch_size)
         import os as _os
         # one staging slot per file: the largest of the first pair's files (a run's files share one format)
@@ -826,7 +972,7 @@ class OfflinePIV:
                         # gives another shape its own plan
                         continue
                     desc_a.append([2 * k * cap, la[0], la[1], la[2], la[3], 0])
-                    desc_b.append([(2 * k + 1) * cap, lb[0], lb[1], lb[2], lb[3], 0])
+                    desc_b.append([(2 * k + 1) * cap, lb[0], lb[1], lb[2], lb[3], 1])      # [5]: background slot
                     lut_a.append(la[4])
                     lut_b.append(lb[4])
                     chunk.append(i)
@@ -845,7 +991,8 @@ class OfflinePIV:
                     desc_d = torch.tensor(desc_a + desc_b, dtype=torch.int64).to(dev, non_blocking=True)
                     lut_d = torch.from_numpy(np.stack(lut_a + lut_b)).to(dev, non_blocking=True)
                     cur.wait_event(up)
-                    frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W)      # [2n, H, W]: a_0..a_n-1, b_0..b_n-1
+                    # [2n, H, W]: a_0..a_n-1, b_0..b_n-1 (with a background: minus bg_a / bg_b, in the same kernel)
+                    frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=bg)
                     consumed[dbuf] = torch.cuda.Event()
                     consumed[dbuf].record(cur)
                     u, v, inv = plan.run(frames[:n], frames[n:])
@@ -875,12 +1022,15 @@ class ResidentPIV(OfflinePIV):
     def __init__(self, frames_a: torch.Tensor, frames_b: torch.Tensor, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
-                 validation_window: int = 3) -> None:
+                 validation_window: int = 3, background=None) -> None:
         if frames_a.shape != frames_b.shape or frames_a.dim() != 3 or frames_a.dtype != torch.uint8 \
                 or frames_b.dtype != torch.uint8:
             raise ValueError("ResidentPIV: two uint8 tensors [n, H, W] of one shape")
         if precision not in PRECISIONS:
             raise KeyError(precision)
+        self._bg_arg = _background_arg(background, frames_a.shape[1:])
+        self._bg = None
+        self._bg_frames = None           # the frames of a launch minus the background: uint8 [2, batch, H, W], reused
         self._precision = precision
         self._val_ratio, self._val_win = float(validation_ratio), int(validation_window)
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
@@ -896,6 +1046,23 @@ class ResidentPIV(OfflinePIV):
     def frame_shape(self):
         return tuple(self._A.shape[1:]) if len(self) else None
 
+    def compute_background(self, indices=None, batch_size=None):
+        """(bg_a, bg_b): the per-pixel minimum of the resident a frames and of the b frames (of the pairs `indices`;
+        None: all), uint8 [H, W] on the device (tpiv_frame_min; 255 everywhere for no pair).  batch_size: pairs gathered
+        at a time for `indices` (default bg_batch)."""
+        H, W = self._A.shape[1:]
+        acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=self._device)
+        if indices is None:
+            engine.frame_min(self._A, acc[0])
+            engine.frame_min(self._B, acc[1])
+            return acc[0], acc[1]
+        idx, bs = list(indices), int(batch_size or self.bg_batch)
+        for s in range(0, len(idx), bs):                     # gathered in bounded chunks
+            sel = torch.tensor(idx[s:s + bs], dtype=torch.int64, device=self._device)
+            engine.frame_min(self._A.index_select(0, sel), acc[0])
+            engine.frame_min(self._B.index_select(0, sel), acc[1])
+        return acc[0], acc[1]
+
     # launches in flight before a batch's census is read.  Two: the copies of a batch's results run on a stream of their own,
     # as kernels (rocprofv3 shows __amd_rocclr_copyBuffer), and the passes of the NEXT batch leave them no registers on any CU
     # until they end -- with one launch in flight the host got a batch's census when the GPU had just run dry (round 5: GPU
@@ -907,6 +1074,11 @@ class ResidentPIV(OfflinePIV):
         if not idx:
             return
         H, W = self._A.shape[1:]
+        bg = self._background((H, W))
+        if bg is not None:
+            buf = self._bg_frames
+            if buf is None or buf.shape[1] < batch_size or buf.device != bg.device:
+                buf = self._bg_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=bg.device)
         plan = self._get_plan(H, W, max_batch=batch_size)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
@@ -927,6 +1099,11 @@ class ResidentPIV(OfflinePIV):
             else:
                 sel = torch.tensor(chunk, device=self._device)
                 A, B = self._A.index_select(0, sel), self._B.index_select(0, sel)
+            if bg is not None:
+                # into the reused buffer (the caller's frames are never written); stream order keeps a launch's passes
+                # ahead of the next launch's subtraction into the same memory
+                A = engine.subtract_background(A, bg[0], out=buf[0, :len(chunk)])
+                B = engine.subtract_background(B, bg[1], out=buf[1, :len(chunk)])
             u, v, inv = plan.run(A, B)
             # host work of the previous batches overlaps this batch's kernels
             yield from emit(pipe.push(chunk, self._post_submit(u, v, inv)))

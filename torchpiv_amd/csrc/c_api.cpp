@@ -857,6 +857,35 @@ int tpiv_bmp_unpack(const uint8_t* raw, const int64_t* desc, const uint8_t* lut,
     return TPIV_OK;
 }
 
+int tpiv_bmp_unpack_bg(const uint8_t* raw, const int64_t* desc, const uint8_t* lut, int n_files, int H, int W,
+                       const uint8_t* bg, uint8_t* out, void* stream) {
+    if (n_files < 0 || H <= 0 || W <= 0) return fail(TPIV_EINVAL, "tpiv_bmp_unpack_bg: bad shape");
+    if (n_files == 0) return TPIV_OK;
+    if (!raw || !desc || !lut || !bg || !out) return fail(TPIV_EINVAL, "tpiv_bmp_unpack_bg: null pointer");
+    HIP_TRY(tpiv::launch_bmp_unpack_bg(raw, reinterpret_cast<const long long*>(desc), lut, n_files, H, W, bg, out,
+                                       (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_frame_min(const uint8_t* frames, int n, long long pixels, uint8_t* acc, void* stream) {
+    if (n < 0 || pixels <= 0) return fail(TPIV_EINVAL, "tpiv_frame_min: bad shape");
+    if (n == 0) return TPIV_OK;
+    if (!frames || !acc) return fail(TPIV_EINVAL, "tpiv_frame_min: null pointer");
+    HIP_TRY(tpiv::launch_frame_min(frames, n, pixels, acc, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_subtract_background(const uint8_t* frames, int n, long long pixels, const uint8_t* bg, uint8_t* out,
+                             void* stream) {
+    if (n < 0 || pixels <= 0) return fail(TPIV_EINVAL, "tpiv_subtract_background: bad shape");
+    if (n == 0) return TPIV_OK;
+    if (!frames || !bg || !out) return fail(TPIV_EINVAL, "tpiv_subtract_background: null pointer");
+    if (out != frames && out < frames + (size_t)n * pixels && frames < out + (size_t)n * pixels)
+        return fail(TPIV_EINVAL, "tpiv_subtract_background: out overlaps frames without being frames");
+    HIP_TRY(tpiv::launch_subtract_background(frames, n, pixels, bg, out, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
 namespace {
 // One file into a slot of at most slot_bytes: bytes read, or -1 (cannot open / not a regular file / too big / short read).
 int64_t read_one_file(const char* path, uint8_t* out, size_t slot_bytes) {

@@ -14,10 +14,14 @@ namespace tpiv {
 
 namespace {
 
-// desc[f] = {file offset in raw, pixel-data offset in the file, row stride, bytes per pixel, flip, unused}
+// desc[f] = {file offset in raw, pixel-data offset in the file, row stride, bytes per pixel, flip, background slot}.
+// kBackground: the unpacked pixels leave as max(px, bg) - bg, with bg = bg2[desc[f][5] != 0] (background.hip: the
+// ensemble-minimum subtraction, fused here so that the file path pays no extra pass over the frames); without it the
+// slot is not read.
+template <bool kBackground>
 __global__ __launch_bounds__(256) void bmp_unpack_kernel(const uint8_t* __restrict__ raw, const long long* __restrict__ desc,
                                                          const uint8_t* __restrict__ lut, int H, int W,
-                                                         uint8_t* __restrict__ out) {
+                                                         const uint8_t* __restrict__ bg2, uint8_t* __restrict__ out) {
     const int f = blockIdx.z;
     const long long* d = desc + (size_t)f * 6;
     const long long base = d[0] + d[1];
@@ -51,6 +55,15 @@ __global__ __launch_bounds__(256) void bmp_unpack_kernel(const uint8_t* __restri
             } else px[k] = 0;
         }
     }
+    if constexpr (kBackground) {
+        const uint8_t* __restrict__ bgp = bg2 + ((size_t)(d[5] != 0) * H + y) * W + x4;
+        uint8_t b[4];
+        if (n == 4 && (W & 3) == 0) __builtin_memcpy(b, bgp, 4);
+        else
+            for (int k = 0; k < 4; ++k) b[k] = k < n ? bgp[k] : 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) px[k] = px[k] > b[k] ? (uint8_t)(px[k] - b[k]) : (uint8_t)0;
+    }
     if (n == 4 && (W & 3) == 0) {
         uint32_t w;
         __builtin_memcpy(&w, px, 4);
@@ -68,7 +81,17 @@ hipError_t launch_bmp_unpack(const uint8_t* raw, const long long* desc, const ui
     const int tx = 256;
     dim3 grid(((W + 3) / 4 + tx - 1) / tx, H, n_files);
     if (grid.y > 65535 || grid.z > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bmp_unpack_kernel, grid, dim3(tx), 0, stream, raw, desc, lut, H, W, out);
+    hipLaunchKernelGGL(bmp_unpack_kernel<false>, grid, dim3(tx), 0, stream, raw, desc, lut, H, W, nullptr, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_bmp_unpack_bg(const uint8_t* raw, const long long* desc, const uint8_t* lut, int n_files, int H, int W,
+                                const uint8_t* bg2, uint8_t* out, hipStream_t stream) {
+    if (n_files <= 0) return hipSuccess;
+    const int tx = 256;
+    dim3 grid(((W + 3) / 4 + tx - 1) / tx, H, n_files);
+    if (grid.y > 65535 || grid.z > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bmp_unpack_kernel<true>, grid, dim3(tx), 0, stream, raw, desc, lut, H, W, bg2, out);
     return hipGetLastError();
 }
 

@@ -163,6 +163,13 @@ hipError_t launch_ensemble_moments(const double* U, const double* V, int n, long
 // image ingest (ingest.hip): raw uncompressed BMP files -> uint8 frames
 hipError_t launch_bmp_unpack(const uint8_t* raw, const long long* desc, const uint8_t* lut, int n_files, int H, int W,
                              uint8_t* out, hipStream_t stream);
+// the same with the ensemble-minimum background subtracted (bg2 [2, H, W]: desc[f][5] picks the slot)
+hipError_t launch_bmp_unpack_bg(const uint8_t* raw, const long long* desc, const uint8_t* lut, int n_files, int H, int W,
+                                const uint8_t* bg2, uint8_t* out, hipStream_t stream);
+// static background (background.hip): acc = min(acc, frames[0..n)) per pixel; out = max(frames, bg) - bg (out may be frames)
+hipError_t launch_frame_min(const uint8_t* frames, int n, long long pixels, uint8_t* acc, hipStream_t stream);
+hipError_t launch_subtract_background(const uint8_t* frames, int n, long long pixels, const uint8_t* bg, uint8_t* out,
+                                      hipStream_t stream);
 
 hipError_t launch_xcorr(const PassParams& p, int mode, int n_cu, hipStream_t stream);
 // bytes of the tile kernels' work-queue counters (8 x one 64-byte line), and of the slow-item list header behind them

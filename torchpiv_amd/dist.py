@@ -148,6 +148,37 @@ def gather_fields(ids: torch.Tensor, fields: torch.Tensor, dst: int = 0, group=N
     return all_i[order].to(out_dev), all_f[order].to(out_dev)
 
 
+def reduce_background(bg, group=None):
+    """Elementwise minimum of the ranks' background images -- one all-reduce with ReduceOp.MIN, every rank gets the
+    result.  bg: a uint8 tensor [H, W] or a pair (bg_a, bg_b) of them (one collective for both); returned in the same
+    form, on the device it came from.  Single process: bg itself."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return bg
+    pair = isinstance(bg, (tuple, list))
+    t = torch.stack(list(bg)) if pair else bg[None]
+    if t.dtype != torch.uint8:
+        raise ValueError(f"reduce_background: uint8 images, got {t.dtype}")
+    out_dev = t.device
+    t = t.contiguous()
+    if dist.get_backend(group) == "gloo" and t.is_cuda:      # gloo moves host memory only
+        t = t.cpu()
+    dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
+    t = t.to(out_dev)
+    return tuple(t.unbind(0)) if pair else t[0]
+
+
+def shard_background(piv, indices, group=None):
+    """background="min" in a sharded run: every rank takes the minimum over the pairs of its own shard (one read of its
+    files), the ranks agree on the elementwise minimum (reduce_background) -- the background of the whole dataset, as a
+    single process computes it -- and piv subtracts that.  A no-op for other backgrounds, for a single process (piv then
+    computes it itself on first use) and once piv holds its background."""
+    if getattr(piv, "_bg_arg", None) != "min" or piv._bg is not None:
+        return
+    if not dist.is_initialized() or dist.get_world_size(group) == 1 or piv.frame_shape() is None:
+        return
+    piv._set_background(*reduce_background(piv.compute_background(indices), group))
+
+
 def run_sharded(piv, batch_size: int = 32, policy: str = "block", group=None):
     """Process an OfflinePIV dataset across all ranks.  Every rank runs its shard through
     piv.batched(); rank 0 returns (ids, x, y, uv[n, 2, R, S]) for the pairs that survived,
@@ -156,6 +187,7 @@ def run_sharded(piv, batch_size: int = 32, policy: str = "block", group=None):
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     mine = shard_indices(len(piv), rank, world, policy)
+    shard_background(piv, mine, group)
     ids, uv, xy = [], [], None
     # the finished fields stay where the last kernel left them: batched() hands out rows of the per-batch device stacks
     # (hole fills of the host stage scattered in), and the gather below reads device memory -- nothing goes host -> device

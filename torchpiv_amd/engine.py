@@ -263,10 +263,12 @@ def ensemble_moments(U, V):
     return tuple(out.unbind(0))
 
 
-def bmp_unpack(raw, desc, lut, H, W, out=None):
+def bmp_unpack(raw, desc, lut, H, W, out=None, background=None):
     """Device unpack of raw uncompressed BMP files (tpiv_bmp_unpack).  raw uint8 [bytes] on the GPU, desc
-    int64 [n, 6] and lut uint8 [n, 256] (device), see include/torchpiv_hip.h.  Returns uint8 [n, H, W]."""
-    _need_cuda(raw, desc, lut)
+    int64 [n, 6] and lut uint8 [n, 256] (device), see include/torchpiv_hip.h.  Returns uint8 [n, H, W].
+    background: uint8 [2, H, W] on the device -- every file leaves as max(px, bg) - bg with bg = background[desc[f][5] != 0],
+    in the same pass (tpiv_bmp_unpack_bg)."""
+    _need_cuda(raw, desc, lut, background)
     n = desc.shape[0]
     if desc.dtype != torch.int64 or lut.dtype != torch.uint8 or raw.dtype != torch.uint8 or tuple(desc.shape) != (n, 6) \
             or tuple(lut.shape) != (n, 256) or not (desc.is_contiguous() and lut.is_contiguous() and raw.is_contiguous()):
@@ -275,8 +277,55 @@ def bmp_unpack(raw, desc, lut, H, W, out=None):
         out = torch.empty(n, H, W, dtype=torch.uint8, device=raw.device)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous() or out.device != raw.device:
         raise ValueError("bmp_unpack: out must be a contiguous uint8 [n, H, W] tensor on the same device")
+    if background is not None and (background.dtype != torch.uint8 or tuple(background.shape) != (2, H, W)
+                                   or not background.is_contiguous() or background.device != raw.device):
+        raise ValueError("bmp_unpack: background must be a contiguous uint8 [2, H, W] tensor on the same device")
     with torch.cuda.device(raw.device):
-        check(lib.tpiv_bmp_unpack(raw.data_ptr(), desc.data_ptr(), lut.data_ptr(), n, H, W, out.data_ptr(), _stream()))
+        if background is None:
+            check(lib.tpiv_bmp_unpack(raw.data_ptr(), desc.data_ptr(), lut.data_ptr(), n, H, W, out.data_ptr(), _stream()))
+        else:
+            check(lib.tpiv_bmp_unpack_bg(raw.data_ptr(), desc.data_ptr(), lut.data_ptr(), n, H, W, background.data_ptr(),
+                                         out.data_ptr(), _stream()))
+    return out
+
+
+def _images(frames, name):
+    """uint8 frames [n, H, W] or [H, W] on the device, contiguous -> (frames [n, H, W], H, W)."""
+    _need_cuda(frames)
+    if frames.dtype != torch.uint8 or frames.dim() not in (2, 3) or not frames.is_contiguous():
+        raise ValueError(f"{name}: frames must be a contiguous uint8 tensor [n, H, W] or [H, W]")
+    f3 = frames[None] if frames.dim() == 2 else frames
+    return f3, int(f3.shape[1]), int(f3.shape[2])
+
+
+def frame_min(frames, acc=None):
+    """Per-pixel minimum of uint8 frames [n, H, W] on the device, folded into acc uint8 [H, W] (updated in place and
+    returned; None: a fresh one, i.e. the minimum of these frames alone).  Calls over parts of a recording compose:
+    frame_min(B, frame_min(A)) == frame_min(cat(A, B)) (tpiv_frame_min)."""
+    f, H, W = _images(frames, "frame_min")
+    if acc is None:
+        acc = torch.full((H, W), 255, dtype=torch.uint8, device=f.device)
+    elif acc.dtype != torch.uint8 or tuple(acc.shape) != (H, W) or not acc.is_contiguous() or acc.device != f.device:
+        raise ValueError("frame_min: acc must be a contiguous uint8 [H, W] tensor on the frames' device")
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_frame_min(f.data_ptr(), f.shape[0], H * W, acc.data_ptr(), _stream()))
+    return acc
+
+
+def subtract_background(frames, bg, out=None):
+    """max(frames, bg) - bg (frame minus background, clamped at 0) for uint8 frames [n, H, W] or [H, W] on the device
+    and a background bg uint8 [H, W].  out: a tensor of the frames' shape to write into -- frames itself (in place) or
+    memory that does not overlap them; None: a fresh one (tpiv_subtract_background)."""
+    f, H, W = _images(frames, "subtract_background")
+    _need_cuda(bg, out)
+    if bg.dtype != torch.uint8 or tuple(bg.shape) != (H, W) or not bg.is_contiguous() or bg.device != f.device:
+        raise ValueError("subtract_background: bg must be a contiguous uint8 [H, W] tensor on the frames' device")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or not out.is_contiguous() or out.device != f.device:
+        raise ValueError("subtract_background: out must be a contiguous uint8 tensor of the frames' shape and device")
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_subtract_background(f.data_ptr(), f.shape[0], H * W, bg.data_ptr(), out.data_ptr(), _stream()))
     return out
 
 

@@ -236,16 +236,18 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
                multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.0, multipass_scale: float = 2.0,
                folder_mode: str = "pairs", save_opt: str = "Dont save", save_dir: str = "Out",
                batch_size: int = 32, on_pair=None, distributed: bool = False, stats_on_device: bool = True,
-               precision: str = "exact", streaming_stats: bool = False):
+               precision: str = "exact", streaming_stats: bool = False, background=None):
     """Process a folder like PIVWorker.run.  save_opt: "Dont save" | "Save all binary" |
     "Save all text" | "Save statistics" (anything but "Dont save" also writes the statistics table).
     streaming_stats: running accumulators instead of the stacked fields (EnsembleStats(streaming=True): O(1) memory in
     the number of pairs, one 6-plane gather between ranks; moments to rounding instead of bit for bit).
+    background: static background removal of OfflinePIV (None, "min", an image or a pair of images); with
+    distributed=True, "min" is the minimum over the whole dataset, each rank reading only its own shard.
     Returns (table, n_pairs_done); with distributed=True every rank processes its shard of the
     pairs and rank 0 returns the table of the whole ensemble (other ranks: (None, n_local))."""
     piv = OfflinePIV(folder, device, file_fmt, wind_size, overlap, multipass=multipass,
                      multipass_mode=multipass_mode, dt=dt, scale=scale, multipass_scale=multipass_scale,
-                     folder_mode=folder_mode, precision=precision)
+                     folder_mode=folder_mode, precision=precision, background=background)
     if len(piv) == 0:
         return None, 0
     rank, world = 0, 1
@@ -260,6 +262,7 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
     stats = EnsembleStats(streaming=streaming_stats)
     if distributed and world > 1:
         piv.auto_host_config()           # reader threads / fill workers from this rank's share of the node's cores
+        pdist.shard_background(piv, indices)
     x = y = None
     done = 0
     for i, xx, yy, u, v in piv.batched(batch_size, indices=indices):
