@@ -54,7 +54,9 @@ SHIFT_SIZES = range(2, 257)                                              # shift
 PASS1_SIZES = range(8, 129)                                              # "fast" first pass
 # Odd sizes are in the dispatch space but not in the map check: the generic kernel reproduces the reference's ws x (ws - 1)
 # irfft2 map for them and writes no debug map (xcorr_generic.hip: `!odd`).  Their kernel, xcorr_generic_kernel<mode, float>,
-# is the one of the even sizes without a two-factor split, which the case table covers (44, 128).
+# is the one of the even sizes without a two-factor split, which the case table covers (44, 128).  Their FIRST pass (the
+# float64 generic kernel, at every precision but "fast") is checked at the field level against a longdouble map in
+# tests/test_gpu_f64_pass1.py.
 ODD_EXCLUDED = "odd window sizes: no debug map (xcorr_generic.hip `!odd`); their kernel is covered at even sizes"
 EXCUSE_CAP = 0.02          # share of a case's non-constant windows that may be excused by a decision inside the band
 

@@ -662,3 +662,33 @@ _ZkernelB:
     assert len(C.check(bad)[0]) == 1 and C.check(good) == ([], 2)
     assert C.main("xcorr_f64") == 0
     assert C.main("xcorr_exact") == 0          # the refinement kernel's single ds_read_b32 spans
+
+
+def test_per_half_copies_agree_on_their_barriers():
+    """xcorr_f64_split_kernel<64> and xcorr_f64_list_kernel<64> instantiate the whole window loop once per line half behind
+    one wave-uniform branch (TPIV_F64_PER_HALF, xcorr_f64.hip); the two wavefronts of a workgroup meet at workgroup
+    barriers, so both copies must hold the same number of s_barrier per window.  tools/check_lds_inflight.py counts them
+    in the device assembly: first on two crafted snippets, then on the real unit.  The in-flight walk must also see both
+    copies: per kernel, at least twice the hand-issued reads of the one-loop build (-DTPIV_F64_PER_HALF=0).
+    (xcorr_big128_cand_kernel under TPIV_BIG_PER_PAR is not walked: that switch is off in the shipped build, and its two
+    copies sit behind a branch inside the kernel's prologue code rather than at its top, which this walk does not model.)"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_lds_inflight as C
+
+    def snippet(second_copy_barriers):
+        loop = lambda tag, nb: (f".LBB0_{tag}:\n" + "\ts_barrier\n" * nb + f"\tv_add_f64 v[0:1], v[2:3], v[4:5]\n"
+                                f"\ts_cbranch_vccz .LBB0_{tag}\n")
+        return ("_ZkernelH:\n\ts_cmp_lt_u32 s0, 64\n\ts_cbranch_scc0 .LBB0_9\n" + loop(1, 3) + "\ts_branch .LBB0_20\n.LBB0_9:\n"
+                + loop(10, second_copy_barriers) + ".LBB0_20:\n\ts_endpgm\n")
+    assert C.half_barriers(snippet(3).splitlines()) == [3, 3]
+    assert C.half_barriers(snippet(2).splitlines()) == [3, 2]
+    assert C.half_barriers("_ZkernelN:\n\ts_barrier\n\ts_endpgm\n".splitlines()) is None
+    text = C.compile_asm("xcorr_f64")
+    rep = C.per_half_report(text)
+    assert len(rep) == 2 and all(any(t in k for k in rep) for t in C.PER_HALF_KERNELS), list(rep)
+    for k, c in rep.items():
+        assert c is not None and c[0] == c[1] and c[0] >= 7, (k, c)        # (seven per window, one more where val_win > 4)
+    one = C.reads_by_kernel(C.compile_asm("xcorr_f64", ["-DTPIV_F64_PER_HALF=0"]))
+    two = C.reads_by_kernel(text)
+    for k in rep:
+        assert two[k][1] >= 2 * one[k][1] > 0, (k, two[k][1], one[k][1])

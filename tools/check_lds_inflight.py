@@ -10,6 +10,15 @@ the translation unit to assembly and walks every kernel: LDS operations are kept
 is reported.
 
     python tools/check_lds_inflight.py [xcorr_f64]      -> exit code 1 and the offending lines if the constraint is broken
+
+Second check (half_barriers): the 64 x 64 float64 kernels instantiate their whole window loop once per line half behind ONE
+wave-uniform branch at the top (TPIV_F64_PER_HALF, xcorr_f64.hip).  The two wavefronts of a workgroup then run DIFFERENT
+code and meet at workgroup barriers, so both copies must execute the same number of s_barrier per window or the workgroup
+hangs.  The walk splits the kernel at its first scalar-condition branch -- copy 0 up to the branch's target, copy 1 from
+there to s_endpgm --, takes the widest backward-branch span of each copy as its window loop and counts the s_barrier
+INSTRUCTIONS in it.  That is a static count: a barrier inside a conditional block (the val_win > 4 zone path) counts as if
+always executed, one inside an inner loop counts once.  Equal static counts are necessary for equal executed counts, not
+sufficient; what the check catches is a copy that gained or lost a barrier instruction.
 """
 import os
 import re
@@ -81,13 +90,90 @@ def check(asm_text):
     return problems, n_reads
 
 
-def main(unit="xcorr_f64"):
+def kernel_bodies(asm_text):
+    """{mangled kernel name: its lines, up to and including s_endpgm's block}"""
+    out, name = {}, None
+    for line in asm_text.splitlines():
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            name = m.group(1)
+            out[name] = []
+        elif line.startswith("\t.end_amdhsa_kernel") or line.startswith(".Lfunc_end"):
+            name = None
+        if name is not None:
+            out[name].append(line)
+    return out
+
+
+def reads_by_kernel(asm_text):
+    """{kernel: (problems, hand-issued reads walked)} -- check() on each kernel's own lines."""
+    return {k: check("\n".join(v)) for k, v in kernel_bodies(asm_text).items()}
+
+
+PER_HALF_KERNELS = ("xcorr_f64_split_kernelILi64E", "xcorr_f64_list_kernelILi64E")      # TPIV_F64_PER_HALF instances (xcorr_f64.hip)
+
+
+def half_barriers(lines):
+    """-> [s_barrier per window-loop iteration in copy 0, in copy 1] of a kernel whose body is instantiated twice behind one
+    wave-uniform branch at the top, or None where the body has no such branch."""
+    ops = []                                  # (kind, argument): label / branch / barrier / end, in program order
+    for line in lines:
+        s = line.split(";")[0].strip()
+        if not s:
+            continue
+        m = re.match(r"^(\.LBB\w+):", s)
+        if m:
+            ops.append(("label", m.group(1)))
+            continue
+        op = s.split()[0]
+        if op == "s_barrier":
+            ops.append(("barrier", None))
+        elif op == "s_endpgm":
+            ops.append(("end", None))
+        elif op.startswith("s_cbranch") or op == "s_branch":
+            ops.append((op, s.split()[-1]))
+    first = next((i for i, (k, _) in enumerate(ops) if k.startswith("s_cbranch_scc")), None)
+    if first is None:
+        return None
+    where = {a: i for i, (k, a) in enumerate(ops) if k == "label"}
+    split = where.get(ops[first][1])
+    end = next((i for i, (k, _) in enumerate(ops) if k == "end"), len(ops))
+    if split is None or not first < split < end:
+        return None
+    counts = []
+    for lo, hi in ((first + 1, split), (split, end)):
+        spans = [(where[a], i) for i, (k, a) in enumerate(ops[:hi]) if i >= lo and k.startswith("s_") and k != "s_barrier"
+                 and a in where and lo <= where[a] < i]
+        if not spans:
+            counts.append(0)
+            continue
+        a, b = max(spans, key=lambda ab: ab[1] - ab[0])
+        counts.append(sum(1 for k, _ in ops[a:b] if k == "barrier"))
+    return counts
+
+
+def compile_asm(unit, extra=()):
     src = os.path.join(ROOT, "torchpiv_amd", "csrc", unit + ".hip")
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, unit + ".s")
-        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, src, "-o", out], check=True, stderr=subprocess.DEVNULL)
-        problems, n_reads = check(open(out).read())
-    print(f"{unit}: {n_reads} hand-issued LDS reads walked, {len(problems)} use(s) of a register whose read is still in flight")
+        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, src, "-o", out], check=True, stderr=subprocess.DEVNULL)
+        return open(out).read()
+
+
+def per_half_report(asm_text):
+    """{per-half kernel: [barriers in copy 0, in copy 1]} of the shipped per-half instances."""
+    return {k: half_barriers(v) for k, v in kernel_bodies(asm_text).items() if any(t in k for t in PER_HALF_KERNELS)}
+
+
+def main(unit="xcorr_f64"):
+    text = compile_asm(unit)
+    problems, n_reads = check(text)
+    for k, c in per_half_report(text).items():
+        print(f"{k}: s_barrier per window in the two per-half copies: {c}")
+        if c is None or c[0] != c[1] or c[0] == 0:
+            problems.append((k, 0, f"per-half copies disagree on their barriers: {c}"))
+    print(f"{unit}: {n_reads} hand-issued LDS reads walked, {len(problems)} problem(s): a register used while its read is in flight, "
+          f"or per-half copies with different barrier counts")
     for k, ln, text in problems[:20]:
         print(f"  {k} line {ln}: {text}")
     return 1 if problems else 0

@@ -17,6 +17,16 @@ struct cd {
 TPIV_HD cd cadd(cd a, cd b) { return cd{a.x + b.x, a.y + b.y}; }
 TPIV_HD cd csub(cd a, cd b) { return cd{a.x - b.x, a.y - b.y}; }
 
+// Test-only switch (tools/diag/libtorchpiv_hip_mutant_tw64.so, tests/test_gpu_f64_pass1.py): -DTPIV_MUTANT_TWIDDLE_F64=eps
+// scales the first non-trivial twiddle w_N^1 of every float64 codelet (and of the radix-2 steps of xcorr_f64_split.hpp, which
+// go through twmul_d too) by 1 + eps, and entry 1 of the double table of xcorr_generic_kernel by 1 + 100 eps.  Compile-time
+// constants only: the shipped library never defines it and is the same instruction for instruction.
+#ifdef TPIV_MUTANT_TWIDDLE_F64
+constexpr double MUT_TW64 = 1.0 + (double)(TPIV_MUTANT_TWIDDLE_F64);
+#else
+constexpr double MUT_TW64 = 1.0;
+#endif
+
 // a * exp(-DIR * 2*pi*i * K / N)   (DIR = +1 forward, -1 inverse)
 template <int K, int N, int DIR>
 TPIV_HD cd twmul_d(cd a) {
@@ -30,8 +40,9 @@ TPIV_HD cd twmul_d(cd a) {
     } else if constexpr (idx == 96) {
         return DIR > 0 ? cd{-a.y, a.x} : cd{a.y, -a.x};
     } else {
-        constexpr double c = TWD_COS[idx];
-        constexpr double s = DIR > 0 ? -TWD_SIN[idx] : TWD_SIN[idx];
+        constexpr double mut = (((K % N) + N) % N == 1) ? MUT_TW64 : 1.0;
+        constexpr double c = TWD_COS[idx] * mut;
+        constexpr double s = (DIR > 0 ? -TWD_SIN[idx] : TWD_SIN[idx]) * mut;
         return cd{a.x * c - a.y * s, a.x * s + a.y * c};
     }
 }

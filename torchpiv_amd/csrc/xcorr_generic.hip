@@ -323,6 +323,10 @@ __global__ __launch_bounds__(GT) void xcorr_generic_kernel(PassParams p, cplx<R>
         //  (n + 3) sqrt(n) u per transform, sits 20-50 x above what a 1e-4 error in it does to the map)
         tw[k] = cf{tw[k].x * (k == 1 ? (R)MUT_TW_PLAIN : (R)1), tw[k].y * (k == 1 ? (R)MUT_TW_PLAIN : (R)1)};     // (fft_inreg.hpp)
 #endif
+#ifdef TPIV_MUTANT_TWIDDLE_F64
+        // (tools/diag/libtorchpiv_hip_mutant_tw64.so: entry 1 of the double table x (1 + 100 eps), as the float32 mutant above)
+        if (F64 && k == 1) tw[k] = cf{tw[k].x * (R)(1.0 + 100.0 * (double)(TPIV_MUTANT_TWIDDLE_F64)), tw[k].y * (R)(1.0 + 100.0 * (double)(TPIV_MUTANT_TWIDDLE_F64))};
+#endif
         if (n > 1) {
             sincospi(2.0 * (double)k / (double)(n - 1), &s, &c);
             tw2[k] = cf{(R)c, (R)(-s)};
