@@ -14,8 +14,11 @@
 //     hand the rows over through LDS (CoopGeo below).
 //   * all 1-D FFTs (WS points) run per lane, entirely in registers (fft_inreg.hpp).
 //   * LDS is used only to transpose between the row and the column transform, in 32x33 (or
-//     WSx(WS+1)) tiles; a 64x64 tile is transposed as four 32x32 blocks after a
-//     v_permlane32_swap of the off-diagonal blocks.  The last transform is a c2r one: only spectrum
+//     WSx(WS+1)) tiles; a 64x64 tile is transposed as four 32x32 blocks, two at a time, without moving data between
+//     the lane halves: rows 32..63 negate their odd samples (their row spectrum comes out rotated by 32 bins), every lane
+//     reads the other half's tile in the second phase, and the rotation by 32 rows this leaves in columns 32..63 is a sign
+//     of the odd cross-spectrum bins (TPIV_NOSWAP64; 0 = v_permlane32_swap of the off-diagonal blocks first).
+//     The last transform is a c2r one: only spectrum
 //     columns 0..WS/2 cross the LDS the second time (transpose_half).  Kernels at three wavefronts per SIMD move one
 //     float plane at a time (8.4 KB per wavefront), the others complex elements (16.9 KB).
 //   * the k <-> -k partner of the packed spectrum is fetched with ds_bpermute (no LDS memory).  The planar 32x32 / 64x64
@@ -263,29 +266,60 @@ __device__ __forceinline__ void wave_sync() {
 // in:  lane (w, i) holds line i of its window, element k at in[POS(k)]  (POS = digit-reversed
 //      position when DIGITREV, else k)
 // out: lane (w, j) holds element j of every line: out[i] = element (line i, position j)
-template <int WS, bool DIGITREV, bool PLANAR>
+//
+// NOSWAP (64x64, first transposition; TPIV_NOSWAP64): no lane-half swaps.  The caller has negated the odd samples of the
+// lanes 32..63 in front of the row transform, so those lanes hold element (k + 32) mod 64 at in[POS(k)]: in BOTH lane halves
+// the low positions are the diagonal block of the 2x2 block matrix and the high positions the off-diagonal one.  Phase 1
+// writes the low positions into the lane half's own tile and every lane reads its own half's tile (the diagonal blocks;
+// the same instructions as phase 1 of the swapped form, which moves the blocks of rows 0..31 with them); phase 2 writes
+// the high positions (the off-diagonal blocks) into the lane half's own tile and every lane reads the OTHER half's tile
+// (same instruction, another base address).  Result: lanes 0..31 as above, lanes 32..63 hold their element rotated by 32
+// lines, out[i] = (line (i + 32) mod 64, position j) -- which the caller undoes as a sign of the odd bins of the next
+// transform (xcorr_tile_body, "Swap-free first transposition").
+#ifndef TPIV_NOSWAP64
+#define TPIV_NOSWAP64 1
+#endif
+// Timing experiment only (wrong results), the ceiling of what the swap-free form can give: -DTPIV_EXP_NOSWAP_CEIL builds the
+// SWAPPED form of the first transposition with its swaps left out; it turns the swap-free form (input signs, two_odd) off
+// whatever TPIV_NOSWAP64 says and leaves a second transposition through transpose_tile (TPIV_C2R64=0) alone.
+#ifdef TPIV_EXP_NOSWAP_CEIL
+constexpr bool EXP_NOSWAP_CEIL = true;
+#else
+constexpr bool EXP_NOSWAP_CEIL = false;
+#endif
+// FORM: 0 = lane-half swaps first, 1 = NOSWAP, 2 = the timing experiment
+template <int WS, bool DIGITREV, bool PLANAR, int FORM = 0>
 __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane) {
     using G = TileGeo<WS, PLANAR>;
     constexpr int P = G::PITCH;
+    constexpr bool NOSWAP = FORM == 1, SWAP = FORM == 0;
+    static_assert(FORM == 0 || WS == 64, "the other forms are 64x64 ones");
     cf* tile = reinterpret_cast<cf*>(lds);
+    // 64x64, unless NOSWAP: the off-diagonal 32x32 blocks change lane halves first
+    auto swap_halves = [&]() TPIV_LAMBDA_INLINE {
+        if constexpr (WS == 64) {
+            static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
+                constexpr int k = decltype(kc)::value;
+                constexpr int lo = DIGITREV ? FFT_POS<k, WS> : k;
+                constexpr int hi = DIGITREV ? FFT_POS<k + 32, WS> : k + 32;
+                auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].x), __float_as_uint(a[hi].x),
+                                                           false, false);
+                auto ry = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].y), __float_as_uint(a[hi].y),
+                                                           false, false);
+                a[lo].x = __uint_as_float(rx[0]);
+                a[hi].x = __uint_as_float(rx[1]);
+                a[lo].y = __uint_as_float(ry[0]);
+                a[hi].y = __uint_as_float(ry[1]);
+            });
+        }
+    };
     if constexpr (PLANAR && WS > 32) {
         // 64x64, one float plane at a time through two 32x33 float tiles (8.4 KB per wavefront, which
-        // is what lets three wavefronts per SIMD fit in the LDS): swap the off-diagonal blocks
-        // between the lane halves, then transpose the four blocks of each plane, two at a time.
-        static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
-            constexpr int k = decltype(kc)::value;
-            constexpr int lo = DIGITREV ? FFT_POS<k, WS> : k;
-            constexpr int hi = DIGITREV ? FFT_POS<k + 32, WS> : k + 32;
-            auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].x), __float_as_uint(a[hi].x),
-                                                       false, false);
-            auto ry = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].y), __float_as_uint(a[hi].y),
-                                                       false, false);
-            a[lo].x = __uint_as_float(rx[0]);
-            a[hi].x = __uint_as_float(rx[1]);
-            a[lo].y = __uint_as_float(ry[0]);
-            a[hi].y = __uint_as_float(ry[1]);
-        });
+        // is what lets three wavefronts per SIMD fit in the LDS): the four blocks of each plane, two at a time
+        // (after the swap of the off-diagonal blocks between the lane halves, or in the NOSWAP order)
+        if constexpr (SWAP) swap_halves();
         float* t = lds + (lane >> 5) * G::TILE;
+        const float* t2 = NOSWAP ? lds + ((lane >> 5) ^ 1) * G::TILE : t;      // phase-2 reads
         const int i = lane & 31;
         auto plane = [&](auto comp) TPIV_LAMBDA_INLINE {
             constexpr bool Y = decltype(comp)::value;
@@ -309,10 +343,10 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
 #pragma unroll
             for (int r = 0; r < 32; ++r) {
                 if constexpr (Y) {
-                    a[32 + r].y = t[r * P + i];
+                    a[32 + r].y = t2[r * P + i];
                     a[r].y = lowhalf[r];
                 } else {
-                    a[32 + r].x = t[r * P + i];
+                    a[32 + r].x = t2[r * P + i];
                     a[r].x = lowhalf[r];
                 }
             }
@@ -353,21 +387,9 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
 #pragma unroll
         for (int r = 0; r < WS; ++r) a[r] = t[r * P + i];
     } else {
-        // 64x64 = 2x2 blocks of 32x32: swap the off-diagonal blocks between the lane halves,
-        // then transpose the four blocks, two at a time, through the two 32x33 tiles
-        static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
-            constexpr int k = decltype(kc)::value;
-            constexpr int lo = DIGITREV ? FFT_POS<k, WS> : k;
-            constexpr int hi = DIGITREV ? FFT_POS<k + 32, WS> : k + 32;
-            auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].x), __float_as_uint(a[hi].x),
-                                                       false, false);
-            auto ry = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].y), __float_as_uint(a[hi].y),
-                                                       false, false);
-            a[lo].x = __uint_as_float(rx[0]);
-            a[hi].x = __uint_as_float(rx[1]);
-            a[lo].y = __uint_as_float(ry[0]);
-            a[hi].y = __uint_as_float(ry[1]);
-        });
+        // 64x64 = 2x2 blocks of 32x32: the four blocks, two at a time, through the two 32x33 tiles (after the swap of
+        // the off-diagonal blocks between the lane halves, or in the NOSWAP order)
+        if constexpr (SWAP) swap_halves();
         cf* t = tile + (lane >> 5) * G::TILE;
         const int i = lane & 31;
         cf lowhalf[32];
@@ -387,8 +409,9 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
             t[i * P + k] = a[src];
         });
         wave_sync();
+        const cf* t2 = NOSWAP ? tile + ((lane >> 5) ^ 1) * G::TILE : t;        // phase-2 reads
 #pragma unroll
-        for (int r = 0; r < 32; ++r) a[32 + r] = t[r * P + i];
+        for (int r = 0; r < 32; ++r) a[32 + r] = t2[r * P + i];
 #pragma unroll
         for (int r = 0; r < 32; ++r) a[r] = lowhalf[r];
     }
@@ -1755,6 +1778,22 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
         // keeps the mean removal in front of the transform (128 fma per 64x64 window row, 2 % of the pass).
         // The shifted passes are float32 in the reference itself, with the full pedestal in both transforms.
         constexpr bool FASTN = FAST && MODE != MODE_PASS1;
+        // ---- Swap-free first transposition (64x64, TPIV_NOSWAP64; see transpose_tile).  Two shift theorems stand in for the
+        //      lane-half swaps.  (1) Lanes 32..63 (rows 32..63) negate their odd samples, x'[n] = (-1)^n x[n]: their row
+        //      transform holds bin (k + 32) mod 64 where it would hold bin k, i.e. every lane has the spectrum block of its OWN
+        //      lane half in the low positions.  (2) The transposition then leaves lanes 32..63 (columns 32..63) with their
+        //      column rotated by 32 rows, which multiplies their column spectrum by (-1)^ky.  In the packed cross-spectrum
+        //      only re = 2 (a d + b c) sees that sign -- im is made of squares -- as the product of the signs of the lane and
+        //      its mirror partner: of the lanes c and 64 - c exactly one is in the upper half, lanes 0 and 32 are their own
+        //      partners.  So the odd bins of every lane but 0 and 32 take the factor -2 instead of 2 (`two_odd`).
+        //      The sign flips and the renaming of bins and rows are exact; the value a register holds takes another path
+        //      through the codelets' roundings than in the swapped form, so the float32 map moves in its last bits (the
+        //      bound of the locating pass's band counts levels, not paths: DESIGN.md 3.4b, "Swap-free first transposition").
+        //      The fast-order DWS instance keeps the swapped form: there the input sign is 64 separate XORs (byte
+        //      conversions carry no constant to ride on) and the instance gains four spilled registers at its 168-VGPR cap.
+        constexpr bool NOSWAP = WS == 64 && TPIV_NOSWAP64 != 0 && !EXP_NOSWAP_CEIL && !(MODE == MODE_DWS && FAST);
+        auto up_sign = []() TPIV_LAMBDA_INLINE { return fresh_lane() >= 32 ? 0x80000000u : 0u; };
+        auto sflip = [](float v, unsigned sg) TPIV_LAMBDA_INLINE { return __uint_as_float(__float_as_uint(v) ^ sg); };
         if constexpr (!FASTN) {
             sa = grp_sum<WS>(sa);
             sb = grp_sum<WS>(sb);
@@ -1790,31 +1829,53 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
             constexpr float PRE = 0.5f / (float)WS;
             const float oa = -ma * ka, ob = -mb * kb;
             const float kas = ka * PRE, kbs = kb * PRE, oas = oa * PRE, obs = ob * PRE;
+            // (NOSWAP: the sign of the odd samples of lanes 32..63 rides on the constants of the same fma, no instruction added)
+            const unsigned sg = NOSWAP ? up_sign() : 0u;
+            const float kao = sflip(kas, sg), kbo = sflip(kbs, sg), oao = sflip(oas, sg), obo = sflip(obs, sg);
 #pragma unroll
             for (int k = 0; k < WS; ++k) {
-                x[k].x = fmaf(x[k].x, kas, oas);        // (x - mean) * k * 0.5/WS
-                x[k].y = fmaf(x[k].y, kbs, obs);
+                x[k].x = (k & 1) ? fmaf(x[k].x, kao, oao) : fmaf(x[k].x, kas, oas);        // (x - mean) * k * 0.5/WS
+                x[k].y = (k & 1) ? fmaf(x[k].y, kbo, obo) : fmaf(x[k].y, kbs, obs);
+            }
+        } else if constexpr (NOSWAP) {
+            const unsigned sg = up_sign();
+#pragma unroll
+            for (int k = 1; k < WS; k += 2) {
+                x[k].x = sflip(x[k].x, sg);
+                x[k].y = sflip(x[k].y, sg);
             }
         }
 
         TPIV_STAMP(2);      // mean reduction + normalisation
         // ---- forward 2-D transform of a + i*b: rows in registers, transpose, columns in registers
-        fft_inreg<WS, 1>(x, tw);                          // over x; bin kx at x[FFT_POS<kx>]
+        fft_inreg<WS, 1>(x, tw);                          // over x; bin kx at x[FFT_POS<kx>] (NOSWAP, lanes 32..63: bin kx + 32)
         if constexpr (FASTN) {
             // The samples went in as they are.  Bin kx = 0 of a lane's row is the row sum (a in .x, b in .y):
             // the window mean is removed THERE (one subtraction per lane instead of one per sample; only
             // the row transform has seen the pedestal), and the constant factor of the map -- 1/n^2 and the
             // 1/4 of the packed spectrum -- is applied by peak_analysis.
             constexpr int P0 = FFT_POS<0, WS>;
-            const float ta = grp_sum<WS>(x[P0].x);
-            const float tb = grp_sum<WS>(x[P0].y);
-            x[P0].x -= ta * (1.0f / WS);
-            x[P0].y -= tb * (1.0f / WS);
+            if constexpr (NOSWAP) {
+                constexpr int PH = FFT_POS<WS / 2, WS>;   // where lanes 32..63 hold bin 0
+                const bool up = up_sign() != 0u;
+                const float ta = grp_sum<WS>(up ? x[PH].x : x[P0].x);
+                const float tb = grp_sum<WS>(up ? x[PH].y : x[P0].y);
+                x[P0].x -= up ? 0.0f : ta * (1.0f / WS);
+                x[P0].y -= up ? 0.0f : tb * (1.0f / WS);
+                x[PH].x -= up ? ta * (1.0f / WS) : 0.0f;
+                x[PH].y -= up ? tb * (1.0f / WS) : 0.0f;
+            } else {
+                const float ta = grp_sum<WS>(x[P0].x);
+                const float tb = grp_sum<WS>(x[P0].y);
+                x[P0].x -= ta * (1.0f / WS);
+                x[P0].y -= tb * (1.0f / WS);
+            }
             end_scale = 0.25f / (float)(WS * WS);
             if constexpr (MODE == MODE_CWS && TPIV_SDWA_LERP) end_scale *= SDWA_INV * SDWA_INV;     // both frames' samples carry 2^-24
         }
         TPIV_STAMP(3);      // forward row FFT
-        transpose_tile<WS, true, PLANAR>(x, tile, fresh_lane());  // lane = kx, x[y] natural
+        // lane = kx, x[y] natural (NOSWAP, lanes 32..63: x[y] = row y + 32)
+        transpose_tile<WS, true, PLANAR, NOSWAP ? 1 : ((EXP_NOSWAP_CEIL && WS == 64) ? 2 : 0)>(x, tile, fresh_lane());
         TPIV_STAMP(4);      // transposition 1
         fft_inreg<WS, 1>(x, tw);                          // over y; Z(ky, kx = lane) at x[FFT_POS<ky>]
         TPIV_STAMP(5);      // forward column FFT
@@ -1850,13 +1911,14 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
                 const int lane_c = fresh_lane();
                 const int r_c = lane_c % WS;
                 const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
-                auto cross = [&](cf zk, cf zm) TPIV_LAMBDA_INLINE {      // the formula of the full form below
+                auto cross = [&](cf zk, cf zm, float two) TPIV_LAMBDA_INLINE {      // the formula of the full form below
                     const float a_ = zk.x, b_ = zk.y, c_ = zm.x, d_ = zm.y;
                     cf pr;
-                    pr.x = (a_ * d_ + b_ * c_) * 2.0f;
+                    pr.x = (a_ * d_ + b_ * c_) * two;
                     pr.y = (c_ * c_ - a_ * a_) + (d_ * d_ - b_ * b_);
                     return pr;
                 };
+                const float two_odd = (NOSWAP && (lane_c & 31) != 0) ? -2.0f : 2.0f;      // see "Swap-free first transposition"
                 cf pc[M + 1];
                 static_for<0, M + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
                     constexpr int ky = decltype(kc)::value;
@@ -1865,7 +1927,7 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
                     cf m1;
                     m1.x = __shfl(z2.x, partner, 64);        // Z(-ky, -kx)
                     m1.y = __shfl(z2.y, partner, 64);
-                    pc[ky] = cross(x[FFT_POS<ky, WS>], m1);
+                    pc[ky] = cross(x[FFT_POS<ky, WS>], m1, (ky & 1) ? two_odd : 2.0f);
                 });
                 TPIV_STAMP(6);      // cross-spectrum incl. the bpermute exchange
                 const bool odd = r_c > M;
@@ -1901,23 +1963,25 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
                 // with zk = a + ib, zm = Z(-k) = c + id:  4 P = conj(2A) * (2B)
                 //   re = (a+c)(b+d) + (b-d)(c-a) = 2 (a d + b c),   im = (c^2 - a^2) + (d^2 - b^2)
                 // (the factor 0.25 / WS^2 is already in the inputs, see the normalisation above)
-                auto cross = [&](cf zk, cf zm) TPIV_LAMBDA_INLINE {
+                auto cross = [&](cf zk, cf zm, float two) TPIV_LAMBDA_INLINE {
                     const float a_ = zk.x, b_ = zk.y, c_ = zm.x, d_ = zm.y;
                     cf pr;
-                    pr.x = (a_ * d_ + b_ * c_) * 2.0f;
+                    pr.x = (a_ * d_ + b_ * c_) * two;
                     pr.y = (c_ * c_ - a_ * a_) + (d_ * d_ - b_ * b_);
                     return pr;
                 };
+                const float two_odd = (NOSWAP && (lane_c & 31) != 0) ? -2.0f : 2.0f;      // see "Swap-free first transposition"
                 static_for<0, WS / 2 + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
                     constexpr int ky = decltype(kc)::value;
                     constexpr int nky = (WS - ky) % WS;
                     constexpr int p1 = FFT_POS<ky, WS>, p2 = FFT_POS<nky, WS>;
+                    const float two = (ky & 1) ? two_odd : 2.0f;
                     const cf z1 = x[p1];
                     if constexpr (ky == nky) {
                         cf m1;
                         m1.x = __shfl(z1.x, partner, 64);
                         m1.y = __shfl(z1.y, partner, 64);
-                        x[p1] = cross(z1, m1);
+                        x[p1] = cross(z1, m1, two);
                     } else {
                         const cf z2 = x[p2];
                         cf m1, m2;
@@ -1925,8 +1989,8 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
                         m1.y = __shfl(z2.y, partner, 64);
                         m2.x = __shfl(z1.x, partner, 64);     // Z(+ky, -kx), the partner of bin -ky
                         m2.y = __shfl(z1.y, partner, 64);
-                        x[p1] = cross(z1, m1);
-                        x[p2] = cross(z2, m2);
+                        x[p1] = cross(z1, m1, two);
+                        x[p2] = cross(z2, m2, two);
                     }
                 });
             }
