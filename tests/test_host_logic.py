@@ -670,7 +670,8 @@ def test_per_half_copies_agree_on_their_barriers():
     barriers, so both copies must hold the same number of s_barrier per window.  tools/check_lds_inflight.py counts them
     in the device assembly: first on two crafted snippets, then on the real unit.  The in-flight walk must also see both
     copies: per kernel, at least twice the hand-issued reads of the one-loop build (-DTPIV_F64_PER_HALF=0).
-    (xcorr_big128_cand_kernel under TPIV_BIG_PER_PAR is not walked: that switch is off in the shipped build, and its two
+    (xcorr_big128_cand_kernel under TPIV_BIG_PER_PAR is not walked.  That switch is ON in the shipped build -- the header's
+    default is 1, and the kernel's device assembly holds 42 s_barrier against 21 with -DTPIV_BIG_PER_PAR=0 -- but its two
     copies sit behind a branch inside the kernel's prologue code rather than at its top, which this walk does not model.)"""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_lds_inflight as C

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/diag/lib_ab.so = the library built with extra flags ($@), e.g. -DTPIV_COOP=0, for same-box A/B runs
+# tools/diag/lib_ab.so = the library built with extra flags ($@), e.g. -DTPIV_F64_PER_HALF=0, for same-box A/B runs
 set -e
 cd "$(dirname "$0")/../../torchpiv_amd/csrc"
 rm -rf ../../build/obj_ab        # make compares time stamps, not flags: a build with other -D flags must start from nothing

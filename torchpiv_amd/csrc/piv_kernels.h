@@ -1,5 +1,5 @@
 // Internal launch interface between the C-ABI layer (c_api.cpp) and the kernels
-// (piv_kernels.hip).  Not part of the public boundary (include/torchpiv_hip.h).
+// (the .hip units of this directory; dispatch in piv_launch.hip).  Not part of the public boundary (include/torchpiv_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,7 +33,7 @@ struct PassParams {
     double* dv;
     double val_ratio;
     int val_win;
-    int precision;         // pass 1 only: 0 = float32 kernels, 1 = float64 (TPIV_PREC_REFERENCE), 3 = exact sums (64x64)
+    int precision;         // pass 1 only: 0 = float32 kernels, 1 = float64 (TPIV_PREC_REFERENCE), 3 = exact sums (every even size from 8 to 128)
     // test hooks (nullptr in production)
     float* dbg_win;        // [batch, N, 2, ws, ws] staged windows (after the shift)
     float* dbg_corr;       // [batch, N, ws, ws] corr - min + eps, fftshift layout
@@ -48,7 +48,7 @@ struct PassParams {
     int* slow_list;
     unsigned* slow_count;
     int list_mode;
-    // precision "exact" (64x64 pass 1, xcorr_exact.hip; all set by launch_xcorr): the float32 kernel's candidate cells
+    // precision "exact" (pass 1 at every even size from 8 to 128, xcorr_exact.hip; all set by launch_xcorr): the float32 kernel's candidate cells
     // per window (8 x int16: arg-max, 3 second-peak cells, 4 minimum cells; -1 = none, arg-max -1 = undecided, -2 = dead),
     // and the windows that go to the float64 kernel instead (undecided ones)
     uint4* cand;
@@ -175,19 +175,14 @@ hipError_t launch_xcorr(const PassParams& p, int mode, int n_cu, hipStream_t str
 // bytes of the tile kernels' work-queue counters (8 x one 64-byte line), and of the slow-item list header behind them
 constexpr size_t TILE_CTR_BYTES = 8 * 16 * sizeof(unsigned), TILE_SLOW_HDR_BYTES = 256;
 // 64x64 CWS pass at the fast operation order: fast-path-only kernel at three wavefronts per SIMD + a second launch of the full
-// kernel over the items it set aside (TPIV_SPLIT64=0: the single launch of rounds 1-4)
-#ifndef TPIV_SPLIT64
-#define TPIV_SPLIT64 1
-#endif
-constexpr bool tile_split64(int ws, int mode) { return TPIV_SPLIT64 && ws == 64 && mode == MODE_CWS; }
-// wavefronts per SIMD the tile kernel of (ws, mode) is built for (the OCC template argument of
-// xcorr_tile_kernel); 0 for sizes that run another kernel
-#ifndef TPIV_OCC64C
-#define TPIV_OCC64C 2      // wavefronts per SIMD of the 64x64 CWS kernel (experiments: 3)
-#endif
+// kernel over the items it set aside
+constexpr bool tile_split64(int ws, int mode) { return ws == 64 && mode == MODE_CWS; }
+// wavefronts per SIMD the tile kernel of (ws, mode) is built for (the OCC template argument of xcorr_tile_kernel;
+// 8x8: of xcorr_tile_cand_kernel only, its passes run xcorr_w8.hip); 0 for sizes that run another kernel.
+// The full 64x64 CWS kernel stays at two: built for three it spills 97 registers.
 constexpr int tile_occ_c(int ws, int mode) {
     return (ws != 8 && ws != 16 && ws != 32 && ws != 64) ? 0
-           : (ws == 16 ? 4 : ((ws == 32 || (ws == 64 && (mode != MODE_CWS || TPIV_OCC64C == 3))) ? 3 : 2));
+           : (ws == 16 ? 4 : ((ws == 32 || (ws == 64 && mode != MODE_CWS)) ? 3 : 2));
 }
 inline int tile_occ(int ws, int mode) { return tile_occ_c(ws, mode); }
 #ifdef __HIPCC__

@@ -9,7 +9,6 @@
 
 namespace tpiv {
 
-hipError_t launch_xcorr_ws8(const PassParams& p, int mode, int n_cu, hipStream_t stream);
 hipError_t launch_xcorr_w8(const PassParams& p, int mode, int n_cu, hipStream_t stream);       // xcorr_w8.hip: one window per lane
 hipError_t launch_peak_debug_w8(const PassParams& p, const float* maps, int n_maps, hipStream_t stream);
 hipError_t launch_xcorr_ws16(const PassParams& p, int mode, int n_cu, hipStream_t stream);
@@ -236,7 +235,7 @@ size_t peak_raw_bytes(int ws, int batch, int n_windows, int precision, bool forc
 // (in the demangled form rocprofv3 prints, so that profile rows can be matched by substring; the MODE
 //  template argument is the tpiv::MODE_* value: 0 pass 1, 1 DWS, 2 CWS)
 // TPIV_PREC_F64 (2): float64 pass 1, fast operation order in the shifted passes
-// TPIV_PREC_EXACT (3): exact integer sums in pass 1 (64x64; float64 kernels for the other sizes), shifted passes as (2)
+// TPIV_PREC_EXACT (3): exact integer sums in pass 1 (every even size from 8 to 128; float64 kernels for the other sizes), shifted passes as (2)
 static int pass_precision(int precision, int mode, int ws) {
     if (precision == 2) return mode == MODE_PASS1 ? 1 : 0;
     if (precision == 3) return mode == MODE_PASS1 ? (exact_size(ws) ? 3 : 1) : 0;
@@ -345,12 +344,7 @@ hipError_t launch_xcorr(const PassParams& p_in, int mode, int n_cu, hipStream_t 
         }
         mark(2);
     } else if (f64) {
-        // (TPIV_F64_GENERIC128=1: the generic-size DFT kernel for 128x128, as before the split kernel existed -- A/B runs)
-        static const bool gen128 = [] {
-            const char* env = getenv("TPIV_F64_GENERIC128");
-            return env && env[0] == '1';
-        }();
-        e = (tile_size(p.ws) || (p.ws == 128 && !gen128)) ? launch_xcorr_f64(p, n_cu, stream) : generic();
+        e = (tile_size(p.ws) || p.ws == 128) ? launch_xcorr_f64(p, n_cu, stream) : generic();
     } else if (tile_size(p.ws)) {       // per-XCD work queue of the tile kernel: counters behind the peak records
         p.work_ctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.peak_raw) +
                                                  work_ctr_offset(p.batch, p.n_rows * p.n_cols));
@@ -364,13 +358,8 @@ hipError_t launch_xcorr(const PassParams& p_in, int mode, int n_cu, hipStream_t 
         }
         e = hipMemsetAsync(p.work_ctr, 0, WORK_CTR_BYTES + (split ? TILE_SLOW_HDR_BYTES : 0), stream);
         if (e != hipSuccess) return e;
-        // 8x8: one window per lane (xcorr_w8.hip); TPIV_W8=0 selects the lane-per-row tile kernel for A/B runs
-        static const bool w8 = [] {
-            const char* env = getenv("TPIV_W8");
-            return !(env && env[0] == '0');
-        }();
         switch (p.ws) {
-            case 8: e = w8 ? launch_xcorr_w8(p, mode, n_cu, stream) : launch_xcorr_ws8(p, mode, n_cu, stream); break;
+            case 8: e = launch_xcorr_w8(p, mode, n_cu, stream); break;      // one window per lane (xcorr_w8.hip)
             case 16: e = launch_xcorr_ws16(p, mode, n_cu, stream); break;
             case 32: e = launch_xcorr_ws32(p, mode, n_cu, stream); break;
             default: e = launch_xcorr_ws64(p, mode, n_cu, stream); break;

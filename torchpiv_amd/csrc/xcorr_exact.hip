@@ -23,15 +23,10 @@
 // tests/test_gpu_exact.py compares this file with it and with the float64 kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "piv_kernels.h"
 #include "xcorr_tile.hpp"      // grp_reduce, wave_sync, load_dwords
-
-// wavefronts (= windows) per workgroup of the 64x64 refinement: 2 -> 16.9 KB of LDS per workgroup, 9 workgroups = 18
-// wavefronts per CU against 4 x 4 = 16 with 4 (1.10 -> 1.06 ms per 1 016 064 windows; profiles/exact_neighbourhood)
-#ifndef TPIV_REFINE_WAVES64
-#define TPIV_REFINE_WAVES64 2
-#endif
 
 namespace tpiv {
 
@@ -44,7 +39,9 @@ struct XGeo {
     static constexpr int GROUP = W < 64 ? W : 64;            // lanes of one window inside a wavefront
     static constexpr int WPW = 64 / GROUP;                   // windows per wavefront (32x32: two)
     static constexpr int PARTS = W / GROUP;                  // wavefronts per window (128x128: two)
-    static constexpr int WAVES = W == 128 ? 2 : (W == 64 ? TPIV_REFINE_WAVES64 : 4);      // wavefronts per workgroup
+    // wavefronts per workgroup.  64x64 (one window per wavefront): 2 -> 16.9 KB of LDS per workgroup, 9 workgroups = 18
+    // wavefronts per CU against 4 x 4 = 16 with 4 (1.10 -> 1.06 ms per 1 016 064 windows; profiles/exact_neighbourhood)
+    static constexpr int WAVES = W == 128 || W == 64 ? 2 : 4;
     static constexpr int WINS = WAVES * WPW / PARTS;         // windows per workgroup: 8 / 2 / 1
     static constexpr int KD = W * W;
     // rows are LOADED by the window's lanes together (W >= 32): 16-byte chunks, chunk ci = row * P16 + part, lane t of the

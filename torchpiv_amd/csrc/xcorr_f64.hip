@@ -27,10 +27,6 @@
 #include "xcorr_tile.hpp"      // grp_reduce: wavefront reductions in the VALU (DPP / permlane swaps)
 #include "xcorr_f64_split.hpp" // 64 / 128: lines split over two threads, 32- / 64-point in-register codelets
 
-#ifndef TPIV_F64_WIDE64
-#define TPIV_F64_WIDE64 1      // 64x64: the parity branch spans the column stages through the T2 write (A/B: 0 = only the cross-spectrum)
-#endif
-
 namespace tpiv {
 
 namespace {
@@ -208,7 +204,7 @@ __device__ __forceinline__ void xcorr_f64_split_body(const PassParams& p, F64Spl
             lds_barrier();                               // every thread has read its T1 column
             S::t2_write(t, TPIV_F64_TID() & (W - 1), G, plane);
         };
-        if constexpr (W == 64 && TPIV_F64_WIDE64) {
+        if constexpr (W == 64) {      // the parity branch spans the column stages through the T2 write
             if (g) column_stages(std::integral_constant<int, 1>{});
             else column_stages(std::integral_constant<int, 0>{});
         } else {

@@ -17,20 +17,20 @@
 //     WSx(WS+1)) tiles; a 64x64 tile is transposed as four 32x32 blocks, two at a time, without moving data between
 //     the lane halves: rows 32..63 negate their odd samples (their row spectrum comes out rotated by 32 bins), every lane
 //     reads the other half's tile in the second phase, and the rotation by 32 rows this leaves in columns 32..63 is a sign
-//     of the odd cross-spectrum bins (TPIV_NOSWAP64; 0 = v_permlane32_swap of the off-diagonal blocks first).
+//     of the odd cross-spectrum bins (the fast-order 64x64 DWS instance alone does a v_permlane32_swap of the off-diagonal
+//     blocks first: 64 swaps per window at 8-14 issue cycles each, see "Swap-free first transposition" in xcorr_tile_body).
 //     The last transform is a c2r one: only spectrum
 //     columns 0..WS/2 cross the LDS the second time (transpose_half).  Kernels at three wavefronts per SIMD move one
 //     float plane at a time (8.4 KB per wavefront), the others complex elements (16.9 KB).
 //   * the k <-> -k partner of the packed spectrum is fetched with ds_bpermute (no LDS memory).  The planar 32x32 / 64x64
 //     kernels split each spectrum column between the lanes of columns c and -c: half the cross-spectrum products, one
-//     radix-2 level and a WS/2-point inverse column transform per lane (TPIV_HALF_INV*, transpose_half_pairs).
+//     radix-2 level and a WS/2-point inverse column transform per lane (transpose_half_pairs).
 //   * peak search: plain max scans per lane, DPP / permlane reductions, one LDS row lookup for the
 //     arg-max position, sign-bit exclusion for the second peak (compares and selects cost twice a
 //     plain fp32 instruction on MI355X); an 8-float record per window goes to finalize_kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "fft_inreg.hpp"
 #include "piv_kernels.h"
@@ -149,23 +149,6 @@ __device__ __forceinline__ float byte_f(const uint32_t (&d)[N]) {
     return (float)((d[K >> 2] >> (8 * (K & 3))) & 0xffu);
 }
 
-// ... the same byte REINTERPRETED as a float32 (a denormal: b x 2^-149), for use as a multiplicand: the compiler folds
-// the byte extraction into the multiply (v_mul_f32_sdwa src_sel:BYTE_k) -- one instruction instead of v_cvt_f32_ubyte +
-// v_mul_f32.  The other factor carries 2^125, so the product is b x w x 2^-24: exact scaling, no rounding differs (the
-// kernels run with float32 denormals on: .amdhsa_float_denorm_mode_32 3).  gfx950 has no SDWA form of v_fmac / v_fma.
-// OFF: measured in round 5 (same box, A B A B; results bit-identical, 82 parity tests green): the 66 v_mul_f32_sdwa per item
-// replace 66 conversions -- and the 32x32 CWS pass takes 7.27 / 7.33 ms with them against 7.19 / 7.26 without, the 64x64 CWS
-// pass 2.35 against 2.27, the 16x16 pass 1.93 against 1.91: the multiply with a denormal (or SDWA) operand is not a
-// full-rate instruction on this chip.
-#ifndef TPIV_SDWA_LERP
-#define TPIV_SDWA_LERP 0
-#endif
-constexpr float SDWA_UP = 0x1p125f, SDWA_DN = 0x1p-24f, SDWA_INV = 0x1p24f;      // 2^125 x 2^-149 = 2^-24
-template <int K, int N>
-__device__ __forceinline__ float byte_d(const uint32_t (&d)[N]) {
-    return __uint_as_float((d[K >> 2] >> (8 * (K & 3))) & 0xffu);
-}
-
 // N dwords from a byte address of any alignment (global memory takes unaligned dword loads)
 template <int N>
 __device__ __forceinline__ void load_dwords(const uint8_t* __restrict__ p, uint32_t (&d)[N]) {
@@ -263,12 +246,11 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 // ---- transposition of the wavefront's tile(s) through LDS ---------------------------------
-// in:  lane (w, i) holds line i of its window, element k at in[POS(k)]  (POS = digit-reversed
-//      position when DIGITREV, else k)
+// in:  lane (w, i) holds line i of its window, element k at in[FFT_POS<k>] (the digit-reversed position the codelets leave it at)
 // out: lane (w, j) holds element j of every line: out[i] = element (line i, position j)
 //
-// NOSWAP (64x64, first transposition; TPIV_NOSWAP64): no lane-half swaps.  The caller has negated the odd samples of the
-// lanes 32..63 in front of the row transform, so those lanes hold element (k + 32) mod 64 at in[POS(k)]: in BOTH lane halves
+// NOSWAP (64x64): no lane-half swaps.  The caller has negated the odd samples of the
+// lanes 32..63 in front of the row transform, so those lanes hold element (k + 32) mod 64 at in[FFT_POS<k>]: in BOTH lane halves
 // the low positions are the diagonal block of the 2x2 block matrix and the high positions the off-diagonal one.  Phase 1
 // writes the low positions into the lane half's own tile and every lane reads its own half's tile (the diagonal blocks;
 // the same instructions as phase 1 of the swapped form, which moves the blocks of rows 0..31 with them); phase 2 writes
@@ -276,32 +258,21 @@ __device__ __forceinline__ void wave_sync() {
 // (same instruction, another base address).  Result: lanes 0..31 as above, lanes 32..63 hold their element rotated by 32
 // lines, out[i] = (line (i + 32) mod 64, position j) -- which the caller undoes as a sign of the odd bins of the next
 // transform (xcorr_tile_body, "Swap-free first transposition").
-#ifndef TPIV_NOSWAP64
-#define TPIV_NOSWAP64 1
-#endif
-// Timing experiment only (wrong results), the ceiling of what the swap-free form can give: -DTPIV_EXP_NOSWAP_CEIL builds the
-// SWAPPED form of the first transposition with its swaps left out; it turns the swap-free form (input signs, two_odd) off
-// whatever TPIV_NOSWAP64 says and leaves a second transposition through transpose_tile (TPIV_C2R64=0) alone.
-#ifdef TPIV_EXP_NOSWAP_CEIL
-constexpr bool EXP_NOSWAP_CEIL = true;
-#else
-constexpr bool EXP_NOSWAP_CEIL = false;
-#endif
-// FORM: 0 = lane-half swaps first, 1 = NOSWAP, 2 = the timing experiment
-template <int WS, bool DIGITREV, bool PLANAR, int FORM = 0>
+// !NOSWAP at 64x64 (the fast-order DWS instance, planar): the off-diagonal 32x32 blocks change lane halves first.
+template <int WS, bool PLANAR, bool NOSWAP = false>
 __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane) {
     using G = TileGeo<WS, PLANAR>;
     constexpr int P = G::PITCH;
-    constexpr bool NOSWAP = FORM == 1, SWAP = FORM == 0;
-    static_assert(FORM == 0 || WS == 64, "the other forms are 64x64 ones");
+    static_assert(!NOSWAP || WS == 64, "the swap-free form is a 64x64 one");
     cf* tile = reinterpret_cast<cf*>(lds);
-    // 64x64, unless NOSWAP: the off-diagonal 32x32 blocks change lane halves first
-    auto swap_halves = [&]() TPIV_LAMBDA_INLINE {
-        if constexpr (WS == 64) {
+    if constexpr (PLANAR && WS > 32) {
+        // 64x64, one float plane at a time through two 32x33 float tiles (8.4 KB per wavefront, which
+        // is what lets three wavefronts per SIMD fit in the LDS): the four blocks of each plane, two at a time
+        // (after the swap of the off-diagonal blocks between the lane halves, or in the NOSWAP order)
+        if constexpr (!NOSWAP) {
             static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
                 constexpr int k = decltype(kc)::value;
-                constexpr int lo = DIGITREV ? FFT_POS<k, WS> : k;
-                constexpr int hi = DIGITREV ? FFT_POS<k + 32, WS> : k + 32;
+                constexpr int lo = FFT_POS<k, WS>, hi = FFT_POS<k + 32, WS>;
                 auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].x), __float_as_uint(a[hi].x),
                                                            false, false);
                 auto ry = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[lo].y), __float_as_uint(a[hi].y),
@@ -312,12 +283,6 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
                 a[hi].y = __uint_as_float(ry[1]);
             });
         }
-    };
-    if constexpr (PLANAR && WS > 32) {
-        // 64x64, one float plane at a time through two 32x33 float tiles (8.4 KB per wavefront, which
-        // is what lets three wavefronts per SIMD fit in the LDS): the four blocks of each plane, two at a time
-        // (after the swap of the off-diagonal blocks between the lane halves, or in the NOSWAP order)
-        if constexpr (SWAP) swap_halves();
         float* t = lds + (lane >> 5) * G::TILE;
         const float* t2 = NOSWAP ? lds + ((lane >> 5) ^ 1) * G::TILE : t;      // phase-2 reads
         const int i = lane & 31;
@@ -327,7 +292,7 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
             wave_sync();
             static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
                 constexpr int k = decltype(kc)::value;
-                constexpr int src = DIGITREV ? FFT_POS<k, WS> : k;
+                constexpr int src = FFT_POS<k, WS>;
                 t[i * P + k] = Y ? a[src].y : a[src].x;
             });
             wave_sync();
@@ -336,7 +301,7 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
             wave_sync();
             static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
                 constexpr int k = decltype(kc)::value;
-                constexpr int src = DIGITREV ? FFT_POS<k + 32, WS> : k + 32;
+                constexpr int src = FFT_POS<k + 32, WS>;
                 t[i * P + k] = Y ? a[src].y : a[src].x;
             });
             wave_sync();
@@ -359,8 +324,7 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
         wave_sync();
         static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
             constexpr int k = decltype(kc)::value;
-            constexpr int src = DIGITREV ? FFT_POS<k, WS> : k;
-            t[i * P + k] = a[src].x;
+            t[i * P + k] = a[FFT_POS<k, WS>].x;
         });
         wave_sync();
 #pragma unroll
@@ -368,8 +332,7 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
         wave_sync();
         static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
             constexpr int k = decltype(kc)::value;
-            constexpr int src = DIGITREV ? FFT_POS<k, WS> : k;
-            t[i * P + k] = a[src].y;
+            t[i * P + k] = a[FFT_POS<k, WS>].y;
         });
         wave_sync();
 #pragma unroll
@@ -380,24 +343,21 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
         wave_sync();
         static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
             constexpr int k = decltype(kc)::value;
-            constexpr int src = DIGITREV ? FFT_POS<k, WS> : k;
-            t[i * P + k] = a[src];
+            t[i * P + k] = a[FFT_POS<k, WS>];
         });
         wave_sync();
 #pragma unroll
         for (int r = 0; r < WS; ++r) a[r] = t[r * P + i];
     } else {
-        // 64x64 = 2x2 blocks of 32x32: the four blocks, two at a time, through the two 32x33 tiles (after the swap of
-        // the off-diagonal blocks between the lane halves, or in the NOSWAP order)
-        if constexpr (SWAP) swap_halves();
+        // 64x64 = 2x2 blocks of 32x32: the four blocks, two at a time, through the two 32x33 tiles, in the NOSWAP order
+        static_assert(NOSWAP, "the complex 64x64 tile (the CWS kernel at two wavefronts per SIMD) is swap-free");
         cf* t = tile + (lane >> 5) * G::TILE;
         const int i = lane & 31;
         cf lowhalf[32];
         wave_sync();
         static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
             constexpr int k = decltype(kc)::value;
-            constexpr int src = DIGITREV ? FFT_POS<k, WS> : k;
-            t[i * P + k] = a[src];
+            t[i * P + k] = a[FFT_POS<k, WS>];
         });
         wave_sync();
 #pragma unroll
@@ -405,11 +365,10 @@ __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane
         wave_sync();
         static_for<0, 32>([&](auto kc) TPIV_LAMBDA_INLINE {
             constexpr int k = decltype(kc)::value;
-            constexpr int src = DIGITREV ? FFT_POS<k + 32, WS> : k + 32;
-            t[i * P + k] = a[src];
+            t[i * P + k] = a[FFT_POS<k + 32, WS>];
         });
         wave_sync();
-        const cf* t2 = NOSWAP ? tile + ((lane >> 5) ^ 1) * G::TILE : t;        // phase-2 reads
+        const cf* t2 = tile + ((lane >> 5) ^ 1) * G::TILE;        // phase-2 reads: the other half's tile
 #pragma unroll
         for (int r = 0; r < 32; ++r) a[32 + r] = t2[r * P + i];
 #pragma unroll
@@ -428,10 +387,12 @@ __device__ __forceinline__ void transpose_half(const cf (&a)[WS], cf (&g)[WS / 2
     constexpr int P = G::PITCH, M = WS / 2;
     const int i = lane % WS;
     if constexpr (WS == 64) {
-        // 64x64, planar: element (row y, column kx) at y * 33 + kx -- 64 x 33 floats, exactly the two 32x33 tiles;
+        // 64x64, complex elements (the CWS kernel at two wavefronts per SIMD: 16.9 KB tile; the planar 64x64 kernels take
+        // transpose_half_pairs): element (row y, column kx) at y * 33 + kx -- 64 x 33 elements, exactly the two 32x33 tiles;
         // lanes kx <= 32 write with stride 1, lane y reads with stride 33: conflict-free, and no lane-half swaps
+        static_assert(!PLANAR, "planar 64x64 tiles run the paired half inverse");
         constexpr int Q = M + 1;
-        static_assert(WS * Q * (PLANAR ? 1 : 2) <= G::LDS_FLOATS, "half-spectrum plane fits the tile");
+        static_assert(WS * Q * 2 <= G::LDS_FLOATS, "half-spectrum plane fits the tile");
         // (the values are pinned in front of the conditional stores: left alone, the compiler sinks the end of the
         //  column transform into the branch and keeps its inputs alive across it -- 32 spills at the register cap)
         cf b[WS];
@@ -441,38 +402,16 @@ __device__ __forceinline__ void transpose_half(const cf (&a)[WS], cf (&g)[WS / 2
             asm volatile("" : "+v"(b[k].x), "+v"(b[k].y));
         });
         wave_sync();
-        if constexpr (!PLANAR) {              // complex elements (two wavefronts per SIMD: 16.9 KB tile)
-            cf* t = reinterpret_cast<cf*>(lds);
-            if (i <= M) {
-                static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
-                    constexpr int k = decltype(kc)::value;
-                    t[k * Q + i] = b[k];
-                });
-            }
-            wave_sync();
-#pragma unroll
-            for (int r = 0; r <= M; ++r) g[r] = t[i * Q + r];
-        } else {
+        cf* t = reinterpret_cast<cf*>(lds);
         if (i <= M) {
             static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
                 constexpr int k = decltype(kc)::value;
-                lds[k * Q + i] = b[k].x;
+                t[k * Q + i] = b[k];
             });
         }
         wave_sync();
 #pragma unroll
-        for (int r = 0; r <= M; ++r) g[r].x = lds[i * Q + r];
-        wave_sync();
-        if (i <= M) {
-            static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
-                constexpr int k = decltype(kc)::value;
-                lds[k * Q + i] = b[k].y;
-            });
-        }
-        wave_sync();
-#pragma unroll
-        for (int r = 0; r <= M; ++r) g[r].y = lds[i * Q + r];
-        }
+        for (int r = 0; r <= M; ++r) g[r] = t[i * Q + r];
     } else if constexpr (PLANAR) {
         float* t = lds + (lane / WS) * G::HTILE;
         wave_sync();
@@ -510,7 +449,7 @@ __device__ __forceinline__ void transpose_half(const cf (&a)[WS], cf (&g)[WS / 2
     }
 }
 
-// ---- half transposition after the paired inverse column transform (TPIV_HALF_INV, planar tiles, WS = 32 / 64) ----------------
+// ---- half transposition after the paired inverse column transform (planar tiles, WS = 32 / 64) ----------------
 // in:  lane (w, r) holds the WS/2-point inverse column result h[FFT_POS<m, WS/2>] (see the body):
 //        r = c in 1 .. WS/2-1:   column c, rows 2m;
 //        r = WS - c:             column c, rows 2m + 1, conjugated (it is the inverse of column -c);
@@ -582,21 +521,11 @@ struct ItemGeom {
     size_t fidx;
 };
 
-// first pass: rows loaded in 16-byte chunks by the window's lanes together (issue_rows / convert_rows, MODE_PASS1).
-// OFF: measured in round 5 (same box, A B A B): locating pass of configs[1] 6.86 / 6.90 ms without, 7.05 / 7.16 ms with; 32x32
-// (configs[3]) 1.58 against 1.61 ms -- the hand-over through the tile costs more than the address unit saves (the shifted
-// CWS passes, whose patches are (WS + 1)^2 and fetched twice per row otherwise, keep their chunk loads: CoopGeo).
-#ifndef TPIV_COOP1
-#define TPIV_COOP1 0
-#endif
-template <int WS>
-struct Coop1 {
-    static constexpr bool ON = TPIV_COOP1 && (WS == 64 || WS == 32);
-    static constexpr int P16 = WS / 16;                       // chunks per row = chunks per lane
-    static constexpr int PITCH4 = WS / 16 + 1;                // hand-over tile: 16-byte units per row (16-byte reads cover all banks)
-};
 template <int WS, int MODE>
 struct RawRows;
+// first pass: every lane loads its own row.  (Chunk loads by the window's lanes together, handed over through the idle tile
+// as in the CWS passes below, measured slower, same box, A B A B: locating pass of configs[1] 6.86 / 6.90 ms without, 7.05 /
+// 7.16 ms with; 32x32 (configs[3]) 1.58 against 1.61 ms -- the hand-over costs more than the address unit saves.)
 template <int WS>
 struct RawRows<WS, MODE_PASS1> {
     uint32_t a[WS / 4], b[WS / 4];
@@ -609,7 +538,7 @@ struct RawRows<WS, MODE_DWS> {
     int cls;             // per lane, 2 bits per row: 0 in frame, 1 entirely before it, 2 entirely behind it
     int fix;             // wave-uniform: some lane has a row of class 1 or 2
 };
-// CWS source patches, loaded by the window's lanes TOGETHER (tile sizes 16 and 32).  A shifted window reads
+// CWS source patches, loaded by the window's lanes TOGETHER (tile sizes 16, 32 and 64).  A shifted window reads
 // (WS+1) x (WS+1) source pixels per frame; with lane = row every load instruction touched 64 different rows,
 // i.e. 64-128 cache lines (TCP_TOTAL_CACHE_ACCESSES: 151 per load instruction against 58 in pass 1, about
 // one tag look-up per CU cycle over the whole kernel), each row was fetched twice (as the upper row of one
@@ -621,10 +550,6 @@ struct RawRows<WS, MODE_DWS> {
 // the two rows it interpolates between.
 template <int WS>
 struct CoopGeo {
-#ifndef TPIV_COOP
-#define TPIV_COOP 1
-#endif
-    static constexpr bool ON = TPIV_COOP && (WS == 16 || WS == 32 || WS == 64);
     static constexpr int NROW = WS + 1;                       // patch rows
     static constexpr int RPG = (WS + 1 + 15) / 16;            // 16-byte chunks loaded per row
     static constexpr int LOADED = 16 * RPG;                   // bytes loaded per row
@@ -640,7 +565,7 @@ struct CoopGeo {
     static constexpr int BLOCK4 = (2 * PATCH4 + 15) / 16 * 16;
     static constexpr int FLOATS = (64 / WS) * BLOCK4 * 4;     // all patches of a wavefront, in floats
     static constexpr int LDS_FLOATS = FLOATS + (64 / WS) * (WS + 1) * 4;      // + the x-weight tables
-    static_assert(!ON || RPG <= PITCH4, "patch row pitch");
+    static_assert(RPG <= PITCH4, "patch row pitch");
     __device__ static __forceinline__ void chunk(int ci, int& j, int& part) {
         if constexpr (RPG == 2) {
             j = ci >> 1;
@@ -658,26 +583,21 @@ struct CoopGeo {
 // loop-invariant part of a lane's chunk addresses: row * W + 16 * part (0 for the idle slots of the last round)
 template <int WS>
 struct CoopOff {
-    int o[CoopGeo<WS>::ON ? CoopGeo<WS>::NCH : 1];
+    int o[CoopGeo<WS>::NCH];
     __device__ __forceinline__ void init(int r, int W) {
-        if constexpr (CoopGeo<WS>::ON) {
 #pragma unroll
-            for (int k = 0; k < CoopGeo<WS>::NCH; ++k) {
-                int j, part;
-                CoopGeo<WS>::chunk(r + WS * k, j, part);
-                o[k] = r + WS * k < CoopGeo<WS>::T ? j * W + 16 * part : 0;
-            }
+        for (int k = 0; k < CoopGeo<WS>::NCH; ++k) {
+            int j, part;
+            CoopGeo<WS>::chunk(r + WS * k, j, part);
+            o[k] = r + WS * k < CoopGeo<WS>::T ? j * W + 16 * part : 0;
         }
     }
 };
 template <int WS>
 struct RawRows<WS, MODE_CWS> {
-    static constexpr int NB = WS / 4 + 1;
-    // WS+1 bytes per row, or the lane's share of the two patches
-    uint32_t a0[CoopGeo<WS>::ON ? 1 : NB], a1[CoopGeo<WS>::ON ? 1 : NB], b0[CoopGeo<WS>::ON ? 1 : NB], b1[CoopGeo<WS>::ON ? 1 : NB];
-    uint32_t ca[CoopGeo<WS>::ON ? CoopGeo<WS>::NCH : 1][4], cb[CoopGeo<WS>::ON ? CoopGeo<WS>::NCH : 1][4];
+    uint32_t ca[CoopGeo<WS>::NCH][4], cb[CoopGeo<WS>::NCH][4];      // the lane's share of the two patches
     int reg;
-    int cls;             // see above (rows a0, a1, b0, b1 in bits 0-1, 2-3, 4-5, 6-7)
+    int cls;             // see above (the lane's lower / upper row of frame a, then of frame b, in bits 0-1, 2-3, 4-5, 6-7)
     int fix;
 };
 
@@ -748,13 +668,6 @@ __device__ __forceinline__ void fix_row(uint32_t (&d)[N], int cls) {
 #pragma unroll
     for (int i = 0; i < N; ++i) d[i] = cls != 0 ? px : d[i];
 }
-// (patch rows: the last loaded byte of a row lies beyond the N dwords a lane holds; `last` = that dword)
-template <int N>
-__device__ __forceinline__ void fix_row(uint32_t (&d)[N], int cls, uint32_t last) {
-    const uint32_t px = (cls == 1 ? (d[0] & 0xffu) : (last >> 24)) * 0x01010101u;
-#pragma unroll
-    for (int i = 0; i < N; ++i) d[i] = cls != 0 ? px : d[i];
-}
 
 // The loads are issued UNCONDITIONALLY: a load under `if` makes the loaded registers the target of
 // a PHI copy, and the compiler then waits for the data right behind the load -- which would
@@ -768,35 +681,8 @@ __device__ __forceinline__ void issue_rows(const PassParams& p, const ItemGeom& 
     const uint8_t* __restrict__ fb = p.B + (size_t)g.pair * HW;
     const long long base = (long long)(g.y0 + r) * p.W + g.x0;
     if constexpr (MODE == MODE_PASS1) {
-        if constexpr (Coop1<WS>::ON) {
-            // rows LOADED by the window's lanes together (round 5): with lane = row every load instruction touches WS cache
-            // lines and the CU's address unit takes them one by one -- the stamps put 18 % of the 64x64 iteration on the issue
-            // of these eight loads.  Chunk ci = row * P16 + part of 16 bytes, lane r takes chunks r, r + WS, ...: consecutive
-            // lanes read consecutive pieces of a row (16 rows per instruction for 64-pixel rows); convert_rows hands the
-            // chunks over through the (idle) transposition tile and every lane gets its row back.
-            using C1 = Coop1<WS>;
-            const unsigned o0 = (unsigned)(g.y0 * p.W + g.x0);
-#pragma unroll
-            for (int k = 0; k < C1::P16; ++k) {
-                const int ci = r + WS * k, j = ci / C1::P16, part = ci % C1::P16;
-                const unsigned o_ = o0 + (unsigned)(j * p.W + 16 * part);
-                load_dwords<4>(fa + o_, *reinterpret_cast<uint32_t(*)[4]>(&raw.a[4 * k]));
-                load_dwords<4>(fb + o_, *reinterpret_cast<uint32_t(*)[4]>(&raw.b[4 * k]));
-            }
-        } else {
-#ifdef TPIV_EXP_P1LOADS      // timing experiment only (wrong results): TPIV_EXP_P1LOADS 16-byte loads per row and frame
-            load_dwords<4 * TPIV_EXP_P1LOADS>(fa + base, *reinterpret_cast<uint32_t(*)[4 * TPIV_EXP_P1LOADS]>(&raw.a[0]));
-            load_dwords<4 * TPIV_EXP_P1LOADS>(fb + base, *reinterpret_cast<uint32_t(*)[4 * TPIV_EXP_P1LOADS]>(&raw.b[0]));
-#pragma unroll
-            for (int k = 4 * TPIV_EXP_P1LOADS; k < WS / 4; ++k) {
-                raw.a[k] = 0x11213141u * (unsigned)(r + 1 + k);
-                raw.b[k] = 0x31112141u * (unsigned)(r + 3 + k);
-            }
-#else
-            load_dwords<WS / 4>(fa + base, raw.a);
-            load_dwords<WS / 4>(fb + base, raw.b);
-#endif
-        }
+        load_dwords<WS / 4>(fa + base, raw.a);
+        load_dwords<WS / 4>(fb + base, raw.b);
     } else if constexpr (MODE == MODE_DWS) {
         // integer shift on the FLAT index (B:213-215): a at idx - (vy*W + vx), b at idx + (...)
         const long long sh = (long long)vy * p.W + (long long)vx;
@@ -810,7 +696,6 @@ __device__ __forceinline__ void issue_rows(const PassParams& p, const ItemGeom& 
         load_dwords<WS / 4>(fa + (raw.reg ? la : base), raw.a);
         load_dwords<WS / 4>(fb + (raw.reg ? lb : base), raw.b);
     } else {
-        constexpr int NB = WS / 4 + 1;
         const CwsRow c = cws_row(g.y0 + r, vy);
         // Fast path: floor(float(gx) + vx) == gx + floor(vx) for every column, no column exactly integral
         // (the "nearest sample" quirk, B:170/193), and all four source rows inside the frame, so that a row is
@@ -832,7 +717,7 @@ __device__ __forceinline__ void issue_rows(const PassParams& p, const ItemGeom& 
         const int qa0 = dya * W_ + xa, qa1 = uya * W_ + xa;
         const int qb0 = dyb * W_ + xb, qb1 = uyb * W_ + xb;
         using CG = CoopGeo<WS>;
-        constexpr int LOADED = CG::ON ? CG::LOADED : 4 * NB;       // bytes a row load reads
+        constexpr int LOADED = CG::LOADED;       // bytes a row load reads
         // (FAST: an integral row coordinate -- B:170, B:193 return the nearest sample -- is left to the
         //  per-pixel path, which implements the quirk; the lerp form of convert_rows does not)
         const float gxr = (float)(g.x0 + r);
@@ -841,74 +726,60 @@ __device__ __forceinline__ void issue_rows(const PassParams& p, const ItemGeom& 
         const bool col_ok = fxa_r == (float)(g.x0 + r - ivx - 1) && fxb_r == (float)(g.x0 + r + ivx) &&
                             fxa_r != nxa_r && fxb_r != nxb_r;
         bool reg = col_ok && fabsf(vx) < (float)p.W && !(FAST && (c.ydeg_a | c.ydeg_b));
-        int la0 = 0, la1 = 0, lb0 = 0, lb1 = 0, cls = 0;
+        int cls = 0;
         auto classify_own = [&]() TPIV_LAMBDA_INLINE {       // the lane's four rows under the flat-index clamp
+            int la0, la1, lb0, lb1;
             const int c0 = classify_row32(qa0, WS + 1, LOADED, HW, la0), c1 = classify_row32(qa1, WS + 1, LOADED, HW, la1);
             const int c2 = classify_row32(qb0, WS + 1, LOADED, HW, lb0), c3 = classify_row32(qb1, WS + 1, LOADED, HW, lb1);
             reg = reg && c0 != 3 && c1 != 3 && c2 != 3 && c3 != 3;
             cls = c0 | (c1 << 2) | (c2 << 4) | (c3 << 6);
         };
-        if constexpr (CG::ON) {
-            // the window's patches start at the (clamped) lower source row of its row 0; a lane's two rows must
-            // lie inside them (they do unless float32 rounding makes the row coordinates jump)
-            const float gy0f = (float)g.y0;
-            const int base_a = clamp_i(f2i_sat_t(floorf(gy0f - vy)), rlo, rhi);
-            const int base_b = clamp_i(f2i_sat_t(floorf(gy0f + vy)), rlo, rhi);
-            reg = reg && (unsigned)(dya - base_a) <= (unsigned)WS && (unsigned)(uya - base_a) <= (unsigned)WS &&
-                  (unsigned)(dyb - base_b) <= (unsigned)WS && (unsigned)(uyb - base_b) <= (unsigned)WS;
-            // Wavefronts whose patches lie inside the frame with LOADED bytes to spare in every row (all but the
-            // border windows) add the loop-invariant chunk offsets to the patch origin -- and every row a lane
-            // may use is an ordinary row (class 0); the others classify every chunk's row like a lane's own rows
-            // (the first version did that always: +160 VALU instructions per item).  Only ADDRESSES differ
-            // between the branches: the loads stay unconditional.
-            const bool inside = base_a >= 0 && base_a + WS < p.H && base_b >= 0 && base_b + WS < p.H &&
-                                xa >= 0 && xa + LOADED <= W_ && xb >= 0 && xb + LOADED <= W_;
-            const bool all_in = __all(inside);
-            if (!all_in) classify_own();
-            raw.reg = __all(reg) ? 1 : 0;
-            raw.cls = cls;
-            raw.fix = (raw.reg && __any(raw.cls != 0)) ? 1 : 0;
-            unsigned oa[CG::NCH], ob[CG::NCH];
-            if (all_in) {
-                const int qa_o = base_a * W_ + xa, qb_o = base_b * W_ + xb;
-#pragma unroll
-                for (int k = 0; k < CG::NCH; ++k) {
-                    oa[k] = (unsigned)(qa_o + coff.o[k]);
-                    ob[k] = (unsigned)(qb_o + coff.o[k]);
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < CG::NCH; ++k) {
-                    const int ci = r + WS * k;
-                    int j, part;
-                    CG::chunk(ci, j, part);
-                    int qa_l, qb_l;
-                    const int ra = clamp_i(base_a + j, rlo, rhi), rb = clamp_i(base_b + j, rlo, rhi);
-                    classify_row32(ra * W_ + xa, WS + 1, LOADED, HW, qa_l);
-                    classify_row32(rb * W_ + xb, WS + 1, LOADED, HW, qb_l);
-                    const bool live = ci < CG::T;                  // (the last chunk round is partly idle)
-                    oa[k] = live ? (unsigned)(qa_l + 16 * part) : 0u;
-                    ob[k] = live ? (unsigned)(qb_l + 16 * part) : 0u;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < CG::NCH; ++k) {
-                load_dwords<4>(fa + oa[k], raw.ca[k]);
-                load_dwords<4>(fb + ob[k], raw.cb[k]);
-            }
-        } else {
-        classify_own();
+        // the window's patches start at the (clamped) lower source row of its row 0; a lane's two rows must
+        // lie inside them (they do unless float32 rounding makes the row coordinates jump)
+        const float gy0f = (float)g.y0;
+        const int base_a = clamp_i(f2i_sat_t(floorf(gy0f - vy)), rlo, rhi);
+        const int base_b = clamp_i(f2i_sat_t(floorf(gy0f + vy)), rlo, rhi);
+        reg = reg && (unsigned)(dya - base_a) <= (unsigned)WS && (unsigned)(uya - base_a) <= (unsigned)WS &&
+              (unsigned)(dyb - base_b) <= (unsigned)WS && (unsigned)(uyb - base_b) <= (unsigned)WS;
+        // Wavefronts whose patches lie inside the frame with LOADED bytes to spare in every row (all but the
+        // border windows) add the loop-invariant chunk offsets to the patch origin -- and every row a lane
+        // may use is an ordinary row (class 0); the others classify every chunk's row like a lane's own rows
+        // (the first version did that always: +160 VALU instructions per item).  Only ADDRESSES differ
+        // between the branches: the loads stay unconditional.
+        const bool inside = base_a >= 0 && base_a + WS < p.H && base_b >= 0 && base_b + WS < p.H &&
+                            xa >= 0 && xa + LOADED <= W_ && xb >= 0 && xb + LOADED <= W_;
+        const bool all_in = __all(inside);
+        if (!all_in) classify_own();
         raw.reg = __all(reg) ? 1 : 0;
         raw.cls = cls;
         raw.fix = (raw.reg && __any(raw.cls != 0)) ? 1 : 0;
-        const int lim = HW - 4 * NB;
-        const int base32 = (g.y0 + r) * W_ + g.x0;
-        const int safe = base32 < lim ? base32 : lim;
-        // (unsigned 32-bit offsets from the wave-uniform frame pointers: scalar base + VGPR offset loads)
-        load_dwords<NB>(fa + (unsigned)(raw.reg ? la0 : safe), raw.a0);
-        load_dwords<NB>(fa + (unsigned)(raw.reg ? la1 : safe), raw.a1);
-        load_dwords<NB>(fb + (unsigned)(raw.reg ? lb0 : safe), raw.b0);
-        load_dwords<NB>(fb + (unsigned)(raw.reg ? lb1 : safe), raw.b1);
+        unsigned oa[CG::NCH], ob[CG::NCH];
+        if (all_in) {
+            const int qa_o = base_a * W_ + xa, qb_o = base_b * W_ + xb;
+#pragma unroll
+            for (int k = 0; k < CG::NCH; ++k) {
+                oa[k] = (unsigned)(qa_o + coff.o[k]);
+                ob[k] = (unsigned)(qb_o + coff.o[k]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < CG::NCH; ++k) {
+                const int ci = r + WS * k;
+                int j, part;
+                CG::chunk(ci, j, part);
+                int qa_l, qb_l;
+                const int ra = clamp_i(base_a + j, rlo, rhi), rb = clamp_i(base_b + j, rlo, rhi);
+                classify_row32(ra * W_ + xa, WS + 1, LOADED, HW, qa_l);
+                classify_row32(rb * W_ + xb, WS + 1, LOADED, HW, qb_l);
+                const bool live = ci < CG::T;                  // (the last chunk round is partly idle)
+                oa[k] = live ? (unsigned)(qa_l + 16 * part) : 0u;
+                ob[k] = live ? (unsigned)(qb_l + 16 * part) : 0u;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < CG::NCH; ++k) {
+            load_dwords<4>(fa + oa[k], raw.ca[k]);
+            load_dwords<4>(fb + ob[k], raw.cb[k]);
         }
     }
 }
@@ -946,32 +817,10 @@ __device__ __forceinline__ void convert_rows(const PassParams& p, const ItemGeom
     static constexpr int RBL = WS / RBH;       // row-buffer length
     float* rowbuf = lds + lane * (RBL + 1);    // slow paths only
     // The rare per-pixel paths must not set the register budget of the small tiles (unrolled, their
-    // gathers keep a 64-bit address per load in flight: 135 VGPRs for an 8x8 kernel whose fast path
-    // needs about 60), so they are fully rolled there.
+    // gathers keep a 64-bit address per load in flight: 135 VGPRs for the 8x8 shifted-pass instance of old, whose fast
+    // path needed about 60; 8x8 shifted passes run xcorr_w8.hip now), so they are fully rolled there.
     static constexpr int UNR_DWS = WS <= 16 ? 1 : 4, UNR_CWS = WS <= 16 ? 1 : 2;
     if constexpr (MODE == MODE_PASS1) {
-        if constexpr (Coop1<WS>::ON) {
-            // chunks -> tile -> the lane's own row, one frame at a time (the tile is idle until the first transposition)
-            using C1 = Coop1<WS>;
-            uint4* const t4 = reinterpret_cast<uint4*>(lds) + (lane / WS) * (WS * C1::PITCH4);
-            auto hand_over = [&](uint32_t (&d)[WS / 4]) TPIV_LAMBDA_INLINE {
-                wave_sync();
-#pragma unroll
-                for (int k = 0; k < C1::P16; ++k) {
-                    const int ci = r + WS * k, j = ci / C1::P16, part = ci % C1::P16;
-                    t4[j * C1::PITCH4 + part] = make_uint4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
-                }
-                wave_sync();
-#pragma unroll
-                for (int k = 0; k < C1::P16; ++k) {
-                    const uint4 v = t4[r * C1::PITCH4 + k];
-                    d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
-                }
-            };
-            hand_over(raw.a);
-            hand_over(raw.b);
-            wave_sync();
-        }
         unsigned ia = 0, ib = 0;
 #pragma unroll
         for (int q = 0; q < WS / 4; ++q) {
@@ -1039,84 +888,73 @@ __device__ __forceinline__ void convert_rows(const PassParams& p, const ItemGeom
         if (PATH == 1 || raw.reg) {
             uint32_t ra0[NB], ra1[NB], rb0[NB], rb1[NB];
             const uint4 *lz0 = nullptr, *lz1 = nullptr, *lz2 = nullptr, *lz3 = nullptr;
-            if constexpr (CG::ON) {
-                // the chunks go to LDS, the lane's rows come back (same wavefront: program order is enough)
-                uint4* pl = reinterpret_cast<uint4*>(lds);
-                const int w_ = lane / WS;
-                uint4* pa = pl + w_ * CG::BLOCK4;
-                uint4* pb = pa + CG::PATCH4;
-                wave_sync();
+            // the chunks go to LDS, the lane's rows come back (same wavefront: program order is enough)
+            uint4* pl = reinterpret_cast<uint4*>(lds);
+            const int w_ = lane / WS;
+            uint4* pa = pl + w_ * CG::BLOCK4;
+            uint4* pb = pa + CG::PATCH4;
+            wave_sync();
 #pragma unroll
-                for (int k = 0; k < CG::NCH; ++k) {
-                    const int ci = r + WS * k;
-                    int j, part;
-                    CG::chunk(ci, j, part);
-                    if (ci < CG::T) {
-                        pa[j * CG::PITCH4 + part] = make_uint4(raw.ca[k][0], raw.ca[k][1], raw.ca[k][2], raw.ca[k][3]);
-                        pb[j * CG::PITCH4 + part] = make_uint4(raw.cb[k][0], raw.cb[k][1], raw.cb[k][2], raw.cb[k][3]);
-                    }
+            for (int k = 0; k < CG::NCH; ++k) {
+                const int ci = r + WS * k;
+                int j, part;
+                CG::chunk(ci, j, part);
+                if (ci < CG::T) {
+                    pa[j * CG::PITCH4 + part] = make_uint4(raw.ca[k][0], raw.ca[k][1], raw.ca[k][2], raw.ca[k][3]);
+                    pb[j * CG::PITCH4 + part] = make_uint4(raw.cb[k][0], raw.cb[k][1], raw.cb[k][2], raw.cb[k][3]);
                 }
-                wave_sync();
-                const int rlo = -8, rhi = p.H + 7;
-                const float gy0f = (float)g.y0;
-                const int base_a = clamp_i(f2i_sat_t(floorf(gy0f - vy)), rlo, rhi);
-                const int base_b = clamp_i(f2i_sat_t(floorf(gy0f + vy)), rlo, rhi);
-                const uint4* s0 = pa + (clamp_i(c.dya, rlo, rhi) - base_a) * CG::PITCH4;
-                const uint4* s1 = pa + (clamp_i(c.uya, rlo, rhi) - base_a) * CG::PITCH4;
-                const uint4* s2 = pb + (clamp_i(c.dyb, rlo, rhi) - base_b) * CG::PITCH4;
-                const uint4* s3 = pb + (clamp_i(c.uyb, rlo, rhi) - base_b) * CG::PITCH4;
-                auto fetch = [&](const uint4* src, uint32_t (&d)[NB]) TPIV_LAMBDA_INLINE {
+            }
+            wave_sync();
+            const int rlo = -8, rhi = p.H + 7;
+            const float gy0f = (float)g.y0;
+            const int base_a = clamp_i(f2i_sat_t(floorf(gy0f - vy)), rlo, rhi);
+            const int base_b = clamp_i(f2i_sat_t(floorf(gy0f + vy)), rlo, rhi);
+            const uint4* s0 = pa + (clamp_i(c.dya, rlo, rhi) - base_a) * CG::PITCH4;
+            const uint4* s1 = pa + (clamp_i(c.uya, rlo, rhi) - base_a) * CG::PITCH4;
+            const uint4* s2 = pb + (clamp_i(c.dyb, rlo, rhi) - base_b) * CG::PITCH4;
+            const uint4* s3 = pb + (clamp_i(c.uyb, rlo, rhi) - base_b) * CG::PITCH4;
+            auto fetch = [&](const uint4* src, uint32_t (&d)[NB]) TPIV_LAMBDA_INLINE {
 #pragma unroll
-                    for (int q = 0; q < NB / 4; ++q) {
-                        const uint4 t = src[q];
-                        d[4 * q] = t.x, d[4 * q + 1] = t.y, d[4 * q + 2] = t.z, d[4 * q + 3] = t.w;
+                for (int q = 0; q < NB / 4; ++q) {
+                    const uint4 t = src[q];
+                    d[4 * q] = t.x, d[4 * q + 1] = t.y, d[4 * q + 2] = t.z, d[4 * q + 3] = t.w;
+                }
+                // NB = 4 m + 1: the last dword comes with one more 16-byte read (the row holds RPG = m + 1 units) -- a
+                // ds_read_b32 at a row pitch of 12 dwords is 4-way bank-conflicted
+                static_assert(CG::RPG * 4 >= NB, "patch rows hold the whole 16-byte unit of the last dword");
+                d[NB - 1] = read_unit_x(src + NB / 4);
+            };
+            if (raw.fix) {
+                // border windows: a source row entirely outside the frame reads the first / last pixel of the
+                // frame everywhere (flat-index clamp).  Its chunks were loaded from the start / the end of the
+                // frame; the lanes that use such a row overwrite it with that pixel (several lanes may write
+                // the same row: same bytes, and the pixel survives the overwrite)
+                constexpr int LAST = CG::LOADED / 4 - 1;       // dword that holds the last loaded byte
+                auto fix_lds = [&](const uint4* src, int cls) TPIV_LAMBDA_INLINE {
+                    if (cls != 0) {
+                        const uint32_t* sw = reinterpret_cast<const uint32_t*>(src);
+                        const uint32_t px = (cls == 1 ? (sw[0] & 0xffu) : (sw[LAST] >> 24)) * 0x01010101u;
+                        uint4* dst = const_cast<uint4*>(src);
+#pragma unroll
+                        for (int q = 0; q < CG::RPG; ++q) dst[q] = make_uint4(px, px, px, px);
                     }
-                    // NB = 4 m + 1: the last dword comes with one more 16-byte read (the row holds RPG = m + 1 units) -- a
-                    // ds_read_b32 at a row pitch of 12 dwords is 4-way bank-conflicted
-                    static_assert(CG::RPG * 4 >= NB, "patch rows hold the whole 16-byte unit of the last dword");
-                    d[NB - 1] = read_unit_x(src + NB / 4);
                 };
-                if (raw.fix) {
-                    // border windows: a source row entirely outside the frame reads the first / last pixel of the
-                    // frame everywhere (flat-index clamp).  Its chunks were loaded from the start / the end of the
-                    // frame; the lanes that use such a row overwrite it with that pixel (several lanes may write
-                    // the same row: same bytes, and the pixel survives the overwrite)
-                    constexpr int LAST = CG::LOADED / 4 - 1;       // dword that holds the last loaded byte
-                    auto fix_lds = [&](const uint4* src, int cls) TPIV_LAMBDA_INLINE {
-                        if (cls != 0) {
-                            const uint32_t* sw = reinterpret_cast<const uint32_t*>(src);
-                            const uint32_t px = (cls == 1 ? (sw[0] & 0xffu) : (sw[LAST] >> 24)) * 0x01010101u;
-                            uint4* dst = const_cast<uint4*>(src);
-#pragma unroll
-                            for (int q = 0; q < CG::RPG; ++q) dst[q] = make_uint4(px, px, px, px);
-                        }
-                    };
-                    fix_lds(s0, raw.cls & 3);
-                    fix_lds(s1, (raw.cls >> 2) & 3);
-                    fix_lds(s2, (raw.cls >> 4) & 3);
-                    fix_lds(s3, (raw.cls >> 6) & 3);
-                    wave_sync();
-                }
-                // (64x64, fast form: the rows come out of LDS 16 pixels at a time inside the sampling loop --
-                //  four whole rows are 68 registers next to the 128 of the samples)
-                constexpr bool LAZY = FAST && WS == 64;
-                if constexpr (LAZY) {
-                    lz0 = s0, lz1 = s1, lz2 = s2, lz3 = s3;
-                } else {
-                    fetch(s0, ra0);
-                    fetch(s1, ra1);
-                    fetch(s2, rb0);
-                    fetch(s3, rb1);
-                }
+                fix_lds(s0, raw.cls & 3);
+                fix_lds(s1, (raw.cls >> 2) & 3);
+                fix_lds(s2, (raw.cls >> 4) & 3);
+                fix_lds(s3, (raw.cls >> 6) & 3);
+                wave_sync();
+            }
+            // (64x64, fast form: the rows come out of LDS 16 pixels at a time inside the sampling loop --
+            //  four whole rows are 68 registers next to the 128 of the samples)
+            constexpr bool LAZY = FAST && WS == 64;
+            if constexpr (LAZY) {
+                lz0 = s0, lz1 = s1, lz2 = s2, lz3 = s3;
             } else {
-#pragma unroll
-                for (int q = 0; q < NB; ++q) ra0[q] = raw.a0[q], ra1[q] = raw.a1[q], rb0[q] = raw.b0[q], rb1[q] = raw.b1[q];
-                if (raw.fix) {            // border windows: rows entirely outside the frame
-                    fix_row(ra0, raw.cls & 3);
-                    fix_row(ra1, (raw.cls >> 2) & 3);
-                    fix_row(rb0, (raw.cls >> 4) & 3);
-                    fix_row(rb1, (raw.cls >> 6) & 3);
-                }
+                fetch(s0, ra0);
+                fetch(s1, ra1);
+                fetch(s2, rb0);
+                fetch(s3, rb1);
             }
             // The x-direction weights depend on the column only (same for every row of the
             // window): lane r evaluates them for column r exactly as B:164-171 does and parks
@@ -1125,7 +963,7 @@ __device__ __forceinline__ void convert_rows(const PassParams& p, const ItemGeom
             // never "integral" (only the row can be, ydeg_*).
             // (one spare float4 per window: without it the 64 / WS windows' tables start a multiple of 256 bytes
             //  apart and their broadcast reads hit the same banks -- a 4-way conflict on every read for 16x16)
-            float4* wbuf = reinterpret_cast<float4*>(lds + (CG::ON ? CG::FLOATS : 0)) + (lane / WS) * (WS + 1);
+            float4* wbuf = reinterpret_cast<float4*>(lds + CG::FLOATS) + (lane / WS) * (WS + 1);
             {
                 const float gxf = gx0f + (float)r;               // exact: small integers
                 const float nxa = gxf - vx, nxb = gxf + vx;
@@ -1140,7 +978,7 @@ __device__ __forceinline__ void convert_rows(const PassParams& p, const ItemGeom
             if constexpr (FAST) {
                 // rows first, then columns: the WS + 1 column values of the row lerp are each used by two
                 // output samples (130 instead of 192 multiply/add instructions per frame and lane)
-                constexpr bool LAZY = CG::ON && WS == 64;
+                constexpr bool LAZY = WS == 64;
                 auto pull = [&](auto qc) TPIV_LAMBDA_INLINE {      // 16-byte unit q of the four rows (or the last dword)
                     constexpr int q = decltype(qc)::value;
                     auto one = [&](const uint4* src, uint32_t (&d)[NB]) TPIV_LAMBDA_INLINE {
@@ -1157,26 +995,25 @@ __device__ __forceinline__ void convert_rows(const PassParams& p, const ItemGeom
                     pull(std::integral_constant<int, 0>{});
                     pull(std::integral_constant<int, 1>{});
                 }
-                // (TPIV_SDWA_LERP: the upper row's byte enters its product as a float32 denormal -- see byte_d -- and every sample
-                //  of the wavefront carries the factor 2^-24 from here on: folded into end_scale by the kernel)
-                constexpr bool SD = TPIV_SDWA_LERP != 0;
-                const float wau = SD ? c.wya_up * SDWA_UP : c.wya_up, wad = SD ? c.wya_dn * SDWA_DN : c.wya_dn;
-                const float wbu = SD ? c.wyb_up * SDWA_UP : c.wyb_up, wbd = SD ? c.wyb_dn * SDWA_DN : c.wyb_dn;
+                // (Each byte is converted on its own, v_cvt_f32_ubyteN.  Folding the upper row's conversion into its multiply --
+                //  the byte reinterpreted as a float32 denormal, v_mul_f32_sdwa src_sel:BYTE_k, the weight carrying 2^125 -- was
+                //  built and measured, same box, A B A B, results bit-identical: the 32x32 CWS pass took 7.27 / 7.33 ms against 7.19
+                //  / 7.26, the 64x64 CWS pass 2.35 against 2.27, the 16x16 pass 1.93 against 1.91 -- a multiply with a denormal (or
+                //  SDWA) operand is not a full-rate instruction on this chip.)
                 auto row_lerp = [&](auto kc, const uint32_t (&r0_)[NB], const uint32_t (&r1_)[NB], float wu_, float wd_) TPIV_LAMBDA_INLINE {
                     constexpr int k = decltype(kc)::value;
-                    if constexpr (SD) return fmaf(byte_f<k, NB>(r1_), wd_, byte_d<k, NB>(r0_) * wu_);
-                    else return fmaf(byte_f<k, NB>(r1_), wd_, byte_f<k, NB>(r0_) * wu_);
+                    return fmaf(byte_f<k, NB>(r1_), wd_, byte_f<k, NB>(r0_) * wu_);
                 };
-                float va = row_lerp(std::integral_constant<int, 0>{}, ra0, ra1, wau, wad);
-                float vb = row_lerp(std::integral_constant<int, 0>{}, rb0, rb1, wbu, wbd);
+                float va = row_lerp(std::integral_constant<int, 0>{}, ra0, ra1, c.wya_up, c.wya_dn);
+                float vb = row_lerp(std::integral_constant<int, 0>{}, rb0, rb1, c.wyb_up, c.wyb_dn);
                 static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
                     constexpr int k = decltype(kc)::value;
                     if constexpr (k % 8 == 0 && k > 0) __builtin_amdgcn_sched_barrier(0);
                     // dwords 4b .. 4b + 4 serve pixels 16b .. 16b + 15 (+1): unit b + 1 arrives at pixel 16b
                     if constexpr (LAZY && k % 16 == 0 && k > 0) pull(std::integral_constant<int, k / 16 + 1>{});
                     const float4 wx = wbuf[k];
-                    const float na = row_lerp(std::integral_constant<int, k + 1>{}, ra0, ra1, wau, wad);
-                    const float nb = row_lerp(std::integral_constant<int, k + 1>{}, rb0, rb1, wbu, wbd);
+                    const float na = row_lerp(std::integral_constant<int, k + 1>{}, ra0, ra1, c.wya_up, c.wya_dn);
+                    const float nb = row_lerp(std::integral_constant<int, k + 1>{}, rb0, rb1, c.wyb_up, c.wyb_dn);
 #ifdef TPIV_MUTANT_LERP
                     // tests only (tools/diag/libtorchpiv_hip_mutant.so, never shipped): one weight of the column
                     // lerp off by 1e-3 -- the parity gates must notice (tests/test_gpu_gates.py)
@@ -1220,7 +1057,7 @@ __device__ __forceinline__ void convert_rows(const PassParams& p, const ItemGeom
                                        nxa - dxa_f, c.wya_up, c.wya_dn, c.ydeg_a || (uxa == dxa));
             }
 #pragma unroll
-            for (int k = 0; k < RBL; ++k) x[k0 + k].x = (FAST && TPIV_SDWA_LERP) ? rowbuf[k] * SDWA_DN : rowbuf[k];
+            for (int k = 0; k < RBL; ++k) x[k0 + k].x = rowbuf[k];
 #pragma unroll UNR_CWS
             for (int k = 0; k < RBL; ++k) {
                 const float nxb = (gx0f + (float)(k0 + k)) + vx;
@@ -1233,7 +1070,7 @@ __device__ __forceinline__ void convert_rows(const PassParams& p, const ItemGeom
                                        nxb - dxb_f, c.wyb_up, c.wyb_dn, c.ydeg_b || (uxb == dxb));
             }
 #pragma unroll
-            for (int k = 0; k < RBL; ++k) x[k0 + k].y = (FAST && TPIV_SDWA_LERP) ? rowbuf[k] * SDWA_DN : rowbuf[k];
+            for (int k = 0; k < RBL; ++k) x[k0 + k].y = rowbuf[k];
             });
             wave_sync();
         }
@@ -1595,18 +1432,15 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
     constexpr int RBH = 64 * (WS + 1) <= G::LDS_FLOATS ? 1 : 2;      // slow-path row buffer pieces
     static_assert(MODE == MODE_PASS1 || 64 * (WS / RBH + 1) <= G::LDS_FLOATS,
                   "slow-path row buffer (shifted passes) must fit the tile LDS");
-    constexpr int LDSF = (MODE == MODE_CWS && CoopGeo<WS>::ON && CoopGeo<WS>::LDS_FLOATS > G::LDS_FLOATS)
+    constexpr int LDSF = (MODE == MODE_CWS && CoopGeo<WS>::LDS_FLOATS > G::LDS_FLOATS)
                              ? CoopGeo<WS>::LDS_FLOATS : G::LDS_FLOATS;
     __shared__ __attribute__((aligned(16))) float tile[LDSF];
 
     // 16x16 has registers to spare: its twiddle constants live in VGPRs (plain 4-byte VOP2 multiplies
     // instead of 8-byte literal forms and half-rate SGPR operands): 169 -> 158 us/pair
     // for the 16x16 CWS pass at 4096^2.  For 32x32 the same change measured 1.3 % SLOWER in a
-    // same-box A/B (36.1 vs 35.6 us/pair; 14 more live VGPRs), so it stays off there.
-#ifndef TPIV_TWREG32
-#define TPIV_TWREG32 0
-#endif
-    using TW = std::conditional_t<((WS == 32 && TPIV_TWREG32) || WS == 16), TwRegs<WS>, TwLiteral>;
+    // same-box A/B (36.1 vs 35.6 us/pair; 14 more live VGPRs), so 32x32 keeps the literals.
+    using TW = std::conditional_t<WS == 16, TwRegs<WS>, TwLiteral>;
     TW tw;
     if constexpr (!std::is_same<TW, TwLiteral>::value) tw.init();
 
@@ -1760,12 +1594,10 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
             int rr = r;
             asm volatile("" : "+v"(rr));
             float* d = p.dbg_win + fidx * 2 * WS * WS + rr * WS;
-            // (fast-order CWS samples carry 2^-24, see byte_d)
-            constexpr float UNS = (MODE == MODE_CWS && FAST && TPIV_SDWA_LERP) ? SDWA_INV : 1.0f;
 #pragma unroll
             for (int k = 0; k < WS; ++k) {
-                d[k] = x[k].x * UNS;
-                d[WS * WS + k] = x[k].y * UNS;
+                d[k] = x[k].x;
+                d[WS * WS + k] = x[k].y;
             }
         }
 
@@ -1778,7 +1610,7 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
         // keeps the mean removal in front of the transform (128 fma per 64x64 window row, 2 % of the pass).
         // The shifted passes are float32 in the reference itself, with the full pedestal in both transforms.
         constexpr bool FASTN = FAST && MODE != MODE_PASS1;
-        // ---- Swap-free first transposition (64x64, TPIV_NOSWAP64; see transpose_tile).  Two shift theorems stand in for the
+        // ---- Swap-free first transposition (64x64; see transpose_tile).  Two shift theorems stand in for the
         //      lane-half swaps.  (1) Lanes 32..63 (rows 32..63) negate their odd samples, x'[n] = (-1)^n x[n]: their row
         //      transform holds bin (k + 32) mod 64 where it would hold bin k, i.e. every lane has the spectrum block of its OWN
         //      lane half in the low positions.  (2) The transposition then leaves lanes 32..63 (columns 32..63) with their
@@ -1791,7 +1623,7 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
         //      bound of the locating pass's band counts levels, not paths: DESIGN.md 3.4b, "Swap-free first transposition").
         //      The fast-order DWS instance keeps the swapped form: there the input sign is 64 separate XORs (byte
         //      conversions carry no constant to ride on) and the instance gains four spilled registers at its 168-VGPR cap.
-        constexpr bool NOSWAP = WS == 64 && TPIV_NOSWAP64 != 0 && !EXP_NOSWAP_CEIL && !(MODE == MODE_DWS && FAST);
+        constexpr bool NOSWAP = WS == 64 && !(MODE == MODE_DWS && FAST);
         auto up_sign = []() TPIV_LAMBDA_INLINE { return fresh_lane() >= 32 ? 0x80000000u : 0u; };
         auto sflip = [](float v, unsigned sg) TPIV_LAMBDA_INLINE { return __uint_as_float(__float_as_uint(v) ^ sg); };
         if constexpr (!FASTN) {
@@ -1871,11 +1703,10 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
                 x[P0].y -= tb * (1.0f / WS);
             }
             end_scale = 0.25f / (float)(WS * WS);
-            if constexpr (MODE == MODE_CWS && TPIV_SDWA_LERP) end_scale *= SDWA_INV * SDWA_INV;     // both frames' samples carry 2^-24
         }
         TPIV_STAMP(3);      // forward row FFT
         // lane = kx, x[y] natural (NOSWAP, lanes 32..63: x[y] = row y + 32)
-        transpose_tile<WS, true, PLANAR, NOSWAP ? 1 : ((EXP_NOSWAP_CEIL && WS == 64) ? 2 : 0)>(x, tile, fresh_lane());
+        transpose_tile<WS, PLANAR, NOSWAP>(x, tile, fresh_lane());
         TPIV_STAMP(4);      // transposition 1
         fft_inreg<WS, 1>(x, tw);                          // over y; Z(ky, kx = lane) at x[FFT_POS<ky>]
         TPIV_STAMP(5);      // forward column FFT
@@ -1889,20 +1720,7 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
         //        lanes 0, WS/2 (their own mirrors: real columns, partner = self): the c2r form of the column,
         //          (P(k) + conj P(WS/2 - k)) + i w^k (P(k) - conj P(WS/2 - k))  -> t(2m) + i t(2m + 1)
         //      with P(k + WS/2) = conj P_partner(WS/2 - k).  Half the products, half the column transform (w = exp(2 pi i / WS)).
-#ifndef TPIV_C2R
-#define TPIV_C2R 1
-#endif
-#ifndef TPIV_C2R64
-#define TPIV_C2R64 1
-#endif
-#ifndef TPIV_HALF_INV64
-#define TPIV_HALF_INV64 1
-#endif
-#ifndef TPIV_HALF_INV32
-#define TPIV_HALF_INV32 1
-#endif
-        constexpr bool HALF_INV = PLANAR && TPIV_C2R &&
-                                  ((WS == 64 && TPIV_C2R64 && TPIV_HALF_INV64) || (WS == 32 && TPIV_HALF_INV32));
+        constexpr bool HALF_INV = PLANAR && (WS == 32 || WS == 64);
         float crow[WS];
         if constexpr (HALF_INV) {
             constexpr int M = WS / 2;
@@ -2004,31 +1822,16 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
             });
             fft_inreg<WS, -1>(t, tw);                         // over ky; row y at t[FFT_POS<y>]
             TPIV_STAMP(7);      // inverse column FFT
-            // (64x64: the planar three-wavefront kernels take the c2r form too -- round 1 and the first try of round 2
-            //  ended in 32-42 spills at the 168-VGPR cap, which were the compiler sinking the tail of the column
-            //  transform into the conditional stores of transpose_half; with the values pinned in front of the branch
-            //  the kernel keeps its one spill and pass 1 went from 6.94 to 6.42 ms per 256 pairs.  The complex-tile
-            //  64x64 CWS kernel keeps the complex last transform.)
-            if constexpr (TPIV_C2R && (WS <= 32 || (TPIV_C2R64 && WS == 64))) {
-                // the map rows are real: only spectrum columns 0..WS/2 cross the LDS and a WS/2-point complex
-                // transform yields the row as z[m] = corr(y, 2m) + i corr(y, 2m + 1)  (c2r_inreg)
-                cf hs[WS / 2 + 1], z[WS / 2];
-                transpose_half<WS, PLANAR>(t, hs, tile, fresh_lane());
-                TPIV_STAMP(8);      // transposition 2
-                c2r_inreg<WS>(hs, z);
-                static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
-                    constexpr int x_ = decltype(xc)::value;
-                    crow[x_] = (x_ & 1) ? z[FFT_POS<x_ / 2, WS / 2>].y : z[FFT_POS<x_ / 2, WS / 2>].x;
-                });
-            } else {
-                transpose_tile<WS, true, PLANAR>(t, tile, fresh_lane());  // lane = y, t[kx] natural
-                TPIV_STAMP(8);      // transposition 2
-                fft_inreg<WS, -1>(t, tw);                     // over kx; corr(y = lane, x) at t[FFT_POS<x>].x
-                static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
-                    constexpr int x_ = decltype(xc)::value;
-                    crow[x_] = t[FFT_POS<x_, WS>].x;
-                });
-            }
+            // the map rows are real: only spectrum columns 0..WS/2 cross the LDS and a WS/2-point complex
+            // transform yields the row as z[m] = corr(y, 2m) + i corr(y, 2m + 1)  (c2r_inreg)
+            cf hs[WS / 2 + 1], z[WS / 2];
+            transpose_half<WS, PLANAR>(t, hs, tile, fresh_lane());
+            TPIV_STAMP(8);      // transposition 2
+            c2r_inreg<WS>(hs, z);
+            static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
+                constexpr int x_ = decltype(xc)::value;
+                crow[x_] = (x_ & 1) ? z[FFT_POS<x_ / 2, WS / 2>].y : z[FFT_POS<x_ / 2, WS / 2>].x;
+            });
         }
         wave_sync();                                  // tile reads done: it becomes the map
         TPIV_STAMP(9);      // inverse row FFT
@@ -2117,79 +1920,58 @@ hipError_t launch_peak_debug(const PassParams& p, const float* maps, int n_maps,
     return hipGetLastError();
 }
 
-template <int WS, int MODE>
-static hipError_t launch_tile(const PassParams& p_in, int n_cu, hipStream_t stream) {
+// What the launchers below share: the item count, the two magic divisions of the kernel's index arithmetic (into p) and
+// the grid size.  0 = the item count is out of range.
+// Up to 64 single-wavefront workgroups per CU; each pulls items from its XCD's counter until the
+// run is empty, so surplus workgroups exit at once and the grid size only has to cover the
+// resident set.  (History: with a static grid-stride order 64/CU beat the exact resident set,
+// 98.2 vs 104.5 us/pair, because of dynamic balancing, but spread every XCD over its whole run:
+// FETCH_SIZE was 1.5x (pass 1) to 3x (pass 2) the algorithmic bytes.  The queue keeps both.)
+template <int WS>
+static unsigned tile_grid(PassParams& p, int n_cu) {
     using G = TileGeo<WS>;
-    PassParams p = p_in;
     const int N = p.n_rows * p.n_cols;
     const long long groups = (N + G::WPW - 1) / G::WPW;
     const long long items = (long long)p.batch * groups;
-    if (items <= 0 || items >= (1ll << 31) - 64) return hipErrorInvalidValue;     // 32-bit item arithmetic
+    if (items <= 0 || items >= (1ll << 31) - 64) return 0;     // 32-bit item arithmetic
     fast_div_setup((unsigned)groups, p.groups_magic, p.groups_shift);
     fast_div_setup((unsigned)p.n_cols, p.ncols_magic, p.ncols_shift);
-    long long blocks = items;
-    // Up to 64 single-wavefront workgroups per CU; each pulls items from its XCD's counter until the
-    // run is empty, so surplus workgroups exit at once and the grid size only has to cover the
-    // resident set.  (History: with a static grid-stride order 64/CU beat the exact resident set,
-    // 98.2 vs 104.5 us/pair, because of dynamic balancing, but spread every XCD over its whole run:
-    // FETCH_SIZE was 1.5x (pass 1) to 3x (pass 2) the algorithmic bytes.  The queue keeps both.)
-    // TPIV_WG_PER_CU overrides for experiments.
-    static const int wg_per_cu = [] {
-        const char* e = getenv("TPIV_WG_PER_CU");
-        return e ? atoi(e) : 0;
-    }();
-    const long long cap = (long long)n_cu * (wg_per_cu > 0 ? wg_per_cu : 64);
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;                  // the XCD remap needs a multiple of 8
+    const long long cap = (long long)n_cu * 64;
+    const long long blocks = items < cap ? items : cap;
+    return (unsigned)((blocks + 7) / 8 * 8);        // the XCD remap needs a multiple of 8
+}
+
+template <int WS, int MODE>
+static hipError_t launch_tile(const PassParams& p_in, int n_cu, hipStream_t stream) {
+    PassParams p = p_in;
+    const unsigned blocks = tile_grid<WS>(p, n_cu);
+    if (blocks == 0) return hipErrorInvalidValue;
     // Register budget (wavefronts per SIMD).  32x32, 16x16 and 64x64 pass 1 run three wavefronts per
     // SIMD (<= 168 VGPRs, planar LDS tiles of 8.4 KB per wavefront).  Measured vs two wavefronts:
     // 32x32 DWS pass 33.6 -> 27.4 us/pair, 32x32 CWS pass 48.0 -> 43.9, 16x16 CWS pass (4096^2)
     // 213.9 -> 189.6, 64x64 pass 1 32.3 -> 29.1; four (possible for 32x32 pass 1 / DWS and 16x16 since
     // the peak search stopped using compare/select chains) gains nothing more: the VALU is saturated.
     // 16x16 is built for four (its CWS variant needs 129 VGPRs unconstrained, one more than four
-    // wavefronts allow: 165 -> 155 us/pair at 4096^2); 8x8 is built for two but small enough (107
-    // VGPRs) to run four.  64x64 pass 1 and DWS run three (planar tiles, three-row map, slow-path row
-    // buffer in two pieces); the 64x64 CWS variant needs 230 VGPRs and stays at two.
-    // Only the chosen variant is instantiated (tile_occ_c, piv_kernels.h); -DTPIV_EXPERIMENT builds all
-    // of them and lets TPIV_OCC=2|3|4 pick one at run time.
+    // wavefronts allow: 165 -> 155 us/pair at 4096^2).  64x64 pass 1 and DWS run three (planar tiles,
+    // three-row map, slow-path row buffer in two pieces); the 64x64 CWS variant needs 230 VGPRs and stays
+    // at two.  (8x8 passes run xcorr_w8.hip; the 8x8 candidate kernel below is built for two.)
+    // Only the chosen variant is instantiated (tile_occ_c, piv_kernels.h).
     constexpr int OCC = tile_occ_c(WS, MODE);
     // precision "reference": shifted passes keep the reference's operation order (bit-identical staged
     // windows); pass 1 at that precision is the float64 kernel (xcorr_f64.hip), so the float32 pass 1
     // exists in the fast form only
     if constexpr (MODE != MODE_PASS1) {
         if (p.precision != 0) {
-            hipLaunchKernelGGL((xcorr_tile_kernel<WS, MODE, OCC, false>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
+            hipLaunchKernelGGL((xcorr_tile_kernel<WS, MODE, OCC, false>), dim3(blocks), dim3(64), 0, stream, p);
             return hipGetLastError();
         }
     }
-#ifdef TPIV_EXPERIMENT
-    static const int occ_env = [] {
-        const char* e = getenv("TPIV_OCC");
-        return e ? atoi(e) : 0;
-    }();
-    if (occ_env == 2 && OCC != 2) {
-        hipLaunchKernelGGL((xcorr_tile_kernel<WS, MODE, 2, true>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
-        return hipGetLastError();
-    }
-    if constexpr (WS <= 32 || MODE != MODE_CWS) {
-        if (occ_env == 3 && OCC != 3) {
-            hipLaunchKernelGGL((xcorr_tile_kernel<WS, MODE, 3, true>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (WS <= 32) {
-        if (occ_env == 4 && OCC != 4) {
-            hipLaunchKernelGGL((xcorr_tile_kernel<WS, MODE, 4, true>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
-            return hipGetLastError();
-        }
-    }
-#endif
     if constexpr (tile_split64(WS, MODE)) {
         // two launches: everything that takes the wide-load path at three wavefronts per SIMD (no per-pixel code in that
         // instance), then the full kernel over the items it set aside (their number is on the device: the grid is a
         // resident set, wavefronts without an item leave at once)
         if (p.slow_list != nullptr && p.slow_count != nullptr) {
-            hipLaunchKernelGGL((xcorr_tile_fastpath_kernel<WS, MODE>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
+            hipLaunchKernelGGL((xcorr_tile_fastpath_kernel<WS, MODE>), dim3(blocks), dim3(64), 0, stream, p);
             hipError_t e_ = hipGetLastError();
             if (e_ != hipSuccess) return e_;
             e_ = hipMemsetAsync(p.work_ctr, 0, TILE_CTR_BYTES, stream);
@@ -2203,24 +1985,17 @@ static hipError_t launch_tile(const PassParams& p_in, int n_cu, hipStream_t stre
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((xcorr_tile_kernel<WS, MODE, OCC, true>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
+    hipLaunchKernelGGL((xcorr_tile_kernel<WS, MODE, OCC, true>), dim3(blocks), dim3(64), 0, stream, p);
     return hipGetLastError();
 }
 
 // the candidate-cell variant of the float32 first pass (precision "exact"); same grid and work queue as launch_tile
 template <int WS>
 hipError_t launch_xcorr_tile_cand_ws(const PassParams& p_in, int n_cu, hipStream_t stream) {
-    using G = TileGeo<WS>;
     PassParams p = p_in;
-    const int N = p.n_rows * p.n_cols;
-    const long long groups = (N + G::WPW - 1) / G::WPW;
-    const long long items = (long long)p.batch * groups;
-    if (items <= 0 || items >= (1ll << 31) - 64 || p.cand == nullptr) return hipErrorInvalidValue;
-    fast_div_setup((unsigned)groups, p.groups_magic, p.groups_shift);
-    fast_div_setup((unsigned)p.n_cols, p.ncols_magic, p.ncols_shift);
-    long long blocks = items < (long long)n_cu * 64 ? items : (long long)n_cu * 64;
-    blocks = (blocks + 7) / 8 * 8;
-    hipLaunchKernelGGL((xcorr_tile_cand_kernel<WS>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
+    const unsigned blocks = tile_grid<WS>(p, n_cu);
+    if (blocks == 0 || p.cand == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((xcorr_tile_cand_kernel<WS>), dim3(blocks), dim3(64), 0, stream, p);
     return hipGetLastError();
 }
 
