@@ -11,8 +11,9 @@
  *   - every pointer named *_dev is device memory on the CURRENT HIP device, owned by
  *     the caller (PyTorch-ROCm tensors: tensor.data_ptr()); the run functions only enqueue
  *     work on `stream` (a hipStream_t passed as void*; NULL = the null stream) and return at
- *     once.  No entry point allocates device memory or synchronises: a plan owns its workspace
- *     (allocated once by tpiv_plan_create), and the function-level entry points (tpiv_pass1 /
+ *     once.  No run function allocates device memory or synchronises: a plan owns its workspace
+ *     (allocated by tpiv_plan_create and, for the outlier test, by tpiv_plan_set_outlier -- both at
+ *     the call, never during a run), and the function-level entry points (tpiv_pass1 /
  *     tpiv_iter) take a caller-provided work buffer of tpiv_work_bytes() bytes (hand-off records
  *     between the tile kernel and the finalize kernel).  The library keeps no state between
  *     calls, so calls on different streams (with different work buffers) may overlap;
@@ -163,6 +164,37 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a_dev, const uint8_t* b_dev, i
  * during the last run (for parity tests of the intermediate passes). */
 int tpiv_plan_pass_fields(const tpiv_plan* plan, int pass, double** u_dev, double** v_dev,
                           uint8_t** invalid_dev);
+
+/* ---- normalized median test (extension; the reference validates by the peak ratio alone) ---------- */
+
+/* The normalized median test of Westerweel & Scarano (Exp. Fluids 39, 2005) on fields u, v float64 and the mask
+ * invalid uint8 [batch, n_rows, n_cols] (read as a snapshot).  Per cell: N = the up to 8 cells around it that lie in
+ * the grid and have invalid == 0, k = |N| (the cell's own mask byte plays no part).  k < min_neighbours: not flagged,
+ * medians = the cell's own u, v.  Otherwise, per component w of (u, v): sort the k neighbour values (the order of <,
+ * -0.0 before +0.0); med = s[(k-1)/2] for odd k, (s[k/2-1] + s[k/2]) * 0.5 for even k; rmed = the same pick from the
+ * sorted residuals |w_i - med|; out_w = |w_centre - med| > threshold * (rmed + eps); flag = out_u | out_v.  Every
+ * operation is one IEEE float64 operation in the order written (no contraction, no division), so a host model that
+ * does the same gives the same bits.  Inputs are finite; with NaN / inf nothing is promised except that nothing faults.
+ * status_dev uint8: bit 0 = flagged, bit 1 = the cell was invalid on input.  med_u_dev / med_v_dev (float64, either
+ * may be NULL): the medians.  No output may overlap an input or another output (TPIV_EINVAL), as are n_rows or
+ * n_cols < 1, threshold <= 0, eps < 0 and min_neighbours outside 1..8.  Enqueues only; allocates nothing. */
+int tpiv_median_test(const double* u_dev, const double* v_dev, const uint8_t* invalid_dev, int batch, int n_rows,
+                     int n_cols, double threshold, double eps, int min_neighbours, uint8_t* status_dev,
+                     double* med_u_dev, double* med_v_dev, void* stream);
+
+/* Outlier test of a plan: kind 0 = off (every plan's default: tpiv_plan_run enqueues exactly what it does without this
+ * call), 1 = tpiv_median_test with the given parameters after the tile kernels of EVERY pass, on that pass's u, v, invalid:
+ *   pass before the last: a flagged cell gets u, v := the medians (out of place: from the fields as the pass left
+ *     them); its mask byte stays as the peak-ratio test left it -- the next predictor follows the neighbourhood
+ *     where a vector was spurious and still zeroes where the correlation itself was poor;
+ *   last pass: invalid |= flag, u and v untouched -- the post-validation treats these cells like peak-ratio holes.
+ * The launches go behind the closing event of the pass's timing slot (tpiv_plan_get_timing keeps its meaning).
+ * Allocates, at this call, a status map per pass and the spare fields of the out-of-place step for max_batch pairs. */
+int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double eps, int min_neighbours);
+
+/* Device pointer to the status map (as tpiv_median_test's) pass `pass` -- the last included -- left during the last
+ * run, [batch, n_rows, n_cols] of that pass.  TPIV_EINVAL when the test is off. */
+int tpiv_plan_pass_outliers(const tpiv_plan* plan, int pass, uint8_t** status_dev);
 
 /* ---- post-validation (B:884-892) ------------------------------------------------- */
 

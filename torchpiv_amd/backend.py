@@ -371,7 +371,7 @@ class OfflinePIV:
     def __init__(self, folder: str, device: str, file_fmt: str, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
-                 validation_ratio: float = 1.2, validation_window: int = 3, background=None) -> None:
+                 validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -384,6 +384,12 @@ class OfflinePIV:
         # background (extension): static background removal -- every frame enters the passes as max(f, bg) - bg.
         # "min": bg_a / bg_b = the per-pixel minimum over the a / b frames of every pair of the dataset (compute_background,
         # computed on first use); a uint8 image [H, W] (both frames) or a pair (bg_a, bg_b): given.  None: frames as read.
+        # outlier (extension): None, "median" or a dict with any of threshold / eps / min_neighbours -- the normalized median
+        # test (Westerweel & Scarano 2005) on the device after every pass (engine.outlier_arg, tpiv_plan_set_outlier): a
+        # flagged vector of a pass before the last is replaced by its neighbourhood median before it predicts the finer
+        # windows; a flagged vector of the last pass joins the invalid ones and is filled by the post-validation.  More
+        # flagged vectors mean more pairs reach the reference's "to many false vectors" rule (4 * ring >= cells, B:299)
+        # and are dropped, exactly as for peak-ratio holes.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         self._precision = precision
@@ -402,6 +408,7 @@ class OfflinePIV:
         self._single_plans = {}          # plans of the one-pair path, per frame shape
         self._bg_arg = _background_arg(background)
         self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
+        self._outlier = engine.outlier_arg(outlier)
         self.reset_stats()
         if not self:
             return
@@ -429,7 +436,7 @@ class OfflinePIV:
                                      n_pass=max(1, int(self._iter)), mode=self._mode,
                                      pass_scale=self._iter_scale, max_batch=max_batch,
                                      val_ratio=self._val_ratio, val_win=self._val_win,
-                                     device=self._device, precision=self._precision)
+                                     device=self._device, precision=self._precision, outlier=self._outlier)
         return self._plan
 
     def _background(self, shape, batch_size=None):
@@ -542,7 +549,9 @@ class OfflinePIV:
                       "host_fallback": 0, "dropped_by_qhull": 0,
                       # host_fallback by hole class: pairs whose only undetermined cells are co-circular
                       # diamonds (isolated invalid vectors: Qhull's tie-break decides), and pairs that hold a wider hole
-                      "host_fallback_diamonds_only": 0, "host_fallback_wide_holes": 0}
+                      "host_fallback_diamonds_only": 0, "host_fallback_wide_holes": 0,
+                      # outlier=...: vectors the test flagged in the last pass (they join the peak-ratio holes)
+                      "outliers_flagged": 0}
 
     fill_workers = 0         # > 0: the host triangulations of a batch run in that many worker processes
     pipeline_depth = 2       # batched() over files: launches in flight before a batch's results are collected
@@ -595,7 +604,7 @@ class OfflinePIV:
 
     RING_CAP = 256           # ring / hole cells per pair (batch average) that ride on the first, asynchronous copy
 
-    def _post_submit(self, u, v, inv, want_raw=False):
+    def _post_submit(self, u, v, inv, want_raw=False, plan=None):
         """Device half of B:884-898 for a batch of final fields (u, v float64 [n, nr, nc], modified in
         place; inv uint8): tpiv_postval (NaN-out, border interpolation, census, triangulation-free fills),
         tpiv_postval_compact (the ring points with their values and the hole cells of the pairs that need Qhull, cut out
@@ -614,6 +623,8 @@ class OfflinePIV:
                "hole_rc": hole_rc[:cap_h], "fu": fu, "fv": fv}
         if want_raw:
             src["u"], src["v"] = u, v
+        if plan is not None and plan.outlier is not None:
+            src["flagged"] = plan.outlier_flag_counts(n)       # rides on the same asynchronous copy as the census
         host = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in src.items()}
         # the copies go down on a stream of their own, behind an event of the compute stream: the next batch's passes
         # start while they run.  (The small kernels above stay on the compute stream: on the side stream too they made
@@ -652,6 +663,8 @@ class OfflinePIV:
         need_host = keep & ((cnt[:, 2] + cnt[:, 3]) > 0)
         st = self.stats
         st["pairs"] += n
+        if "flagged" in host:
+            st["outliers_flagged"] += int(host["flagged"].sum())
         st["dropped_no_invalid"] += int(no_ring.sum())
         st["dropped_too_many"] += int(too_many.sum())
         st["device_complete"] += int((keep & ~need_host).sum())
@@ -742,8 +755,8 @@ class OfflinePIV:
         uk, vk = state["host"]["u"].numpy(), state["host"]["v"].numpy()
         return [(uk[i], vk[i]) if state["keep_final"][i] else None for i in range(uk.shape[0])]
 
-    def _post_validate_batch(self, u, v, inv):
-        return self._post_collect(self._post_submit(u, v, inv, want_raw=True))
+    def _post_validate_batch(self, u, v, inv, plan=None):
+        return self._post_collect(self._post_submit(u, v, inv, want_raw=True, plan=plan))
 
     def _post_pipeline(self, x, y, depth=1):
         """The host side of batched() as a pipeline: push(meta, ticket) after every launch returns the finished
@@ -834,11 +847,11 @@ class OfflinePIV:
                                               n_pass=max(1, int(self._iter)), mode=self._mode,
                                               pass_scale=self._iter_scale, max_batch=1, device=self._device,
                                               val_ratio=self._val_ratio, val_win=self._val_win,
-                                              precision=self._precision)
+                                              precision=self._precision, outlier=self._outlier)
         u, v, inv = plan.run(a, b)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates(shape, w, o)
-        return self._finish(self._post_validate_batch(u, v, inv)[0], x, y)
+        return self._finish(self._post_validate_batch(u, v, inv, plan=plan)[0], x, y)
 
     def __call__(self) -> Generator:
         if int(self.call_batch) > 1 and len(self._dataset) > 1:
@@ -996,7 +1009,7 @@ class OfflinePIV:
                     consumed[dbuf] = torch.cuda.Event()
                     consumed[dbuf].record(cur)
                     u, v, inv = plan.run(frames[:n], frames[n:])
-                    ticket = self._post_submit(u, v, inv)
+                    ticket = self._post_submit(u, v, inv, plan=plan)
                 let_go(release)
                 release = (up,)
                 # the host work of the PREVIOUS batches runs while the GPU works on this one
@@ -1022,7 +1035,7 @@ class ResidentPIV(OfflinePIV):
     def __init__(self, frames_a: torch.Tensor, frames_b: torch.Tensor, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
-                 validation_window: int = 3, background=None) -> None:
+                 validation_window: int = 3, background=None, outlier=None) -> None:
         if frames_a.shape != frames_b.shape or frames_a.dim() != 3 or frames_a.dtype != torch.uint8 \
                 or frames_b.dtype != torch.uint8:
             raise ValueError("ResidentPIV: two uint8 tensors [n, H, W] of one shape")
@@ -1031,6 +1044,7 @@ class ResidentPIV(OfflinePIV):
         self._bg_arg = _background_arg(background, frames_a.shape[1:])
         self._bg = None
         self._bg_frames = None           # the frames of a launch minus the background: uint8 [2, batch, H, W], reused
+        self._outlier = engine.outlier_arg(outlier)
         self._precision = precision
         self._val_ratio, self._val_win = float(validation_ratio), int(validation_window)
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
@@ -1106,7 +1120,7 @@ class ResidentPIV(OfflinePIV):
                 B = engine.subtract_background(B, bg[1], out=buf[1, :len(chunk)])
             u, v, inv = plan.run(A, B)
             # host work of the previous batches overlaps this batch's kernels
-            yield from emit(pipe.push(chunk, self._post_submit(u, v, inv)))
+            yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan)))
         yield from emit(pipe.flush())
 
     def __call__(self) -> Generator:

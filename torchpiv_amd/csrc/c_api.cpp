@@ -233,6 +233,12 @@ struct tpiv_plan {
     int last_batch = 0;                  // batch of the last tpiv_plan_run (tpiv_plan_exact_fallbacks)
     unsigned* exact_count = nullptr;     // TPIV_PREC_EXACT: the float64-list length of the last run's first pass (copied out
                                          // of peak_raw, which the later passes reuse)
+    // normalized median test between / after the passes (tpiv_plan_set_outlier); off: nothing below is allocated
+    int outlier_kind = 0, outlier_min = 3;
+    double outlier_threshold = 2.0, outlier_eps = 0.1;
+    std::vector<uint8_t*> ostatus;       // per pass: [max_batch, N_p] status map of the last run
+    double *raw_u = nullptr, *raw_v = nullptr;   // a pass before the last writes here; the test writes the pass's fields
+    uint8_t* raw_val = nullptr;          // the last pass's mask as the peak-ratio test left it; the test writes the caller's
     std::vector<void*> allocs;
     // optional per-kernel timing: events[run][2*slot + {0,1}]
     bool timing = false;
@@ -748,6 +754,95 @@ int tpiv_plan_debug_predict(tpiv_plan* plan, int pass, int batch, const double* 
     return run_banded_predict(plan, pass, batch, u_c, v_c, invalid_c, u0, v0, u2, v2, (hipStream_t)stream);
 }
 
+static int run_median_test(const double* u, const double* v, const uint8_t* invalid, int batch, int n_rows, int n_cols,
+                           double threshold, double eps, int min_neighbours, uint8_t* status, double* out_u, double* out_v,
+                           int replace, uint8_t* invalid_out, hipStream_t st) {
+    tpiv::OutlierParams q{};
+    q.u = u;
+    q.v = v;
+    q.invalid = invalid;
+    q.batch = batch;
+    q.n_rows = n_rows;
+    q.n_cols = n_cols;
+    q.threshold = threshold;
+    q.eps = eps;
+    q.min_neighbours = min_neighbours;
+    q.status = status;
+    q.out_u = out_u;
+    q.out_v = out_v;
+    q.replace = replace;
+    q.invalid_out = invalid_out;
+    hipError_t he = tpiv::launch_median_test(q, st);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_median_test");
+}
+
+int tpiv_median_test(const double* u, const double* v, const uint8_t* invalid, int batch, int n_rows, int n_cols,
+                     double threshold, double eps, int min_neighbours, uint8_t* status, double* med_u, double* med_v,
+                     void* stream) {
+    if (batch < 0 || n_rows < 1 || n_cols < 1) return fail(TPIV_EINVAL, "tpiv_median_test: empty grid");
+    if (!(threshold > 0) || !(eps >= 0)) return fail(TPIV_EINVAL, "tpiv_median_test: threshold must be > 0 and eps >= 0");
+    if (min_neighbours < 1 || min_neighbours > 8) return fail(TPIV_EINVAL, "tpiv_median_test: min_neighbours must be in 1..8");
+    if (!u || !v || !invalid || !status) return fail(TPIV_EINVAL, "tpiv_median_test: null pointer");
+    if ((long long)n_rows * n_cols >= (1LL << 31)) return fail(TPIV_EUNSUPPORTED, "field too large");
+    if (batch == 0) return TPIV_OK;
+    // no output may overlap an input or another output: every decision is taken on the fields as they came in
+    const size_t cells = (size_t)batch * n_rows * n_cols;
+    struct Span { const char* p; size_t n; };
+    const Span in[3] = {{(const char*)u, cells * 8}, {(const char*)v, cells * 8}, {(const char*)invalid, cells}};
+    const Span out[3] = {{(const char*)status, cells}, {(const char*)med_u, cells * 8}, {(const char*)med_v, cells * 8}};
+    auto overlap = [](const Span& x, const Span& y) { return x.p && y.p && x.p < y.p + y.n && y.p < x.p + x.n; };
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j)
+            if (overlap(out[i], in[j])) return fail(TPIV_EINVAL, "tpiv_median_test: an output aliases an input");
+        for (int j = i + 1; j < 3; ++j)
+            if (overlap(out[i], out[j])) return fail(TPIV_EINVAL, "tpiv_median_test: two outputs overlap");
+    }
+    return run_median_test(u, v, invalid, batch, n_rows, n_cols, threshold, eps, min_neighbours, status, med_u, med_v, 0,
+                           nullptr, (hipStream_t)stream);
+}
+
+int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double eps, int min_neighbours) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (kind != 0 && kind != 1) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: kind must be 0 (off) or 1 (normalized median)");
+    if (kind == 0) {
+        plan->outlier_kind = 0;
+        return TPIV_OK;
+    }
+    if (!(threshold > 0) || !(eps >= 0)) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: threshold must be > 0 and eps >= 0");
+    if (min_neighbours < 1 || min_neighbours > 8) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: min_neighbours must be in 1..8");
+    if (plan->ostatus.empty()) {                     // first time on: the workspace (kept until the plan is destroyed)
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+        std::vector<uint8_t*> status(plan->n_pass, nullptr);
+        size_t spare = 0;
+        int rc = TPIV_OK;
+        for (int p = 0; p < plan->n_pass && !rc; ++p) {
+            const size_t N = (size_t)plan->geo[p].n_rows * plan->geo[p].n_cols;
+            rc = plan->alloc(&status[p], N * plan->max_batch);
+            if (p < plan->n_pass - 1 && N > spare) spare = N;
+        }
+        const PassGeo& g = plan->geo[plan->n_pass - 1];
+        if (!rc && spare) rc = plan->alloc(&plan->raw_u, spare * plan->max_batch);
+        if (!rc && spare) rc = plan->alloc(&plan->raw_v, spare * plan->max_batch);
+        if (!rc) rc = plan->alloc(&plan->raw_val, (size_t)g.n_rows * g.n_cols * plan->max_batch);
+        if (rc) return rc;                           // (what was allocated stays in plan->allocs and goes with the plan)
+        plan->ostatus = std::move(status);
+    }
+    plan->outlier_kind = kind;
+    plan->outlier_threshold = threshold;
+    plan->outlier_eps = eps;
+    plan->outlier_min = min_neighbours;
+    return TPIV_OK;
+}
+
+int tpiv_plan_pass_outliers(const tpiv_plan* plan, int pass, uint8_t** status) {
+    if (!plan || !status || pass < 0 || pass >= plan->n_pass) return fail(TPIV_EINVAL, "bad plan / pass index");
+    if (!plan->outlier_kind) return fail(TPIV_EINVAL, "the plan runs no outlier test (tpiv_plan_set_outlier)");
+    *status = plan->ostatus[pass];
+    return TPIV_OK;
+}
+
 int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch, double* u, double* v,
                   uint8_t* invalid, void* stream) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
@@ -768,6 +863,17 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
         double* pu = p == last ? u : plan->u[p];
         double* pv = p == last ? v : plan->v[p];
         uint8_t* pval = p == last ? invalid : plan->val[p];
+        // with the median test on, the tile kernels write what the test replaces somewhere else and the test writes it
+        // where the next stage reads it: the fields of a pass before the last, the mask of the last pass
+        const bool test = plan->outlier_kind != 0;
+        double *const fu = pu, *const fv = pv;
+        uint8_t* const fval = pval;
+        if (test && p < last) {
+            pu = plan->raw_u;
+            pv = plan->raw_v;
+        } else if (test) {
+            pval = plan->raw_val;
+        }
         int rc;
         if (p == 0) {
             mark(0, 0);
@@ -795,6 +901,12 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
             mark(2 * p, 1);
         }
         if (rc) return rc;
+        if (test) {      // (behind the closing event of the pass's timing slot: the slots keep their meaning)
+            rc = run_median_test(pu, pv, pval, batch, g.n_rows, g.n_cols, plan->outlier_threshold, plan->outlier_eps,
+                                 plan->outlier_min, plan->ostatus[p], p < last ? fu : nullptr, p < last ? fv : nullptr, 1,
+                                 p < last ? nullptr : fval, st);
+            if (rc) return rc;
+        }
     }
     if (plan->timing && plan->runs_recorded < 512) plan->runs_recorded++;
     return TPIV_OK;

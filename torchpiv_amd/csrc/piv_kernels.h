@@ -171,6 +171,24 @@ hipError_t launch_frame_min(const uint8_t* frames, int n, long long pixels, uint
 hipError_t launch_subtract_background(const uint8_t* frames, int n, long long pixels, const uint8_t* bg, uint8_t* out,
                                       hipStream_t stream);
 
+// normalized median test (outlier.hip): one lane per cell, one workgroup per OUTLIER_TILE_COLS x OUTLIER_TILE_ROWS tile
+// (a wavefront per tile row), the tile and its one-cell halo staged in LDS
+constexpr int OUTLIER_TILE_COLS = 64, OUTLIER_TILE_ROWS = 8;
+struct OutlierParams {
+    const double* u;         // [batch, n_rows, n_cols]
+    const double* v;
+    const uint8_t* invalid;  // the mask as the peak-ratio test left it; read as a snapshot
+    int batch, n_rows, n_cols;
+    double threshold, eps;
+    int min_neighbours;      // 1..8
+    uint8_t* status;         // out: bit 0 = flagged here, bit 1 = invalid on input
+    double* out_u;           // optional; replace == 0: the neighbourhood medians, replace != 0: the field with its
+    double* out_v;           //   flagged cells at their medians (the plan's passes before the last)
+    int replace;
+    uint8_t* invalid_out;    // optional: invalid | flag (the plan's last pass); none of the outputs may alias an input
+};
+hipError_t launch_median_test(const OutlierParams& p, hipStream_t stream);
+
 hipError_t launch_xcorr(const PassParams& p, int mode, int n_cu, hipStream_t stream);
 // bytes of the tile kernels' work-queue counters (8 x one 64-byte line), and of the slow-item list header behind them
 constexpr size_t TILE_CTR_BYTES = 8 * 16 * sizeof(unsigned), TILE_SLOW_HDR_BYTES = 256;

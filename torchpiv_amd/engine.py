@@ -195,6 +195,60 @@ def debug_peaks(maps: torch.Tensor, val_ratio=1.2, val_win=3, planar=False):
     return u, v, inv
 
 
+OUTLIER_DEFAULTS = {"threshold": 2.0, "eps": 0.1, "min_neighbours": 3}
+
+
+def outlier_arg(outlier):
+    """The outlier= argument of Plan / OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no test),
+    "median" (the normalized median test at OUTLIER_DEFAULTS) or a dict with any of threshold (> 0), eps (>= 0, pixels)
+    and min_neighbours (1..8).  Returns None or the full parameter dict; anything else raises ValueError."""
+    if outlier is None:
+        return None
+    if isinstance(outlier, str):
+        if outlier != "median":
+            raise ValueError(f"outlier: None, 'median' or a dict of {sorted(OUTLIER_DEFAULTS)}, got {outlier!r}")
+        return dict(OUTLIER_DEFAULTS)
+    if not isinstance(outlier, dict):
+        raise ValueError(f"outlier: None, 'median' or a dict of {sorted(OUTLIER_DEFAULTS)}, got {type(outlier).__name__}")
+    unknown = sorted(set(outlier) - set(OUTLIER_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"outlier: unknown key(s) {unknown}; known: {sorted(OUTLIER_DEFAULTS)}")
+    par = dict(OUTLIER_DEFAULTS, **outlier)
+    try:
+        thr, eps, mn = float(par["threshold"]), float(par["eps"]), par["min_neighbours"]
+    except (TypeError, ValueError):
+        raise ValueError(f"outlier: threshold and eps must be numbers, got {outlier!r}") from None
+    if not thr > 0 or thr == float("inf"):
+        raise ValueError(f"outlier: threshold must be a finite number > 0, got {par['threshold']!r}")
+    if not eps >= 0 or eps == float("inf"):
+        raise ValueError(f"outlier: eps must be a finite number >= 0, got {par['eps']!r}")
+    if isinstance(mn, bool) or not isinstance(mn, (int, np.integer)) or not 1 <= mn <= 8:
+        raise ValueError(f"outlier: min_neighbours must be an integer in 1..8, got {mn!r}")
+    return {"threshold": thr, "eps": eps, "min_neighbours": int(mn)}
+
+
+def median_test(u, v, inv, threshold=2.0, eps=0.1, min_neighbours=3, want_medians=False):
+    """Normalized median test (Westerweel & Scarano 2005; tpiv_median_test) on fields u, v float64 and the mask inv uint8,
+    [batch, n_rows, n_cols] on the GPU.  Returns status uint8 (bit 0: flagged, bit 1: invalid on input), with
+    want_medians also the neighbourhood medians (status, med_u, med_v).  The inputs are not written."""
+    _need_cuda(u, v, inv)
+    if u.dtype != torch.float64 or v.dtype != torch.float64 or inv.dtype != torch.uint8:
+        raise TypeError("median_test: u, v float64 and invalid uint8")
+    if u.dim() != 3 or u.shape != v.shape or u.shape != inv.shape:
+        raise ValueError("median_test: [batch, n_rows, n_cols] tensors of one shape")
+    par = outlier_arg({"threshold": threshold, "eps": eps, "min_neighbours": min_neighbours})
+    u, v, inv = u.contiguous(), v.contiguous(), inv.contiguous()
+    B, nr, nc = u.shape
+    status = torch.empty(B, nr, nc, dtype=torch.uint8, device=u.device)
+    mu = torch.empty_like(u) if want_medians else None
+    mv = torch.empty_like(v) if want_medians else None
+    with torch.cuda.device(u.device):
+        check(lib.tpiv_median_test(u.data_ptr(), v.data_ptr(), inv.data_ptr(), B, nr, nc, par["threshold"], par["eps"],
+                                   par["min_neighbours"], status.data_ptr(), mu.data_ptr() if want_medians else None,
+                                   mv.data_ptr() if want_medians else None, _stream()))
+    return (status, mu, mv) if want_medians else status
+
+
 def postval(u, v, inv):
     """Device part of the post-validation (PIVbackend.py:884-892) for a batch, IN PLACE on u, v
     (float64 [B, nr, nc]): border interpolation, ring / hole census, fills that do not depend on the
@@ -334,7 +388,11 @@ class Plan:
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
 
     def __init__(self, H, W, ws, ov, n_pass=1, mode="CWS", pass_scale=2.0, val_ratio=1.2,
-                 val_win=3, max_batch=1, device=None, precision="exact"):
+                 val_win=3, max_batch=1, device=None, precision="exact", outlier=None):
+        # outlier: None, "median" or a dict (outlier_arg): the normalized median test after every pass -- flagged vectors of
+        # a pass before the last are replaced by their neighbourhood median before the predictor reads them, flagged
+        # vectors of the last pass join the invalid mask (tpiv_plan_set_outlier)
+        self.outlier = outlier_arg(outlier)
         if not torch.cuda.is_available():
             raise RuntimeError("torchpiv_amd.Plan needs a ROCm device (there is no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None \
@@ -351,6 +409,13 @@ class Plan:
             check(lib.tpiv_plan_create(C.byref(self._h), H, W, ws, ov, n_pass, MODES.get(mode, 0),
                                        float(pass_scale), float(val_ratio), int(val_win),
                                        int(max_batch), prec))
+            if self.outlier is not None:
+                try:
+                    check(lib.tpiv_plan_set_outlier(self._h, 1, self.outlier["threshold"], self.outlier["eps"],
+                                                    self.outlier["min_neighbours"]))
+                except Exception:
+                    self.close()
+                    raise
         self.n_pass = lib.tpiv_plan_n_pass(self._h)
         self.geometry = []
         for p in range(self.n_pass):
@@ -451,6 +516,15 @@ class Plan:
             names += [f"pass{p + 1}_predict", f"pass{p + 1}_xcorr"]
         return dict(zip(names, list(arr))), runs.value
 
+    def _copy_out(self, pairs):
+        """Copies of plan-owned device arrays: [(destination tensor, source pointer, bytes)]; waits for the device."""
+        torch.cuda.synchronize(self.device)
+        hip = C.CDLL("libamdhip64.so")
+        for dst, src, nbytes in pairs:
+            rc = hip.hipMemcpy(C.c_void_p(dst.data_ptr()), src, C.c_size_t(nbytes), 3)  # D2D
+            if rc != 0:
+                raise _lib.HipError(f"hipMemcpy failed: {rc}")
+
     def pass_fields(self, p, batch):
         """Fields pass p (< n_pass-1) left in the workspace by the last run (copies)."""
         pu, pv, pi = C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -460,10 +534,29 @@ class Plan:
         u = torch.empty(batch, nr, nc, dtype=torch.float64, device=self.device)
         v = torch.empty_like(u)
         inv = torch.empty(batch, nr, nc, dtype=torch.uint8, device=self.device)
-        torch.cuda.synchronize(self.device)
-        hip = C.CDLL("libamdhip64.so")
-        for dst, src, nbytes in ((u, pu, n * 8), (v, pv, n * 8), (inv, pi, n)):
-            rc = hip.hipMemcpy(C.c_void_p(dst.data_ptr()), src, C.c_size_t(nbytes), 3)  # D2D
-            if rc != 0:
-                raise _lib.HipError(f"hipMemcpy failed: {rc}")
+        self._copy_out(((u, pu, n * 8), (v, pv, n * 8), (inv, pi, n)))
         return u, v, inv
+
+    def outlier_flag_counts(self, batch):
+        """int32 [batch] on the device: vectors per pair the outlier test flagged in the last pass of the last run.
+        Enqueued on the current stream behind the run (a copy of the status map and a reduction); no host wait."""
+        ps = C.c_void_p()
+        check(lib.tpiv_plan_pass_outliers(self._h, self.n_pass - 1, C.byref(ps)))
+        nr, nc = self.out_shape
+        status = torch.empty(batch, nr, nc, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = C.CDLL("libamdhip64.so").hipMemcpyAsync(C.c_void_p(status.data_ptr()), ps, C.c_size_t(batch * nr * nc), 3,
+                                                          C.c_void_p(_stream()))      # D2D
+        if rc != 0:
+            raise _lib.HipError(f"hipMemcpyAsync failed: {rc}")
+        return (status & 1).sum(dim=(1, 2), dtype=torch.int32)
+
+    def outlier_status(self, p, batch):
+        """Status map (uint8 [batch, n_rows, n_cols]: bit 0 flagged by the outlier test, bit 1 invalid by the peak ratio)
+        pass p -- the last included -- left during the last run (a copy).  ValueError for a plan without the test."""
+        ps = C.c_void_p()
+        check(lib.tpiv_plan_pass_outliers(self._h, p, C.byref(ps)))
+        _, _, nr, nc = self.geometry[p]
+        status = torch.empty(batch, nr, nc, dtype=torch.uint8, device=self.device)
+        self._copy_out(((status, ps, batch * nr * nc),))
+        return status
