@@ -255,6 +255,69 @@ def test_offline_background_equals_presubtracted_frames(tmp_path, frames, precis
     pg.close()
 
 
+def test_file_staging_with_unstageable_pairs_and_a_stale_reader(tmp_path):
+    """The file staging that batched() and compute_background() share, over 6 pairs of 96 x 128 BMPs of which pair 2 has
+    a truncated a file (undecodable) and pair 4 another frame shape: the minimum leaves both out at any batch size; the
+    fields of the good pairs are those of ResidentPIV on frames subtracted in torch; pair 4 reaches the one-pair path
+    when its turn comes, where the dataset's background does not fit its shape (ValueError, after the pairs before it);
+    a generator abandoned without close() leaves a live reader behind, which the next run -- of either kind -- stops."""
+    from PIL import Image
+    import torchpiv_amd as T
+    from torchpiv_amd import synth
+    H, W, good = 96, 128, [0, 1, 3, 5]
+    A, B = synth.make_batch(6, H, W, kind="wavy", noise=1.5)
+    g = torch.Generator().manual_seed(3)
+    band = torch.zeros(H, W, dtype=torch.int32)
+    band[8:30] = torch.randint(0, 90, (22, W), generator=g, dtype=torch.int32)
+    A = (A.int() + band).clamp(max=255).to(torch.uint8)
+    B = (B.int() + band).clamp(max=255).to(torch.uint8)
+    A[:, 40:64, 50:74] = 0                       # dead windows: every pair holds invalid vectors to fill
+    B[:, 40:64, 50:74] = 0
+    _write_folder(tmp_path, A, B)
+    blob = (tmp_path / "image2_a.bmp").read_bytes()
+    (tmp_path / "image2_a.bmp").write_bytes(blob[:len(blob) // 2])
+    for s_, F in (("a", A), ("b", B)):
+        Image.fromarray(F[4, :80].numpy(), "L").save(tmp_path / f"image4_{s_}.bmp")
+    kw = dict(multipass=2, multipass_mode="CWS")
+    min_a, min_b = A[good].amin(0), B[good].amin(0)
+    res = _fields(T.ResidentPIV(_sub(A[good], min_a).cuda(), _sub(B[good], min_b).cuda(), 32, 16, **kw).batched(4))
+    want = {good[k]: f for k, f in res.items()}
+    assert len(want) >= 2
+    piv = T.OfflinePIV(str(tmp_path), "cuda:0", "bmp", 32, 16, background="min", **kw)
+    assert len(piv) == 6 and piv.frame_shape() == (H, W)
+    for bs in (2, 32):
+        bg_a, bg_b = piv.compute_background(batch_size=bs)
+        assert torch.equal(bg_a.cpu(), min_a) and torch.equal(bg_b.cpu(), min_b), bs
+    e_a, e_b = piv.compute_background(indices=[])
+    assert e_a.shape == (H, W) and int(e_a.min()) == 255 and int(e_b.min()) == 255
+    every = [0, 1, 2, 3, 5]
+    _same(_fields(piv.batched(4, indices=every)), want)
+    # the whole folder: pair 4 takes the one-pair path, which refuses the background of another shape
+    got = {}
+    with pytest.raises(ValueError, match="background of shape"):
+        for i, x, y, u, v in piv.batched(4):
+            got[i] = (np.asarray(u), np.asarray(v))
+    _same(got, {i: want[i] for i in want if i < 4})
+    # abandoned generators, still referenced (their finally has not run: the reader is live)
+    gen1 = piv.batched(2, indices=every)
+    first = next(gen1)
+    assert first[0] == min(want) and np.array_equal(first[3], want[first[0]][0], equal_nan=True)
+    rd1 = piv._reader
+    assert rd1._h is not None
+    bg_a, bg_b = piv.compute_background()
+    assert rd1._h is None                         # stopped by compute_background
+    assert torch.equal(bg_a.cpu(), min_a) and torch.equal(bg_b.cpu(), min_b)
+    gen2 = piv.batched(2, indices=every)
+    next(gen2)
+    rd2 = piv._reader
+    assert rd2._h is not None
+    _same(_fields(piv.batched(2, indices=every)), want)
+    assert rd2._h is None and piv._reader._h is None
+    gen1.close()
+    gen2.close()
+    piv.close()
+
+
 def test_runner_passes_background(tmp_path, frames):
     from torchpiv_amd import runner
     A, B = frames

@@ -595,6 +595,88 @@ def test_read_ahead_ring(tmp_path):
     assert k == 0 and list(sizes) == [-1] * per
 
 
+def test_staged_batches_against_stage_raw(tmp_path, monkeypatch):
+    """io.StagedBatches, the host side that OfflinePIV.batched and compute_background share: which pair is staged, in
+    which slot, with which descriptor row and grey table -- against io.stage_raw file by file.  7 pairs at 3 per batch
+    (a short last batch), in an order other than the folder's: plain and palette BMPs, a PNG under its own name in a
+    .bmp run (decoded on the host), and three pairs that are left to the caller (b of another shape, a not a BMP, b
+    missing).  A run whose first file is no .bmp reads nothing natively; close() is idempotent and works mid-run."""
+    from PIL import Image
+
+    from torchpiv_amd import io as pio
+    rng = np.random.default_rng(11)
+    H, W = 37, 50
+
+    def gray(name, shape=(H, W)):
+        Image.fromarray(rng.integers(0, 256, size=shape).astype(np.uint8), "L").save(tmp_path / name)
+        return str(tmp_path / name)
+
+    def palette(name):
+        pal = Image.fromarray(rng.integers(0, 256, size=(H, W)).astype(np.uint8), "P")
+        pal.putpalette(list(rng.integers(0, 256, size=768)))
+        pal.save(tmp_path / name)
+        return str(tmp_path / name)
+    (tmp_path / "bad_a.bmp").write_bytes(b"BMnot")
+    pairs = [(gray("p0_a.bmp"), gray("p0_b.bmp")), (palette("p1_a.bmp"), palette("p1_b.bmp")),
+             (gray("p2_a.bmp"), gray("p2_b.bmp", (H + 1, W))), (gray("p3_a.bmp"), gray("p3_b.bmp")),
+             (str(tmp_path / "bad_a.bmp"), gray("p4_b.bmp")), (gray("p5_a.bmp"), str(tmp_path / "missing.bmp")),
+             (gray("p6_a.png"), gray("p6_b.png"))]
+    bad = {2, 4, 5}
+    cap = pio.slot_bytes(H, W, pairs[1])
+    assert cap % 4096 == 0 and cap >= H * W and cap >= max(os.path.getsize(f) for f in pairs[1])
+    assert pio.slot_bytes(H, W, pairs[5]) == cap and pio.slot_bytes(H, W, ()) == 4096       # a missing file is skipped
+    assert pio.slot_bytes(64, 64, pairs[0]) == 4096 and pio.slot_bytes(64, 65, pairs[0]) == 8192
+    idx, per = [1, 4, 0, 6, 2, 3, 5], 3
+    bufs = [np.zeros((2 * per, cap), np.uint8) for _ in range(3)]
+    sb = pio.StagedBatches(idx, pairs, per, H, W, bufs, cap, threads=3)
+    assert isinstance(sb.reader, pio.ReadAhead) and sb.reader._h is not None
+    seen = []
+    for b, st in enumerate(sb):
+        ids = idx[b * per:(b + 1) * per]
+        seen += ids
+        assert st.buf == b % 3 and st.n_files == 2 * len(ids)
+        assert st.order == [(i, i not in bad) for i in ids]
+        assert st.chunk == [i for i in ids if i not in bad]
+        n = len(st.chunk)
+        assert st.desc.shape == (2 * n, 6) and st.desc.dtype == np.int64
+        assert st.lut.shape == (2 * n, 256) and st.lut.dtype == np.uint8
+        for row, i in enumerate(st.chunk):
+            k = ids.index(i)                              # the slot is numbered by the pair's place in the BATCH
+            for side, slot in ((0, 2 * k), (1, 2 * k + 1)):
+                scratch = np.zeros(cap, np.uint8)
+                ref = pio.stage_raw(pairs[i][side], scratch, H, W)
+                r = row + side * n                        # every a row first, then every b row
+                assert st.desc[r].tolist() == [slot * cap, *ref[:4], side], (i, side)
+                assert np.array_equal(st.lut[r], ref[4])
+                assert np.array_equal(bufs[st.buf][slot], scratch), (i, side)
+        sb.release()
+    assert seen == idx
+    sb.close()
+    sb.close()
+    assert sb.reader._h is None
+    # mid-run
+    sb = pio.StagedBatches(idx, pairs, per, H, W, bufs, cap, threads=3)
+    it = iter(sb)
+    assert next(it).chunk == [1, 0]
+    sb.close()
+    assert sb.reader._h is None and sb._decoders is None
+    sb.close()
+    # a run whose first file is no .bmp: nothing is read natively (every size -1), every decodable pair is staged by stage_raw
+    sizes_seen = []
+    sweep = pio.parse_bmp_headers
+    monkeypatch.setattr(pio, "parse_bmp_headers", lambda raw, sizes, H, W: sizes_seen.append(list(sizes)) or sweep(raw, sizes, H, W))
+    sb = pio.StagedBatches([6, 0, 4, 3], pairs, per, H, W, bufs, cap, threads=2)
+    assert sb.reader._h is None
+    got = list(sb)
+    sb.close()
+    assert sizes_seen == [[-1] * 6, [-1] * 2]
+    assert [st.order for st in got] == [[(6, True), (0, True), (4, False)], [(3, True)]]
+    assert [st.chunk for st in got] == [[6, 0], [3]]
+    scratch = np.zeros(cap, np.uint8)
+    ref = pio.stage_raw(pairs[0][1], scratch, H, W)
+    assert got[0].desc[3].tolist() == [3 * cap, *ref[:4], 1] and np.array_equal(bufs[got[0].buf][3], scratch)
+
+
 def test_qhull_diamond_choice_is_not_a_local_rule():
     """Why the isolated invalid vector stays a (counted) host triangulation: its four ring points are co-circular, both
     diagonals are Delaunay, and the one SciPy/Qhull takes -- hence the value, (N + S) / 2 or (E + W) / 2 -- changes with

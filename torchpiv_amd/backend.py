@@ -26,8 +26,8 @@ import torch
 
 from . import engine
 from ._lib import PRECISIONS
-from ._qhull import qhull_fill, qhull_fill_many      # numpy/scipy-only module: the fill worker processes import nothing else
-from .io import PIVDataset, ToTensor, natural_keys  # noqa: F401  (re-exported like the reference)
+from ._qhull import blas_one_thread, qhull_fill, qhull_fill_many      # numpy/scipy-only module: the fill worker processes import nothing else
+from .io import PIVDataset, StagedBatches, ToTensor, natural_keys, slot_bytes  # noqa: F401  (re-exported like the reference)
 
 
 # ----------------------------------------------------------------------------------------
@@ -392,52 +392,90 @@ class OfflinePIV:
         # and are dropped, exactly as for peak-ratio holes.
         if precision not in PRECISIONS:
             raise KeyError(precision)
-        self._precision = precision
-        self._val_ratio, self._val_win = float(validation_ratio), int(validation_window)
-        self._wind_size = wind_size
-        self._overlap = overlap
-        self._dt = dt
-        self._iter = multipass
-        self._iter_scale = multipass_scale
-        self._scale = scale
-        self._device = DeviceMap.devicies[device]                       # KeyError like B:845
-        self._dataset = PIVDataset(folder, file_fmt, folder_mode, transform=ToTensor(dtype=torch.uint8))
-        self._iter_function = IterModMap.functions[multipass_mode]      # KeyError like B:850
-        self._mode = multipass_mode
-        self._plan = None
-        self._single_plans = {}          # plans of the one-pair path, per frame shape
-        self._bg_arg = _background_arg(background)
-        self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
-        self._outlier = engine.outlier_arg(outlier)
-        self.reset_stats()
+        device = DeviceMap.devicies[device]                             # KeyError like B:845
+        dataset = PIVDataset(folder, file_fmt, folder_mode, transform=ToTensor(dtype=torch.uint8))
+        iter_function = IterModMap.functions[multipass_mode]            # KeyError like B:850
+        self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
+                         multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
+                         engine.outlier_arg(outlier))
         if not self:
             return
         if self._bg_arg is not None and self._bg_arg != "min":
             _background_arg(background, self.frame_shape())
         _require_gpu(self._device)
 
+    def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
+                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier):
+        """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
+        run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's) and the state that the methods
+        build up, empty."""
+        self._device, self._dataset, self._iter_function = device, dataset, iter_function
+        self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
+        self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
+        self._mode, self._precision = multipass_mode, precision
+        self._val_ratio, self._val_win = float(validation_ratio), int(validation_window)
+        self._bg_arg = bg_arg
+        self._outlier = outlier
+        self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
+        self._bg_frames = None           # ResidentPIV: the frames of a launch minus the background, uint8 [2, batch, H, W], reused
+        self._plan = None
+        self._single_plans = {}          # plans of the one-pair path, per frame shape
+        self._reader = None              # the ReadAhead of the latest run over files (closed when that run ended)
+        self._stage, self._stage_key = None, None            # pinned staging buffers, kept from call to call
+        self._raw_dev, self._raw_dev_key = None, None        # their device copies
+        self._pool, self._pool_size = None, 0                # fill-worker processes
+        self._down_stream = None         # the stream of _post_submit's copies
+        self.reset_stats()
+
     def __len__(self) -> int:
         return len(self._dataset)
 
-    def frame_shape(self):
-        """(H, W) of the first decodable pair, None for an empty / undecodable folder."""
-        for i in range(len(self._dataset)):
+    def _first_decodable(self, idx):
+        """(pair id, frame shape) of the first pair of `idx` that decodes, None without one."""
+        for i in idx:
             a, _ = self._dataset[i]
             if a is not None:
-                return tuple(a.shape)
+                return i, tuple(a.shape)
         return None
+
+    def frame_shape(self):
+        """(H, W) of the first decodable pair, None for an empty / undecodable folder."""
+        first = self._first_decodable(range(len(self._dataset)))
+        return None if first is None else first[1]
+
+    def _new_plan(self, H, W, max_batch):
+        return engine.Plan(H, W, int(self._wind_size), int(self._overlap), n_pass=max(1, int(self._iter)),
+                           mode=self._mode, pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio,
+                           val_win=self._val_win, device=self._device, precision=self._precision, outlier=self._outlier)
 
     def _get_plan(self, H, W, max_batch=1):
         if (self._plan is None or (self._plan.H, self._plan.W) != (H, W)
                 or self._plan.max_batch < max_batch):
             if self._plan is not None:
                 self._plan.close()
-            self._plan = engine.Plan(H, W, int(self._wind_size), int(self._overlap),
-                                     n_pass=max(1, int(self._iter)), mode=self._mode,
-                                     pass_scale=self._iter_scale, max_batch=max_batch,
-                                     val_ratio=self._val_ratio, val_win=self._val_win,
-                                     device=self._device, precision=self._precision, outlier=self._outlier)
+            self._plan = self._new_plan(H, W, max_batch)
         return self._plan
+
+    def _staging(self, batch_size, cap):
+        """(stage, raw_dev) for a run over files of `batch_size` pairs per batch and `cap` bytes per file slot: three
+        page-locked staging buffers [2 * batch_size, cap] (one being read into, one uploading, one of slack) and two device
+        copies, kept for the next call (page-locking half a gigabyte takes a tenth of a second)."""
+        dev = self._device
+        if self._reader is not None:
+            # a reader that outlived its (abandoned) generator still fills the buffers ...
+            self._reader.close()
+            self._reader = None
+            # ... and uploads / unpack kernels of that run may still be queued on ITS upload stream and on the compute
+            # stream: the staging and device buffers are the same memory, and the new run's first upload carries no
+            # dependency on them (an old upload landing afterwards would be unpacked as the new batch 0)
+            torch.cuda.synchronize(dev)
+        if self._stage_key != (batch_size, cap):
+            self._stage = [torch.empty(2 * batch_size, cap, dtype=torch.uint8).pin_memory() for _ in range(3)]
+            self._stage_key = (batch_size, cap)
+        if self._raw_dev_key != (batch_size, cap, str(dev)):
+            self._raw_dev = [torch.empty(2 * batch_size, cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self._raw_dev_key = (batch_size, cap, str(dev))
+        return self._stage, self._raw_dev
 
     def _background(self, shape, batch_size=None):
         """The background the frames of shape (H, W) lose (uint8 [2, H, W] on the device: bg_a, bg_b), None without one.
@@ -465,7 +503,6 @@ class OfflinePIV:
         images are 255 everywhere (the identity of the minimum: a rank's empty shard).  The files go through the native
         read-ahead ring and the device unpack, like batched() (whose staging buffers they share when batch_size and the
         file size agree), and each batch is folded in with tpiv_frame_min."""
-        from .io import ReadAhead, parse_bmp_headers, stage_raw
         shape = self.frame_shape()
         if shape is None:
             raise ValueError("compute_background: the dataset holds no decodable pair")
@@ -475,70 +512,30 @@ class OfflinePIV:
         idx = list(range(len(self._dataset))) if indices is None else list(indices)
         if not idx:
             return acc[0], acc[1]
-        import os as _os
         bs = int(batch_size or self.bg_batch)
         pairs = self._dataset.img_pairs
-        paths = []
-        for i in idx:
-            paths += [pairs[i][0], pairs[i][-1]]
-        sizes = [H * W] + [_os.path.getsize(p_) for p_ in paths[:2] if _os.path.exists(p_)]
-        cap = (max(sizes) + 4095) // 4096 * 4096
-        prev = getattr(self, "_reader", None)            # an abandoned batched() run's reader still fills the buffers
-        if prev is not None:
-            prev.close()
-            self._reader = None
-            torch.cuda.synchronize(dev)
-        if getattr(self, "_stage_key", None) != (bs, cap):
-            self._stage = [torch.empty(2 * bs, cap, dtype=torch.uint8).pin_memory() for _ in range(3)]
-            self._stage_key = (bs, cap)
-        stage = self._stage
-        if getattr(self, "_raw_dev_key", None) != (bs, cap, str(dev)):
-            self._raw_dev = [torch.empty(2 * bs, cap, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self._raw_dev_key = (bs, cap, str(dev))
-        raw_d = self._raw_dev[0]
+        first = self._first_decodable(idx)
+        cap = slot_bytes(H, W, pairs[first[0]] if first is not None else ())
+        stage, raw_dev = self._staging(bs, cap)
+        raw_d = raw_dev[0]
         cur = torch.cuda.current_stream(dev)
-        rd = ReadAhead(paths, 2 * bs, [t.data_ptr() for t in stage], cap, threads=self.read_threads,
-                       read=str(paths[0]).lower().endswith(".bmp"))
-        decoders = None
+        batches = StagedBatches(idx, pairs, bs, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads)
+        self._reader = batches.reader
         try:
-            for s0 in range(0, len(idx), bs):
-                got = rd.next()
-                if got is None:
-                    break
-                buf, sizes = got
-                raw = stage[buf].numpy()
-                lays = parse_bmp_headers(raw[:len(sizes)], sizes, H, W)
-                rest = [j for j, lay in enumerate(lays) if lay is None]
-                if rest:
-                    if decoders is None:
-                        from concurrent.futures import ThreadPoolExecutor
-                        decoders = ThreadPoolExecutor(max_workers=self.read_threads)
-                    for j, lay in zip(rest, decoders.map(lambda j: stage_raw(paths[2 * s0 + j], raw[j], H, W), rest)):
-                        lays[j] = lay
-                desc_a, desc_b, luts_a, luts_b = [], [], [], []
-                for k in range(len(sizes) // 2):
-                    la, lb = lays[2 * k], lays[2 * k + 1]
-                    if la is None or lb is None:            # left out, as batched() leaves it to the one-pair path
-                        continue
-                    desc_a.append([2 * k * cap, la[0], la[1], la[2], la[3], 0])
-                    desc_b.append([(2 * k + 1) * cap, lb[0], lb[1], lb[2], lb[3], 1])
-                    luts_a.append(la[4])
-                    luts_b.append(lb[4])
-                if desc_a:
-                    n = len(desc_a)
-                    raw_d[:len(sizes)].copy_(stage[buf][:len(sizes)], non_blocking=True)
-                    desc_d = torch.tensor(desc_a + desc_b, dtype=torch.int64).to(dev, non_blocking=True)
-                    lut_d = torch.from_numpy(np.stack(luts_a + luts_b)).to(dev, non_blocking=True)
+            for st in batches:
+                n = len(st.chunk)       # (pairs that are not staged are left out, as batched() leaves them to the one-pair path)
+                if n:
+                    raw_d[:st.n_files].copy_(stage[st.buf][:st.n_files], non_blocking=True)
+                    desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
+                    lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
                     frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W)      # [2n, H, W]: a_0..a_n-1, b_0..b_n-1
                     engine.frame_min(frames[:n], acc[0])
                     engine.frame_min(frames[n:], acc[1])
                     cur.synchronize()           # the upload is through: the readers may refill the staging buffer
-                rd.release()
+                batches.release()
         finally:
-            rd.close()
+            batches.close()
             torch.cuda.synchronize(dev)
-            if decoders is not None:
-                decoders.shutdown(wait=False)
         return acc[0], acc[1]
 
     def reset_stats(self):
@@ -573,8 +570,8 @@ class OfflinePIV:
         """The fill-worker processes (_qhull.FillWorkers), started on first use and again when fill_workers changes."""
         if self.fill_workers <= 0:
             return None
-        pool = getattr(self, "_pool", None)
-        if pool is None or getattr(self, "_pool_size", 0) != self.fill_workers:
+        pool = self._pool
+        if pool is None or self._pool_size != self.fill_workers:
             if pool is not None:
                 pool.terminate()
             # spawned: the workers never see this process's HIP state; they only run scipy on small arrays (with ONE BLAS
@@ -585,20 +582,18 @@ class OfflinePIV:
         return pool
 
     def close(self):
-        pool = getattr(self, "_pool", None)
-        if pool is not None:
-            pool.terminate()
+        if self._pool is not None:
+            self._pool.terminate()
             self._pool = None
-        if getattr(self, "_plan", None) is not None:
+        if self._plan is not None:
             self._plan.close()
             self._plan = None
-        rd = getattr(self, "_reader", None)
-        if rd is not None:
-            rd.close()
+        if self._reader is not None:
+            self._reader.close()
             self._reader = None
         self._stage, self._stage_key = None, None
         self._raw_dev, self._raw_dev_key = None, None
-        for pl in getattr(self, "_single_plans", {}).values():
+        for pl in self._single_plans.values():
             pl.close()
         self._single_plans = {}
 
@@ -630,7 +625,7 @@ class OfflinePIV:
         # start while they run.  (The small kernels above stay on the compute stream: on the side stream too they made
         # the whole generator slower -- 9.1 -> 8.2 k pairs/s, same box.)
         cur = torch.cuda.current_stream(u.device)
-        down = getattr(self, "_down_stream", None)
+        down = self._down_stream
         if down is None or down.device != u.device:
             down = self._down_stream = torch.cuda.Stream(u.device)
         ready = torch.cuda.Event()
@@ -692,11 +687,7 @@ class OfflinePIV:
                 #  6.5 k -> 4.8 k pairs/s -- and a batch of 64 pairs waited 2-4 ms for its triangulations)
                 state["pending"] = (pool, pool.submit(jobs))
             else:
-                if not getattr(OfflinePIV, "_blas_limited", False):
-                    from ._qhull import blas_one_thread
-                    OfflinePIV._blas_ctx = blas_one_thread
-                    OfflinePIV._blas_limited = True
-                with OfflinePIV._blas_ctx():
+                with blas_one_thread():
                     state["sols"] = qhull_fill_many(jobs)
         return state
 
@@ -840,14 +831,9 @@ class OfflinePIV:
         if bg is not None:
             a = engine.subtract_background(a, bg[0])
             b = engine.subtract_background(b, bg[1])
-        plans = self._single_plans
-        plan = plans.get(shape)
+        plan = self._single_plans.get(shape)
         if plan is None:
-            plan = plans[shape] = engine.Plan(shape[0], shape[1], int(self._wind_size), int(self._overlap),
-                                              n_pass=max(1, int(self._iter)), mode=self._mode,
-                                              pass_scale=self._iter_scale, max_batch=1, device=self._device,
-                                              val_ratio=self._val_ratio, val_win=self._val_win,
-                                              precision=self._precision, outlier=self._outlier)
+            plan = self._single_plans[shape] = self._new_plan(shape[0], shape[1], 1)
         u, v, inv = plan.run(a, b)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates(shape, w, o)
@@ -879,51 +865,21 @@ class OfflinePIV:
         FILE BYTES (no host decode: header skip, row flip, padding strip and palette / gray conversion
         run on the device, tpiv_bmp_unpack), other formats decoded on the host -- while the GPU works on
         the current batch (triple-buffered staging, uploads on their own stream).  Yields (pair_index, x, y, u, v); dropped pairs yield nothing."""
-        from .io import ReadAhead, parse_bmp_headers, stage_raw
         idx = list(range(len(self._dataset))) if indices is None else list(indices)
         if not idx:
             return
-        first = None
-        for i in idx:                       # frame shape from the first decodable pair
-            a0, _ = self._dataset[i]
-            if a0 is not None:
-                first = (i, tuple(a0.shape))
-                break
+        first = self._first_decodable(idx)       # the frame shape is the first decodable pair's
         if first is None:
             return
         H, W = first[1]
         bg = self._background((H, W), batch_size)     # (background="min": the prepass over the files runs here, once)
         plan = self._get_plan(H, W, max_batch=batch_size)
-        import os as _os
-        # one staging slot per file: the largest of the first pair's files (a run's files share one format)
-        # and a headerless frame, rounded up to 4 KiB
-        sizes = [H * W] + [_os.path.getsize(p_) for p_ in self._dataset.img_pairs[first[0]] if _os.path.exists(p_)]
-        cap = (max(sizes) + 4095) // 4096 * 4096
-        # (page-locking half a gigabyte takes a tenth of a second: the staging buffers are kept for the next call)
-        key = (batch_size, cap)
-        prev = getattr(self, "_reader", None)            # a reader that outlived its (abandoned) generator still fills the buffers
-        if prev is not None:
-            prev.close()
-            # ... and uploads / unpack kernels of that run may still be queued on ITS upload stream and on the compute
-            # stream: the staging and device buffers below are the same memory, and the new run's first upload carries no
-            # dependency on them (an old upload landing afterwards would be unpacked as the new batch 0)
-            torch.cuda.synchronize(self._device)
-        if getattr(self, "_stage_key", None) != key:
-            # three staging buffers: one being read into, one uploading, one of slack
-            self._stage = [torch.empty(2 * batch_size, cap, dtype=torch.uint8).pin_memory() for _ in range(3)]
-            self._stage_key = key
-        stage = self._stage
         pairs = self._dataset.img_pairs
-        paths = []
-        for i in idx:                       # slot 2k: frame a of the batch's pair k, slot 2k + 1: frame b
-            paths += [pairs[i][0], pairs[i][-1]]
-        # the loader is native (tpiv_reader_*): reader threads of the library stream the run's files into the staging
-        # buffers ahead of this loop, which only blocks -- without the GIL -- for the next complete batch.  Formats the
-        # device cannot unpack are not read here at all: they take the per-file path (host decode) below
-        rd = ReadAhead(paths, 2 * batch_size, [t.data_ptr() for t in stage], cap, threads=self.read_threads,
-                       read=str(paths[0]).lower().endswith(".bmp"))
-        self._reader = rd
-        decoders = None
+        cap = slot_bytes(H, W, pairs[first[0]])
+        stage, raw_dev = self._staging(batch_size, cap)
+        # the host side of the loop below: read-ahead ring, header sweep, host decode of other formats, descriptor tables
+        batches = StagedBatches(idx, pairs, batch_size, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads)
+        self._reader = batches.reader
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
         dev = self._device
@@ -944,11 +900,6 @@ class OfflinePIV:
         # transfer of batch n + 1 (4 MP: 268 MB, ~5 ms) overlaps the passes of batch n (~3 ms) instead of preceding them
         cur = torch.cuda.current_stream(dev)
         up_stream = torch.cuda.Stream(dev)
-        key_d = (batch_size, cap, str(dev))
-        if getattr(self, "_raw_dev_key", None) != key_d:
-            self._raw_dev = [torch.empty(2 * batch_size, cap, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self._raw_dev_key = key_d
-        raw_dev = self._raw_dev
         consumed = [None, None]             # event: the unpack kernel that read raw_dev[k] has run
         release = None                      # upload event of the batch before (its staging buffer is still held)
         n_up = 0
@@ -957,52 +908,27 @@ class OfflinePIV:
             if rel is not None:
                 if rel[0] is not None:
                     rel[0].synchronize()              # its upload is through: the readers may refill the staging buffer
-                rd.release()
+                batches.release()
 
         try:
-            for s0 in range(0, len(idx), batch_size):
-                got = rd.next()
-                if got is None:
-                    break
-                buf, sizes = got
-                ids = idx[s0:s0 + batch_size]
-                raw = stage[buf].numpy()
-                lays = parse_bmp_headers(raw[:len(sizes)], sizes, H, W)
-                rest = [j for j, lay in enumerate(lays) if lay is None]
-                if rest:
-                    if decoders is None:
-                        from concurrent.futures import ThreadPoolExecutor
-                        decoders = ThreadPoolExecutor(max_workers=self.read_threads)
-                    for j, lay in zip(rest, decoders.map(lambda j: stage_raw(paths[2 * s0 + j], raw[j], H, W), rest)):
-                        lays[j] = lay
-                chunk, desc_a, desc_b, lut_a, lut_b, order = [], [], [], [], [], []
-                for k, i in enumerate(ids):
-                    la, lb = lays[2 * k], lays[2 * k + 1]
-                    order.append((i, la is not None and lb is not None))
-                    if la is None or lb is None:
-                        # not stageable (undecodable, or a frame shape other than the batch's): the pair takes the
-                        # one-pair path when its turn comes -- which skips an undecodable pair like B:138-139 and
-                        # gives another shape its own plan
-                        continue
-                    desc_a.append([2 * k * cap, la[0], la[1], la[2], la[3], 0])
-                    desc_b.append([(2 * k + 1) * cap, lb[0], lb[1], lb[2], lb[3], 1])      # [5]: background slot
-                    lut_a.append(la[4])
-                    lut_b.append(lb[4])
-                    chunk.append(i)
+            for st in batches:
+                # (a pair that is not staged -- undecodable, or a frame shape other than the batch's -- takes the one-pair
+                #  path when its turn comes, in emit: that skips an undecodable pair like B:138-139 and gives another
+                #  shape its own plan)
                 ticket, up = None, None
-                if chunk:
-                    n, n_slots = len(chunk), len(ids)
+                if st.chunk:
+                    n = len(st.chunk)
                     dbuf, n_up = n_up % 2, n_up + 1
                     with torch.cuda.stream(up_stream):
                         if consumed[dbuf] is not None:
                             up_stream.wait_event(consumed[dbuf])
-                        raw_d = raw_dev[dbuf][:2 * n_slots]
-                        raw_d.copy_(stage[buf][:2 * n_slots], non_blocking=True)
+                        raw_d = raw_dev[dbuf][:st.n_files]
+                        raw_d.copy_(stage[st.buf][:st.n_files], non_blocking=True)
                         up = torch.cuda.Event()
                         up.record(up_stream)
                     # unpacked frame order: every a of the batch, then every b (two contiguous stacks)
-                    desc_d = torch.tensor(desc_a + desc_b, dtype=torch.int64).to(dev, non_blocking=True)
-                    lut_d = torch.from_numpy(np.stack(lut_a + lut_b)).to(dev, non_blocking=True)
+                    desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
+                    lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
                     cur.wait_event(up)
                     # [2n, H, W]: a_0..a_n-1, b_0..b_n-1 (with a background: minus bg_a / bg_b, in the same kernel)
                     frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=bg)
@@ -1013,18 +939,16 @@ class OfflinePIV:
                 let_go(release)
                 release = (up,)
                 # the host work of the PREVIOUS batches runs while the GPU works on this one
-                yield from emit(pipe.push((order, chunk), ticket))
+                yield from emit(pipe.push((st.order, st.chunk), ticket))
             let_go(release)
             release = None
             yield from emit(pipe.flush())
         finally:
             # consumer finished, raised, or abandoned the generator (GeneratorExit lands here): stop the reader threads,
             # then wait for every upload / unpack still queued (they read the staging buffers and write raw_dev, which the
-            # next batched() call on this object reuses with a fresh upload stream and no events to order itself behind)
-            rd.close()
+            # next run over files on this object reuses with a fresh upload stream and no events to order itself behind)
+            batches.close()
             torch.cuda.synchronize(dev)
-            if decoders is not None:
-                decoders.shutdown(wait=False)
 
 
 class ResidentPIV(OfflinePIV):
@@ -1041,21 +965,13 @@ class ResidentPIV(OfflinePIV):
             raise ValueError("ResidentPIV: two uint8 tensors [n, H, W] of one shape")
         if precision not in PRECISIONS:
             raise KeyError(precision)
-        self._bg_arg = _background_arg(background, frames_a.shape[1:])
-        self._bg = None
-        self._bg_frames = None           # the frames of a launch minus the background: uint8 [2, batch, H, W], reused
-        self._outlier = engine.outlier_arg(outlier)
-        self._precision = precision
-        self._val_ratio, self._val_win = float(validation_ratio), int(validation_window)
-        self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
-        self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
-        self._device = _require_gpu(frames_a.device)
-        self._iter_function = IterModMap.functions[multipass_mode]
-        self._mode = multipass_mode
-        self._plan = None
+        bg_arg = _background_arg(background, frames_a.shape[1:])
+        outlier = engine.outlier_arg(outlier)
+        device = _require_gpu(frames_a.device)
+        self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
+                         multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
+                         validation_window, bg_arg, outlier)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
-        self._dataset = range(frames_a.shape[0])
-        self.reset_stats()
 
     def frame_shape(self):
         return tuple(self._A.shape[1:]) if len(self) else None

@@ -9,6 +9,7 @@ formats are opened with Pillow and converted with OpenCV's rules (16-bit >> 8, f
 """
 from __future__ import annotations
 
+import collections
 import os
 import re
 import struct
@@ -216,6 +217,72 @@ class ReadAhead:
             self._h = None
 
     __del__ = close
+
+
+def slot_bytes(H: int, W: int, files) -> int:
+    """Bytes of one staging slot: the largest of `files` (a pair's files stand for the run's, which share one format;
+    missing ones are skipped) and a headerless frame [H, W], rounded up to 4 KiB."""
+    sizes = [H * W] + [os.path.getsize(p_) for p_ in files if os.path.exists(p_)]
+    return (max(sizes) + 4095) // 4096 * 4096
+
+
+# A batch of StagedBatches: the staging buffer that holds it, its file slots in use, [(pair id, staged)] of all its pairs,
+# the ids of the n staged ones and their tables for tpiv_bmp_unpack (desc int64 [2n, 6], lut uint8 [2n, 256]: every a, then every b)
+Staged = collections.namedtuple("Staged", "buf n_files order chunk desc lut")
+
+
+class StagedBatches:
+    """The host side of a run over files (OfflinePIV.batched, compute_background): iterating gives one Staged per `batch`
+    pairs of `idx`.  pairs[i][0] / pairs[i][-1] are pair i's files; slot 2k of a batch is frame a of its pair k, slot
+    2k + 1 frame b.  The files arrive through the read-ahead ring (`reader`) in `bufs`, uint8 numpy views [2 * batch, cap] of
+    page-locked memory; the sweep over a batch's headers (parse_bmp_headers) hands the files it cannot place -- and every
+    file of a format the ring does not read -- to stage_raw in a thread pool.  A pair with a file that cannot be staged
+    (undecodable, another frame shape) is left to the caller.  release(): the oldest batch's bytes have left its buffer."""
+
+    def __init__(self, idx, pairs, batch: int, H: int, W: int, bufs, cap: int, threads: int = 8):
+        self._idx, self._batch, self._shape, self._bufs, self._cap, self._threads = idx, batch, (H, W), bufs, cap, threads
+        self._paths = [p_ for i in idx for p_ in (pairs[i][0], pairs[i][-1])]
+        self._decoders = None
+        # (formats the device cannot unpack are not read by the ring at all)
+        self.reader = ReadAhead(self._paths, 2 * batch, [b_.ctypes.data for b_ in bufs], cap, threads=threads,
+                                read=str(self._paths[0]).lower().endswith(".bmp"))
+        self.release = self.reader.release
+
+    def __iter__(self):
+        (H, W), cap = self._shape, self._cap
+        for s0 in range(0, len(self._idx), self._batch):
+            got = self.reader.next()
+            if got is None:
+                break
+            buf, sizes = got
+            raw = self._bufs[buf]
+            lays = parse_bmp_headers(raw[:len(sizes)], sizes, H, W)
+            rest = [j for j, lay in enumerate(lays) if lay is None]
+            if rest:
+                if self._decoders is None:
+                    from concurrent.futures import ThreadPoolExecutor
+                    self._decoders = ThreadPoolExecutor(max_workers=self._threads)
+                for j, lay in zip(rest, self._decoders.map(lambda j: stage_raw(self._paths[2 * s0 + j], raw[j], H, W), rest)):
+                    lays[j] = lay
+            order, chunk, desc_a, desc_b, lut_a, lut_b = [], [], [], [], [], []
+            for k, i in enumerate(self._idx[s0:s0 + self._batch]):
+                la, lb = lays[2 * k], lays[2 * k + 1]
+                order.append((i, la is not None and lb is not None))
+                if la is not None and lb is not None:
+                    desc_a.append([2 * k * cap, la[0], la[1], la[2], la[3], 0])
+                    desc_b.append([(2 * k + 1) * cap, lb[0], lb[1], lb[2], lb[3], 1])      # [5]: background slot
+                    lut_a.append(la[4])
+                    lut_b.append(lb[4])
+                    chunk.append(i)
+            yield Staged(buf, len(sizes), order, chunk, np.array(desc_a + desc_b, dtype=np.int64).reshape(-1, 6),
+                         np.array(lut_a + lut_b, dtype=np.uint8).reshape(-1, 256))
+
+    def close(self):
+        """Stops the reader threads and the decoders, also mid-run (idempotent: for a `finally`)."""
+        self.reader.close()
+        if self._decoders is not None:
+            self._decoders.shutdown(wait=False)
+            self._decoders = None
 
 
 def imdecode_gray(path: str):
