@@ -271,6 +271,25 @@ int tpiv_frame_min(const uint8_t* frames_dev, int n, long long pixels, uint8_t* 
 int tpiv_subtract_background(const uint8_t* frames_dev, int n, long long pixels, const uint8_t* bg_dev,
                              uint8_t* out_dev, void* stream);
 
+/* ---- spatial pre-filters ------------------------------------------------------------------ */
+
+enum tpiv_prefilter_kind {
+    TPIV_PREFILTER_NONE = 0, /* background and cap only */
+    TPIV_PREFILTER_MIN = 1,  /* minus the minimum of the size x size neighbourhood */
+    TPIV_PREFILTER_MEAN = 2  /* minus the rounded mean of the size x size neighbourhood, clamped at 0 */
+};
+
+/* Filters n frames frames_dev [n, H, W] uint8 into out_dev, one launch for all of them, in integer arithmetic (every
+ * implementation of these lines gives the same bytes).  g = max(f, bg) - bg with bg_dev [H, W], g = f with bg_dev NULL.
+ * The neighbourhood of a pixel is the size x size square around it clipped to the image (no padding value), c its
+ * pixel count, size odd in 3..63.  MIN: out = g - min(neighbourhood of g).  MEAN: S = the neighbourhood's sum,
+ * m = (2 S + c) / (2 c) (integer division: the mean rounded half up), out = max(g - m, 0).  NONE: out = g, size is not
+ * read.  Then out = min(out, cap), cap in 1..255 (255: no capping).  out_dev must not overlap frames_dev, not even as
+ * frames_dev itself (the filter is a stencil): TPIV_EINVAL, like a bad kind, size, cap or shape; nothing is launched
+ * then.  Enqueues only; allocates nothing. */
+int tpiv_prefilter(const uint8_t* frames_dev, int n, int H, int W, const uint8_t* bg_dev, int kind, int size, int cap,
+                   uint8_t* out_dev, void* stream);
+
 /* Host side of the ingest (no GPU involved): reads n_files files into dst + i * slot_bytes (page-locked staging memory
  * of the caller, at most slot_bytes each) with up to n_threads native reader threads -- what PIVDataset.__getitem__
  * (B:129-144) does file by file with np.fromfile, here for a whole batch without the interpreter in the loop.

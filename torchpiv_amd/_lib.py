@@ -18,6 +18,8 @@ MODES = {"DWS": MODE_DWS, "CWS": MODE_CWS}           # the multipass modes of Of
 ITER_MODES = dict(MODES, CWS_Fast=MODE_CWS_FAST)     # + piv_iteration_CWS_Fast (function-level seam only)
 PREC_FAST, PREC_REFERENCE, PREC_F64, PREC_EXACT = 0, 1, 2, 3
 PRECISIONS = {"fast": PREC_FAST, "reference": PREC_REFERENCE, "f64": PREC_F64, "exact": PREC_EXACT}
+PREFILTER_NONE, PREFILTER_MIN, PREFILTER_MEAN = 0, 1, 2
+PREFILTERS = {None: PREFILTER_NONE, "min": PREFILTER_MIN, "mean": PREFILTER_MEAN}    # tpiv_prefilter's kinds
 ABI_VERSION = 2
 
 
@@ -80,6 +82,7 @@ SIGNATURES = {
     "tpiv_bmp_unpack_bg": (C.c_int, [_u8p, _vp, _u8p, _int, _int, _int, _u8p, _u8p, _vp]),
     "tpiv_frame_min": (C.c_int, [_u8p, _int, C.c_longlong, _u8p, _vp]),
     "tpiv_subtract_background": (C.c_int, [_u8p, _int, C.c_longlong, _u8p, _u8p, _vp]),
+    "tpiv_prefilter": (C.c_int, [_u8p, _int, _int, _int, _u8p, _int, _int, _int, _u8p, _vp]),
     "tpiv_read_files": (C.c_int, [C.POINTER(C.c_char_p), _int, C.c_void_p, C.c_size_t, _int, C.POINTER(C.c_longlong)]),
     "tpiv_reader_open": (C.c_void_p, [C.POINTER(C.c_char_p), C.c_longlong, _int, C.POINTER(C.c_void_p), _int, C.c_size_t, _int]),
     "tpiv_reader_next": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),

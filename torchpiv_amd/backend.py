@@ -371,7 +371,8 @@ class OfflinePIV:
     def __init__(self, folder: str, device: str, file_fmt: str, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
-                 validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None) -> None:
+                 validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
+                 prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -390,6 +391,10 @@ class OfflinePIV:
         # windows; a flagged vector of the last pass joins the invalid ones and is filled by the post-validation.  More
         # flagged vectors mean more pairs reach the reference's "to many false vectors" rule (4 * ring >= cells, B:299)
         # and are dropped, exactly as for peak-ratio holes.
+        # prefilter (extension): None or a dict with kind ("min", "mean" or None), size (odd, 3..63) and optionally cap
+        # (1..255) -- the spatial pre-filter every frame passes on the device after the background and before the passes
+        # (engine.prefilter_arg, tpiv_prefilter): minus the minimum / the rounded mean of its size x size neighbourhood,
+        # then capped.  For background that is smooth in space but differs from frame to frame.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
@@ -397,7 +402,7 @@ class OfflinePIV:
         iter_function = IterModMap.functions[multipass_mode]            # KeyError like B:850
         self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
-                         engine.outlier_arg(outlier))
+                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter))
         if not self:
             return
         if self._bg_arg is not None and self._bg_arg != "min":
@@ -405,10 +410,10 @@ class OfflinePIV:
         _require_gpu(self._device)
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
-                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier):
+                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
-        run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's) and the state that the methods
-        build up, empty."""
+        run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
+        engine.prefilter_arg's) and the state that the methods build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
         self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
@@ -416,8 +421,10 @@ class OfflinePIV:
         self._val_ratio, self._val_win = float(validation_ratio), int(validation_window)
         self._bg_arg = bg_arg
         self._outlier = outlier
+        self._prefilter = prefilter
+        self._pf_frames = None           # batched(): the filtered frames of a launch, uint8 [2 * batch, H, W], reused
         self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
-        self._bg_frames = None           # ResidentPIV: the frames of a launch minus the background, uint8 [2, batch, H, W], reused
+        self._bg_frames = None           # ResidentPIV: the frames of a launch minus the background / filtered, uint8 [2, batch, H, W], reused
         self._plan = None
         self._single_plans = {}          # plans of the one-pair path, per frame shape
         self._reader = None              # the ReadAhead of the latest run over files (closed when that run ended)
@@ -828,7 +835,10 @@ class OfflinePIV:
         b = b.to(self._device, non_blocking=True)
         shape = (int(a.shape[-2]), int(a.shape[-1]))
         bg = self._background(shape)
-        if bg is not None:
+        if self._prefilter is not None:                 # one launch per frame, the background subtracted in the same one
+            a = engine.prefilter(a, background=None if bg is None else bg[0], **self._prefilter)
+            b = engine.prefilter(b, background=None if bg is None else bg[1], **self._prefilter)
+        elif bg is not None:
             a = engine.subtract_background(a, bg[0])
             b = engine.subtract_background(b, bg[1])
         plan = self._single_plans.get(shape)
@@ -934,6 +944,13 @@ class OfflinePIV:
                     frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=bg)
                     consumed[dbuf] = torch.cuda.Event()
                     consumed[dbuf].record(cur)
+                    if self._prefilter is not None:
+                        # one launch over the stack (the unpack subtracted already), into a buffer kept from batch to
+                        # batch: stream order keeps a batch's passes ahead of the next batch's filter
+                        pf = self._pf_frames
+                        if pf is None or pf.shape[0] < 2 * batch_size or tuple(pf.shape[1:]) != (H, W) or pf.device != frames.device:
+                            pf = self._pf_frames = torch.empty((2 * batch_size, H, W), dtype=torch.uint8, device=frames.device)
+                        frames = engine.prefilter(frames, out=pf[:frames.shape[0]], **self._prefilter)
                     u, v, inv = plan.run(frames[:n], frames[n:])
                     ticket = self._post_submit(u, v, inv, plan=plan)
                 let_go(release)
@@ -959,7 +976,7 @@ class ResidentPIV(OfflinePIV):
     def __init__(self, frames_a: torch.Tensor, frames_b: torch.Tensor, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
-                 validation_window: int = 3, background=None, outlier=None) -> None:
+                 validation_window: int = 3, background=None, outlier=None, prefilter=None) -> None:
         if frames_a.shape != frames_b.shape or frames_a.dim() != 3 or frames_a.dtype != torch.uint8 \
                 or frames_b.dtype != torch.uint8:
             raise ValueError("ResidentPIV: two uint8 tensors [n, H, W] of one shape")
@@ -967,10 +984,11 @@ class ResidentPIV(OfflinePIV):
             raise KeyError(precision)
         bg_arg = _background_arg(background, frames_a.shape[1:])
         outlier = engine.outlier_arg(outlier)
+        prefilter = engine.prefilter_arg(prefilter)
         device = _require_gpu(frames_a.device)
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
-                         validation_window, bg_arg, outlier)
+                         validation_window, bg_arg, outlier, prefilter)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):
@@ -1005,10 +1023,11 @@ class ResidentPIV(OfflinePIV):
             return
         H, W = self._A.shape[1:]
         bg = self._background((H, W))
-        if bg is not None:
+        pf = self._prefilter
+        if bg is not None or pf is not None:
             buf = self._bg_frames
-            if buf is None or buf.shape[1] < batch_size or buf.device != bg.device:
-                buf = self._bg_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=bg.device)
+            if buf is None or buf.shape[1] < batch_size or buf.device != self._A.device:
+                buf = self._bg_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
         plan = self._get_plan(H, W, max_batch=batch_size)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
@@ -1029,7 +1048,11 @@ class ResidentPIV(OfflinePIV):
             else:
                 sel = torch.tensor(chunk, device=self._device)
                 A, B = self._A.index_select(0, sel), self._B.index_select(0, sel)
-            if bg is not None:
+            if pf is not None:
+                # one launch per frame stack, the background subtracted in the same one, into the same reused buffer
+                A = engine.prefilter(A, background=None if bg is None else bg[0], out=buf[0, :len(chunk)], **pf)
+                B = engine.prefilter(B, background=None if bg is None else bg[1], out=buf[1, :len(chunk)], **pf)
+            elif bg is not None:
                 # into the reused buffer (the caller's frames are never written); stream order keeps a launch's passes
                 # ahead of the next launch's subtraction into the same memory
                 A = engine.subtract_background(A, bg[0], out=buf[0, :len(chunk)])

@@ -998,6 +998,25 @@ int tpiv_subtract_background(const uint8_t* frames, int n, long long pixels, con
     return TPIV_OK;
 }
 
+int tpiv_prefilter(const uint8_t* frames, int n, int H, int W, const uint8_t* bg, int kind, int size, int cap,
+                   uint8_t* out, void* stream) {
+    if (n < 0 || H <= 0 || W <= 0) return fail(TPIV_EINVAL, "tpiv_prefilter: bad shape");
+    if (kind != TPIV_PREFILTER_NONE && kind != TPIV_PREFILTER_MIN && kind != TPIV_PREFILTER_MEAN)
+        return fail(TPIV_EINVAL, "tpiv_prefilter: kind must be TPIV_PREFILTER_NONE, _MIN or _MEAN");
+    if (kind != TPIV_PREFILTER_NONE && (size < 3 || size > 63 || size % 2 == 0))
+        return fail(TPIV_EINVAL, "tpiv_prefilter: size must be odd and in 3..63");
+    if (cap < 1 || cap > 255) return fail(TPIV_EINVAL, "tpiv_prefilter: cap must be in 1..255 (255: none)");
+    if (n == 0) return TPIV_OK;
+    if (!frames || !out) return fail(TPIV_EINVAL, "tpiv_prefilter: null pointer");
+    const size_t bytes = (size_t)n * H * W;
+    if (out < frames + bytes && frames < out + bytes)
+        return fail(TPIV_EINVAL, "tpiv_prefilter: out overlaps frames (the filter is a stencil: not in place)");
+    if (bg && out < bg + (size_t)H * W && bg < out + bytes)
+        return fail(TPIV_EINVAL, "tpiv_prefilter: out overlaps the background");
+    HIP_TRY(tpiv::launch_prefilter(frames, n, H, W, bg, kind, size, cap, out, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
 namespace {
 // One file into a slot of at most slot_bytes: bytes read, or -1 (cannot open / not a regular file / too big / short read).
 int64_t read_one_file(const char* path, uint8_t* out, size_t slot_bytes) {

@@ -170,6 +170,14 @@ hipError_t launch_bmp_unpack_bg(const uint8_t* raw, const long long* desc, const
 hipError_t launch_frame_min(const uint8_t* frames, int n, long long pixels, uint8_t* acc, hipStream_t stream);
 hipError_t launch_subtract_background(const uint8_t* frames, int n, long long pixels, const uint8_t* bg, uint8_t* out,
                                       hipStream_t stream);
+// spatial pre-filters (prefilter.hip): out = filter(max(frames, bg) - bg), bg [H, W] or nullptr; kind PREFILTER_MIN: minus the
+// minimum of the size x size neighbourhood, PREFILTER_MEAN: minus its rounded mean (clamped at 0), PREFILTER_NONE: nothing; then
+// min(., cap) (cap 255: none).  One workgroup per PREFILTER_TILE_COLS x PREFILTER_TILE_ROWS tile of a frame, the tile and its
+// halo staged in LDS; out must not overlap frames (a stencil).
+constexpr int PREFILTER_NONE = 0, PREFILTER_MIN = 1, PREFILTER_MEAN = 2;
+constexpr int PREFILTER_TILE_COLS = 128, PREFILTER_TILE_ROWS = 64;
+hipError_t launch_prefilter(const uint8_t* frames, int n, int H, int W, const uint8_t* bg, int kind, int size, int cap,
+                            uint8_t* out, hipStream_t stream);
 
 // normalized median test (outlier.hip): one lane per cell, one workgroup per OUTLIER_TILE_COLS x OUTLIER_TILE_ROWS tile
 // (a wavefront per tile row), the tile and its one-cell halo staged in LDS

@@ -383,6 +383,65 @@ def subtract_background(frames, bg, out=None):
     return out
 
 
+PREFILTER_KEYS = ("kind", "size", "cap")
+
+
+def prefilter_arg(prefilter):
+    """The prefilter= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no filter) or a
+    dict with kind ("min": sliding-minimum subtraction, "mean": local-mean high-pass, None: capping only), size (odd, 3..63;
+    required with a kind) and optionally cap (1..255).  Returns None or {"kind", "size", "cap"} with ints (size None
+    without a kind, cap None without capping); anything else, a dict that asks for nothing included, raises ValueError."""
+    if prefilter is None:
+        return None
+    if not isinstance(prefilter, dict):
+        raise ValueError(f"prefilter: None or a dict of {list(PREFILTER_KEYS)}, got {type(prefilter).__name__}")
+    unknown = sorted(set(prefilter) - set(PREFILTER_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"prefilter: unknown key(s) {unknown}; known: {list(PREFILTER_KEYS)}")
+    kind, size, cap = prefilter.get("kind"), prefilter.get("size"), prefilter.get("cap")
+
+    def integer(x):
+        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+    if kind is not None and (not isinstance(kind, str) or kind not in ("min", "mean")):
+        raise ValueError(f"prefilter: kind must be 'min', 'mean' or None, got {kind!r}")
+    if kind is None:
+        if size is not None and not (integer(size) and 3 <= size <= 63 and size % 2 == 1):
+            raise ValueError(f"prefilter: size must be an odd integer in 3..63, got {size!r}")
+        size = None
+    elif size is None:
+        raise ValueError(f"prefilter: kind {kind!r} needs a size (odd, 3..63)")
+    elif not (integer(size) and 3 <= size <= 63 and size % 2 == 1):
+        raise ValueError(f"prefilter: size must be an odd integer in 3..63, got {size!r}")
+    if cap is not None and not (integer(cap) and 1 <= cap <= 255):
+        raise ValueError(f"prefilter: cap must be an integer in 1..255, got {cap!r}")
+    if kind is None and cap is None:
+        raise ValueError("prefilter: the dict asks for nothing (no kind and no cap); pass None for no filter")
+    return {"kind": kind, "size": None if size is None else int(size), "cap": None if cap is None else int(cap)}
+
+
+def prefilter(frames, kind, size=None, cap=None, background=None, out=None):
+    """Spatial pre-filter of uint8 frames [n, H, W] or [H, W] on the device, one launch (tpiv_prefilter): with g = max(f,
+    background) - background (g = f without one, background uint8 [H, W]) and the size x size neighbourhood clipped to
+    the image, kind "min": g - min(neighbourhood), "mean": max(g - rounded mean(neighbourhood), 0), None: g; then
+    min(., cap).  out: a tensor of the frames' shape that does not overlap them (the filter is a stencil: never in
+    place); None: a fresh one.  The frames are not written."""
+    par = prefilter_arg({"kind": kind, "size": size, "cap": cap})
+    f, H, W = _images(frames, "prefilter")
+    _need_cuda(background, out)
+    if background is not None and (background.dtype != torch.uint8 or tuple(background.shape) != (H, W)
+                                   or not background.is_contiguous() or background.device != f.device):
+        raise ValueError("prefilter: background must be a contiguous uint8 [H, W] tensor on the frames' device")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or not out.is_contiguous() or out.device != f.device:
+        raise ValueError("prefilter: out must be a contiguous uint8 tensor of the frames' shape and device")
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_prefilter(f.data_ptr(), f.shape[0], H, W, None if background is None else background.data_ptr(),
+                                 _lib.PREFILTERS[par["kind"]], par["size"] or 0, par["cap"] or 255, out.data_ptr(),
+                                 _stream()))
+    return out
+
+
 class Plan:
     """The multipass pipeline of OfflinePIV.__call__ (PIVbackend.py:873-882) for batches of
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
