@@ -350,6 +350,18 @@ int tpiv_debug_pass(int mode, int precision, const uint8_t* a_dev, const uint8_t
                     double* u_dev, double* v_dev, uint8_t* invalid_dev,
                     float* win_dev, float* corr_dev, void* work_dev, size_t work_bytes, void* stream);
 
+/* Runs one shifted pass (mode DWS or CWS) from the COMPACT predictor hand-off, exactly as tpiv_plan_run does after its
+ * predictor: u_raw_dev, v_raw_dev [batch, n_rows, n_cols] float64 are the raw predictor (before the invalid-zeroing) and
+ * mask_dev [batch, n_rows, n_cols] uint8 its thresholded mask (non-zero = the interpolated mask reached 0.5); the zeroing,
+ * the halving and DWS's rint are formed by the kernels where they read them.  Everything else -- outputs, du_dev / dv_dev
+ * (either may be NULL), work buffer -- is tpiv_iter's.  Lets the tests plant a predictor and compare the compact form with
+ * the four fields of tpiv_iter bit for bit.  TPIV_EINVAL for CWS_Fast (which has no compact form) and for a NULL mask. */
+int tpiv_debug_iter_compact(int mode, const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H, int W,
+                            int ws, int ov, const double* u_raw_dev, const double* v_raw_dev, const uint8_t* mask_dev,
+                            double val_ratio, int val_win, int precision,
+                            double* u_dev, double* v_dev, uint8_t* invalid_dev, double* du_dev, double* dv_dev,
+                            void* work_dev, size_t work_bytes, void* stream);
+
 /* Peak analysis alone -- correlation_to_displacement (B:360-422) + peak2peak_secondpeak
  * (B:346-358) -- on caller-supplied correlation maps [n_maps, ws, ws] float32 in fftshift layout
  * (ws = 8, 16, 32, 64 or 128): runs the kernels' peak stage and finalize on them.  planar != 0

@@ -172,7 +172,8 @@ def predictors(mode, ws, F, nr, nc, seed):
     row coordinates, which send 64 x 64 items to the per-pixel path); shifts that push border windows off the frame edge
     (each window moved away from the frame centre, so the border windows' samples leave the frame).  DWS: tpiv_debug_pass
     takes the half shift after the predictor's rint (B:782-785), so it gets integers in every family and no rint tie can
-    be exercised through it (the ties are the predictor's, tested with it)."""
+    be exercised through it (the ties belong to the predictor hand-off: tests/test_gpu_handoff.py,
+    test_compact_and_four_field_hand_off, plants them; tests/test_handoff_model.py pins the rule)."""
     rng = np.random.default_rng(seed)
     integral = mode == DWS
     r = rng.uniform(-9, 9, (2, F, nr, nc))

@@ -536,6 +536,18 @@ int tpiv_debug_pass(int mode, int precision, const uint8_t* a, const uint8_t* b,
                     invalid, nullptr, nullptr, win, corr, work, work_bytes, stream);
 }
 
+int tpiv_debug_iter_compact(int mode, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
+                            const double* u_raw, const double* v_raw, const uint8_t* mask, double val_ratio, int val_win,
+                            int precision, double* u, double* v, uint8_t* invalid, double* du, double* dv, void* work,
+                            size_t work_bytes, void* stream) {
+    if (mode != TPIV_MODE_DWS && mode != TPIV_MODE_CWS)
+        return fail(TPIV_EINVAL, "tpiv_debug_iter_compact: the compact hand-off exists for DWS and CWS only");
+    if (!mask) return fail(TPIV_EINVAL, "tpiv_debug_iter_compact: mask missing");
+    // the call of tpiv_plan_run: raw predictor + mask byte, no half-shift fields
+    return run_iter(mode, precision, a, b, batch, H, W, ws, ov, u_raw, v_raw, nullptr, nullptr, val_ratio, val_win, u, v,
+                    invalid, du, dv, nullptr, nullptr, work, work_bytes, stream, mask);
+}
+
 int tpiv_debug_peaks(const float* maps, int n_maps, int ws, int planar, double val_ratio, int val_win, double* u,
                      double* v, uint8_t* invalid, void* work, size_t work_bytes, void* stream) {
     if (ws != 8 && ws != 16 && ws != 32 && ws != 64 && ws != 128)

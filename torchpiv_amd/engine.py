@@ -148,6 +148,41 @@ def iterate(mode, a, b, ws, ov, u0, v0, u2, v2, val_ratio=1.2, val_win=3, want_r
     return u, v, inv
 
 
+def iterate_compact(mode, a, b, ws, ov, u_raw, v_raw, mask, val_ratio=1.2, val_win=3, want_raw=False, precision="exact"):
+    """Test hook: iterate() fed with the compact hand-off of Plan.run -- the raw predictor u_raw, v_raw (float64, before
+    the invalid-zeroing) and its thresholded mask (uint8) -- instead of the four fields u0, v0, u2, v2: the zeroing, the
+    halving and DWS's rint happen where the kernels read them.  mode "DWS" or "CWS"; same outputs as iterate()."""
+    prec = _precision(precision)
+    a, b = _frames(a, b)
+    _need_cuda(u_raw, v_raw, mask)
+    if mask.dtype != torch.uint8:
+        raise TypeError("mask must be uint8")
+    B, H, W = a.shape
+    nr, nc = field_shape(H, W, ws, ov)
+    for t in (u_raw, v_raw, mask):
+        if tuple(t.shape) != (B, nr, nc):
+            raise ValueError(f"predictor fields must be [{B}, {nr}, {nc}], got {tuple(t.shape)}")
+    if u_raw.dtype != torch.float64 or v_raw.dtype != torch.float64:
+        raise TypeError("u_raw, v_raw must be float64")
+    u_raw, v_raw, mask = u_raw.contiguous(), v_raw.contiguous(), mask.contiguous()
+    dev = a.device
+    u = torch.empty(B, nr, nc, dtype=torch.float64, device=dev)
+    v = torch.empty_like(u)
+    inv = torch.empty(B, nr, nc, dtype=torch.uint8, device=dev)
+    du = torch.empty_like(u) if want_raw else None
+    dv = torch.empty_like(u) if want_raw else None
+    with torch.cuda.device(dev):
+        work, nbytes = _work(H, W, ws, ov, B, dev)
+        check(lib.tpiv_debug_iter_compact(ITER_MODES[mode], a.data_ptr(), b.data_ptr(), B, H, W, ws, ov,
+                                          u_raw.data_ptr(), v_raw.data_ptr(), mask.data_ptr(), val_ratio, val_win, prec,
+                                          u.data_ptr(), v.data_ptr(), inv.data_ptr(),
+                                          du.data_ptr() if want_raw else None, dv.data_ptr() if want_raw else None,
+                                          work.data_ptr(), nbytes, _stream()))
+    if want_raw:
+        return u, v, inv, du, dv
+    return u, v, inv
+
+
 def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference"):
     """Test hook: one pass plus the staged windows and the correlation maps (shifted passes at
     `precision`: "reference" = the reference's operation order, bit-identical windows).  Pass 1
