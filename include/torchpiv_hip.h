@@ -290,6 +290,26 @@ enum tpiv_prefilter_kind {
 int tpiv_prefilter(const uint8_t* frames_dev, int n, int H, int W, const uint8_t* bg_dev, int kind, int size, int cap,
                    uint8_t* out_dev, void* stream);
 
+/* ---- deep (10..16-bit) frames ---------------------------------------------------------------- */
+
+/* Tone map: out_dev[f][y][x] = lut_dev[src_dev[src_off_dev[f] + y * W + x]] for n frames of uint16 samples, one launch.
+ * lut_dev: uint8 [65536] on the device (torchpiv_amd.engine.depth_lut builds the linear and the square-root curve on the
+ * host; any table is allowed).  src_off_dev: n element offsets into src_dev, on the device, each frame inside memory of
+ * the caller (not checked: they live on the device); NULL: frame f starts at f * H * W.  One launch so turns the
+ * interleaved a / b slots of a staged batch into the contiguous stacks the plan reads.  out_dev [n, H, W] must overlap
+ * neither the source nor the table; src_dev is not written and no byte outside out_dev's n * H * W is.  src_dev needs
+ * 2-byte alignment only (16-byte aligned frames with 8-byte aligned outputs move fastest).  TPIV_EINVAL for a null
+ * pointer, n < 0, H or W < 1, an overlap that can be seen from the host; n == 0 succeeds and launches nothing.
+ * Enqueues only; allocates nothing. */
+int tpiv_depth_map(const uint16_t* src_dev, const long long* src_off_dev, int n, int H, int W, const uint8_t* lut_dev,
+                   uint8_t* out_dev, void* stream);
+
+/* hist_dev[v] += the number of samples equal to v among the n frames src_dev [n, pixels_per_frame] uint16, for all 65536
+ * values, exactly.  hist_dev: uint64 [65536] on the device, accumulated (start from zeros): one call or several over
+ * parts of a recording give the histogram of all of them.  Same error rules as tpiv_depth_map. */
+int tpiv_depth_histogram(const uint16_t* src_dev, int n, long long pixels_per_frame, unsigned long long* hist_dev,
+                         void* stream);
+
 /* Host side of the ingest (no GPU involved): reads n_files files into dst + i * slot_bytes (page-locked staging memory
  * of the caller, at most slot_bytes each) with up to n_threads native reader threads -- what PIVDataset.__getitem__
  * (B:129-144) does file by file with np.fromfile, here for a whole batch without the interpreter in the loop.

@@ -372,7 +372,7 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 prefilter=None) -> None:
+                 depth=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -395,14 +395,22 @@ class OfflinePIV:
         # (1..255) -- the spatial pre-filter every frame passes on the device after the background and before the passes
         # (engine.prefilter_arg, tpiv_prefilter): minus the minimum / the rounded mean of its size x size neighbourhood,
         # then capped.  For background that is smooth in space but differs from frame to frame.
+        # depth (extension): None -- 8-bit frames, a 16-bit file decoded as value >> 8 like the reference (cv2's
+        # IMREAD_GRAYSCALE) --, or the tone map of deep frames (engine.depth_arg): the files are decoded to uint16 with their
+        # full sample range (io.imdecode_deep) and every frame passes out = lut[sample] on the device (tpiv_depth_map) before
+        # the background, the pre-filter and the passes.  {"lo", "hi", "curve"}: a fixed range; "auto" / {"auto": True, ...}:
+        # the range from the histogram of a sample of pairs (tpiv_depth_histogram + engine.depth_range), resolved on first
+        # use; {"lut": table}: the caller's table.  A background image given by the caller is in mapped (uint8) units.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
-        dataset = PIVDataset(folder, file_fmt, folder_mode, transform=ToTensor(dtype=torch.uint8))
+        depth = engine.depth_arg(depth)
+        dataset = PIVDataset(folder, file_fmt, folder_mode, deep=depth is not None,
+                             transform=ToTensor(dtype=torch.uint8 if depth is None else torch.uint16))
         iter_function = IterModMap.functions[multipass_mode]            # KeyError like B:850
         self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
-                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter))
+                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth)
         if not self:
             return
         if self._bg_arg is not None and self._bg_arg != "min":
@@ -410,10 +418,10 @@ class OfflinePIV:
         _require_gpu(self._device)
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
-                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None):
+                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
-        engine.prefilter_arg's) and the state that the methods build up, empty."""
+        engine.prefilter_arg's, depth: engine.depth_arg's) and the state that the methods build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
         self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
@@ -422,6 +430,10 @@ class OfflinePIV:
         self._bg_arg = bg_arg
         self._outlier = outlier
         self._prefilter = prefilter
+        self._depth = depth
+        self._depth_range = (depth["lo"], depth["hi"]) if depth is not None and "lo" in depth else None
+        self._depth_lut = None           # the tone-map table in use: uint8 [65536] on the device, once resolved
+        self._depth_frames = None        # the mapped frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
         self._pf_frames = None           # batched(): the filtered frames of a launch, uint8 [2 * batch, H, W], reused
         self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
         self._bg_frames = None           # ResidentPIV: the frames of a launch minus the background / filtered, uint8 [2, batch, H, W], reused
@@ -484,6 +496,54 @@ class OfflinePIV:
             self._raw_dev_key = (batch_size, cap, str(dev))
         return self._stage, self._raw_dev
 
+    @property
+    def depth_range_(self):
+        """(lo, hi) of the tone map of depth=: the given range, or what depth="auto" found once it has run; None before
+        that, for a caller's own table and without depth."""
+        return self._depth_range
+
+    def _depth_pairs(self, sample):
+        """The uint16 frames (a, b) of the pairs engine.depth_sample picks from the whole dataset, on the device; pairs that
+        cannot be decoded or have another frame shape than the dataset's are left out."""
+        shape = self.frame_shape()
+        for i in engine.depth_sample(len(self._dataset), sample):
+            a, b = self._dataset[int(i)]
+            if a is not None and b is not None and tuple(a.shape) == tuple(b.shape) == tuple(shape):
+                yield a.to(self._device), b.to(self._device)
+
+    def _depth_table(self):
+        """The tone-map table of depth= on the device (uint8 [65536]), None without depth.  "auto" takes the histogram of
+        both frames of the sampled pairs here (one common histogram, so frame a and frame b get the same map), once per
+        object -- always over the whole dataset, whatever part of it a run then processes, so that every rank of a
+        sharded run finds the same range without a collective."""
+        d = self._depth
+        if d is None:
+            return None
+        if self._depth_lut is None:
+            if "lut" in d:
+                table = d["lut"]
+            else:
+                if "auto" in d:
+                    acc = None
+                    for a, b in self._depth_pairs(d["sample"]):
+                        acc = engine.depth_histogram(b, engine.depth_histogram(a, acc))
+                    if acc is None:
+                        raise ValueError("depth='auto': none of the sampled pairs could be decoded")
+                    self._depth_range = engine.depth_range(acc.cpu().numpy(), d["clip_low"], d["clip_high"])
+                table = engine.depth_lut(self._depth_range[0], self._depth_range[1], d["curve"])
+            self._depth_lut = torch.from_numpy(table).to(self._device)
+        return self._depth_lut
+
+    def _map_staged(self, raw_d, st, H, W, lut, batch_size):
+        """The staged uint16 slots of a batch (raw_d uint8 [files, cap] on the device, io.StagedBatches(deep=True)) through
+        the tone map, one launch: uint8 [2n, H, W] = a_0..a_n-1, b_0..b_n-1, in a buffer kept from batch to batch."""
+        buf = self._depth_frames
+        if buf is None or buf.dim() != 3 or buf.shape[0] < 2 * batch_size or tuple(buf.shape[1:]) != (H, W) \
+                or buf.device != raw_d.device:
+            buf = self._depth_frames = torch.empty((2 * batch_size, H, W), dtype=torch.uint8, device=raw_d.device)
+        off = torch.from_numpy(st.desc[:, 0] // 2)              # the slots' element offsets, every a, then every b
+        return engine.depth_map(raw_d.view(-1).view(torch.uint16), lut, offsets=off, shape=(H, W), out=buf[:off.shape[0]])
+
     def _background(self, shape, batch_size=None):
         """The background the frames of shape (H, W) lose (uint8 [2, H, W] on the device: bg_a, bg_b), None without one.
         "min" runs compute_background() here, once per object."""
@@ -509,7 +569,8 @@ class OfflinePIV:
         be decoded or whose frame shape differs from the dataset's (frame_shape()) are left out; with none left both
         images are 255 everywhere (the identity of the minimum: a rank's empty shard).  The files go through the native
         read-ahead ring and the device unpack, like batched() (whose staging buffers they share when batch_size and the
-        file size agree), and each batch is folded in with tpiv_frame_min."""
+        file size agree), and each batch is folded in with tpiv_frame_min.  With depth= the minimum is taken over the
+        tone-mapped frames (depth="auto" resolves here first)."""
         shape = self.frame_shape()
         if shape is None:
             raise ValueError("compute_background: the dataset holds no decodable pair")
@@ -520,22 +581,27 @@ class OfflinePIV:
         if not idx:
             return acc[0], acc[1]
         bs = int(batch_size or self.bg_batch)
+        lut = self._depth_table()
+        deep = lut is not None
         pairs = self._dataset.img_pairs
         first = self._first_decodable(idx)
-        cap = slot_bytes(H, W, pairs[first[0]] if first is not None else ())
+        cap = slot_bytes(H, W, pairs[first[0]] if first is not None else (), deep=deep)
         stage, raw_dev = self._staging(bs, cap)
         raw_d = raw_dev[0]
         cur = torch.cuda.current_stream(dev)
-        batches = StagedBatches(idx, pairs, bs, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads)
+        batches = StagedBatches(idx, pairs, bs, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads, deep=deep)
         self._reader = batches.reader
         try:
             for st in batches:
                 n = len(st.chunk)       # (pairs that are not staged are left out, as batched() leaves them to the one-pair path)
                 if n:
                     raw_d[:st.n_files].copy_(stage[st.buf][:st.n_files], non_blocking=True)
-                    desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
-                    lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
-                    frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W)      # [2n, H, W]: a_0..a_n-1, b_0..b_n-1
+                    if deep:
+                        frames = self._map_staged(raw_d[:st.n_files], st, H, W, lut, bs)
+                    else:
+                        desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
+                        lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
+                        frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W)      # [2n, H, W]: a_0..a_n-1, b_0..b_n-1
                     engine.frame_min(frames[:n], acc[0])
                     engine.frame_min(frames[n:], acc[1])
                     cur.synchronize()           # the upload is through: the readers may refill the staging buffer
@@ -834,6 +900,9 @@ class OfflinePIV:
         a = a.to(self._device, non_blocking=True)
         b = b.to(self._device, non_blocking=True)
         shape = (int(a.shape[-2]), int(a.shape[-1]))
+        lut = self._depth_table()
+        if lut is not None:                             # uint16 as decoded -> uint8, right after the upload
+            a, b = engine.depth_map(a, lut), engine.depth_map(b, lut)
         bg = self._background(shape)
         if self._prefilter is not None:                 # one launch per frame, the background subtracted in the same one
             a = engine.prefilter(a, background=None if bg is None else bg[0], **self._prefilter)
@@ -882,13 +951,16 @@ class OfflinePIV:
         if first is None:
             return
         H, W = first[1]
+        lut = self._depth_table()                     # (depth="auto": the histogram prepass runs here, once, before ...)
+        deep = lut is not None
         bg = self._background((H, W), batch_size)     # (background="min": the prepass over the files runs here, once)
         plan = self._get_plan(H, W, max_batch=batch_size)
         pairs = self._dataset.img_pairs
-        cap = slot_bytes(H, W, pairs[first[0]])
+        cap = slot_bytes(H, W, pairs[first[0]], deep=deep)
         stage, raw_dev = self._staging(batch_size, cap)
         # the host side of the loop below: read-ahead ring, header sweep, host decode of other formats, descriptor tables
-        batches = StagedBatches(idx, pairs, batch_size, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads)
+        batches = StagedBatches(idx, pairs, batch_size, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads,
+                                deep=deep)
         self._reader = batches.reader
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
@@ -937,14 +1009,31 @@ class OfflinePIV:
                         up = torch.cuda.Event()
                         up.record(up_stream)
                     # unpacked frame order: every a of the batch, then every b (two contiguous stacks)
-                    desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
-                    lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
+                    if not deep:
+                        desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
+                        lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
                     cur.wait_event(up)
-                    # [2n, H, W]: a_0..a_n-1, b_0..b_n-1 (with a background: minus bg_a / bg_b, in the same kernel)
-                    frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=bg)
+                    if deep:
+                        # the tone map where the unpack sits: one launch, slots a0 b0 a1 b1 .. -> stacks a_0..a_n-1, b_0..b_n-1
+                        frames = self._map_staged(raw_d, st, H, W, lut, batch_size)
+                    else:
+                        # [2n, H, W]: a_0..a_n-1, b_0..b_n-1 (with a background: minus bg_a / bg_b, in the same kernel)
+                        frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=bg)
                     consumed[dbuf] = torch.cuda.Event()
                     consumed[dbuf].record(cur)
-                    if self._prefilter is not None:
+                    if deep and bg is not None:
+                        if self._prefilter is not None:
+                            # per stack, the background subtracted in the filter's own launch
+                            pf = self._pf_frames
+                            if pf is None or pf.shape[0] < 2 * batch_size or tuple(pf.shape[1:]) != (H, W) or pf.device != frames.device:
+                                pf = self._pf_frames = torch.empty((2 * batch_size, H, W), dtype=torch.uint8, device=frames.device)
+                            engine.prefilter(frames[:n], background=bg[0], out=pf[:n], **self._prefilter)
+                            engine.prefilter(frames[n:], background=bg[1], out=pf[n:2 * n], **self._prefilter)
+                            frames = pf[:2 * n]
+                        else:
+                            engine.subtract_background(frames[:n], bg[0], out=frames[:n])
+                            engine.subtract_background(frames[n:], bg[1], out=frames[n:])
+                    elif self._prefilter is not None:
                         # one launch over the stack (the unpack subtracted already), into a buffer kept from batch to
                         # batch: stream order keeps a batch's passes ahead of the next batch's filter
                         pf = self._pf_frames
@@ -976,10 +1065,20 @@ class ResidentPIV(OfflinePIV):
     def __init__(self, frames_a: torch.Tensor, frames_b: torch.Tensor, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
-                 validation_window: int = 3, background=None, outlier=None, prefilter=None) -> None:
-        if frames_a.shape != frames_b.shape or frames_a.dim() != 3 or frames_a.dtype != torch.uint8 \
-                or frames_b.dtype != torch.uint8:
-            raise ValueError("ResidentPIV: two uint8 tensors [n, H, W] of one shape")
+                 validation_window: int = 3, background=None, outlier=None, depth=None, prefilter=None) -> None:
+        # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
+        # launch maps its pairs into a reused uint8 buffer
+        depth = engine.depth_arg(depth)
+        dtypes = (frames_a.dtype, frames_b.dtype)
+        if depth is None and dtypes == (torch.uint16, torch.uint16):
+            raise ValueError("ResidentPIV: uint16 frames need depth= (e.g. depth='auto' or {'lo': 0, 'hi': 4095}) to say how "
+                             "they map to 8 bits")
+        if depth is not None and dtypes == (torch.uint8, torch.uint8):
+            raise ValueError("ResidentPIV: depth= goes with uint16 frames; leave it out for uint8 frames")
+        want = torch.uint8 if depth is None else torch.uint16
+        if frames_a.shape != frames_b.shape or frames_a.dim() != 3 or dtypes != (want, want):
+            raise ValueError("ResidentPIV: two uint8 tensors [n, H, W] of one shape" if depth is None else
+                             "ResidentPIV: with depth=, two uint16 tensors [n, H, W] of one shape")
         if precision not in PRECISIONS:
             raise KeyError(precision)
         bg_arg = _background_arg(background, frames_a.shape[1:])
@@ -988,18 +1087,37 @@ class ResidentPIV(OfflinePIV):
         device = _require_gpu(frames_a.device)
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
-                         validation_window, bg_arg, outlier, prefilter)
+                         validation_window, bg_arg, outlier, prefilter, depth)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):
         return tuple(self._A.shape[1:]) if len(self) else None
 
+    def _depth_pairs(self, sample):
+        for i in engine.depth_sample(len(self), sample):
+            yield self._A[int(i)], self._B[int(i)]
+
+    def _mapped(self, frames, chunk, lut, out=None):
+        """The pairs `chunk` of a resident uint16 stack through the tone map: uint8 [len(chunk), H, W], one launch that
+        addresses the frames by their offsets (nothing is gathered first)."""
+        H, W = frames.shape[1:]
+        off = torch.tensor(chunk, dtype=torch.int64) * (H * W)
+        return engine.depth_map(frames.view(-1), lut, offsets=off, shape=(H, W), out=out)
+
     def compute_background(self, indices=None, batch_size=None):
         """(bg_a, bg_b): the per-pixel minimum of the resident a frames and of the b frames (of the pairs `indices`;
         None: all), uint8 [H, W] on the device (tpiv_frame_min; 255 everywhere for no pair).  batch_size: pairs gathered
-        at a time for `indices` (default bg_batch)."""
+        at a time for `indices` (default bg_batch).  With depth= the minimum is taken over the tone-mapped frames, mapped
+        batch_size pairs at a time."""
         H, W = self._A.shape[1:]
         acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=self._device)
+        lut = self._depth_table()
+        if lut is not None:
+            idx, bs = list(range(len(self))) if indices is None else list(indices), int(batch_size or self.bg_batch)
+            for s in range(0, len(idx), bs):
+                engine.frame_min(self._mapped(self._A, idx[s:s + bs], lut), acc[0])
+                engine.frame_min(self._mapped(self._B, idx[s:s + bs], lut), acc[1])
+            return acc[0], acc[1]
         if indices is None:
             engine.frame_min(self._A, acc[0])
             engine.frame_min(self._B, acc[1])
@@ -1022,6 +1140,11 @@ class ResidentPIV(OfflinePIV):
         if not idx:
             return
         H, W = self._A.shape[1:]
+        lut = self._depth_table()                     # (depth="auto": the histogram of the sampled pairs, once, before ...)
+        if lut is not None:
+            dbuf = self._depth_frames
+            if dbuf is None or dbuf.dim() != 4 or dbuf.shape[1] < batch_size or dbuf.device != self._A.device:
+                dbuf = self._depth_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
         bg = self._background((H, W))
         pf = self._prefilter
         if bg is not None or pf is not None:
@@ -1043,7 +1166,12 @@ class ResidentPIV(OfflinePIV):
             chunk = idx[s:s + batch_size]
             # a run of consecutive pairs is a view of the resident frames; anything else is gathered (a copy of 2 x 4 MB per pair:
             # 0.36 ms per 64 pairs at 4 MP -- the check is per launch, so a stream that repeats or skips stays copy-free per run)
-            if chunk[-1] - chunk[0] == len(chunk) - 1 and chunk == list(range(chunk[0], chunk[0] + len(chunk))):
+            if lut is not None:
+                # uint16 -> uint8 into the reused buffer, the pairs addressed by offset (consecutive or not: no gather);
+                # stream order keeps a launch's passes ahead of the next launch's map into the same memory
+                A = self._mapped(self._A, chunk, lut, out=dbuf[0, :len(chunk)])
+                B = self._mapped(self._B, chunk, lut, out=dbuf[1, :len(chunk)])
+            elif chunk[-1] - chunk[0] == len(chunk) - 1 and chunk == list(range(chunk[0], chunk[0] + len(chunk))):
                 A, B = self._A[chunk[0]:chunk[0] + len(chunk)], self._B[chunk[0]:chunk[0] + len(chunk)]
             else:
                 sel = torch.tensor(chunk, device=self._device)

@@ -1029,6 +1029,35 @@ int tpiv_prefilter(const uint8_t* frames, int n, int H, int W, const uint8_t* bg
     return TPIV_OK;
 }
 
+int tpiv_depth_map(const uint16_t* src, const long long* src_off, int n, int H, int W, const uint8_t* lut, uint8_t* out,
+                   void* stream) {
+    if (n < 0 || H <= 0 || W <= 0) return fail(TPIV_EINVAL, "tpiv_depth_map: bad shape");
+    if (n == 0) return TPIV_OK;
+    if (!src || !lut || !out) return fail(TPIV_EINVAL, "tpiv_depth_map: null pointer");
+    if ((uintptr_t)src % 2 != 0) return fail(TPIV_EINVAL, "tpiv_depth_map: src must be 2-byte aligned");
+    const size_t px = (size_t)n * H * W;
+    const uint8_t* s8 = reinterpret_cast<const uint8_t*>(src);
+    if (!src_off && out < s8 + 2 * px && s8 < out + px) return fail(TPIV_EINVAL, "tpiv_depth_map: out overlaps src");
+    if (out < lut + 65536 && lut < out + px) return fail(TPIV_EINVAL, "tpiv_depth_map: out overlaps the table");
+    int n_cu = 0;
+    if (int rc = n_cu_of_current_device(&n_cu)) return rc;
+    HIP_TRY(tpiv::launch_depth_map(src, src_off, n, H, W, lut, out, n_cu, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_depth_histogram(const uint16_t* src, int n, long long pixels_per_frame, unsigned long long* hist, void* stream) {
+    if (n < 0 || pixels_per_frame <= 0) return fail(TPIV_EINVAL, "tpiv_depth_histogram: bad shape");
+    if (n == 0) return TPIV_OK;
+    if (!src || !hist) return fail(TPIV_EINVAL, "tpiv_depth_histogram: null pointer");
+    if ((uintptr_t)src % 2 != 0 || (uintptr_t)hist % 8 != 0)
+        return fail(TPIV_EINVAL, "tpiv_depth_histogram: src must be 2-byte aligned, hist 8-byte aligned");
+    if (pixels_per_frame > (1LL << 62) / n) return fail(TPIV_EINVAL, "tpiv_depth_histogram: bad shape");
+    int n_cu = 0;
+    if (int rc = n_cu_of_current_device(&n_cu)) return rc;
+    HIP_TRY(tpiv::launch_depth_histogram(src, (long long)n * pixels_per_frame, hist, n_cu, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
 namespace {
 // One file into a slot of at most slot_bytes: bytes read, or -1 (cannot open / not a regular file / too big / short read).
 int64_t read_one_file(const char* path, uint8_t* out, size_t slot_bytes) {

@@ -179,6 +179,15 @@ constexpr int PREFILTER_TILE_COLS = 128, PREFILTER_TILE_ROWS = 64;
 hipError_t launch_prefilter(const uint8_t* frames, int n, int H, int W, const uint8_t* bg, int kind, int size, int cap,
                             uint8_t* out, hipStream_t stream);
 
+// deep frames (depth.hip).  Tone map: out[f][p] = lut[src[src_off[f] + p]] for n frames of H x W uint16 samples (src_off:
+// n element offsets on the device, nullptr: f * H * W), the 64 KiB table staged in LDS once per persistent workgroup, two
+// workgroups per CU.  Histogram: hist[v] += count of v among src[0 .. total), exact, privatised in LDS as packed 16-bit
+// counters (one workgroup per CU) and flushed with 64-bit atomics; src must be 2-byte aligned, hist 8-byte aligned.
+hipError_t launch_depth_map(const uint16_t* src, const long long* src_off, int n, int H, int W, const uint8_t* lut,
+                            uint8_t* out, int n_cu, hipStream_t stream);
+hipError_t launch_depth_histogram(const uint16_t* src, long long total, unsigned long long* hist, int n_cu,
+                                  hipStream_t stream);
+
 // normalized median test (outlier.hip): one lane per cell, one workgroup per OUTLIER_TILE_COLS x OUTLIER_TILE_ROWS tile
 // (a wavefront per tile row), the tile and its one-cell halo staged in LDS
 constexpr int OUTLIER_TILE_COLS = 64, OUTLIER_TILE_ROWS = 8;

@@ -477,6 +477,205 @@ def prefilter(frames, kind, size=None, cap=None, background=None, out=None):
     return out
 
 
+DEPTH_BINS = 65536
+DEPTH_CURVES = ("linear", "sqrt")
+DEPTH_AUTO_DEFAULTS = {"clip_low": 0.0, "clip_high": 1e-4, "sample": 32}
+DEPTH_KEYS = ("lo", "hi", "curve", "auto", "clip_low", "clip_high", "sample", "lut")
+
+
+def depth_arg(depth):
+    """The depth= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved).  None: 8-bit frames as
+    before.  {"lo", "hi", "curve"}: uint16 frames through depth_lut(lo, hi, curve) (integers 0 <= lo < hi <= 65535; curve
+    "linear" by default, or "sqrt").  "auto" or {"auto": True, "clip_low", "clip_high", "sample", "curve"}: lo, hi from
+    depth_range of the histogram of `sample` pairs of the recording (clips: fractions in [0, 0.5), defaults 0 and 1e-4;
+    sample >= 1, default 32).  {"lut": table}: the caller's own uint8 [65536] table (numpy array or tensor).  Returns None
+    or the full dict of its form -- {"lo", "hi", "curve"}, {"auto": True, "clip_low", "clip_high", "sample", "curve"} or
+    {"lut": numpy uint8 [65536]}; anything else (unknown keys, mixed forms, a dict that asks for nothing) raises ValueError."""
+    if depth is None:
+        return None
+    if isinstance(depth, str):
+        if depth != "auto":
+            raise ValueError(f"depth: None, 'auto' or a dict of {list(DEPTH_KEYS)}, got {depth!r}")
+        depth = {"auto": True}
+    if not isinstance(depth, dict):
+        raise ValueError(f"depth: None, 'auto' or a dict of {list(DEPTH_KEYS)}, got {type(depth).__name__}")
+    unknown = sorted(set(depth) - set(DEPTH_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"depth: unknown key(s) {unknown}; known: {list(DEPTH_KEYS)}")
+
+    def integer(x):
+        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+
+    def only(form, allowed):
+        extra = sorted(set(depth) - set(allowed))
+        if extra:
+            raise ValueError(f"depth: key(s) {extra} do not go with {form} (that form takes {list(allowed)})")
+    if "lut" in depth:
+        only("'lut'", ("lut",))
+        lut = depth["lut"]
+        if isinstance(lut, torch.Tensor):
+            if lut.dtype != torch.uint8:
+                raise ValueError(f"depth: lut must be uint8 [{DEPTH_BINS}], got dtype {lut.dtype}")
+            lut = lut.detach().cpu().numpy()
+        if not isinstance(lut, np.ndarray) or lut.dtype != np.uint8 or lut.shape != (DEPTH_BINS,):
+            raise ValueError(f"depth: lut must be a uint8 array or tensor of shape ({DEPTH_BINS},), got "
+                             f"{getattr(lut, 'dtype', type(lut).__name__)} {getattr(lut, 'shape', '')}")
+        return {"lut": np.ascontiguousarray(lut)}
+    curve = depth.get("curve", "linear")
+    if not isinstance(curve, str) or curve not in DEPTH_CURVES:
+        raise ValueError(f"depth: curve must be one of {list(DEPTH_CURVES)}, got {curve!r}")
+    if "auto" in depth:
+        only("'auto'", ("auto", "clip_low", "clip_high", "sample", "curve"))
+        if depth["auto"] is not True:
+            raise ValueError(f"depth: auto must be True (leave the key out for a fixed range), got {depth['auto']!r}")
+        par = dict(DEPTH_AUTO_DEFAULTS, **{k: depth[k] for k in DEPTH_AUTO_DEFAULTS if k in depth})
+        for k in ("clip_low", "clip_high"):
+            c = par[k]
+            if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)) or not 0 <= c < 0.5:
+                raise ValueError(f"depth: {k} must be a fraction in [0, 0.5), got {c!r}")
+        if not integer(par["sample"]) or par["sample"] < 1:
+            raise ValueError(f"depth: sample must be an integer >= 1, got {par['sample']!r}")
+        return {"auto": True, "clip_low": float(par["clip_low"]), "clip_high": float(par["clip_high"]),
+                "sample": int(par["sample"]), "curve": curve}
+    if "lo" in depth or "hi" in depth:
+        only("a fixed range", ("lo", "hi", "curve"))
+        if "lo" not in depth or "hi" not in depth:
+            raise ValueError("depth: a fixed range needs both lo and hi")
+        lo, hi = depth["lo"], depth["hi"]
+        if not integer(lo) or not integer(hi) or not 0 <= lo < hi <= DEPTH_BINS - 1:
+            raise ValueError(f"depth: lo and hi must be integers with 0 <= lo < hi <= {DEPTH_BINS - 1}, got {lo!r}, {hi!r}")
+        return {"lo": int(lo), "hi": int(hi), "curve": curve}
+    raise ValueError("depth: the dict asks for nothing (no lo / hi, no auto, no lut); pass None for 8-bit frames")
+
+
+def depth_lut(lo, hi, curve="linear"):
+    """The tone-map table of a range: numpy uint8 [65536] with, for c = clip(v, lo, hi) - lo and d = hi - lo, "linear":
+    (c * 510 + d) // (2 * d) -- 255 c / d rounded half up, in int64 --, "sqrt": floor(255 * sqrt(c / d) + 0.5) in float64.
+    Monotone, 0 up to lo and 255 from hi on.  lo, hi: integers, 0 <= lo < hi <= 65535."""
+    par = depth_arg({"lo": lo, "hi": hi, "curve": curve})
+    lo, hi = par["lo"], par["hi"]
+    c = np.clip(np.arange(DEPTH_BINS, dtype=np.int64), lo, hi) - lo
+    d = hi - lo
+    if par["curve"] == "linear":
+        return ((c * 510 + d) // (2 * d)).astype(np.uint8)
+    return np.floor(255.0 * np.sqrt(c.astype(np.float64) / np.float64(d)) + 0.5).astype(np.uint8)
+
+
+def depth_range(hist, clip_low=0.0, clip_high=1e-4):
+    """(lo, hi) of a 65536-bin histogram of N > 0 samples (numpy, no GPU): lo = the largest l with count(v < l) <=
+    floor(clip_low * N), hi = the smallest h with count(v > h) <= floor(clip_high * N) -- the range that leaves at most
+    those fractions of the samples clipped at either end.  hi <= lo (a constant recording) gives hi = lo + 1, and
+    (65534, 65535) at lo = 65535."""
+    h = np.asarray(hist)
+    if h.shape != (DEPTH_BINS,) or h.dtype.kind not in "iu":
+        raise ValueError(f"depth_range: hist must be an integer array of shape ({DEPTH_BINS},)")
+    for name, c in (("clip_low", clip_low), ("clip_high", clip_high)):
+        if isinstance(c, bool) or not 0 <= c < 0.5:
+            raise ValueError(f"depth_range: {name} must be a fraction in [0, 0.5), got {c!r}")
+    h = h.astype(np.int64)
+    if (h < 0).any():
+        raise ValueError("depth_range: negative count")
+    N = int(h.sum())
+    if N <= 0:
+        raise ValueError("depth_range: the histogram is empty")
+    cum = np.cumsum(h)
+    below = np.concatenate([[0], cum[:-1]])              # count(v < l), non-decreasing in l
+    above = N - cum                                      # count(v > h), non-increasing in h
+    lo = int(np.count_nonzero(below <= int(np.floor(clip_low * N)))) - 1
+    hi = int(np.argmax(above <= int(np.floor(clip_high * N))))
+    if hi <= lo:
+        lo, hi = (DEPTH_BINS - 2, DEPTH_BINS - 1) if lo == DEPTH_BINS - 1 else (lo, lo + 1)
+    return lo, hi
+
+
+def depth_sample(n, sample):
+    """The pairs of a recording of n pairs whose frames feed the histogram of depth="auto": min(n, sample) positions spread
+    evenly over 0 .. n - 1."""
+    if n <= 0:
+        return np.zeros(0, dtype=int)
+    return np.unique(np.rint(np.linspace(0, n - 1, min(n, int(sample)))).astype(int))
+
+
+def _deep_frames(frames, name):
+    """uint16 frames [n, H, W] or [H, W] on the device, contiguous -> (frames [n, H, W], H, W)."""
+    _need_cuda(frames)
+    if frames.dtype != torch.uint16 or frames.dim() not in (2, 3) or not frames.is_contiguous():
+        raise ValueError(f"{name}: frames must be a contiguous uint16 tensor [n, H, W] or [H, W]")
+    f3 = frames[None] if frames.dim() == 2 else frames
+    return f3, int(f3.shape[1]), int(f3.shape[2])
+
+
+def depth_histogram(frames, acc=None):
+    """Exact counts of all 65536 values of uint16 frames [n, H, W] (or [H, W]) on the device, added into acc int64 [65536]
+    (updated in place and returned; None: a fresh one of zeros).  Calls over parts of a recording compose:
+    depth_histogram(B, depth_histogram(A)) is the histogram of cat(A, B) (tpiv_depth_histogram).  The frames are not written."""
+    f, H, W = _deep_frames(frames, "depth_histogram")
+    if acc is None:
+        acc = torch.zeros(DEPTH_BINS, dtype=torch.int64, device=f.device)
+    elif not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or tuple(acc.shape) != (DEPTH_BINS,) \
+            or not acc.is_contiguous() or acc.device != f.device:
+        raise ValueError(f"depth_histogram: acc must be a contiguous int64 [{DEPTH_BINS}] tensor on the frames' device")
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_depth_histogram(f.data_ptr(), f.shape[0], H * W, acc.data_ptr(), _stream()))
+    return acc
+
+
+def _overlap(a, a_bytes, b, b_bytes):
+    return a.data_ptr() < b.data_ptr() + b_bytes and b.data_ptr() < a.data_ptr() + a_bytes
+
+
+def depth_map(frames, lut, offsets=None, shape=None, out=None):
+    """Tone map on the device, one launch: out = lut[frames] as uint8 (tpiv_depth_map).  frames: a contiguous uint16
+    tensor [n, H, W] or [H, W]; or, the staged form, a flat uint16 buffer with offsets (int64 [n]: the element offset of
+    every frame in the buffer; a tensor, array or list -- checked on the host, so hand over host values where a
+    synchronisation matters) and shape = (H, W): frame f of the result is the H * W samples from offsets[f] on, in the
+    order given (the interleaved slots of a staged batch leave as two contiguous stacks).  lut: uint8 [65536] on the
+    frames' device (depth_lut, or any table).  out: a contiguous uint8 tensor of the result's shape that overlaps neither
+    the source nor the table; None: a fresh one.  An overlap is refused and nothing is launched.  The source is not written."""
+    _need_cuda(frames)
+    if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (DEPTH_BINS,) \
+            or not lut.is_contiguous() or lut.device != frames.device:
+        raise ValueError(f"depth_map: lut must be a contiguous uint8 [{DEPTH_BINS}] tensor on the frames' device")
+    if offsets is None:
+        if shape is not None:
+            raise ValueError("depth_map: shape goes with offsets (the frames carry their own)")
+        f, H, W = _deep_frames(frames, "depth_map")
+        n, off_d, out_shape = int(f.shape[0]), None, tuple(frames.shape)
+    else:
+        if frames.dtype != torch.uint16 or frames.dim() != 1 or not frames.is_contiguous():
+            raise ValueError("depth_map: with offsets, frames must be a flat contiguous uint16 buffer")
+        try:
+            H, W = (int(s) for s in shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"depth_map: with offsets, shape = (H, W) is needed, got {shape!r}") from None
+        if H < 1 or W < 1:
+            raise ValueError(f"depth_map: shape must be positive, got {(H, W)}")
+        off_h = offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else torch.as_tensor(np.asarray(offsets))
+        if off_h.dtype != torch.int64 or off_h.dim() != 1:
+            raise ValueError("depth_map: offsets must be int64 [n]")
+        n = int(off_h.shape[0])
+        if n and (int(off_h.min()) < 0 or int(off_h.max()) + H * W > frames.numel()):
+            raise ValueError(f"depth_map: a frame of {H} x {W} samples at offsets {int(off_h.min())}..{int(off_h.max())} "
+                             f"leaves the buffer of {frames.numel()} samples")
+        f = frames
+        off_d = offsets if isinstance(offsets, torch.Tensor) and offsets.device == frames.device and offsets.is_contiguous() \
+            else off_h.contiguous().to(frames.device, non_blocking=True)
+        out_shape = (n, H, W)
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.uint8, device=frames.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(out_shape) \
+            or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError(f"depth_map: out must be a contiguous uint8 tensor of shape {tuple(out_shape)} on the frames' device")
+    if _overlap(out, out.numel(), f, 2 * f.numel()):
+        raise ValueError("depth_map: out overlaps the source frames")
+    if _overlap(out, out.numel(), lut, DEPTH_BINS):
+        raise ValueError("depth_map: out overlaps the table")
+    with torch.cuda.device(frames.device):
+        check(lib.tpiv_depth_map(f.data_ptr(), None if off_d is None else off_d.data_ptr(), n, H, W, lut.data_ptr(),
+                                 out.data_ptr(), _stream()))
+    return out
+
+
 class Plan:
     """The multipass pipeline of OfflinePIV.__call__ (PIVbackend.py:873-882) for batches of
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""

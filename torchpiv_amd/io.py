@@ -95,11 +95,19 @@ def decode_bmp_gray(buf: bytes):
 IDENTITY_LUT = np.arange(256, dtype=np.uint8)
 
 
-def stage_raw(path: str, slot: np.ndarray, H: int, W: int):
+def stage_raw(path: str, slot: np.ndarray, H: int, W: int, deep: bool = False):
     """Put the file `path` into `slot` (a uint8 view of pinned staging memory) for the device unpack
     (tpiv_bmp_unpack): an uncompressed BMP of the right shape goes in as its raw file bytes; anything
     else is decoded on the host (imdecode_gray) and stored as headerless top-down pixels.  Returns
-    (data_off, stride, bytes_pp, flip, lut) or None when the file cannot be decoded / has another shape."""
+    (data_off, stride, bytes_pp, flip, lut) or None when the file cannot be decoded / has another shape.
+    deep: every file is decoded on the host (imdecode_deep) and stored as headerless little-endian uint16 [H, W] -- 2 * H * W
+    bytes from the start of the slot, for tpiv_depth_map; the tuple then says (0, 2 * W, 2, 0, identity)."""
+    if deep:
+        img = imdecode_deep(path)
+        if img is None or img.shape != (H, W) or 2 * H * W > slot.size:
+            return None
+        slot[:2 * H * W].view("<u2")[:] = img.reshape(-1)
+        return 0, 2 * W, 2, 0, IDENTITY_LUT
     try:
         with open(path, "rb", buffering=0) as f:
             size = os.fstat(f.fileno()).st_size
@@ -219,9 +227,12 @@ class ReadAhead:
     __del__ = close
 
 
-def slot_bytes(H: int, W: int, files) -> int:
+def slot_bytes(H: int, W: int, files, deep: bool = False) -> int:
     """Bytes of one staging slot: the largest of `files` (a pair's files stand for the run's, which share one format;
-    missing ones are skipped) and a headerless frame [H, W], rounded up to 4 KiB."""
+    missing ones are skipped) and a headerless frame [H, W], rounded up to 4 KiB.  deep: a headerless uint16 frame,
+    2 * H * W bytes (the files are decoded on the host, so their own sizes do not count)."""
+    if deep:
+        return (2 * H * W + 4095) // 4096 * 4096
     sizes = [H * W] + [os.path.getsize(p_) for p_ in files if os.path.exists(p_)]
     return (max(sizes) + 4095) // 4096 * 4096
 
@@ -237,15 +248,18 @@ class StagedBatches:
     2k + 1 frame b.  The files arrive through the read-ahead ring (`reader`) in `bufs`, uint8 numpy views [2 * batch, cap] of
     page-locked memory; the sweep over a batch's headers (parse_bmp_headers) hands the files it cannot place -- and every
     file of a format the ring does not read -- to stage_raw in a thread pool.  A pair with a file that cannot be staged
-    (undecodable, another frame shape) is left to the caller.  release(): the oldest batch's bytes have left its buffer."""
+    (undecodable, another frame shape) is left to the caller.  release(): the oldest batch's bytes have left its buffer.
+    deep: uint16 frames -- the ring reads nothing, every file (BMPs included) is decoded by stage_raw(deep=True) into
+    headerless uint16 [H, W] at the start of its slot, and desc[:, 0] // 2 are the element offsets tpiv_depth_map takes."""
 
-    def __init__(self, idx, pairs, batch: int, H: int, W: int, bufs, cap: int, threads: int = 8):
+    def __init__(self, idx, pairs, batch: int, H: int, W: int, bufs, cap: int, threads: int = 8, deep: bool = False):
         self._idx, self._batch, self._shape, self._bufs, self._cap, self._threads = idx, batch, (H, W), bufs, cap, threads
+        self._deep = bool(deep)
         self._paths = [p_ for i in idx for p_ in (pairs[i][0], pairs[i][-1])]
         self._decoders = None
         # (formats the device cannot unpack are not read by the ring at all)
         self.reader = ReadAhead(self._paths, 2 * batch, [b_.ctypes.data for b_ in bufs], cap, threads=threads,
-                                read=str(self._paths[0]).lower().endswith(".bmp"))
+                                read=not self._deep and str(self._paths[0]).lower().endswith(".bmp"))
         self.release = self.reader.release
 
     def __iter__(self):
@@ -262,7 +276,7 @@ class StagedBatches:
                 if self._decoders is None:
                     from concurrent.futures import ThreadPoolExecutor
                     self._decoders = ThreadPoolExecutor(max_workers=self._threads)
-                for j, lay in zip(rest, self._decoders.map(lambda j: stage_raw(self._paths[2 * s0 + j], raw[j], H, W), rest)):
+                for j, lay in zip(rest, self._decoders.map(lambda j: stage_raw(self._paths[2 * s0 + j], raw[j], H, W, self._deep), rest)):
                     lays[j] = lay
             order, chunk, desc_a, desc_b, lut_a, lut_b = [], [], [], [], [], []
             for k, i in enumerate(self._idx[s0:s0 + self._batch]):
@@ -317,6 +331,37 @@ def imdecode_gray(path: str):
         return None
 
 
+def imdecode_deep(path: str):
+    """uint16 [H, W] image with the file's full sample range, or None when the file cannot be decoded: 16-bit grey files
+    (Pillow modes I;16, I;16L, I;16B, I;16N) as they are, in native byte order; 32-bit integer files (mode I) likewise
+    when every value fits 16 bits (None otherwise); 8-bit grey and colour files decoded like imdecode_gray and widened,
+    values 0 .. 255 unchanged."""
+    try:
+        with open(path, "rb") as f:
+            buf = f.read()
+    except OSError:
+        return None
+    img = decode_bmp_gray(buf)
+    if img is not None:
+        return img.astype(np.uint16)
+    try:
+        import io as _io
+
+        from PIL import Image
+        with Image.open(_io.BytesIO(buf)) as im:
+            if im.mode in ("I;16", "I;16L", "I;16B", "I;16N"):
+                return np.ascontiguousarray(np.asarray(im).astype(np.uint16))
+            if im.mode == "I":
+                wide = np.asarray(im)
+                if wide.size and (wide.min() < 0 or wide.max() > 65535):
+                    return None
+                return np.ascontiguousarray(wide.astype(np.uint16))
+    except Exception:
+        return None
+    img = imdecode_gray(path)
+    return None if img is None else img.astype(np.uint16)
+
+
 def decode_into(path: str, out: np.ndarray) -> bool:
     """Decode `path` straight into a preallocated uint8 [H, W] buffer (e.g. a view of pinned
     staging memory).  False if the file cannot be decoded or has another shape."""
@@ -344,10 +389,13 @@ class ToTensor:
 
 class PIVDataset(torch.utils.data.Dataset):
     """Image pairs of a folder (PIVbackend.py:114-144): names ending in `file_fmt`, natural
-    sort, 'pairs' = (0,1),(2,3),...; 'sequential' = (0,1),(1,2),...; anything else = empty."""
+    sort, 'pairs' = (0,1),(2,3),...; 'sequential' = (0,1),(1,2),...; anything else = empty.
+    deep (extension): the frames are decoded with imdecode_deep -- uint16, the files' full sample range -- instead of
+    imdecode_gray."""
 
-    def __init__(self, folder, file_fmt, folder_mode, transform=None):
+    def __init__(self, folder, file_fmt, folder_mode, transform=None, deep=False):
         self.transform = transform
+        self._decode = imdecode_deep if deep else imdecode_gray
         filenames = [os.path.join(folder, name) for name in os.listdir(folder) if name.endswith(file_fmt)]
         filenames.sort(key=natural_keys)
         if folder_mode == "pairs":
@@ -365,7 +413,7 @@ class PIVDataset(torch.utils.data.Dataset):
         (the reference then skips the pair, B:138-139)."""
         index = index.tolist() if torch.is_tensor(index) else index
         path_a, path_b = self.img_pairs[index][0], self.img_pairs[index][-1]
-        frames = [imdecode_gray(path_b), imdecode_gray(path_a)]          # (the reference reads b first)
+        frames = [self._decode(path_b), self._decode(path_a)]          # (the reference reads b first)
         if any(f is None for f in frames):
             return None, None
         frame_b, frame_a = frames
