@@ -310,6 +310,27 @@ int tpiv_depth_map(const uint16_t* src_dev, const long long* src_off_dev, int n,
 int tpiv_depth_histogram(const uint16_t* src_dev, int n, long long pixels_per_frame, unsigned long long* hist_dev,
                          void* stream);
 
+/* ---- tile-wise adaptive histogram equalization (CLAHE) ----------------------------------------- */
+
+/* Equalizes n frames frames_dev [n, H, W] uint8 into out_dev, in integer arithmetic (every implementation of these lines
+ * gives the same bytes).  tile in 8..256; clip_q8 in 256..65536, the clip limit in 1/256 of the uniform bin height.
+ *   Tile grid, per axis of n pixels: k = max(1, (2 n + tile) / (2 tile)) tiles with the edges e_i = (i n) / k, i = 0..k.
+ *   Per tile with N pixels and the histogram h[256]: L = max(1, (clip_q8 N) >> 16) (64-bit product), E = sum max(h - L, 0),
+ *   r = E % 256, h'[b] = min(h[b], L) + E / 256 + ((b + 1) r / 256 - b r / 256) (one redistribution, sum h' = N),
+ *   C[b] = h'[0] + .. + h'[b], b0 = the lowest bin with h > 0, d = N - C[b0],
+ *   lut[b] = (510 max(C[b] - C[b0], 0) + d) / (2 d), 0 for every b when d == 0: the darkest level of a tile maps to 0.
+ *   Per pixel p of an axis, doubled coordinates: P = 2 p + 1, tile centres c_i = e_i + e_(i+1), i = the last i with
+ *   c_i <= P clamped to 0..k-2, D = c_(i+1) - c_i, w1 = clamp(P - c_i, 0, D), w0 = D - w1 (k == 1: one tile, weight 1, D = 1).
+ *   out = (2 s + Dy Dx) / (2 Dy Dx), s = the sum over the four neighbour tiles of wy wx lut_tile[g].
+ * work_dev: at least tpiv_equalize_work_bytes(n, H, W, tile) bytes on the device; afterwards it starts with the tables,
+ * uint8 [n, ky, kx, 256].  out_dev may be frames_dev itself (the map is pointwise once the tables exist); any other overlap
+ * of out_dev with frames_dev, or of work_dev with either, is TPIV_EINVAL, like tile or clip_q8 out of range, a null
+ * pointer, a workspace that is too small, n < 0, H or W outside 1..2^28: decided on the host, nothing is launched then.
+ * n == 0 succeeds and launches nothing.  Enqueues two kernels; allocates nothing and never synchronises. */
+size_t tpiv_equalize_work_bytes(int n, int H, int W, int tile);
+int tpiv_equalize(const uint8_t* frames_dev, int n, int H, int W, int tile, int clip_q8, uint8_t* out_dev, void* work_dev,
+                  size_t work_bytes, void* stream);
+
 /* Host side of the ingest (no GPU involved): reads n_files files into dst + i * slot_bytes (page-locked staging memory
  * of the caller, at most slot_bytes each) with up to n_threads native reader threads -- what PIVDataset.__getitem__
  * (B:129-144) does file by file with np.fromfile, here for a whole batch without the interpreter in the loop.

@@ -85,6 +85,8 @@ SIGNATURES = {
     "tpiv_prefilter": (C.c_int, [_u8p, _int, _int, _int, _u8p, _int, _int, _int, _u8p, _vp]),
     "tpiv_depth_map": (C.c_int, [_vp, _vp, _int, _int, _int, _u8p, _u8p, _vp]),
     "tpiv_depth_histogram": (C.c_int, [_vp, _int, C.c_longlong, _vp, _vp]),
+    "tpiv_equalize_work_bytes": (C.c_size_t, [_int, _int, _int, _int]),
+    "tpiv_equalize": (C.c_int, [_u8p, _int, _int, _int, _int, _int, _u8p, _vp, C.c_size_t, _vp]),
     "tpiv_read_files": (C.c_int, [C.POINTER(C.c_char_p), _int, C.c_void_p, C.c_size_t, _int, C.POINTER(C.c_longlong)]),
     "tpiv_reader_open": (C.c_void_p, [C.POINTER(C.c_char_p), C.c_longlong, _int, C.POINTER(C.c_void_p), _int, C.c_size_t, _int]),
     "tpiv_reader_next": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),

@@ -372,7 +372,7 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 depth=None, prefilter=None) -> None:
+                 depth=None, equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -395,6 +395,10 @@ class OfflinePIV:
         # (1..255) -- the spatial pre-filter every frame passes on the device after the background and before the passes
         # (engine.prefilter_arg, tpiv_prefilter): minus the minimum / the rounded mean of its size x size neighbourhood,
         # then capped.  For background that is smooth in space but differs from frame to frame.
+        # equalize (extension): None, "clahe" or a dict with any of tile (8..256) and clip (1..256) -- tile-wise adaptive
+        # histogram equalization of every frame on the device (engine.equalize_arg, tpiv_equalize), the last step in front of
+        # the passes: tone map, background, pre-filter and cap, equalize.  For illumination that differs across the frame and
+        # for particle images of very different brightness inside one window.
         # depth (extension): None -- 8-bit frames, a 16-bit file decoded as value >> 8 like the reference (cv2's
         # IMREAD_GRAYSCALE) --, or the tone map of deep frames (engine.depth_arg): the files are decoded to uint16 with their
         # full sample range (io.imdecode_deep) and every frame passes out = lut[sample] on the device (tpiv_depth_map) before
@@ -410,7 +414,7 @@ class OfflinePIV:
         iter_function = IterModMap.functions[multipass_mode]            # KeyError like B:850
         self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
-                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth)
+                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize))
         if not self:
             return
         if self._bg_arg is not None and self._bg_arg != "min":
@@ -418,10 +422,11 @@ class OfflinePIV:
         _require_gpu(self._device)
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
-                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None):
+                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
+                    equalize=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
-        engine.prefilter_arg's, depth: engine.depth_arg's) and the state that the methods build up, empty."""
+        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's) and the state that the methods build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
         self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
@@ -431,6 +436,8 @@ class OfflinePIV:
         self._outlier = outlier
         self._prefilter = prefilter
         self._depth = depth
+        self._equalize = equalize
+        self._eq_work = None             # equalize=: the table workspace, uint8 [n * ky * kx * 256], kept from launch to launch
         self._depth_range = (depth["lo"], depth["hi"]) if depth is not None and "lo" in depth else None
         self._depth_lut = None           # the tone-map table in use: uint8 [65536] on the device, once resolved
         self._depth_frames = None        # the mapped frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
@@ -510,6 +517,19 @@ class OfflinePIV:
             a, b = self._dataset[int(i)]
             if a is not None and b is not None and tuple(a.shape) == tuple(b.shape) == tuple(shape):
                 yield a.to(self._device), b.to(self._device)
+
+    def _equalized(self, frames, out=None):
+        """uint8 frames [n, H, W] or [H, W] through equalize= (one tpiv_equalize call: the table and the map kernel), into
+        out -- the frames themselves where an earlier step wrote them into memory of this object, never a caller's tensor
+        -- or a fresh tensor.  The table workspace is kept from call to call."""
+        eq = self._equalize
+        n = frames.shape[0] if frames.dim() == 3 else 1
+        ky, kx = engine.equalize_grid(frames.shape[-2], frames.shape[-1], eq["tile"])
+        need = n * ky * kx * 256
+        work = self._eq_work
+        if work is None or work.numel() < need or work.device != frames.device:
+            work = self._eq_work = torch.empty(need, dtype=torch.uint8, device=frames.device)
+        return engine.equalize(frames, eq["tile"], eq["clip"], out=out, work=work)
 
     def _depth_table(self):
         """The tone-map table of depth= on the device (uint8 [65536]), None without depth.  "auto" takes the histogram of
@@ -910,6 +930,10 @@ class OfflinePIV:
         elif bg is not None:
             a = engine.subtract_background(a, bg[0])
             b = engine.subtract_background(b, bg[1])
+        if self._equalize is not None:                  # one call per frame; in place on what the steps above made
+            own = lut is not None or bg is not None or self._prefilter is not None
+            a = self._equalized(a, out=a if own else None)
+            b = self._equalized(b, out=b if own else None)
         plan = self._single_plans.get(shape)
         if plan is None:
             plan = self._single_plans[shape] = self._new_plan(shape[0], shape[1], 1)
@@ -1040,6 +1064,10 @@ class OfflinePIV:
                         if pf is None or pf.shape[0] < 2 * batch_size or tuple(pf.shape[1:]) != (H, W) or pf.device != frames.device:
                             pf = self._pf_frames = torch.empty((2 * batch_size, H, W), dtype=torch.uint8, device=frames.device)
                         frames = engine.prefilter(frames, out=pf[:frames.shape[0]], **self._prefilter)
+                    if self._equalize is not None:
+                        # one call over the stack, in place: the unpack, the tone map or the pre-filter wrote it into
+                        # memory of this object
+                        frames = self._equalized(frames, out=frames)
                     u, v, inv = plan.run(frames[:n], frames[n:])
                     ticket = self._post_submit(u, v, inv, plan=plan)
                 let_go(release)
@@ -1065,7 +1093,8 @@ class ResidentPIV(OfflinePIV):
     def __init__(self, frames_a: torch.Tensor, frames_b: torch.Tensor, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
-                 validation_window: int = 3, background=None, outlier=None, depth=None, prefilter=None) -> None:
+                 validation_window: int = 3, background=None, outlier=None, depth=None, equalize=None,
+                 prefilter=None) -> None:
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
         # launch maps its pairs into a reused uint8 buffer
         depth = engine.depth_arg(depth)
@@ -1084,10 +1113,11 @@ class ResidentPIV(OfflinePIV):
         bg_arg = _background_arg(background, frames_a.shape[1:])
         outlier = engine.outlier_arg(outlier)
         prefilter = engine.prefilter_arg(prefilter)
+        equalize = engine.equalize_arg(equalize)
         device = _require_gpu(frames_a.device)
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
-                         validation_window, bg_arg, outlier, prefilter, depth)
+                         validation_window, bg_arg, outlier, prefilter, depth, equalize)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):
@@ -1146,8 +1176,8 @@ class ResidentPIV(OfflinePIV):
             if dbuf is None or dbuf.dim() != 4 or dbuf.shape[1] < batch_size or dbuf.device != self._A.device:
                 dbuf = self._depth_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
         bg = self._background((H, W))
-        pf = self._prefilter
-        if bg is not None or pf is not None:
+        pf, eq = self._prefilter, self._equalize
+        if bg is not None or pf is not None or (eq is not None and lut is None):
             buf = self._bg_frames
             if buf is None or buf.shape[1] < batch_size or buf.device != self._A.device:
                 buf = self._bg_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
@@ -1185,6 +1215,12 @@ class ResidentPIV(OfflinePIV):
                 # ahead of the next launch's subtraction into the same memory
                 A = engine.subtract_background(A, bg[0], out=buf[0, :len(chunk)])
                 B = engine.subtract_background(B, bg[1], out=buf[1, :len(chunk)])
+            if eq is not None:
+                # in place where the tone map, the background or the pre-filter wrote a reused buffer, else from the
+                # caller's frames into that buffer
+                own = lut is not None or bg is not None or pf is not None
+                A = self._equalized(A, out=A if own else buf[0, :len(chunk)])
+                B = self._equalized(B, out=B if own else buf[1, :len(chunk)])
             u, v, inv = plan.run(A, B)
             # host work of the previous batches overlaps this batch's kernels
             yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan)))

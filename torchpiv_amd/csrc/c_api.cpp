@@ -1045,6 +1045,35 @@ int tpiv_depth_map(const uint16_t* src, const long long* src_off, int n, int H, 
     return TPIV_OK;
 }
 
+size_t tpiv_equalize_work_bytes(int n, int H, int W, int tile) {
+    if (n <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28) || tile < tpiv::EQUALIZE_TILE_MIN ||
+        tile > tpiv::EQUALIZE_TILE_MAX)
+        return 0;
+    return (size_t)n * tpiv::equalize_tiles(H, tile) * tpiv::equalize_tiles(W, tile) * 256;
+}
+
+int tpiv_equalize(const uint8_t* frames, int n, int H, int W, int tile, int clip_q8, uint8_t* out, void* work,
+                  size_t work_bytes, void* stream) {
+    if (n < 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28)) return fail(TPIV_EINVAL, "tpiv_equalize: bad shape");
+    if (tile < tpiv::EQUALIZE_TILE_MIN || tile > tpiv::EQUALIZE_TILE_MAX)
+        return fail(TPIV_EINVAL, "tpiv_equalize: tile must be in 8..256");
+    if (clip_q8 < tpiv::EQUALIZE_CLIP_Q8_MIN || clip_q8 > tpiv::EQUALIZE_CLIP_Q8_MAX)
+        return fail(TPIV_EINVAL, "tpiv_equalize: clip_q8 must be in 256..65536");
+    if (n == 0) return TPIV_OK;
+    if (!frames || !out || !work) return fail(TPIV_EINVAL, "tpiv_equalize: null pointer");
+    const size_t need = tpiv_equalize_work_bytes(n, H, W, tile);
+    if (work_bytes < need) return fail(TPIV_EINVAL, "tpiv_equalize: workspace too small (tpiv_equalize_work_bytes)");
+    if (tpiv::equalize_tiles(H, tile) > 65535) return fail(TPIV_EINVAL, "tpiv_equalize: more than 65535 tile rows");
+    const size_t bytes = (size_t)n * H * W;
+    if (out != frames && out < frames + bytes && frames < out + bytes)
+        return fail(TPIV_EINVAL, "tpiv_equalize: out overlaps frames in part (in place means out == frames)");
+    const uint8_t* w8 = static_cast<const uint8_t*>(work);
+    if ((w8 < frames + bytes && frames < w8 + need) || (w8 < out + bytes && out < w8 + need))
+        return fail(TPIV_EINVAL, "tpiv_equalize: the workspace overlaps the frames or out");
+    HIP_TRY(tpiv::launch_equalize(frames, n, H, W, tile, clip_q8, out, static_cast<uint8_t*>(work), (hipStream_t)stream));
+    return TPIV_OK;
+}
+
 int tpiv_depth_histogram(const uint16_t* src, int n, long long pixels_per_frame, unsigned long long* hist, void* stream) {
     if (n < 0 || pixels_per_frame <= 0) return fail(TPIV_EINVAL, "tpiv_depth_histogram: bad shape");
     if (n == 0) return TPIV_OK;

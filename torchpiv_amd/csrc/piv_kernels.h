@@ -188,6 +188,17 @@ hipError_t launch_depth_map(const uint16_t* src, const long long* src_off, int n
 hipError_t launch_depth_histogram(const uint16_t* src, long long total, unsigned long long* hist, int n_cu,
                                   hipStream_t stream);
 
+// tile-wise adaptive histogram equalization (equalize.hip, defined in include/torchpiv_hip.h): a table kernel, one workgroup
+// per (frame, tile), writes luts [n, ky, kx, 256]; a map kernel, one workgroup per rectangle between tile centres, blends the
+// four neighbour tables into out, which may be frames itself.  equalize_tiles: the tiles k of an axis of n pixels.
+constexpr int EQUALIZE_TILE_MIN = 8, EQUALIZE_TILE_MAX = 256, EQUALIZE_CLIP_Q8_MIN = 256, EQUALIZE_CLIP_Q8_MAX = 65536;
+inline int equalize_tiles(int n, int tile) {
+    const long long k = (2LL * n + tile) / (2LL * tile);
+    return k < 1 ? 1 : (int)k;
+}
+hipError_t launch_equalize(const uint8_t* frames, int n, int H, int W, int tile, int clip_q8, uint8_t* out, uint8_t* luts,
+                           hipStream_t stream);
+
 // normalized median test (outlier.hip): one lane per cell, one workgroup per OUTLIER_TILE_COLS x OUTLIER_TILE_ROWS tile
 // (a wavefront per tile row), the tile and its one-cell halo staged in LDS
 constexpr int OUTLIER_TILE_COLS = 64, OUTLIER_TILE_ROWS = 8;

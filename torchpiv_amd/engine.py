@@ -477,6 +477,77 @@ def prefilter(frames, kind, size=None, cap=None, background=None, out=None):
     return out
 
 
+EQUALIZE_KEYS = ("tile", "clip")
+EQUALIZE_DEFAULTS = {"tile": 64, "clip": 3.0}
+
+
+def equalize_arg(equalize):
+    """The equalize= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no equalization),
+    "clahe" (tile 64, clip 3.0) or a dict with any of tile (integer, 8..256: the tile size aimed at, in pixels) and clip
+    (1..256: the clip limit in units of the uniform bin height; 256 never clips).  Returns None or {"tile": int, "clip":
+    float, "clip_q8": int} with clip_q8 = round(256 clip), what tpiv_equalize takes; anything else -- unknown strings or
+    keys, bools, a non-integer tile, values out of range, an empty dict -- raises ValueError."""
+    if equalize is None:
+        return None
+    if isinstance(equalize, str):
+        if equalize != "clahe":
+            raise ValueError(f"equalize: None, 'clahe' or a dict of {list(EQUALIZE_KEYS)}, got {equalize!r}")
+        equalize = dict(EQUALIZE_DEFAULTS)
+    if not isinstance(equalize, dict):
+        raise ValueError(f"equalize: None, 'clahe' or a dict of {list(EQUALIZE_KEYS)}, got {type(equalize).__name__}")
+    unknown = sorted(set(equalize) - set(EQUALIZE_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"equalize: unknown key(s) {unknown}; known: {list(EQUALIZE_KEYS)}")
+    if not equalize:
+        raise ValueError("equalize: the dict names neither tile nor clip; pass 'clahe' for the defaults, None for no filter")
+    tile = equalize.get("tile", EQUALIZE_DEFAULTS["tile"])
+    clip = equalize.get("clip", EQUALIZE_DEFAULTS["clip"])
+    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or not 8 <= tile <= 256:
+        raise ValueError(f"equalize: tile must be an integer in 8..256, got {tile!r}")
+    if isinstance(clip, (bool, np.bool_)) or not isinstance(clip, (int, float, np.integer, np.floating)) \
+            or not 1 <= clip <= 256:                                    # (a NaN fails the comparison)
+        raise ValueError(f"equalize: clip must be a number in 1..256, got {clip!r}")
+    return {"tile": int(tile), "clip": float(clip), "clip_q8": int(round(float(clip) * 256))}
+
+
+def equalize_grid(H, W, tile):
+    """(ky, kx): the tiles of tpiv_equalize along y and x for frames of H x W."""
+    return tuple(max(1, (2 * n + tile) // (2 * tile)) for n in (int(H), int(W)))
+
+
+def equalize(frames, tile=EQUALIZE_DEFAULTS["tile"], clip=EQUALIZE_DEFAULTS["clip"], out=None, return_luts=False, work=None):
+    """Tile-wise adaptive histogram equalization of uint8 frames [n, H, W] or [H, W] on the device (tpiv_equalize: a table
+    kernel and a map kernel; the definition is in include/torchpiv_hip.h).  tile, clip: as in equalize_arg.  The frames
+    may be any view (one that is not contiguous is copied first).  out: a contiguous tensor of the frames' shape -- the
+    frames themselves (in place) or memory that does not overlap them; None: a fresh one.  work: a uint8 workspace of at
+    least n * ky * kx * 256 bytes to reuse from call to call (None: a fresh one).  return_luts: also return the tables,
+    uint8 [n, ky, kx, 256] (a view of the workspace)."""
+    par = equalize_arg({"tile": tile, "clip": clip})
+    _need_cuda(frames, out, work)
+    if frames.dtype != torch.uint8 or frames.dim() not in (2, 3):
+        raise ValueError("equalize: frames must be a uint8 tensor [n, H, W] or [H, W]")
+    src = frames if frames.is_contiguous() else frames.contiguous()
+    f = src[None] if src.dim() == 2 else src
+    n, H, W = (int(s) for s in f.shape)
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or not out.is_contiguous() or out.device != f.device:
+        raise ValueError("equalize: out must be a contiguous uint8 tensor of the frames' shape and device")
+    ky, kx = equalize_grid(H, W, par["tile"])
+    need = n * ky * kx * 256
+    if work is None:
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=f.device)
+    elif work.dtype != torch.uint8 or work.dim() != 1 or not work.is_contiguous() or work.device != f.device \
+            or work.numel() < need:
+        raise ValueError(f"equalize: work must be a contiguous uint8 vector of at least {need} bytes on the frames' device")
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_equalize(f.data_ptr(), n, H, W, par["tile"], par["clip_q8"], out.data_ptr(), work.data_ptr(),
+                                work.numel(), _stream()))
+    if return_luts:
+        return out, work[:need].view(n, ky, kx, 256)
+    return out
+
+
 DEPTH_BINS = 65536
 DEPTH_CURVES = ("linear", "sqrt")
 DEPTH_AUTO_DEFAULTS = {"clip_low": 0.0, "clip_high": 1e-4, "sample": 32}

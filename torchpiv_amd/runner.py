@@ -237,7 +237,7 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
                folder_mode: str = "pairs", save_opt: str = "Dont save", save_dir: str = "Out",
                batch_size: int = 32, on_pair=None, distributed: bool = False, stats_on_device: bool = True,
                precision: str = "exact", streaming_stats: bool = False, background=None, outlier=None, depth=None,
-               prefilter=None):
+               equalize=None, prefilter=None):
     """Process a folder like PIVWorker.run.  save_opt: "Dont save" | "Save all binary" |
     "Save all text" | "Save statistics" (anything but "Dont save" also writes the statistics table).
     streaming_stats: running accumulators instead of the stacked fields (EnsembleStats(streaming=True): O(1) memory in
@@ -246,6 +246,8 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
     distributed=True, "min" is the minimum over the whole dataset, each rank reading only its own shard.
     outlier: the normalized median test of OfflinePIV after every pass (None, "median" or a dict of its parameters).
     prefilter: the spatial pre-filter of OfflinePIV (None or a dict with kind, size and optionally cap).
+    equalize: tile-wise adaptive histogram equalization of OfflinePIV, the last step in front of the passes (None, "clahe" or a
+    dict with tile and / or clip, engine.equalize_arg); per frame, so sharded runs need nothing more.
     depth: the tone map of deep (10..16-bit) files of OfflinePIV (None, "auto" or a dict, engine.depth_arg); with
     distributed=True every rank takes "auto"'s histogram over the sample of the whole dataset, not of its shard, so all
     ranks use the same range.
@@ -254,7 +256,7 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
     piv = OfflinePIV(folder, device, file_fmt, wind_size, overlap, multipass=multipass,
                      multipass_mode=multipass_mode, dt=dt, scale=scale, multipass_scale=multipass_scale,
                      folder_mode=folder_mode, precision=precision, background=background, outlier=outlier, prefilter=prefilter,
-                     depth=depth)
+                     depth=depth, equalize=equalize)
     if len(piv) == 0:
         return None, 0
     rank, world = 0, 1
