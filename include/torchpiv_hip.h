@@ -196,6 +196,47 @@ int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double ep
  * run, [batch, n_rows, n_cols] of that pass.  TPIV_EINVAL when the test is off. */
 int tpiv_plan_pass_outliers(const tpiv_plan* plan, int pass, uint8_t** status_dev);
 
+/* ---- geometric mask (extension; the reference has none) ------------------------------------------ */
+
+/* Pixel step: out_dev[f][p] = mask_dev[p] != 0 ? 0 : frames_dev[f][p] for n frames [n, pixels] uint8 against one image
+ * mask_dev [pixels] uint8 -- any non-zero byte masks, not only 1.  The result is frames & keep with keep = 0x00 on masked
+ * pixels and 0xFF elsewhere: a uint8 frame like any other.  out_dev may be frames_dev itself; a partial overlap is
+ * TPIV_EINVAL, like a null pointer, n < 0 or pixels < 1.  n == 0 succeeds and launches nothing.  Enqueues only; allocates
+ * nothing. */
+int tpiv_apply_mask(const uint8_t* frames_dev, int n, long long pixels, const uint8_t* mask_dev, uint8_t* out_dev,
+                    void* stream);
+
+/* count_dev [n_rows, n_cols] int32 (the grid of tpiv_field_shape(H, W, ws, ov)) = the number of non-zero bytes of
+ * mask_dev [H, W] inside window (i, j), which covers rows i (ws - ov) ... + ws and columns j (ws - ov) ... + ws: the nominal
+ * window of a pass, whatever shift a later pass applies to it.  Any ws in 8..256 -- odd and non-power-of-two sizes
+ * included -- with any overlap below ws that the passes accept.  Enqueues only; allocates nothing. */
+int tpiv_mask_coverage(const uint8_t* mask_dev, int H, int W, int ws, int ov, int32_t* count_dev, void* stream);
+
+/* Excluded cells into the fields of a pass: wherever grid_dev [n_rows, n_cols] uint8 is non-zero, in every pair of
+ * u_dev, v_dev float64 and invalid_dev uint8 [batch, n_rows, n_cols]: u = v = +0.0 (whatever was there, a NaN included),
+ * invalid = invalid_value (0 or 1), and status = 2 -- tpiv_median_test's "invalid on input, not flagged" -- when status_dev
+ * is not NULL.  Every other cell is untouched.  batch == 0 succeeds and launches nothing.  Enqueues only; allocates nothing. */
+int tpiv_mask_fields(double* u_dev, double* v_dev, uint8_t* invalid_dev, uint8_t* status_dev, const uint8_t* grid_dev,
+                     int batch, int n_rows, int n_cols, int invalid_value, void* stream);
+
+/* Mask of a plan.  mask_dev [H, W] uint8, non-zero = masked; threshold in [0, 1].  For every pass with (ws, ov) the cell
+ * (i, j) is EXCLUDED if and only if tpiv_mask_coverage's count > limit, limit = (int)(threshold * (double)(ws * ws)): one
+ * float64 product, truncated (limit == ws * ws excludes nothing).  The grids are computed here, once, and kept -- one
+ * uint8 [n_rows, n_cols] per pass, allocated at the first call; the image is not needed after the call returns (it waits
+ * for the stream).  tpiv_plan_run then, behind the closing event of the pass's timing slot as the median test:
+ *   pass before the last: excluded cells read u = v = +0.0, invalid = 1 -- the predictor zeroes them as it zeroes any
+ *     invalid vector (no slip at a wall) and the median test does not count them as neighbours;
+ *   last pass: u = v = +0.0, invalid = 0 -- to the post-validation an excluded cell is a valid zero vector, never a hole;
+ *   with tpiv_plan_set_outlier: one tpiv_mask_fields call with invalid = 1 before the test of every pass (the test runs
+ *     on the masked fields), one more on what the test wrote (invalid as above) with the status map, where every excluded
+ *     cell then reads exactly 2.  Without the test: one call per pass.
+ * The plan does not touch the frames: the pixel step is tpiv_apply_mask, the caller's.  mask_dev NULL switches the mask
+ * off (every plan's default): tpiv_plan_run again enqueues exactly what it does without this call. */
+int tpiv_plan_set_mask(tpiv_plan* plan, const uint8_t* mask_dev, double threshold, void* stream);
+
+/* Device pointer to the grid of pass `pass`, uint8 [n_rows, n_cols], 1 = excluded.  TPIV_EINVAL when the mask is off. */
+int tpiv_plan_pass_mask(const tpiv_plan* plan, int pass, uint8_t** grid_dev);
+
 /* ---- post-validation (B:884-892) ------------------------------------------------- */
 
 /* Device part of the reference's per-pair host post-processing, for a whole batch:

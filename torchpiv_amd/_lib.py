@@ -74,6 +74,11 @@ SIGNATURES = {
     "tpiv_median_test": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _dbl, _dbl, _int, _u8p, _f64p, _f64p, _vp]),
     "tpiv_plan_set_outlier": (C.c_int, [C.c_void_p, _int, _dbl, _dbl, _int]),
     "tpiv_plan_pass_outliers": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p)]),
+    "tpiv_apply_mask": (C.c_int, [_u8p, _int, C.c_longlong, _u8p, _u8p, _vp]),
+    "tpiv_mask_coverage": (C.c_int, [_u8p, _int, _int, _int, _int, _vp, _vp]),
+    "tpiv_mask_fields": (C.c_int, [_f64p, _f64p, _u8p, _u8p, _u8p, _int, _int, _int, _int, _vp]),
+    "tpiv_plan_set_mask": (C.c_int, [C.c_void_p, _u8p, _dbl, _vp]),
+    "tpiv_plan_pass_mask": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p)]),
     "tpiv_postval": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _u8p, _vp, _vp]),
     "tpiv_postval_compact": (C.c_int, [_f64p, _f64p, _u8p, _vp, _int, _int, _int, _vp, _vp, _f64p, _vp, _vp]),
     "tpiv_finish_fields": (C.c_int, [_f64p, _f64p, _int, _int, _int, C.c_double, C.c_double, _f64p, _f64p, _vp]),

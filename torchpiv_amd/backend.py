@@ -372,7 +372,7 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 depth=None, equalize=None, prefilter=None) -> None:
+                 depth=None, mask=None, equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -399,6 +399,12 @@ class OfflinePIV:
         # histogram equalization of every frame on the device (engine.equalize_arg, tpiv_equalize), the last step in front of
         # the passes: tone map, background, pre-filter and cap, equalize.  For illumination that differs across the frame and
         # for particle images of very different brightness inside one window.
+        # mask (extension): None, an image (uint8 or bool [H, W], non-zero = masked) or a dict with "image" and any of
+        # threshold / pixels / fill (engine.mask_arg) -- where there is no flow: a wall, a model, its shadow, the rim of the
+        # frame.  Masked pixels are set to 0 in both frames (tpiv_apply_mask), the last step of the frame chain: tone map,
+        # background, pre-filter and cap, equalize, mask.  The windows of every pass whose share of masked pixels exceeds
+        # the threshold are excluded (tpiv_plan_set_mask): zero vectors that the predictor and the median test treat as
+        # invalid and the post-validation as valid; the delivered fields carry `fill` there (mask_grid() tells where).
         # depth (extension): None -- 8-bit frames, a 16-bit file decoded as value >> 8 like the reference (cv2's
         # IMREAD_GRAYSCALE) --, or the tone map of deep frames (engine.depth_arg): the files are decoded to uint16 with their
         # full sample range (io.imdecode_deep) and every frame passes out = lut[sample] on the device (tpiv_depth_map) before
@@ -414,19 +420,22 @@ class OfflinePIV:
         iter_function = IterModMap.functions[multipass_mode]            # KeyError like B:850
         self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
-                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize))
+                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize),
+                         engine.mask_arg(mask))
         if not self:
             return
+        if self._mask is not None:
+            self._mask_shape(self.frame_shape())
         if self._bg_arg is not None and self._bg_arg != "min":
             _background_arg(background, self.frame_shape())
         _require_gpu(self._device)
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                     multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
-                    equalize=None):
+                    equalize=None, mask=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
-        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's) and the state that the methods build up, empty."""
+        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's) and the state that the methods build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
         self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
@@ -437,6 +446,8 @@ class OfflinePIV:
         self._prefilter = prefilter
         self._depth = depth
         self._equalize = equalize
+        self._mask = mask
+        self._mask_dev = None            # mask=: the image on the device, uint8 [H, W], once a run needs it
         self._eq_work = None             # equalize=: the table workspace, uint8 [n * ky * kx * 256], kept from launch to launch
         self._depth_range = (depth["lo"], depth["hi"]) if depth is not None and "lo" in depth else None
         self._depth_lut = None           # the tone-map table in use: uint8 [65536] on the device, once resolved
@@ -472,7 +483,8 @@ class OfflinePIV:
     def _new_plan(self, H, W, max_batch):
         return engine.Plan(H, W, int(self._wind_size), int(self._overlap), n_pass=max(1, int(self._iter)),
                            mode=self._mode, pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio,
-                           val_win=self._val_win, device=self._device, precision=self._precision, outlier=self._outlier)
+                           val_win=self._val_win, device=self._device, precision=self._precision, outlier=self._outlier,
+                           mask=self._mask)
 
     def _get_plan(self, H, W, max_batch=1):
         if (self._plan is None or (self._plan.H, self._plan.W) != (H, W)
@@ -530,6 +542,46 @@ class OfflinePIV:
         if work is None or work.numel() < need or work.device != frames.device:
             work = self._eq_work = torch.empty(need, dtype=torch.uint8, device=frames.device)
         return engine.equalize(frames, eq["tile"], eq["clip"], out=out, work=work)
+
+    def _mask_shape(self, shape):
+        """ValueError unless the mask image has the frame shape (None: not known, e.g. an undecodable folder)."""
+        got = tuple(self._mask["image"].shape)
+        if shape is not None and got != tuple(shape):
+            raise ValueError(f"mask of shape {got} for frames of shape {tuple(shape)}")
+
+    def _zeroes_pixels(self):
+        return self._mask is not None and self._mask["pixels"] == "zero"
+
+    def _masked(self, frames, out=None):
+        """uint8 frames [n, H, W] or [H, W] through the pixel step of mask= (one tpiv_apply_mask call), into out -- the
+        frames themselves where an earlier step wrote them into memory of this object, never a caller's tensor -- or a
+        fresh tensor.  The image goes to the device once."""
+        self._mask_shape(frames.shape[-2:])
+        img = self._mask_dev
+        if img is None or img.device != frames.device:
+            img = self._mask_dev = self._mask["image"].to(frames.device).contiguous()
+        return engine.apply_mask(frames, img, out=out)
+
+    def _fill_grid(self, plan):
+        """(grid, grid on the device): the excluded cells of the plan's last pass as bool [n_rows, n_cols] in the orientation
+        of the delivered fields (flipped along axis 0), kept on the plan."""
+        got = getattr(plan, "_fill_grid", None)
+        if got is None:
+            dev = torch.flip(plan.mask_grid(plan.n_pass - 1), dims=(0,)).contiguous()
+            got = plan._fill_grid = (dev.cpu().numpy(), dev)
+        return got
+
+    def mask_grid(self):
+        """bool [n_rows, n_cols]: the cells of the delivered u, v that are excluded by mask= and carry its fill value, in
+        their orientation (flipped along axis 0 against Plan.mask_grid).  None without a mask or without a decodable pair."""
+        shape = self.frame_shape()
+        if self._mask is None or shape is None:
+            return None
+        shape = (int(shape[0]), int(shape[1]))
+        plan = self._single_plans.get(shape)
+        if plan is None:
+            plan = self._single_plans[shape] = self._new_plan(shape[0], shape[1], 1)
+        return self._fill_grid(plan)[0].copy()
 
     def _depth_table(self):
         """The tone-map table of depth= on the device (uint8 [65536]), None without depth.  "auto" takes the histogram of
@@ -842,7 +894,7 @@ class OfflinePIV:
     def _post_validate_batch(self, u, v, inv, plan=None):
         return self._post_collect(self._post_submit(u, v, inv, want_raw=True, plan=plan))
 
-    def _post_pipeline(self, x, y, depth=1):
+    def _post_pipeline(self, x, y, depth=1, plan=None):
         """The host side of batched() as a pipeline: push(meta, ticket) after every launch returns the finished
         entries [(meta, per-pair results)] of the batch pushed `depth` + 1 launches before -- while the GPU works on batch k,
         the census of batch k - depth is taken and its triangulations go to the worker processes; their answers are read,
@@ -861,7 +913,7 @@ class OfflinePIV:
                 extracted.append((meta, self._post_extract(ticket) if ticket is not None else None))
             if extracted and (len(extracted) > 1 or (drain and not waiting)):
                 meta, state = extracted.pop(0)
-                out.append((meta, self._finish_batch(self._post_complete(state), x, y) if state is not None else []))
+                out.append((meta, self._finish_batch(self._post_complete(state), x, y, plan) if state is not None else []))
             return out
 
         class Pipe:
@@ -877,7 +929,7 @@ class OfflinePIV:
                 return out
         return Pipe()
 
-    def _finish_batch(self, state, x, y):
+    def _finish_batch(self, state, x, y, plan=None):
         """The finished tuples of a batch: the device has flipped and scaled the fields (_post_submit), the host stage has
         patched the filled cells (_post_complete); what is left is ONE copy of the two stacks out of the pinned staging
         memory (so that results a caller keeps do not pin pages) and the per-pair views.  Returns per pair None or
@@ -890,13 +942,23 @@ class OfflinePIV:
             U, V = state["dev"]["fu"], state["dev"]["fv"]           # rows of the batch's device stacks (views)
         else:
             U, V = np.array(state["host"]["fu"].numpy()), np.array(state["host"]["fv"].numpy())
+        if self._mask is not None and plan is not None:
+            # mask=: the fill value into the excluded cells of every pair, after flip and scale (the grid is flipped too)
+            grid = self._fill_grid(plan)
+            if self.device_out:
+                U.masked_fill_(grid[1], self._mask["fill"])
+                V.masked_fill_(grid[1], self._mask["fill"])
+            else:
+                U[:, grid[0]] = self._mask["fill"]
+                V[:, grid[0]] = self._mask["fill"]
         xs, ys = x * self._scale, y * self._scale
         xs.flags.writeable = False
         ys.flags.writeable = False
         return [(xs, ys, U[k], V[k]) if keep[k] else None for k in range(keep.size)]
 
-    def _finish(self, uv, x, y):
-        """Flip and unit scaling of B:894-898 (numpy, the reference's own expressions)."""
+    def _finish(self, uv, x, y, plan=None):
+        """Flip and unit scaling of B:894-898 (numpy, the reference's own expressions); then, with mask=, the fill value
+        into the excluded cells of the plan's last pass."""
         if uv is None:
             return None
         u, v = uv
@@ -904,6 +966,10 @@ class OfflinePIV:
         v = -np.flip(v, axis=0)
         u = u * self._scale / self._dt * 1000
         v = v * self._scale / self._dt * 1000
+        if self._mask is not None and plan is not None:
+            grid = self._fill_grid(plan)[0]
+            u[grid] = self._mask["fill"]
+            v[grid] = self._mask["fill"]
         return x * self._scale, y * self._scale, u, v
 
     # pairs per launch of __call__ (extension): the generator of the reference's API reads ahead and runs
@@ -934,13 +1000,15 @@ class OfflinePIV:
             own = lut is not None or bg is not None or self._prefilter is not None
             a = self._equalized(a, out=a if own else None)
             b = self._equalized(b, out=b if own else None)
+        if self._zeroes_pixels():                       # in place on what the steps above made (the upload is this object's too)
+            a, b = self._masked(a, out=a), self._masked(b, out=b)
         plan = self._single_plans.get(shape)
         if plan is None:
             plan = self._single_plans[shape] = self._new_plan(shape[0], shape[1], 1)
         u, v, inv = plan.run(a, b)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates(shape, w, o)
-        return self._finish(self._post_validate_batch(u, v, inv, plan=plan)[0], x, y)
+        return self._finish(self._post_validate_batch(u, v, inv, plan=plan)[0], x, y, plan=plan)
 
     def __call__(self) -> Generator:
         if int(self.call_batch) > 1 and len(self._dataset) > 1:
@@ -989,7 +1057,7 @@ class OfflinePIV:
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
         dev = self._device
-        pipe = self._post_pipeline(x, y, depth=self.pipeline_depth)
+        pipe = self._post_pipeline(x, y, depth=self.pipeline_depth, plan=plan)
 
         def emit(finished):
             """Results of finished batches in dataset order; the pairs that were not staged run now."""
@@ -1068,6 +1136,9 @@ class OfflinePIV:
                         # one call over the stack, in place: the unpack, the tone map or the pre-filter wrote it into
                         # memory of this object
                         frames = self._equalized(frames, out=frames)
+                    if self._zeroes_pixels():
+                        # one call over the stack, in place (memory of this object, as above)
+                        frames = self._masked(frames, out=frames)
                     u, v, inv = plan.run(frames[:n], frames[n:])
                     ticket = self._post_submit(u, v, inv, plan=plan)
                 let_go(release)
@@ -1093,8 +1164,8 @@ class ResidentPIV(OfflinePIV):
     def __init__(self, frames_a: torch.Tensor, frames_b: torch.Tensor, wind_size: int, overlap: int,
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
-                 validation_window: int = 3, background=None, outlier=None, depth=None, equalize=None,
-                 prefilter=None) -> None:
+                 validation_window: int = 3, background=None, outlier=None, depth=None, mask=None,
+                 equalize=None, prefilter=None) -> None:
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
         # launch maps its pairs into a reused uint8 buffer
         depth = engine.depth_arg(depth)
@@ -1114,10 +1185,13 @@ class ResidentPIV(OfflinePIV):
         outlier = engine.outlier_arg(outlier)
         prefilter = engine.prefilter_arg(prefilter)
         equalize = engine.equalize_arg(equalize)
+        mask = engine.mask_arg(mask)
+        if mask is not None and tuple(mask["image"].shape) != tuple(frames_a.shape[1:]):
+            raise ValueError(f"mask of shape {tuple(mask['image'].shape)} for frames of shape {tuple(frames_a.shape[1:])}")
         device = _require_gpu(frames_a.device)
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
-                         validation_window, bg_arg, outlier, prefilter, depth, equalize)
+                         validation_window, bg_arg, outlier, prefilter, depth, equalize, mask)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):
@@ -1176,15 +1250,15 @@ class ResidentPIV(OfflinePIV):
             if dbuf is None or dbuf.dim() != 4 or dbuf.shape[1] < batch_size or dbuf.device != self._A.device:
                 dbuf = self._depth_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
         bg = self._background((H, W))
-        pf, eq = self._prefilter, self._equalize
-        if bg is not None or pf is not None or (eq is not None and lut is None):
+        pf, eq, zero = self._prefilter, self._equalize, self._zeroes_pixels()
+        if bg is not None or pf is not None or ((eq is not None or zero) and lut is None):
             buf = self._bg_frames
             if buf is None or buf.shape[1] < batch_size or buf.device != self._A.device:
                 buf = self._bg_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
         plan = self._get_plan(H, W, max_batch=batch_size)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
-        pipe = self._post_pipeline(x, y, depth=self.resident_depth)
+        pipe = self._post_pipeline(x, y, depth=self.resident_depth, plan=plan)
 
         def emit(finished):
             for chunk_ids, res in finished:
@@ -1194,6 +1268,7 @@ class ResidentPIV(OfflinePIV):
 
         for s in range(0, len(idx), batch_size):
             chunk = idx[s:s + batch_size]
+            views = False                                # A, B are views of the caller's frames
             # a run of consecutive pairs is a view of the resident frames; anything else is gathered (a copy of 2 x 4 MB per pair:
             # 0.36 ms per 64 pairs at 4 MP -- the check is per launch, so a stream that repeats or skips stays copy-free per run)
             if lut is not None:
@@ -1203,6 +1278,7 @@ class ResidentPIV(OfflinePIV):
                 B = self._mapped(self._B, chunk, lut, out=dbuf[1, :len(chunk)])
             elif chunk[-1] - chunk[0] == len(chunk) - 1 and chunk == list(range(chunk[0], chunk[0] + len(chunk))):
                 A, B = self._A[chunk[0]:chunk[0] + len(chunk)], self._B[chunk[0]:chunk[0] + len(chunk)]
+                views = True
             else:
                 sel = torch.tensor(chunk, device=self._device)
                 A, B = self._A.index_select(0, sel), self._B.index_select(0, sel)
@@ -1221,6 +1297,11 @@ class ResidentPIV(OfflinePIV):
                 own = lut is not None or bg is not None or pf is not None
                 A = self._equalized(A, out=A if own else buf[0, :len(chunk)])
                 B = self._equalized(B, out=B if own else buf[1, :len(chunk)])
+            if zero:
+                # in place on a reused buffer or on gathered copies; from the caller's frames into the reused buffer
+                own = not views or bg is not None or pf is not None or eq is not None
+                A = self._masked(A, out=A if own else buf[0, :len(chunk)])
+                B = self._masked(B, out=B if own else buf[1, :len(chunk)])
             u, v, inv = plan.run(A, B)
             # host work of the previous batches overlaps this batch's kernels
             yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan)))

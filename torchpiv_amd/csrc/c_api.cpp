@@ -239,6 +239,9 @@ struct tpiv_plan {
     std::vector<uint8_t*> ostatus;       // per pass: [max_batch, N_p] status map of the last run
     double *raw_u = nullptr, *raw_v = nullptr;   // a pass before the last writes here; the test writes the pass's fields
     uint8_t* raw_val = nullptr;          // the last pass's mask as the peak-ratio test left it; the test writes the caller's
+    // geometric mask (tpiv_plan_set_mask); off: nothing is enqueued for it.  mgrid: per pass [N_p], 1 = excluded cell
+    bool mask_on = false;
+    std::vector<uint8_t*> mgrid;
     std::vector<void*> allocs;
     // optional per-kernel timing: events[run][2*slot + {0,1}]
     bool timing = false;
@@ -855,6 +858,80 @@ int tpiv_plan_pass_outliers(const tpiv_plan* plan, int pass, uint8_t** status) {
     return TPIV_OK;
 }
 
+int tpiv_apply_mask(const uint8_t* frames, int n, long long pixels, const uint8_t* mask, uint8_t* out, void* stream) {
+    if (n < 0 || pixels <= 0) return fail(TPIV_EINVAL, "tpiv_apply_mask: bad shape");
+    if (n == 0) return TPIV_OK;
+    if (!frames || !mask || !out) return fail(TPIV_EINVAL, "tpiv_apply_mask: null pointer");
+    if (out != frames && out < frames + (size_t)n * pixels && frames < out + (size_t)n * pixels)
+        return fail(TPIV_EINVAL, "tpiv_apply_mask: out overlaps frames without being frames");
+    HIP_TRY(tpiv::launch_apply_mask(frames, n, pixels, mask, out, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+// the window sizes a plan accepts for a mask grid: check_window's, from 8 on
+static int check_mask_window(int H, int W, int ws, int ov) {
+    if (int rc = check_window(H, W, ws, ov, 0)) return rc;
+    if (ws < 8) return fail(TPIV_EUNSUPPORTED, "mask: window size must be in 8..256 (got " + std::to_string(ws) + ")");
+    return TPIV_OK;
+}
+
+int tpiv_mask_coverage(const uint8_t* mask, int H, int W, int ws, int ov, int32_t* count, void* stream) {
+    if (!mask || !count) return fail(TPIV_EINVAL, "tpiv_mask_coverage: null pointer");
+    if (int rc = check_mask_window(H, W, ws, ov)) return rc;
+    int nr = 0, nc = 0;
+    field_shape(H, W, ws, ov, &nr, &nc);
+    HIP_TRY(tpiv::launch_mask_coverage(mask, H, W, ws, ov, nr, nc, count, nullptr, 0, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_mask_fields(double* u, double* v, uint8_t* invalid, uint8_t* status, const uint8_t* grid, int batch, int n_rows,
+                     int n_cols, int invalid_value, void* stream) {
+    if (batch < 0 || n_rows < 1 || n_cols < 1) return fail(TPIV_EINVAL, "tpiv_mask_fields: empty grid");
+    if (invalid_value != 0 && invalid_value != 1) return fail(TPIV_EINVAL, "tpiv_mask_fields: invalid_value must be 0 or 1");
+    if ((long long)n_rows * n_cols >= (1LL << 31)) return fail(TPIV_EUNSUPPORTED, "field too large");
+    if (batch == 0) return TPIV_OK;
+    if (!u || !v || !invalid || !grid) return fail(TPIV_EINVAL, "tpiv_mask_fields: null pointer");
+    HIP_TRY(tpiv::launch_mask_fields(u, v, invalid, status, grid, batch, n_rows, n_cols, invalid_value, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_plan_set_mask(tpiv_plan* plan, const uint8_t* mask, double threshold, void* stream) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!mask) {
+        plan->mask_on = false;
+        return TPIV_OK;
+    }
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(TPIV_EINVAL, "tpiv_plan_set_mask: threshold must be in [0, 1]");
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+    for (const PassGeo& g : plan->geo)
+        if (int rc = check_mask_window(plan->H, plan->W, g.ws, g.ov)) return rc;
+    if (plan->mgrid.empty()) {                       // first time on: the grids (kept until the plan is destroyed)
+        std::vector<uint8_t*> grids(plan->n_pass, nullptr);
+        for (int p = 0; p < plan->n_pass; ++p)
+            if (int rc = plan->alloc(&grids[p], (size_t)plan->geo[p].n_rows * plan->geo[p].n_cols)) return rc;
+        plan->mgrid = std::move(grids);
+    }
+    plan->mask_on = false;                           // (stays off if a launch below fails)
+    for (int p = 0; p < plan->n_pass; ++p) {
+        const PassGeo& g = plan->geo[p];
+        const int limit = (int)(threshold * (double)(g.ws * g.ws));       // one float64 product, truncated
+        HIP_TRY(tpiv::launch_mask_coverage(mask, plan->H, plan->W, g.ws, g.ov, g.n_rows, g.n_cols, nullptr, plan->mgrid[p],
+                                           limit, (hipStream_t)stream));
+    }
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));       // the caller may let go of the image
+    plan->mask_on = true;
+    return TPIV_OK;
+}
+
+int tpiv_plan_pass_mask(const tpiv_plan* plan, int pass, uint8_t** grid) {
+    if (!plan || !grid || pass < 0 || pass >= plan->n_pass) return fail(TPIV_EINVAL, "bad plan / pass index");
+    if (!plan->mask_on) return fail(TPIV_EINVAL, "the plan has no mask (tpiv_plan_set_mask)");
+    *grid = plan->mgrid[pass];
+    return TPIV_OK;
+}
+
 int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch, double* u, double* v,
                   uint8_t* invalid, void* stream) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
@@ -913,11 +990,23 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
             mark(2 * p, 1);
         }
         if (rc) return rc;
-        if (test) {      // (behind the closing event of the pass's timing slot: the slots keep their meaning)
+        // (what follows goes behind the closing event of the pass's timing slot: the slots keep their meaning)
+        const bool masked = plan->mask_on;
+        if (masked) {    // excluded cells: zero vectors, invalid to the predictor and to the test, valid to the post-validation
+            hipError_t he = tpiv::launch_mask_fields(pu, pv, pval, nullptr, plan->mgrid[p], batch, g.n_rows, g.n_cols,
+                                                     (test || p < last) ? 1 : 0, st);
+            if (he != hipSuccess) return hip_fail(he, "launch_mask_fields");
+        }
+        if (test) {
             rc = run_median_test(pu, pv, pval, batch, g.n_rows, g.n_cols, plan->outlier_threshold, plan->outlier_eps,
                                  plan->outlier_min, plan->ostatus[p], p < last ? fu : nullptr, p < last ? fv : nullptr, 1,
                                  p < last ? nullptr : fval, st);
             if (rc) return rc;
+            if (masked) {        // once more, on what the test wrote: the pass's fields or the caller's mask, and the status map
+                hipError_t he = tpiv::launch_mask_fields(fu, fv, fval, plan->ostatus[p], plan->mgrid[p], batch, g.n_rows,
+                                                         g.n_cols, p < last ? 1 : 0, st);
+                if (he != hipSuccess) return hip_fail(he, "launch_mask_fields");
+            }
         }
     }
     if (plan->timing && plan->runs_recorded < 512) plan->runs_recorded++;

@@ -217,6 +217,17 @@ struct OutlierParams {
 };
 hipError_t launch_median_test(const OutlierParams& p, hipStream_t stream);
 
+// geometric mask (mask.hip, defined in include/torchpiv_hip.h).  apply: out = mask ? 0 : frames for n frames against one
+// image (out may be frames itself).  coverage: a wavefront per window of the (ws, ov) grid counts its masked pixels into count
+// (optional) and writes grid = count > limit (optional).  fields: u = v = +0.0, invalid = invalid_value, status = 2 (optional)
+// at the cells of every pair where grid != 0.
+hipError_t launch_apply_mask(const uint8_t* frames, int n, long long pixels, const uint8_t* mask, uint8_t* out,
+                             hipStream_t stream);
+hipError_t launch_mask_coverage(const uint8_t* mask, int H, int W, int ws, int ov, int n_rows, int n_cols, int32_t* count,
+                                uint8_t* grid, int limit, hipStream_t stream);
+hipError_t launch_mask_fields(double* u, double* v, uint8_t* invalid, uint8_t* status, const uint8_t* grid, int batch,
+                              int n_rows, int n_cols, int invalid_value, hipStream_t stream);
+
 hipError_t launch_xcorr(const PassParams& p, int mode, int n_cu, hipStream_t stream);
 // bytes of the tile kernels' work-queue counters (8 x one 64-byte line), and of the slow-item list header behind them
 constexpr size_t TILE_CTR_BYTES = 8 * 16 * sizeof(unsigned), TILE_SLOW_HDR_BYTES = 256;

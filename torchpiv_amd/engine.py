@@ -418,6 +418,111 @@ def subtract_background(frames, bg, out=None):
     return out
 
 
+MASK_KEYS = ("image", "threshold", "pixels", "fill")
+MASK_DEFAULTS = {"threshold": 0.5, "pixels": "zero", "fill": 0.0}
+
+
+def mask_arg(mask):
+    """The mask= argument of Plan / OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no mask), an
+    image -- uint8 or bool [H, W], numpy array or tensor, non-zero = masked -- or a dict with that image under "image" and
+    any of threshold (a number in [0, 1]: the share of masked pixels above which a window is excluded), pixels ("zero":
+    masked pixels are set to 0 in both frames before the passes, "keep": the frames stay as they are) and fill (any
+    float, NaN allowed: the value delivered at excluded cells).  Returns None or {"image": contiguous uint8 tensor [H, W],
+    "threshold": float, "pixels": str, "fill": float}; anything else raises ValueError."""
+    if mask is None:
+        return None
+    if not isinstance(mask, dict):
+        mask = {"image": mask}
+    unknown = sorted(set(mask) - set(MASK_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"mask: unknown key(s) {unknown}; known: {list(MASK_KEYS)}")
+    if "image" not in mask:
+        raise ValueError("mask: the dict needs an 'image' (uint8 or bool [H, W])")
+    im = mask["image"]
+    if isinstance(im, np.ndarray):
+        if im.dtype not in (np.uint8, np.bool_):
+            raise ValueError(f"mask: a uint8 or bool image, got {im.dtype}")
+        im = torch.from_numpy(np.ascontiguousarray(im))
+    elif not isinstance(im, torch.Tensor):
+        raise ValueError(f"mask: a uint8 or bool numpy array or tensor [H, W], got {type(im).__name__}")
+    elif im.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"mask: a uint8 or bool image, got {im.dtype}")
+    if im.dim() != 2 or im.numel() == 0:
+        raise ValueError(f"mask: an image [H, W], got shape {tuple(im.shape)}")
+    im = im.to(torch.uint8).contiguous()             # (True -> 1; a uint8 image keeps its bytes: any non-zero one masks)
+    par = dict(MASK_DEFAULTS, **{k: v for k, v in mask.items() if k != "image"})
+    thr, fill = par["threshold"], par["fill"]
+    if isinstance(thr, (bool, np.bool_)) or not isinstance(thr, (int, float, np.integer, np.floating)) \
+            or not 0 <= thr <= 1:                                       # (a NaN fails the comparison)
+        raise ValueError(f"mask: threshold must be a number in [0, 1], got {thr!r}")
+    if not isinstance(par["pixels"], str) or par["pixels"] not in ("zero", "keep"):
+        raise ValueError(f"mask: pixels must be 'zero' or 'keep', got {par['pixels']!r}")
+    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, (int, float, np.integer, np.floating)):
+        raise ValueError(f"mask: fill must be a float (NaN allowed), got {fill!r}")
+    return {"image": im, "threshold": float(thr), "pixels": par["pixels"], "fill": float(fill)}
+
+
+def _mask_image(mask, H, W, device, name):
+    _need_cuda(mask)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or not mask.is_contiguous() or mask.device != device:
+        raise ValueError(f"{name}: mask must be a contiguous uint8 [H, W] tensor of the frame shape on the frames' device")
+
+
+def apply_mask(frames, mask, out=None):
+    """mask != 0 ? 0 : frames for uint8 frames [n, H, W] or [H, W] on the device and a mask image uint8 [H, W] (any
+    non-zero byte masks).  out: a tensor of the frames' shape to write into -- frames itself (in place) or memory that
+    does not overlap them; None: a fresh one (tpiv_apply_mask)."""
+    f, H, W = _images(frames, "apply_mask")
+    _need_cuda(out)
+    _mask_image(mask, H, W, f.device, "apply_mask")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or not out.is_contiguous() or out.device != f.device:
+        raise ValueError("apply_mask: out must be a contiguous uint8 tensor of the frames' shape and device")
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_apply_mask(f.data_ptr(), f.shape[0], H * W, mask.data_ptr(), out.data_ptr(), _stream()))
+    return out
+
+
+def mask_coverage(mask, ws, ov):
+    """int32 [n_rows, n_cols]: the masked (non-zero) pixels of mask uint8 [H, W] (on the device) inside every window of
+    the (ws, ov) grid of field_shape (tpiv_mask_coverage)."""
+    _need_cuda(mask)
+    if mask.dim() != 2:
+        raise ValueError("mask_coverage: mask must be a contiguous uint8 [H, W] tensor")
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    _mask_image(mask, H, W, mask.device, "mask_coverage")
+    nr, nc = C.c_int(), C.c_int()
+    check(lib.tpiv_field_shape(H, W, int(ws), int(ov), C.byref(nr), C.byref(nc)))
+    count = torch.empty(max(nr.value, 0), max(nc.value, 0), dtype=torch.int32, device=mask.device)
+    with torch.cuda.device(mask.device):
+        check(lib.tpiv_mask_coverage(mask.data_ptr(), H, W, int(ws), int(ov), count.data_ptr(), _stream()))
+    return count
+
+
+def mask_fields(u, v, inv, grid, invalid_value, status=None):
+    """IN PLACE on u, v float64 and inv uint8 [batch, n_rows, n_cols] (contiguous, on the device): wherever grid (uint8 or
+    bool [n_rows, n_cols]) is non-zero, u = v = +0.0, inv = invalid_value (0 or 1) and, with a status map (uint8, the
+    fields' shape), status = 2 (tpiv_mask_fields).  Returns (u, v, inv) or (u, v, inv, status)."""
+    _need_cuda(u, v, inv, grid, status)
+    if u.dtype != torch.float64 or v.dtype != torch.float64 or inv.dtype != torch.uint8:
+        raise TypeError("mask_fields: u, v float64 and invalid uint8")
+    if not (u.is_contiguous() and v.is_contiguous() and inv.is_contiguous()) or u.dim() != 3 \
+            or u.shape != v.shape or u.shape != inv.shape:
+        raise ValueError("mask_fields: contiguous [batch, n_rows, n_cols] tensors of one shape")
+    B, nr, nc = u.shape
+    if grid.dtype not in (torch.uint8, torch.bool) or tuple(grid.shape) != (nr, nc) or grid.device != u.device:
+        raise ValueError("mask_fields: grid must be a uint8 or bool [n_rows, n_cols] tensor on the fields' device")
+    g = grid.to(torch.uint8).contiguous()
+    if status is not None and (status.dtype != torch.uint8 or status.shape != u.shape or not status.is_contiguous()
+                               or status.device != u.device):
+        raise ValueError("mask_fields: status must be a contiguous uint8 tensor of the fields' shape and device")
+    with torch.cuda.device(u.device):
+        check(lib.tpiv_mask_fields(u.data_ptr(), v.data_ptr(), inv.data_ptr(), None if status is None else status.data_ptr(),
+                                   g.data_ptr(), B, nr, nc, int(invalid_value), _stream()))
+    return (u, v, inv) if status is None else (u, v, inv, status)
+
+
 PREFILTER_KEYS = ("kind", "size", "cap")
 
 
@@ -752,11 +857,18 @@ class Plan:
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
 
     def __init__(self, H, W, ws, ov, n_pass=1, mode="CWS", pass_scale=2.0, val_ratio=1.2,
-                 val_win=3, max_batch=1, device=None, precision="exact", outlier=None):
+                 val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None):
         # outlier: None, "median" or a dict (outlier_arg): the normalized median test after every pass -- flagged vectors of
         # a pass before the last are replaced by their neighbourhood median before the predictor reads them, flagged
         # vectors of the last pass join the invalid mask (tpiv_plan_set_outlier)
+        # mask: None, an image [H, W] or a dict (mask_arg): the windows of every pass whose share of masked pixels exceeds
+        # the threshold are excluded -- zero vectors that are invalid to the predictor and to the median test, valid to the
+        # post-validation (tpiv_plan_set_mask).  The plan reads the image and the threshold only: the pixel step
+        # (apply_mask) and the fill value are the business of whoever owns the frames and delivers the fields.
         self.outlier = outlier_arg(outlier)
+        self.mask = mask_arg(mask)
+        if self.mask is not None and tuple(self.mask["image"].shape) != (H, W):
+            raise ValueError(f"mask of shape {tuple(self.mask['image'].shape)} for frames of shape {(H, W)}")
         if not torch.cuda.is_available():
             raise RuntimeError("torchpiv_amd.Plan needs a ROCm device (there is no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None \
@@ -777,6 +889,12 @@ class Plan:
                 try:
                     check(lib.tpiv_plan_set_outlier(self._h, 1, self.outlier["threshold"], self.outlier["eps"],
                                                     self.outlier["min_neighbours"]))
+                except Exception:
+                    self.close()
+                    raise
+            if self.mask is not None:
+                try:
+                    self.set_mask(self.mask["image"], self.mask["threshold"])
                 except Exception:
                     self.close()
                     raise
@@ -914,6 +1032,28 @@ class Plan:
         if rc != 0:
             raise _lib.HipError(f"hipMemcpyAsync failed: {rc}")
         return (status & 1).sum(dim=(1, 2), dtype=torch.int32)
+
+    def set_mask(self, image, threshold=MASK_DEFAULTS["threshold"]):
+        """(Re)computes the plan's grids of excluded cells from a mask image (uint8 [H, W], any device; non-zero = masked)
+        and a threshold (tpiv_plan_set_mask: one coverage launch per pass, waits for them); None switches the mask off."""
+        with torch.cuda.device(self.device):
+            if image is None:
+                check(lib.tpiv_plan_set_mask(self._h, None, 0.0, _stream()))
+                return
+            img = image.to(self.device).contiguous()
+            if img.dtype != torch.uint8 or tuple(img.shape) != (self.H, self.W):
+                raise ValueError(f"set_mask: a uint8 image of the plan's frame shape {(self.H, self.W)}")
+            check(lib.tpiv_plan_set_mask(self._h, img.data_ptr(), float(threshold), _stream()))
+
+    def mask_grid(self, p):
+        """bool [n_rows, n_cols] on the device: the excluded cells of pass p, unflipped (row 0 = the top window row); a
+        copy.  ValueError for a plan without a mask."""
+        pg = C.c_void_p()
+        check(lib.tpiv_plan_pass_mask(self._h, p, C.byref(pg)))
+        _, _, nr, nc = self.geometry[p]
+        grid = torch.empty(nr, nc, dtype=torch.uint8, device=self.device)
+        self._copy_out(((grid, pg, nr * nc),))
+        return grid != 0
 
     def outlier_status(self, p, batch):
         """Status map (uint8 [batch, n_rows, n_cols]: bit 0 flagged by the outlier test, bit 1 invalid by the peak ratio)
