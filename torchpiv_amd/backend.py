@@ -530,10 +530,40 @@ class OfflinePIV:
             if a is not None and b is not None and tuple(a.shape) == tuple(b.shape) == tuple(shape):
                 yield a.to(self._device), b.to(self._device)
 
+    def _scratch(self, name, lead, H, W, device):
+        """The reused uint8 buffer of attribute `name`, at least lead + (H, W) large: the one kept there if it has that
+        rank, leading extents no smaller than `lead`, the frame shape (H, W) and the device; else a fresh one, kept."""
+        buf = getattr(self, name)
+        if buf is None or buf.dim() != len(lead) + 2 or any(have < need for have, need in zip(buf.shape, lead)) \
+                or tuple(buf.shape[len(lead):]) != (H, W) or buf.device != device:
+            buf = torch.empty(tuple(lead) + (H, W), dtype=torch.uint8, device=device)
+            setattr(self, name, buf)
+        return buf
+
+    def _filtered(self, x, bg, out=None):
+        """uint8 frames x [n, H, W] or [H, W] through the background and pre-filter step: with prefilter= one
+        tpiv_prefilter launch that subtracts bg (uint8 [H, W], None: nothing) as well, else with bg the subtraction alone,
+        else x itself.  out: where a step writes (None: a fresh tensor; the filter is a stencil, never in place)."""
+        if self._prefilter is not None:
+            return engine.prefilter(x, background=bg, out=out, **self._prefilter)
+        if bg is not None:
+            return engine.subtract_background(x, bg, out=out)
+        return x
+
+    def _finished(self, x, owned, out=None):
+        """uint8 frames x through the last two steps in front of the passes: equalize, then mask pixels (one call each
+        over x).  owned: x is memory this object made -- an upload, a reused buffer, a gathered copy -- and a step writes
+        in place; a caller's tensor is never written: the first step that runs writes into out (None: a fresh tensor),
+        and what it wrote is owned.  The one place that decides between in place and copy."""
+        for on, step in ((self._equalize is not None, self._equalized), (self._zeroes_pixels(), self._masked)):
+            if on:
+                x = step(x, out=x if owned else out)
+                owned = True
+        return x
+
     def _equalized(self, frames, out=None):
         """uint8 frames [n, H, W] or [H, W] through equalize= (one tpiv_equalize call: the table and the map kernel), into
-        out -- the frames themselves where an earlier step wrote them into memory of this object, never a caller's tensor
-        -- or a fresh tensor.  The table workspace is kept from call to call."""
+        out (None: a fresh tensor; _finished chooses).  The table workspace is kept from call to call."""
         eq = self._equalize
         n = frames.shape[0] if frames.dim() == 3 else 1
         ky, kx = engine.equalize_grid(frames.shape[-2], frames.shape[-1], eq["tile"])
@@ -553,9 +583,8 @@ class OfflinePIV:
         return self._mask is not None and self._mask["pixels"] == "zero"
 
     def _masked(self, frames, out=None):
-        """uint8 frames [n, H, W] or [H, W] through the pixel step of mask= (one tpiv_apply_mask call), into out -- the
-        frames themselves where an earlier step wrote them into memory of this object, never a caller's tensor -- or a
-        fresh tensor.  The image goes to the device once."""
+        """uint8 frames [n, H, W] or [H, W] through the pixel step of mask= (one tpiv_apply_mask call), into out (None: a
+        fresh tensor; _finished chooses).  The image goes to the device once."""
         self._mask_shape(frames.shape[-2:])
         img = self._mask_dev
         if img is None or img.device != frames.device:
@@ -577,11 +606,14 @@ class OfflinePIV:
         shape = self.frame_shape()
         if self._mask is None or shape is None:
             return None
-        shape = (int(shape[0]), int(shape[1]))
+        return self._fill_grid(self._single_plan((int(shape[0]), int(shape[1]))))[0].copy()
+
+    def _single_plan(self, shape):
+        """The plan of the one-pair path for frames of shape (H, W), made on first use and kept."""
         plan = self._single_plans.get(shape)
         if plan is None:
             plan = self._single_plans[shape] = self._new_plan(shape[0], shape[1], 1)
-        return self._fill_grid(plan)[0].copy()
+        return plan
 
     def _depth_table(self):
         """The tone-map table of depth= on the device (uint8 [65536]), None without depth.  "auto" takes the histogram of
@@ -609,10 +641,7 @@ class OfflinePIV:
     def _map_staged(self, raw_d, st, H, W, lut, batch_size):
         """The staged uint16 slots of a batch (raw_d uint8 [files, cap] on the device, io.StagedBatches(deep=True)) through
         the tone map, one launch: uint8 [2n, H, W] = a_0..a_n-1, b_0..b_n-1, in a buffer kept from batch to batch."""
-        buf = self._depth_frames
-        if buf is None or buf.dim() != 3 or buf.shape[0] < 2 * batch_size or tuple(buf.shape[1:]) != (H, W) \
-                or buf.device != raw_d.device:
-            buf = self._depth_frames = torch.empty((2 * batch_size, H, W), dtype=torch.uint8, device=raw_d.device)
+        buf = self._scratch("_depth_frames", (2 * batch_size,), H, W, raw_d.device)
         off = torch.from_numpy(st.desc[:, 0] // 2)              # the slots' element offsets, every a, then every b
         return engine.depth_map(raw_d.view(-1).view(torch.uint16), lut, offsets=off, shape=(H, W), out=buf[:off.shape[0]])
 
@@ -990,22 +1019,11 @@ class OfflinePIV:
         if lut is not None:                             # uint16 as decoded -> uint8, right after the upload
             a, b = engine.depth_map(a, lut), engine.depth_map(b, lut)
         bg = self._background(shape)
-        if self._prefilter is not None:                 # one launch per frame, the background subtracted in the same one
-            a = engine.prefilter(a, background=None if bg is None else bg[0], **self._prefilter)
-            b = engine.prefilter(b, background=None if bg is None else bg[1], **self._prefilter)
-        elif bg is not None:
-            a = engine.subtract_background(a, bg[0])
-            b = engine.subtract_background(b, bg[1])
-        if self._equalize is not None:                  # one call per frame; in place on what the steps above made
-            own = lut is not None or bg is not None or self._prefilter is not None
-            a = self._equalized(a, out=a if own else None)
-            b = self._equalized(b, out=b if own else None)
-        if self._zeroes_pixels():                       # in place on what the steps above made (the upload is this object's too)
-            a, b = self._masked(a, out=a), self._masked(b, out=b)
-        plan = self._single_plans.get(shape)
-        if plan is None:
-            plan = self._single_plans[shape] = self._new_plan(shape[0], shape[1], 1)
-        u, v, inv = plan.run(a, b)
+        bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
+        # one launch per frame and step; in place from equalize on: the upload and what the steps made are this object's
+        a, b = self._filtered(a, bg_a), self._filtered(b, bg_b)
+        plan = self._single_plan(shape)
+        u, v, inv = plan.run(self._finished(a, True), self._finished(b, True))
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates(shape, w, o)
         return self._finish(self._post_validate_batch(u, v, inv, plan=plan)[0], x, y, plan=plan)
@@ -1113,32 +1131,21 @@ class OfflinePIV:
                         frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=bg)
                     consumed[dbuf] = torch.cuda.Event()
                     consumed[dbuf].record(cur)
+                    # the filter writes a buffer kept from batch to batch (stream order keeps a batch's passes ahead of the
+                    # next batch's filter), the subtraction alone goes in place
+                    dst = frames if self._prefilter is None else \
+                        self._scratch("_pf_frames", (2 * batch_size,), H, W, frames.device)[:2 * n]
                     if deep and bg is not None:
-                        if self._prefilter is not None:
-                            # per stack, the background subtracted in the filter's own launch
-                            pf = self._pf_frames
-                            if pf is None or pf.shape[0] < 2 * batch_size or tuple(pf.shape[1:]) != (H, W) or pf.device != frames.device:
-                                pf = self._pf_frames = torch.empty((2 * batch_size, H, W), dtype=torch.uint8, device=frames.device)
-                            engine.prefilter(frames[:n], background=bg[0], out=pf[:n], **self._prefilter)
-                            engine.prefilter(frames[n:], background=bg[1], out=pf[n:2 * n], **self._prefilter)
-                            frames = pf[:2 * n]
-                        else:
-                            engine.subtract_background(frames[:n], bg[0], out=frames[:n])
-                            engine.subtract_background(frames[n:], bg[1], out=frames[n:])
-                    elif self._prefilter is not None:
-                        # one launch over the stack (the unpack subtracted already), into a buffer kept from batch to
-                        # batch: stream order keeps a batch's passes ahead of the next batch's filter
-                        pf = self._pf_frames
-                        if pf is None or pf.shape[0] < 2 * batch_size or tuple(pf.shape[1:]) != (H, W) or pf.device != frames.device:
-                            pf = self._pf_frames = torch.empty((2 * batch_size, H, W), dtype=torch.uint8, device=frames.device)
-                        frames = engine.prefilter(frames, out=pf[:frames.shape[0]], **self._prefilter)
-                    if self._equalize is not None:
-                        # one call over the stack, in place: the unpack, the tone map or the pre-filter wrote it into
-                        # memory of this object
-                        frames = self._equalized(frames, out=frames)
-                    if self._zeroes_pixels():
-                        # one call over the stack, in place (memory of this object, as above)
-                        frames = self._masked(frames, out=frames)
+                        # per stack: the tone map subtracted nothing
+                        self._filtered(frames[:n], bg[0], out=dst[:n])
+                        self._filtered(frames[n:], bg[1], out=dst[n:])
+                        frames = dst
+                    else:
+                        # one launch over the stack (the unpack subtracted already)
+                        frames = self._filtered(frames, None, out=dst)
+                    # one call per step over the stack, in place: the unpack, the tone map or the filter wrote it into
+                    # memory of this object
+                    frames = self._finished(frames, True)
                     u, v, inv = plan.run(frames[:n], frames[n:])
                     ticket = self._post_submit(u, v, inv, plan=plan)
                 let_go(release)
@@ -1208,6 +1215,21 @@ class ResidentPIV(OfflinePIV):
         off = torch.tensor(chunk, dtype=torch.int64) * (H * W)
         return engine.depth_map(frames.view(-1), lut, offsets=off, shape=(H, W), out=out)
 
+    def _select(self, chunk, lut, out=None):
+        """(A, B, owned): the uint8 frames of the pairs `chunk` and whether they are memory of this object.  Under depth=
+        (lut) they are mapped, the pairs addressed by offset (consecutive or not: no gather), into out[0] and out[1]
+        (None: fresh tensors): owned.  A run of consecutive pairs is a view of the caller's frames: not owned.  Anything
+        else is gathered (a copy of 2 x 4 MB per pair: 0.36 ms per 64 pairs at 4 MP -- the check is per chunk, so a stream
+        that repeats or skips stays copy-free per run): owned."""
+        n = len(chunk)
+        if lut is not None:
+            out_a, out_b = (None, None) if out is None else (out[0], out[1])
+            return self._mapped(self._A, chunk, lut, out=out_a), self._mapped(self._B, chunk, lut, out=out_b), True
+        if chunk[-1] - chunk[0] == n - 1 and chunk == list(range(chunk[0], chunk[0] + n)):
+            return self._A[chunk[0]:chunk[0] + n], self._B[chunk[0]:chunk[0] + n], False
+        sel = torch.tensor(chunk, dtype=torch.int64, device=self._device)
+        return self._A.index_select(0, sel), self._B.index_select(0, sel), True
+
     def compute_background(self, indices=None, batch_size=None):
         """(bg_a, bg_b): the per-pixel minimum of the resident a frames and of the b frames (of the pairs `indices`;
         None: all), uint8 [H, W] on the device (tpiv_frame_min; 255 everywhere for no pair).  batch_size: pairs gathered
@@ -1216,21 +1238,15 @@ class ResidentPIV(OfflinePIV):
         H, W = self._A.shape[1:]
         acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=self._device)
         lut = self._depth_table()
-        if lut is not None:
-            idx, bs = list(range(len(self))) if indices is None else list(indices), int(batch_size or self.bg_batch)
-            for s in range(0, len(idx), bs):
-                engine.frame_min(self._mapped(self._A, idx[s:s + bs], lut), acc[0])
-                engine.frame_min(self._mapped(self._B, idx[s:s + bs], lut), acc[1])
-            return acc[0], acc[1]
-        if indices is None:
+        if lut is None and indices is None:                  # the resident stacks as they are: one launch each
             engine.frame_min(self._A, acc[0])
             engine.frame_min(self._B, acc[1])
             return acc[0], acc[1]
-        idx, bs = list(indices), int(batch_size or self.bg_batch)
-        for s in range(0, len(idx), bs):                     # gathered in bounded chunks
-            sel = torch.tensor(idx[s:s + bs], dtype=torch.int64, device=self._device)
-            engine.frame_min(self._A.index_select(0, sel), acc[0])
-            engine.frame_min(self._B.index_select(0, sel), acc[1])
+        idx, bs = list(range(len(self))) if indices is None else list(indices), int(batch_size or self.bg_batch)
+        for s in range(0, len(idx), bs):                     # mapped, viewed or gathered in bounded chunks
+            A, B, _ = self._select(idx[s:s + bs], lut)
+            engine.frame_min(A, acc[0])
+            engine.frame_min(B, acc[1])
         return acc[0], acc[1]
 
     # launches in flight before a batch's census is read.  Two: the copies of a batch's results run on a stream of their own,
@@ -1245,16 +1261,15 @@ class ResidentPIV(OfflinePIV):
             return
         H, W = self._A.shape[1:]
         lut = self._depth_table()                     # (depth="auto": the histogram of the sampled pairs, once, before ...)
-        if lut is not None:
-            dbuf = self._depth_frames
-            if dbuf is None or dbuf.dim() != 4 or dbuf.shape[1] < batch_size or dbuf.device != self._A.device:
-                dbuf = self._depth_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
+        # the reused buffers: the mapped frames of a launch (uint16 -> uint8; stream order keeps a launch's passes ahead of the
+        # next launch's map into the same memory), and what the later steps make of frames they may not write in place
+        dbuf = None if lut is None else self._scratch("_depth_frames", (2, batch_size), H, W, self._A.device)
         bg = self._background((H, W))
-        pf, eq, zero = self._prefilter, self._equalize, self._zeroes_pixels()
-        if bg is not None or pf is not None or ((eq is not None or zero) and lut is None):
-            buf = self._bg_frames
-            if buf is None or buf.shape[1] < batch_size or buf.device != self._A.device:
-                buf = self._bg_frames = torch.empty((2, batch_size, H, W), dtype=torch.uint8, device=self._A.device)
+        bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
+        buf = None
+        if bg is not None or self._prefilter is not None \
+                or ((self._equalize is not None or self._zeroes_pixels()) and lut is None):
+            buf = self._scratch("_bg_frames", (2, batch_size), H, W, self._A.device)
         plan = self._get_plan(H, W, max_batch=batch_size)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
@@ -1268,41 +1283,15 @@ class ResidentPIV(OfflinePIV):
 
         for s in range(0, len(idx), batch_size):
             chunk = idx[s:s + batch_size]
-            views = False                                # A, B are views of the caller's frames
-            # a run of consecutive pairs is a view of the resident frames; anything else is gathered (a copy of 2 x 4 MB per pair:
-            # 0.36 ms per 64 pairs at 4 MP -- the check is per launch, so a stream that repeats or skips stays copy-free per run)
-            if lut is not None:
-                # uint16 -> uint8 into the reused buffer, the pairs addressed by offset (consecutive or not: no gather);
-                # stream order keeps a launch's passes ahead of the next launch's map into the same memory
-                A = self._mapped(self._A, chunk, lut, out=dbuf[0, :len(chunk)])
-                B = self._mapped(self._B, chunk, lut, out=dbuf[1, :len(chunk)])
-            elif chunk[-1] - chunk[0] == len(chunk) - 1 and chunk == list(range(chunk[0], chunk[0] + len(chunk))):
-                A, B = self._A[chunk[0]:chunk[0] + len(chunk)], self._B[chunk[0]:chunk[0] + len(chunk)]
-                views = True
-            else:
-                sel = torch.tensor(chunk, device=self._device)
-                A, B = self._A.index_select(0, sel), self._B.index_select(0, sel)
-            if pf is not None:
-                # one launch per frame stack, the background subtracted in the same one, into the same reused buffer
-                A = engine.prefilter(A, background=None if bg is None else bg[0], out=buf[0, :len(chunk)], **pf)
-                B = engine.prefilter(B, background=None if bg is None else bg[1], out=buf[1, :len(chunk)], **pf)
-            elif bg is not None:
-                # into the reused buffer (the caller's frames are never written); stream order keeps a launch's passes
-                # ahead of the next launch's subtraction into the same memory
-                A = engine.subtract_background(A, bg[0], out=buf[0, :len(chunk)])
-                B = engine.subtract_background(B, bg[1], out=buf[1, :len(chunk)])
-            if eq is not None:
-                # in place where the tone map, the background or the pre-filter wrote a reused buffer, else from the
-                # caller's frames into that buffer
-                own = lut is not None or bg is not None or pf is not None
-                A = self._equalized(A, out=A if own else buf[0, :len(chunk)])
-                B = self._equalized(B, out=B if own else buf[1, :len(chunk)])
-            if zero:
-                # in place on a reused buffer or on gathered copies; from the caller's frames into the reused buffer
-                own = not views or bg is not None or pf is not None or eq is not None
-                A = self._masked(A, out=A if own else buf[0, :len(chunk)])
-                B = self._masked(B, out=B if own else buf[1, :len(chunk)])
-            u, v, inv = plan.run(A, B)
+            n = len(chunk)
+            A, B, owned = self._select(chunk, lut, out=None if dbuf is None else (dbuf[0, :n], dbuf[1, :n]))
+            out_a, out_b = (None, None) if buf is None else (buf[0, :n], buf[1, :n])
+            # one launch per frame stack and step.  The background and the filter write the reused buffer (stream order
+            # keeps a launch's passes ahead of the next launch's writes into the same memory), and so does the first later
+            # step that meets the caller's frames; everything else goes in place
+            fa, fb = self._filtered(A, bg_a, out=out_a), self._filtered(B, bg_b, out=out_b)
+            owned |= fa is not A
+            u, v, inv = plan.run(self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b))
             # host work of the previous batches overlaps this batch's kernels
             yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan)))
         yield from emit(pipe.flush())
