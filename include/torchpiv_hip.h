@@ -351,6 +351,32 @@ int tpiv_depth_map(const uint16_t* src_dev, const long long* src_off_dev, int n,
 int tpiv_depth_histogram(const uint16_t* src_dev, int n, long long pixels_per_frame, unsigned long long* hist_dev,
                          void* stream);
 
+/* ---- geometric rectification (extension; the reference has none) ------------------------------- */
+
+#define TPIV_DEWARP_LINEAR 0
+#define TPIV_DEWARP_CUBIC 1
+
+/* Rectifies n frames through one backward map, in integer arithmetic (every implementation of these lines gives the same
+ * bytes), one launch: out_dev[f][r][c] = frame f sampled at the source position map_dev holds for output pixel (r, c).
+ *   Frames: uint8, frame f = the H * W bytes from frames_dev + src_off_dev[f] on (src_off_dev: n element offsets on the
+ *   device, each frame inside memory of the caller -- not checked: they live on the device; NULL: f * H * W).
+ *   Map: int32 [H, W, 2], source x then source y in signed Q8, q = floor(s * 256 + 0.5), pixel centres at the integers.
+ *   A pixel is OUTSIDE when qx < 0, qy < 0, qx > (W - 1) << 8 or qy > (H - 1) << 8 (torchpiv_amd.engine.dewarp_map stores
+ *   such entries as (-1, -1)): out = fill.  Else ix = qx >> 8, fx = qx & 255, likewise y, every tap coordinate clamped to
+ *   0 .. W - 1 / 0 .. H - 1 (edge replicate; the kernel clamps unconditionally, whatever the map holds), and
+ *     TPIV_DEWARP_LINEAR: out = (sum wy wx p + 32768) >> 16 over the taps (iy, iy + 1) x (ix, ix + 1), weights (256 - f, f);
+ *     TPIV_DEWARP_CUBIC: out = clamp((sum Ty[a] Tx[b] p + (1 << 19)) >> 20, 0, 255) over the taps iy - 1 .. iy + 2, ix - 1 ..
+ *       ix + 2, arithmetic shift, T = table_dev[f]: int16 [256, 4] in Q10, the Catmull-Rom weights (a = -0.5) of t = f / 256
+ *       as floor(c * 1024 + 0.5) with the remainder to 1024 added to weight 1 (f < 128) or 2 (f >= 128)
+ *       (torchpiv_amd.engine.dewarp_cubic_table; any table whose rows keep sum |w| <= 1280 stays inside int32).
+ *   table_dev is read by TPIV_DEWARP_CUBIC only and may be NULL otherwise.
+ * out_dev [n, H, W] must overlap neither the frames nor the map nor the table (a gather: never in place); the frames are
+ * not written and no byte outside out_dev's n * H * W is.  TPIV_EINVAL for a null pointer, n < 0, H or W outside 1..2^22,
+ * H * W >= 2^31, an unknown interp, fill outside 0..255, a map that is not 4-byte aligned, an overlap that can be seen
+ * from the host; nothing is launched then.  n == 0 succeeds and launches nothing.  Enqueues only; allocates nothing. */
+int tpiv_dewarp(const uint8_t* frames_dev, const long long* src_off_dev, int n, int H, int W, const int32_t* map_dev,
+                const int16_t* table_dev, int interp, int fill, uint8_t* out_dev, void* stream);
+
 /* ---- tile-wise adaptive histogram equalization (CLAHE) ----------------------------------------- */
 
 /* Equalizes n frames frames_dev [n, H, W] uint8 into out_dev, in integer arithmetic (every implementation of these lines

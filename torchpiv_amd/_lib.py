@@ -20,6 +20,8 @@ PREC_FAST, PREC_REFERENCE, PREC_F64, PREC_EXACT = 0, 1, 2, 3
 PRECISIONS = {"fast": PREC_FAST, "reference": PREC_REFERENCE, "f64": PREC_F64, "exact": PREC_EXACT}
 PREFILTER_NONE, PREFILTER_MIN, PREFILTER_MEAN = 0, 1, 2
 PREFILTERS = {None: PREFILTER_NONE, "min": PREFILTER_MIN, "mean": PREFILTER_MEAN}    # tpiv_prefilter's kinds
+DEWARP_LINEAR, DEWARP_CUBIC = 0, 1
+DEWARP_INTERPS = {"linear": DEWARP_LINEAR, "cubic": DEWARP_CUBIC}                    # tpiv_dewarp's interpolations
 ABI_VERSION = 2
 
 
@@ -89,6 +91,7 @@ SIGNATURES = {
     "tpiv_subtract_background": (C.c_int, [_u8p, _int, C.c_longlong, _u8p, _u8p, _vp]),
     "tpiv_prefilter": (C.c_int, [_u8p, _int, _int, _int, _u8p, _int, _int, _int, _u8p, _vp]),
     "tpiv_depth_map": (C.c_int, [_vp, _vp, _int, _int, _int, _u8p, _u8p, _vp]),
+    "tpiv_dewarp": (C.c_int, [_u8p, _vp, _int, _int, _int, _vp, _vp, _int, _int, _u8p, _vp]),
     "tpiv_depth_histogram": (C.c_int, [_vp, _int, C.c_longlong, _vp, _vp]),
     "tpiv_equalize_work_bytes": (C.c_size_t, [_int, _int, _int, _int]),
     "tpiv_equalize": (C.c_int, [_u8p, _int, _int, _int, _int, _int, _u8p, _vp, C.c_size_t, _vp]),

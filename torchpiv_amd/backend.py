@@ -372,7 +372,7 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 depth=None, mask=None, equalize=None, prefilter=None) -> None:
+                 depth=None, mask=None, dewarp=None, equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -411,6 +411,13 @@ class OfflinePIV:
         # the background, the pre-filter and the passes.  {"lo", "hi", "curve"}: a fixed range; "auto" / {"auto": True, ...}:
         # the range from the histogram of a sample of pairs (tpiv_depth_histogram + engine.depth_range), resolved on first
         # use; {"lut": table}: the caller's table.  A background image given by the caller is in mapped (uint8) units.
+        # dewarp (extension): None or a dict with one backward map -- "homography", "poly" or "map" -- and optionally "interp"
+        # and "fill" (engine.dewarp_arg): every frame is rectified on the device (tpiv_dewarp) right after the decode / tone
+        # map and before everything else: tone map, dewarp, background, pre-filter and cap, equalize, mask.  For views
+        # through an oblique window, a Scheimpflug adapter or a short lens, where the magnification varies across the
+        # frame.  A background image given by the caller, the mask and the delivered x, y are in rectified coordinates;
+        # background="min" is the minimum of the rectified frames.  Pixels whose source lies outside the camera frame carry
+        # `fill`; dewarp_outside() gives their image, fit to be passed as mask=.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
@@ -421,21 +428,23 @@ class OfflinePIV:
         self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
                          engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize),
-                         engine.mask_arg(mask))
+                         engine.mask_arg(mask), engine.dewarp_arg(dewarp))
         if not self:
             return
         if self._mask is not None:
             self._mask_shape(self.frame_shape())
+        if self._dewarp is not None:
+            self._dewarp_shape(self.frame_shape())
         if self._bg_arg is not None and self._bg_arg != "min":
             _background_arg(background, self.frame_shape())
         _require_gpu(self._device)
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                     multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
-                    equalize=None, mask=None):
+                    equalize=None, mask=None, dewarp=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
-        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's) and the state that the methods build up, empty."""
+        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's, dewarp: engine.dewarp_arg's) and the state that the methods build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
         self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
@@ -447,6 +456,9 @@ class OfflinePIV:
         self._depth = depth
         self._equalize = equalize
         self._mask = mask
+        self._dewarp = dewarp
+        self._dw_map = None              # dewarp=: the Q8 map on the device, int32 [H, W, 2], once a run needs it
+        self._dw_frames = None           # dewarp=: the rectified frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
         self._mask_dev = None            # mask=: the image on the device, uint8 [H, W], once a run needs it
         self._eq_work = None             # equalize=: the table workspace, uint8 [n * ky * kx * 256], kept from launch to launch
         self._depth_range = (depth["lo"], depth["hi"]) if depth is not None and "lo" in depth else None
@@ -591,6 +603,36 @@ class OfflinePIV:
             img = self._mask_dev = self._mask["image"].to(frames.device).contiguous()
         return engine.apply_mask(frames, img, out=out)
 
+    def _dewarp_shape(self, shape):
+        """ValueError unless a map given as coordinate arrays has the frame shape (None: not known)."""
+        if shape is not None and "map" in self._dewarp and tuple(self._dewarp["map"][0].shape) != tuple(shape):
+            raise ValueError(f"dewarp map of shape {tuple(self._dewarp['map'][0].shape)} for frames of shape {tuple(shape)}")
+
+    def _dewarp_map(self, shape, device):
+        """The Q8 map of dewarp= for frames of `shape` on `device` (int32 [H, W, 2]): built on the host, checked and
+        uploaded once per object and device."""
+        m = self._dw_map
+        if m is None or tuple(m.shape[:2]) != tuple(shape) or m.device != device:
+            self._dewarp_shape(shape)
+            m = self._dw_map = engine.dewarp_upload(engine.dewarp_map(self._dewarp, shape[0], shape[1]), device)
+        return m
+
+    def _dewarped(self, x, out, offsets=None, shape=None):
+        """uint8 frames through dewarp= (one tpiv_dewarp launch) into out, memory of this object: x [n, H, W] or [H, W], or
+        a flat buffer whose frames `offsets` address (shape = (H, W)).  The source is not written."""
+        dw = self._dewarp
+        m = self._dewarp_map(tuple(x.shape[-2:]) if offsets is None else tuple(shape), x.device)
+        return engine.dewarp(x, m, dw["interp"], dw["fill"], offsets=offsets, shape=shape, out=out)
+
+    def dewarp_outside(self):
+        """bool [H, W]: the pixels of the rectified frames whose source lies outside the camera frame and that carry the
+        fill value of dewarp= -- fit to be passed as mask=.  None without dewarp= or without a decodable pair."""
+        shape = self.frame_shape()
+        if self._dewarp is None or shape is None:
+            return None
+        self._dewarp_shape(shape)
+        return engine.dewarp_outside(engine.dewarp_map(self._dewarp, shape[0], shape[1]))
+
     def _fill_grid(self, plan):
         """(grid, grid on the device): the excluded cells of the plan's last pass as bool [n_rows, n_cols] in the orientation
         of the delivered fields (flipped along axis 0), kept on the plan."""
@@ -671,7 +713,7 @@ class OfflinePIV:
         images are 255 everywhere (the identity of the minimum: a rank's empty shard).  The files go through the native
         read-ahead ring and the device unpack, like batched() (whose staging buffers they share when batch_size and the
         file size agree), and each batch is folded in with tpiv_frame_min.  With depth= the minimum is taken over the
-        tone-mapped frames (depth="auto" resolves here first)."""
+        tone-mapped frames (depth="auto" resolves here first), with dewarp= over the rectified frames."""
         shape = self.frame_shape()
         if shape is None:
             raise ValueError("compute_background: the dataset holds no decodable pair")
@@ -703,6 +745,8 @@ class OfflinePIV:
                         desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
                         lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
                         frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W)      # [2n, H, W]: a_0..a_n-1, b_0..b_n-1
+                    if self._dewarp is not None:
+                        frames = self._dewarped(frames, self._scratch("_dw_frames", (2 * bs,), H, W, dev)[:2 * n])
                     engine.frame_min(frames[:n], acc[0])
                     engine.frame_min(frames[n:], acc[1])
                     cur.synchronize()           # the upload is through: the readers may refill the staging buffer
@@ -1018,6 +1062,10 @@ class OfflinePIV:
         lut = self._depth_table()
         if lut is not None:                             # uint16 as decoded -> uint8, right after the upload
             a, b = engine.depth_map(a, lut), engine.depth_map(b, lut)
+        if self._dewarp is not None:                    # rectified next, into the reused buffer (stream order keeps a
+            self._dewarp_shape(shape)                   # launch's passes ahead of the next write into it)
+            buf = self._scratch("_dw_frames", (2,), shape[0], shape[1], a.device)
+            a, b = self._dewarped(a, buf[0]), self._dewarped(b, buf[1])
         bg = self._background(shape)
         bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
         # one launch per frame and step; in place from equalize on: the upload and what the steps made are this object's
@@ -1063,6 +1111,9 @@ class OfflinePIV:
         H, W = first[1]
         lut = self._depth_table()                     # (depth="auto": the histogram prepass runs here, once, before ...)
         deep = lut is not None
+        dewarp = self._dewarp is not None
+        if dewarp:
+            self._dewarp_shape((H, W))
         bg = self._background((H, W), batch_size)     # (background="min": the prepass over the files runs here, once)
         plan = self._get_plan(H, W, max_batch=batch_size)
         pairs = self._dataset.img_pairs
@@ -1127,16 +1178,20 @@ class OfflinePIV:
                         # the tone map where the unpack sits: one launch, slots a0 b0 a1 b1 .. -> stacks a_0..a_n-1, b_0..b_n-1
                         frames = self._map_staged(raw_d, st, H, W, lut, batch_size)
                     else:
-                        # [2n, H, W]: a_0..a_n-1, b_0..b_n-1 (with a background: minus bg_a / bg_b, in the same kernel)
-                        frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=bg)
+                        # [2n, H, W]: a_0..a_n-1, b_0..b_n-1 (with a background: minus bg_a / bg_b, in the same kernel --
+                        # unless the frames are rectified first: the background is in rectified coordinates)
+                        frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=None if dewarp else bg)
                     consumed[dbuf] = torch.cuda.Event()
                     consumed[dbuf].record(cur)
+                    if dewarp:
+                        # one launch over both stacks, into a buffer kept from batch to batch
+                        frames = self._dewarped(frames, self._scratch("_dw_frames", (2 * batch_size,), H, W, frames.device)[:2 * n])
                     # the filter writes a buffer kept from batch to batch (stream order keeps a batch's passes ahead of the
                     # next batch's filter), the subtraction alone goes in place
                     dst = frames if self._prefilter is None else \
                         self._scratch("_pf_frames", (2 * batch_size,), H, W, frames.device)[:2 * n]
-                    if deep and bg is not None:
-                        # per stack: the tone map subtracted nothing
+                    if (deep or dewarp) and bg is not None:
+                        # per stack: the tone map subtracted nothing, and neither did an unpack in front of dewarp=
                         self._filtered(frames[:n], bg[0], out=dst[:n])
                         self._filtered(frames[n:], bg[1], out=dst[n:])
                         frames = dst
@@ -1172,7 +1227,9 @@ class ResidentPIV(OfflinePIV):
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
                  validation_window: int = 3, background=None, outlier=None, depth=None, mask=None,
-                 equalize=None, prefilter=None) -> None:
+                 dewarp=None, equalize=None, prefilter=None) -> None:
+        # dewarp (see OfflinePIV): every launch rectifies its pairs into a reused buffer, addressed by their offsets in the
+        # caller's stacks (nothing is gathered first, and the caller's frames are never written)
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
         # launch maps its pairs into a reused uint8 buffer
         depth = engine.depth_arg(depth)
@@ -1195,10 +1252,14 @@ class ResidentPIV(OfflinePIV):
         mask = engine.mask_arg(mask)
         if mask is not None and tuple(mask["image"].shape) != tuple(frames_a.shape[1:]):
             raise ValueError(f"mask of shape {tuple(mask['image'].shape)} for frames of shape {tuple(frames_a.shape[1:])}")
+        dewarp = engine.dewarp_arg(dewarp)
+        if dewarp is not None and "map" in dewarp and tuple(dewarp["map"][0].shape) != tuple(frames_a.shape[1:]):
+            raise ValueError(f"dewarp map of shape {tuple(dewarp['map'][0].shape)} for frames of shape "
+                             f"{tuple(frames_a.shape[1:])}")
         device = _require_gpu(frames_a.device)
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
-                         validation_window, bg_arg, outlier, prefilter, depth, equalize, mask)
+                         validation_window, bg_arg, outlier, prefilter, depth, equalize, mask, dewarp)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):
@@ -1215,16 +1276,26 @@ class ResidentPIV(OfflinePIV):
         off = torch.tensor(chunk, dtype=torch.int64) * (H * W)
         return engine.depth_map(frames.view(-1), lut, offsets=off, shape=(H, W), out=out)
 
-    def _select(self, chunk, lut, out=None):
+    def _select(self, chunk, lut, out=None, dw=None):
         """(A, B, owned): the uint8 frames of the pairs `chunk` and whether they are memory of this object.  Under depth=
         (lut) they are mapped, the pairs addressed by offset (consecutive or not: no gather), into out[0] and out[1]
-        (None: fresh tensors): owned.  A run of consecutive pairs is a view of the caller's frames: not owned.  Anything
+        (None: fresh tensors): owned.  Under dewarp= they are then rectified into dw[0] and dw[1] (the rectified-frame
+        buffer, [2, >= n, H, W]) -- the mapped frames, or without depth= the caller's own, addressed by offset like the tone
+        map's: owned.  A run of consecutive pairs is a view of the caller's frames: not owned.  Anything
         else is gathered (a copy of 2 x 4 MB per pair: 0.36 ms per 64 pairs at 4 MP -- the check is per chunk, so a stream
         that repeats or skips stays copy-free per run): owned."""
         n = len(chunk)
         if lut is not None:
             out_a, out_b = (None, None) if out is None else (out[0], out[1])
-            return self._mapped(self._A, chunk, lut, out=out_a), self._mapped(self._B, chunk, lut, out=out_b), True
+            A, B = self._mapped(self._A, chunk, lut, out=out_a), self._mapped(self._B, chunk, lut, out=out_b)
+            if dw is not None:
+                A, B = self._dewarped(A, dw[0, :n]), self._dewarped(B, dw[1, :n])
+            return A, B, True
+        if dw is not None:
+            H, W = self._A.shape[1:]
+            off = torch.tensor(chunk, dtype=torch.int64) * (H * W)
+            return (self._dewarped(self._A.view(-1), dw[0, :n], offsets=off, shape=(H, W)),
+                    self._dewarped(self._B.view(-1), dw[1, :n], offsets=off, shape=(H, W)), True)
         if chunk[-1] - chunk[0] == n - 1 and chunk == list(range(chunk[0], chunk[0] + n)):
             return self._A[chunk[0]:chunk[0] + n], self._B[chunk[0]:chunk[0] + n], False
         sel = torch.tensor(chunk, dtype=torch.int64, device=self._device)
@@ -1233,18 +1304,20 @@ class ResidentPIV(OfflinePIV):
     def compute_background(self, indices=None, batch_size=None):
         """(bg_a, bg_b): the per-pixel minimum of the resident a frames and of the b frames (of the pairs `indices`;
         None: all), uint8 [H, W] on the device (tpiv_frame_min; 255 everywhere for no pair).  batch_size: pairs gathered
-        at a time for `indices` (default bg_batch).  With depth= the minimum is taken over the tone-mapped frames, mapped
-        batch_size pairs at a time."""
+        at a time for `indices` (default bg_batch).  With depth= the minimum is taken over the tone-mapped frames, with
+        dewarp= over the rectified frames, batch_size pairs at a time."""
         H, W = self._A.shape[1:]
         acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=self._device)
         lut = self._depth_table()
-        if lut is None and indices is None:                  # the resident stacks as they are: one launch each
+        dewarp = self._dewarp is not None
+        if lut is None and not dewarp and indices is None:   # the resident stacks as they are: one launch each
             engine.frame_min(self._A, acc[0])
             engine.frame_min(self._B, acc[1])
             return acc[0], acc[1]
         idx, bs = list(range(len(self))) if indices is None else list(indices), int(batch_size or self.bg_batch)
-        for s in range(0, len(idx), bs):                     # mapped, viewed or gathered in bounded chunks
-            A, B, _ = self._select(idx[s:s + bs], lut)
+        dw = self._scratch("_dw_frames", (2, min(bs, max(len(idx), 1))), H, W, self._A.device) if dewarp else None
+        for s in range(0, len(idx), bs):                     # mapped, rectified, viewed or gathered in bounded chunks
+            A, B, _ = self._select(idx[s:s + bs], lut, dw=dw)
             engine.frame_min(A, acc[0])
             engine.frame_min(B, acc[1])
         return acc[0], acc[1]
@@ -1264,11 +1337,12 @@ class ResidentPIV(OfflinePIV):
         # the reused buffers: the mapped frames of a launch (uint16 -> uint8; stream order keeps a launch's passes ahead of the
         # next launch's map into the same memory), and what the later steps make of frames they may not write in place
         dbuf = None if lut is None else self._scratch("_depth_frames", (2, batch_size), H, W, self._A.device)
-        bg = self._background((H, W))
+        bg = self._background((H, W))                 # (background="min" with dewarp=: its prepass uses the buffer below first)
+        dw = None if self._dewarp is None else self._scratch("_dw_frames", (2, batch_size), H, W, self._A.device)
         bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
         buf = None
         if bg is not None or self._prefilter is not None \
-                or ((self._equalize is not None or self._zeroes_pixels()) and lut is None):
+                or ((self._equalize is not None or self._zeroes_pixels()) and lut is None and dw is None):
             buf = self._scratch("_bg_frames", (2, batch_size), H, W, self._A.device)
         plan = self._get_plan(H, W, max_batch=batch_size)
         w, o, _, _ = plan.geometry[-1]
@@ -1284,7 +1358,7 @@ class ResidentPIV(OfflinePIV):
         for s in range(0, len(idx), batch_size):
             chunk = idx[s:s + batch_size]
             n = len(chunk)
-            A, B, owned = self._select(chunk, lut, out=None if dbuf is None else (dbuf[0, :n], dbuf[1, :n]))
+            A, B, owned = self._select(chunk, lut, out=None if dbuf is None else (dbuf[0, :n], dbuf[1, :n]), dw=dw)
             out_a, out_b = (None, None) if buf is None else (buf[0, :n], buf[1, :n])
             # one launch per frame stack and step.  The background and the filter write the reused buffer (stream order
             # keeps a launch's passes ahead of the next launch's writes into the same memory), and so does the first later

@@ -1134,6 +1134,28 @@ int tpiv_depth_map(const uint16_t* src, const long long* src_off, int n, int H, 
     return TPIV_OK;
 }
 
+int tpiv_dewarp(const uint8_t* frames, const long long* src_off, int n, int H, int W, const int32_t* map, const int16_t* table,
+                int interp, int fill, uint8_t* out, void* stream) {
+    if (n < 0 || H <= 0 || W <= 0 || H > (1 << 22) || W > (1 << 22) || (long long)H * W >= (1LL << 31))
+        return fail(TPIV_EINVAL, "tpiv_dewarp: bad shape");
+    if (interp != TPIV_DEWARP_LINEAR && interp != TPIV_DEWARP_CUBIC)
+        return fail(TPIV_EINVAL, "tpiv_dewarp: interp must be TPIV_DEWARP_LINEAR or TPIV_DEWARP_CUBIC");
+    if (fill < 0 || fill > 255) return fail(TPIV_EINVAL, "tpiv_dewarp: fill must be in 0..255");
+    if (n == 0) return TPIV_OK;
+    if (!frames || !map || !out || (interp == TPIV_DEWARP_CUBIC && !table)) return fail(TPIV_EINVAL, "tpiv_dewarp: null pointer");
+    if ((uintptr_t)map % 4 != 0 || (uintptr_t)table % 2 != 0)
+        return fail(TPIV_EINVAL, "tpiv_dewarp: the map must be 4-byte and the table 2-byte aligned");
+    const size_t px = (size_t)n * H * W;
+    const uint8_t* m8 = reinterpret_cast<const uint8_t*>(map);
+    const uint8_t* t8 = reinterpret_cast<const uint8_t*>(table);
+    if (!src_off && out < frames + px && frames < out + px)
+        return fail(TPIV_EINVAL, "tpiv_dewarp: out overlaps frames (a gather: not in place)");
+    if (out < m8 + (size_t)H * W * 8 && m8 < out + px) return fail(TPIV_EINVAL, "tpiv_dewarp: out overlaps the map");
+    if (t8 && out < t8 + 2048 && t8 < out + px) return fail(TPIV_EINVAL, "tpiv_dewarp: out overlaps the table");
+    HIP_TRY(tpiv::launch_dewarp(frames, src_off, n, H, W, map, table, interp, fill, out, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
 size_t tpiv_equalize_work_bytes(int n, int H, int W, int tile) {
     if (n <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28) || tile < tpiv::EQUALIZE_TILE_MIN ||
         tile > tpiv::EQUALIZE_TILE_MAX)

@@ -228,6 +228,14 @@ hipError_t launch_mask_coverage(const uint8_t* mask, int H, int W, int ws, int o
 hipError_t launch_mask_fields(double* u, double* v, uint8_t* invalid, uint8_t* status, const uint8_t* grid, int batch,
                               int n_rows, int n_cols, int invalid_value, hipStream_t stream);
 
+// geometric rectification (dewarp.hip, defined in include/torchpiv_hip.h): out[f] = frame f (at element offset src_off[f] on
+// the device, nullptr: f * H * W) sampled through map int32 [H, W, 2] (signed Q8, x first), bilinear or Catmull-Rom with the
+// Q10 weight table int16 [256, 4] (read by DEWARP_CUBIC only); a lane per four adjacent output pixels, the frames of a
+// launch in chunks of DEWARP_FRAME_CHUNK along the grid's second dimension.  Out of place only; H * W < 2^31.
+constexpr int DEWARP_LINEAR = 0, DEWARP_CUBIC = 1, DEWARP_FRAME_CHUNK = 8;
+hipError_t launch_dewarp(const uint8_t* frames, const long long* src_off, int n, int H, int W, const int32_t* map,
+                         const int16_t* table, int interp, int fill, uint8_t* out, hipStream_t stream);
+
 hipError_t launch_xcorr(const PassParams& p, int mode, int n_cu, hipStream_t stream);
 // bytes of the tile kernels' work-queue counters (8 x one 64-byte line), and of the slow-item list header behind them
 constexpr size_t TILE_CTR_BYTES = 8 * 16 * sizeof(unsigned), TILE_SLOW_HDR_BYTES = 256;

@@ -852,6 +852,329 @@ def depth_map(frames, lut, offsets=None, shape=None, out=None):
     return out
 
 
+DEWARP_FORMS = ("homography", "poly", "map")
+DEWARP_KEYS = DEWARP_FORMS + ("interp", "fill")
+DEWARP_DEFAULTS = {"interp": "cubic", "fill": 0}
+DEWARP_POLY_ORDERS = {3: 1, 6: 2, 10: 3}            # coefficients per axis -> order
+
+
+def dewarp_arg(dewarp):
+    """The dewarp= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (frames as recorded)
+    or a dict that holds exactly one backward map -- where in the camera frame every pixel of the rectified frame comes
+    from; pixel centres at the integers, x along the columns, y along the rows, the rectified frame has the camera
+    frame's shape --
+      "homography": 3 x 3, (x, y, 1) of the output pixel -> the source pixel, homogeneous;
+      "poly": float [2, K], K = 3, 6 or 10 -- source x (row 0) and source y (row 1) in pixels as polynomials of order 1, 2
+        or 3 in the output coordinates normalised to [-1, 1], xn = 2 x / (W - 1) - 1, yn = 2 y / (H - 1) - 1, with the terms
+        in the order 1, xn, yn | xn^2, xn yn, yn^2 | xn^3, xn^2 yn, xn yn^2, yn^3;
+      "map": a pair (xs, ys) of float arrays [H, W], the source coordinates themselves (radial models, the output of a
+        calibration package); non-finite entries count as outside;
+    and optionally "interp" ("cubic", the default: Catmull-Rom; or "linear") and "fill" (integer 0..255, default 0: the
+    value of pixels whose source lies outside the camera frame).  Returns None or {form: float64 array(s), "interp": str,
+    "fill": int}; anything else raises ValueError."""
+    if dewarp is None:
+        return None
+    if not isinstance(dewarp, dict):
+        raise ValueError(f"dewarp: None or a dict with one of {list(DEWARP_FORMS)}, got {type(dewarp).__name__}")
+    unknown = sorted(set(dewarp) - set(DEWARP_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"dewarp: unknown key(s) {unknown}; known: {list(DEWARP_KEYS)}")
+    forms = [k for k in DEWARP_FORMS if k in dewarp]
+    if len(forms) != 1:
+        raise ValueError(f"dewarp: exactly one of {list(DEWARP_FORMS)} is needed, got {forms}")
+    form = forms[0]
+
+    def array(x, what):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        try:
+            a = np.asarray(x)
+            if a.dtype.kind not in "fiu":
+                raise TypeError
+            return np.ascontiguousarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"dewarp: {what} must be an array of numbers") from None
+    if form == "homography":
+        val = array(dewarp[form], "the homography")
+        if val.shape != (3, 3) or not np.isfinite(val).all():
+            raise ValueError(f"dewarp: the homography must be a finite 3 x 3 matrix, got shape {val.shape}")
+        if not np.any(val[2] != 0):
+            raise ValueError("dewarp: the homography's last row is zero")
+    elif form == "poly":
+        val = array(dewarp[form], "the polynomial")
+        if val.ndim != 2 or val.shape[0] != 2 or val.shape[1] not in DEWARP_POLY_ORDERS or not np.isfinite(val).all():
+            raise ValueError(f"dewarp: the polynomial must be finite [2, K] with K in {sorted(DEWARP_POLY_ORDERS)}, got "
+                             f"shape {val.shape}")
+    else:
+        pair = dewarp[form]
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError("dewarp: map must be a pair (xs, ys) of float arrays [H, W]")
+        xs, ys = array(pair[0], "map xs"), array(pair[1], "map ys")
+        if xs.ndim != 2 or xs.shape != ys.shape or xs.size == 0:
+            raise ValueError(f"dewarp: map must be a pair of arrays [H, W] of one shape, got {xs.shape} and {ys.shape}")
+        val = (xs, ys)
+    interp = dewarp.get("interp", DEWARP_DEFAULTS["interp"])
+    fill = dewarp.get("fill", DEWARP_DEFAULTS["fill"])
+    if not isinstance(interp, str) or interp not in _lib.DEWARP_INTERPS:
+        raise ValueError(f"dewarp: interp must be one of {sorted(_lib.DEWARP_INTERPS)}, got {interp!r}")
+    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, (int, np.integer)) or not 0 <= fill <= 255:
+        raise ValueError(f"dewarp: fill must be an integer in 0..255, got {fill!r}")
+    return {form: val, "interp": interp, "fill": int(fill)}
+
+
+def _dewarp_form(arg):
+    par = dewarp_arg(arg)                    # (its own result passes unchanged)
+    if par is None:
+        raise ValueError("dewarp: no map given")
+    return next(k for k in DEWARP_FORMS if k in par), par
+
+
+def _poly_terms(xn, yn, K):
+    terms = [np.ones_like(xn), xn, yn]
+    if K >= 6:
+        terms += [xn * xn, xn * yn, yn * yn]
+    if K >= 10:
+        terms += [xn * xn * xn, xn * xn * yn, xn * yn * yn, yn * yn * yn]
+    return terms
+
+
+def _normalised(x, y, H, W):
+    xn = 2.0 * x / (W - 1) - 1.0 if W > 1 else np.zeros_like(x)
+    yn = 2.0 * y / (H - 1) - 1.0 if H > 1 else np.zeros_like(y)
+    return xn, yn
+
+
+def dewarp_coords(arg, H, W):
+    """(sx, sy): the source coordinates of every pixel of the rectified frame [H, W] under the dewarp= argument, float64
+    numpy, before quantisation."""
+    form, par = _dewarp_form(arg)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"dewarp: frame shape must be positive, got {(H, W)}")
+    if form == "map":
+        xs, ys = par["map"]
+        if xs.shape != (H, W):
+            raise ValueError(f"dewarp: map of shape {xs.shape} for frames of shape {(H, W)}")
+        return xs, ys
+    y, x = np.mgrid[0:H, 0:W]
+    x, y = x.astype(np.float64), y.astype(np.float64)
+    if form == "homography":
+        M = par["homography"]
+        X = M[0, 0] * x + M[0, 1] * y + M[0, 2]
+        Y = M[1, 0] * x + M[1, 1] * y + M[1, 2]
+        D = M[2, 0] * x + M[2, 1] * y + M[2, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return X / D, Y / D
+    P = par["poly"]
+    xn, yn = _normalised(x, y, H, W)
+    sx, sy = np.zeros((H, W)), np.zeros((H, W))
+    for k, t in enumerate(_poly_terms(xn, yn, P.shape[1])):
+        sx = sx + P[0, k] * t
+        sy = sy + P[1, k] * t
+    return sx, sy
+
+
+def dewarp_map(arg, H, W):
+    """The backward map of tpiv_dewarp for frames of H x W: numpy int32 [H, W, 2], source x then source y in signed Q8,
+    q = floor(s * 256 + 0.5) in float64.  An entry with qx < 0, qy < 0, qx > (W - 1) << 8 or qy > (H - 1) << 8, or with a
+    non-finite coordinate, is outside and stored as (-1, -1).  arg: the dewarp= argument (dewarp_arg)."""
+    H, W = int(H), int(W)
+    if H > 1 << 22 or W > 1 << 22:
+        raise ValueError(f"dewarp: frames of {(H, W)} are too large")
+    sx, sy = dewarp_coords(arg, H, W)
+    ok = np.isfinite(sx) & np.isfinite(sy)
+    qx = np.floor(np.where(ok, sx, -1.0) * 256.0 + 0.5)
+    qy = np.floor(np.where(ok, sy, -1.0) * 256.0 + 0.5)
+    ok &= (qx >= 0) & (qy >= 0) & (qx <= (W - 1) * 256) & (qy <= (H - 1) * 256)
+    m = np.full((H, W, 2), -1, dtype=np.int32)
+    m[..., 0][ok] = qx[ok].astype(np.int32)
+    m[..., 1][ok] = qy[ok].astype(np.int32)
+    return m
+
+
+def dewarp_outside(map):
+    """bool [H, W]: the pixels the map int32 [H, W, 2] (numpy array or tensor) leaves to `fill` -- what to pass as mask=
+    to keep them out of the fields."""
+    m = map.detach().cpu().numpy() if isinstance(map, torch.Tensor) else np.asarray(map)
+    if m.ndim != 3 or m.shape[2] != 2 or m.dtype != np.int32:
+        raise ValueError("dewarp_outside: the map must be int32 [H, W, 2]")
+    H, W = m.shape[:2]
+    return (m[..., 0] < 0) | (m[..., 1] < 0) | (m[..., 0] > (W - 1) * 256) | (m[..., 1] > (H - 1) * 256)
+
+
+def dewarp_cubic_table():
+    """The weight table of tpiv_dewarp's cubic interpolation: numpy int16 [256, 4], row f = the Catmull-Rom weights (a =
+    -0.5) of t = f / 256 on the taps -1, 0, 1, 2 in Q10, floor(c * 1024 + 0.5) (t and its powers are exact in float64), the
+    remainder to 1024 added to weight 1 (f < 128) or 2 (f >= 128): every row sums to 1024, row 0 is (0, 1024, 0, 0), row f
+    is row 256 - f reversed, and sum |w| <= 1280."""
+    t = np.arange(256, dtype=np.float64) / 256.0
+    c = np.stack([((2.0 - t) * t - 1.0) * t * 0.5, (1.5 * t - 2.5) * t * t + 1.0, ((2.0 - 1.5 * t) * t + 0.5) * t,
+                  (0.5 * t - 0.5) * t * t], axis=1)
+    T = np.floor(c * 1024.0 + 0.5).astype(np.int64)
+    rest = 1024 - T.sum(axis=1)
+    T[:128, 1] += rest[:128]
+    T[128:, 2] += rest[128:]
+    return T.astype(np.int16)
+
+
+def _dewarp_check_map(m, H, W):
+    """ValueError unless every entry of the numpy map int32 [H, W, 2] is inside the frame or the outside marker."""
+    if m.dtype != np.int32 or m.shape != (H, W, 2):
+        raise ValueError(f"dewarp: the map must be int32 [{H}, {W}, 2], got {m.dtype} {m.shape}")
+    inside = (m[..., 0] >= 0) & (m[..., 1] >= 0) & (m[..., 0] <= (W - 1) * 256) & (m[..., 1] <= (H - 1) * 256)
+    marker = (m[..., 0] == -1) & (m[..., 1] == -1)
+    bad = ~(inside | marker)
+    if bad.any():
+        r, c = np.argwhere(bad)[0]
+        raise ValueError(f"dewarp: illegal map entry {tuple(int(q) for q in m[r, c])} at pixel ({int(r)}, {int(c)}): neither "
+                         f"inside the {H} x {W} frame nor the outside marker (-1, -1)")
+
+
+_DEWARP_CHECKED = "_tpiv_dewarp_checked"
+_DEWARP_TABLES = {}
+
+
+def dewarp_upload(map, device):
+    """The map (numpy int32 [H, W, 2], dewarp_map's) checked on the host and put on `device` once: the tensor dewarp()
+    takes.  ValueError for an entry that is neither inside the frame nor the outside marker."""
+    m = np.ascontiguousarray(map)
+    if m.ndim != 3:
+        raise ValueError("dewarp: the map must be int32 [H, W, 2]")
+    _dewarp_check_map(m, m.shape[0], m.shape[1])
+    t = torch.from_numpy(m).to(device)
+    setattr(t, _DEWARP_CHECKED, t._version)
+    return t
+
+
+def _dewarp_table(device):
+    """The cubic weight table on `device`, made once per device."""
+    key = str(device)
+    if key not in _DEWARP_TABLES:
+        _DEWARP_TABLES[key] = torch.from_numpy(dewarp_cubic_table()).to(device)
+    return _DEWARP_TABLES[key]
+
+
+def dewarp(frames, map, interp="cubic", fill=0, offsets=None, shape=None, out=None):
+    """Rectification on the device, one launch (tpiv_dewarp; the definition is in include/torchpiv_hip.h): every frame
+    sampled through the backward map.  frames: a contiguous uint8 tensor [n, H, W] or [H, W]; or, the offsets form, a flat
+    uint8 buffer with offsets (int64 [n]: the element offset of every frame in the buffer; a tensor, array or list,
+    checked on the host) and shape = (H, W) -- frames addressed in any order, repeatedly, nothing gathered first.  map:
+    int32 [H, W, 2] on the frames' device (dewarp_upload(dewarp_map(...))); a tensor that did not come from dewarp_upload
+    is checked on the host at its first use (one copy down), and again only after it was written.  interp "cubic" or
+    "linear", fill 0..255.  out: a contiguous uint8 tensor of the result's shape that overlaps none of the source, the map
+    or the table; None: a fresh one.  An overlap is refused and nothing is launched.  The source is not written."""
+    _need_cuda(frames)
+    if not isinstance(interp, str) or interp not in _lib.DEWARP_INTERPS:
+        raise ValueError(f"dewarp: interp must be one of {sorted(_lib.DEWARP_INTERPS)}, got {interp!r}")
+    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, (int, np.integer)) or not 0 <= fill <= 255:
+        raise ValueError(f"dewarp: fill must be an integer in 0..255, got {fill!r}")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"dewarp: frames must be uint8, got {frames.dtype}")
+    if offsets is None:
+        if shape is not None:
+            raise ValueError("dewarp: shape goes with offsets (the frames carry their own)")
+        f, H, W = _images(frames, "dewarp")
+        n, off_d, out_shape = int(f.shape[0]), None, tuple(frames.shape)
+    else:
+        if frames.dim() != 1 or not frames.is_contiguous():
+            raise ValueError("dewarp: with offsets, frames must be a flat contiguous uint8 buffer")
+        try:
+            H, W = (int(s) for s in shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"dewarp: with offsets, shape = (H, W) is needed, got {shape!r}") from None
+        if H < 1 or W < 1:
+            raise ValueError(f"dewarp: shape must be positive, got {(H, W)}")
+        off_h = offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else torch.as_tensor(np.asarray(offsets))
+        if off_h.dtype != torch.int64 or off_h.dim() != 1:
+            raise ValueError("dewarp: offsets must be int64 [n]")
+        n = int(off_h.shape[0])
+        if n and (int(off_h.min()) < 0 or int(off_h.max()) + H * W > frames.numel()):
+            raise ValueError(f"dewarp: a frame of {H} x {W} pixels at offsets {int(off_h.min())}..{int(off_h.max())} leaves "
+                             f"the buffer of {frames.numel()} bytes")
+        f = frames
+        off_d = offsets if isinstance(offsets, torch.Tensor) and offsets.device == frames.device and offsets.is_contiguous() \
+            else off_h.contiguous().to(frames.device, non_blocking=True)
+        out_shape = (n, H, W)
+    if not isinstance(map, torch.Tensor) or map.dtype != torch.int32 or tuple(map.shape) != (H, W, 2) \
+            or not map.is_contiguous() or map.device != frames.device:
+        raise ValueError(f"dewarp: map must be a contiguous int32 [{H}, {W}, 2] tensor on the frames' device")
+    if getattr(map, _DEWARP_CHECKED, None) != map._version:
+        _dewarp_check_map(map.cpu().numpy(), H, W)
+        setattr(map, _DEWARP_CHECKED, map._version)
+    table = _dewarp_table(frames.device)
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.uint8, device=frames.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(out_shape) \
+            or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError(f"dewarp: out must be a contiguous uint8 tensor of shape {tuple(out_shape)} on the frames' device")
+    if _overlap(out, out.numel(), f, f.numel()):
+        raise ValueError("dewarp: out overlaps the source frames (a gather: never in place)")
+    if _overlap(out, out.numel(), map, 4 * map.numel()):
+        raise ValueError("dewarp: out overlaps the map")
+    if _overlap(out, out.numel(), table, 2 * table.numel()):
+        raise ValueError("dewarp: out overlaps the table")
+    with torch.cuda.device(frames.device):
+        check(lib.tpiv_dewarp(f.data_ptr(), None if off_d is None else off_d.data_ptr(), n, H, W, map.data_ptr(),
+                              table.data_ptr(), _lib.DEWARP_INTERPS[interp], int(fill), out.data_ptr(), _stream()))
+    return out
+
+
+DEWARP_FIT_KINDS = {"homography": 4, "poly1": 3, "poly2": 6, "poly3": 10}       # kind -> the fewest points
+
+
+def dewarp_fit(target_px, image_px, kind="homography", shape=None):
+    """Least-squares fit of the backward map from a dot target (numpy, no GPU).  target_px [N, 2]: where the dots belong in
+    the rectified frame, (x, y) in pixels; image_px [N, 2]: where they were found in the camera frame.  kind "homography"
+    (normalised DLT: both point sets shifted to their centroid and scaled to a mean distance of sqrt 2, the matrix from
+    the SVD) or "poly1" / "poly2" / "poly3" (numpy.linalg.lstsq on the coordinates normalised to [-1, 1], for which shape
+    = (H, W) of the frames is needed; dewarp_arg has the term order).  Returns the dict for dewarp= -- {"homography": 3 x 3}
+    or {"poly": [2, K]}.  ValueError for fewer points than the kind has unknowns (4, 3, 6, 10), or points that do not
+    determine the fit."""
+    if kind not in DEWARP_FIT_KINDS:
+        raise ValueError(f"dewarp_fit: kind must be one of {list(DEWARP_FIT_KINDS)}, got {kind!r}")
+    try:
+        t, s = np.asarray(target_px, dtype=np.float64), np.asarray(image_px, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("dewarp_fit: target_px and image_px must be arrays [N, 2]") from None
+    if t.ndim != 2 or t.shape[1] != 2 or t.shape != s.shape or not (np.isfinite(t).all() and np.isfinite(s).all()):
+        raise ValueError(f"dewarp_fit: target_px and image_px must be finite arrays [N, 2] of one shape, got {t.shape} "
+                         f"and {s.shape}")
+    need = DEWARP_FIT_KINDS[kind]
+    if t.shape[0] < need:
+        raise ValueError(f"dewarp_fit: kind {kind!r} needs at least {need} points, got {t.shape[0]}")
+    if kind == "homography":
+        def norm(p):
+            c = p.mean(axis=0)
+            d = np.sqrt(((p - c) ** 2).sum(axis=1)).mean()
+            if not d > 0:
+                raise ValueError("dewarp_fit: the points coincide")
+            k = np.sqrt(2.0) / d
+            return np.array([[k, 0, -k * c[0]], [0, k, -k * c[1]], [0, 0, 1.0]])
+        Nt, Ns = norm(t), norm(s)
+        tn = (Nt @ np.column_stack([t, np.ones(len(t))]).T).T
+        sn = (Ns @ np.column_stack([s, np.ones(len(s))]).T).T
+        A = np.zeros((2 * len(t), 9))
+        A[0::2, 0:3], A[0::2, 6:9] = tn, -sn[:, 0:1] * tn
+        A[1::2, 3:6], A[1::2, 6:9] = tn, -sn[:, 1:2] * tn
+        _, sv, vt = np.linalg.svd(A)
+        if not sv[7] > 1e-12 * sv[0]:
+            raise ValueError("dewarp_fit: the points do not determine a homography (collinear?)")
+        M = np.linalg.inv(Ns) @ vt[-1].reshape(3, 3) @ Nt
+        return {"homography": M / M[2, 2] if M[2, 2] != 0 else M}
+    try:
+        H, W = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"dewarp_fit: kind {kind!r} needs shape = (H, W) of the frames, got {shape!r}") from None
+    if H < 2 or W < 2:
+        raise ValueError(f"dewarp_fit: shape must be at least 2 x 2, got {(H, W)}")
+    xn, yn = _normalised(t[:, 0], t[:, 1], H, W)
+    A = np.stack(_poly_terms(xn, yn, need), axis=1)
+    coef, _, rank, _ = np.linalg.lstsq(A, s, rcond=None)
+    if rank < need:
+        raise ValueError(f"dewarp_fit: the points do not determine a polynomial of kind {kind!r}")
+    return {"poly": np.ascontiguousarray(coef.T)}
+
+
 class Plan:
     """The multipass pipeline of OfflinePIV.__call__ (PIVbackend.py:873-882) for batches of
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
