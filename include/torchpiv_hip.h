@@ -237,6 +237,51 @@ int tpiv_plan_set_mask(tpiv_plan* plan, const uint8_t* mask_dev, double threshol
 /* Device pointer to the grid of pass `pass`, uint8 [n_rows, n_cols], 1 = excluded.  TPIV_EINVAL when the mask is off. */
 int tpiv_plan_pass_mask(const tpiv_plan* plan, int pass, uint8_t** grid_dev);
 
+/* ---- per-vector uncertainty (extension; the reference has none) ---------------------------------- */
+
+/* Correlation-statistics uncertainty (B. Wieneke, Meas. Sci. Technol. 26 (2015) 074002): the 1-sigma random error, in
+ * pixels, of every vector of a field u, v float64 [batch, n_rows, n_cols] at geometry (ws, ov) measured on frames a, b
+ * uint8 [batch, H, W].  u is the displacement along x (columns), v along y (rows), from a to b.  st = ws - ov; window
+ * (r, c) starts at y0 = r st, x0 = c st.  Supported: 4 <= ws <= 128 of any parity, 0 <= ov < ws, 0 <= radius R <= 4, a
+ * frame that holds at least one window.  Per window, in integers:
+ *   1. hx = clamp(rint(u * 128), -32767, 32767) (ties to even; the product is exact), hy likewise from v: the half shift
+ *      in Q8.  A non-finite u or v: su = sv = NaN and an all-zero stats row.
+ *   2. Two patches, indices i, j = -R ... ws + R (P = ws + 2R + 1 a side).  a*[i][j] is frame a at qy = ((y0 + i) << 8)
+ *      - hy, qx = ((x0 + j) << 8) - hx, b*[i][j] frame b at + hy, + hx: iy = qy >> 8 (arithmetic), fy = qy & 255, ix, fx
+ *      likewise; taps at rows clamp(iy, 0, H-1), clamp(iy + 1, 0, H-1) and the columns alike; value = (sum wy wx p +
+ *      8192) >> 14 with weights (256 - f, f): 0 ... 1020, grey levels in Q2.
+ *   3. N = ws^2, core = 0 <= i, j < ws.  ma = (sum_core a* + N/2) / N (integer division), mb likewise; a' = a* - ma,
+ *      b' = b* - mb everywhere.
+ *   4. C0 = sum_core a'[i][j] b'[i][j].  Component x: d[i][j] = a'[i][j] b'[i][j+1] - a'[i][j+1] b'[i][j], s the same with
+ *      +; component y with [i+1][j] for [i][j+1].  S2 = sum_core s (= C(+1) + C(-1)); S(k,l) = sum_core d[i][j] d[i+k][j+l];
+ *      S00 = S(0,0); the lags of the half plane {1 <= k <= R, -R <= l <= R} and {k = 0, 1 <= l <= R} count iff
+ *      20 S(k,l) > S00; var = S00 + 2 sum_counted S(k,l); n = the number counted.  |d| < 2^21 and every sum stays below
+ *      2^63 inside the supported range.
+ *   5. In float64, every operation rounded on its own: sd = sqrt((double)var), s2 = (double)S2, c0 = (double)C0,
+ *      cp = (s2 + sd) * 0.5, cm = (s2 - sd) * 0.5.  sigma = NaN when C0 <= 0, !(cm > 0) or !(c0 c0 > cp cm); otherwise
+ *      sigma = (log cp - log cm) / (4 log c0 - 2 log cm - 2 log cp): unsigned, > 0 when finite.
+ * su_dev, sv_dev float64 [batch, n_rows, n_cols]; stats_dev (may be NULL) int64 [batch, n_rows, n_cols, 8] = C0, S2x, S00x,
+ * varx, S2y, S00y, vary, nx + 256 ny.  invalid_dev (may be NULL) uint8 [batch, n_rows, n_cols]: a non-zero byte gives NaN
+ * in both components and an all-zero stats row.  The integers are the same in every implementation of these lines; only
+ * the logarithms carry a tolerance.  TPIV_EINVAL, with nothing launched: a size outside the ranges above, a null pointer,
+ * an output that overlaps an input or another output, H or W >= 2^22 or H * W >= 2^30 (the Q8 coordinates and the flat
+ * pixel indices are 32-bit), batch * n_rows * n_cols >= 2^31.  batch == 0 succeeds and launches nothing.  Enqueues only; allocates
+ * nothing and needs no work memory. */
+int tpiv_uncertainty(const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H, int W, int ws, int ov,
+                     const double* u_dev, const double* v_dev, const uint8_t* invalid_dev, int radius, double* su_dev,
+                     double* sv_dev, long long* stats_dev, void* stream);
+
+/* Uncertainty of a plan: kind 0 = off (every plan's default: tpiv_plan_run enqueues exactly what it does without this
+ * call), 1 = tpiv_uncertainty with the given radius behind the last pass -- behind its outlier and mask steps and behind the
+ * closing event of its timing slot (tpiv_plan_get_timing keeps its meaning) -- on the frames the run was given and on the
+ * u, v, invalid it returns: cells the run returns as invalid (median-flagged ones included) are NaN, and so are the cells
+ * of the last pass's mask grid.  Allocates, at this call, su and sv for max_batch pairs at the last pass's geometry.  A
+ * last pass with ws > 128 or ws < 4, or a radius outside 0..4: TPIV_EINVAL. */
+int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius);
+
+/* Device pointers to su, sv of the last run, [batch, n_rows, n_cols] of the last pass.  TPIV_EINVAL when it is off. */
+int tpiv_plan_uncertainty(const tpiv_plan* plan, double** su_dev, double** sv_dev);
+
 /* ---- post-validation (B:884-892) ------------------------------------------------- */
 
 /* Device part of the reference's per-pair host post-processing, for a whole batch:

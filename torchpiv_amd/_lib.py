@@ -81,6 +81,9 @@ SIGNATURES = {
     "tpiv_mask_fields": (C.c_int, [_f64p, _f64p, _u8p, _u8p, _u8p, _int, _int, _int, _int, _vp]),
     "tpiv_plan_set_mask": (C.c_int, [C.c_void_p, _u8p, _dbl, _vp]),
     "tpiv_plan_pass_mask": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p)]),
+    "tpiv_uncertainty": (C.c_int, [_u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _u8p, _int, _f64p, _f64p, _vp, _vp]),
+    "tpiv_plan_set_uncertainty": (C.c_int, [C.c_void_p, _int, _int]),
+    "tpiv_plan_uncertainty": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "tpiv_postval": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _u8p, _vp, _vp]),
     "tpiv_postval_compact": (C.c_int, [_f64p, _f64p, _u8p, _vp, _int, _int, _int, _vp, _vp, _f64p, _vp, _vp]),
     "tpiv_finish_fields": (C.c_int, [_f64p, _f64p, _int, _int, _int, C.c_double, C.c_double, _f64p, _f64p, _vp]),

@@ -372,7 +372,7 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 depth=None, mask=None, dewarp=None, equalize=None, prefilter=None) -> None:
+                 depth=None, mask=None, dewarp=None, uncertainty=None, equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -418,6 +418,12 @@ class OfflinePIV:
         # frame.  A background image given by the caller, the mask and the delivered x, y are in rectified coordinates;
         # background="min" is the minimum of the rectified frames.  Pixels whose source lies outside the camera frame carry
         # `fill`; dewarp_outside() gives their image, fit to be passed as mask=.
+        # uncertainty (extension): None, "cs" or a dict with any of kind ("cs") and radius (0..4) -- the correlation-statistics
+        # estimate (Wieneke 2015) of every delivered vector's random error, 1 sigma, on the device behind the last pass
+        # (engine.uncertainty_arg, tpiv_plan_set_uncertainty).  When set, __call__ yields (x, y, u, v, su, sv) and batched()
+        # (i, x, y, u, v, su, sv): su, sv are flipped and scaled like u, v (no sign change), and NaN where the last pass's
+        # vector was invalid (the delivered value is an interpolation), in mask-excluded cells and where the correlation
+        # peak gives no estimate.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
@@ -428,7 +434,7 @@ class OfflinePIV:
         self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
                          engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize),
-                         engine.mask_arg(mask), engine.dewarp_arg(dewarp))
+                         engine.mask_arg(mask), engine.dewarp_arg(dewarp), engine.uncertainty_arg(uncertainty))
         if not self:
             return
         if self._mask is not None:
@@ -441,10 +447,11 @@ class OfflinePIV:
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                     multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
-                    equalize=None, mask=None, dewarp=None):
+                    equalize=None, mask=None, dewarp=None, uncertainty=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
-        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's, dewarp: engine.dewarp_arg's) and the state that the methods build up, empty."""
+        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's, dewarp: engine.dewarp_arg's,
+        uncertainty: engine.uncertainty_arg's) and the state that the methods build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
         self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
         self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
@@ -457,6 +464,7 @@ class OfflinePIV:
         self._equalize = equalize
         self._mask = mask
         self._dewarp = dewarp
+        self._uncertainty = uncertainty
         self._dw_map = None              # dewarp=: the Q8 map on the device, int32 [H, W, 2], once a run needs it
         self._dw_frames = None           # dewarp=: the rectified frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
         self._mask_dev = None            # mask=: the image on the device, uint8 [H, W], once a run needs it
@@ -496,7 +504,7 @@ class OfflinePIV:
         return engine.Plan(H, W, int(self._wind_size), int(self._overlap), n_pass=max(1, int(self._iter)),
                            mode=self._mode, pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio,
                            val_win=self._val_win, device=self._device, precision=self._precision, outlier=self._outlier,
-                           mask=self._mask)
+                           mask=self._mask, uncertainty=self._uncertainty)
 
     def _get_plan(self, H, W, max_batch=1):
         if (self._plan is None or (self._plan.H, self._plan.W) != (H, W)
@@ -817,7 +825,7 @@ class OfflinePIV:
 
     RING_CAP = 256           # ring / hole cells per pair (batch average) that ride on the first, asynchronous copy
 
-    def _post_submit(self, u, v, inv, want_raw=False, plan=None):
+    def _post_submit(self, u, v, inv, want_raw=False, plan=None, sigma=True):
         """Device half of B:884-898 for a batch of final fields (u, v float64 [n, nr, nc], modified in
         place; inv uint8): tpiv_postval (NaN-out, border interpolation, census, triangulation-free fills),
         tpiv_postval_compact (the ring points with their values and the hole cells of the pairs that need Qhull, cut out
@@ -826,7 +834,8 @@ class OfflinePIV:
         the whole batch: bit-identical, and the host is spared five passes over every field), then ASYNCHRONOUS copies of
         the census, the packed lists and the finished fields into pinned memory, on a stream of their own.  Nothing here
         waits for the GPU: the caller may enqueue the next batch before it collects this one.  want_raw: also the raw
-        (unflipped, unscaled) fields, for callers of the function-level API."""
+        (unflipped, unscaled) fields, for callers of the function-level API.  sigma=False: leave the uncertainty= fields out
+        (the one-pair path fetches and finishes them itself)."""
         cls, counts = engine.postval(u, v, inv)
         offsets, ring_rc, ring_uv, hole_rc = engine.postval_compact(u, v, cls, counts)
         fu, fv = engine.finish_fields(u, v, self._scale, self._dt)
@@ -838,6 +847,11 @@ class OfflinePIV:
             src["u"], src["v"] = u, v
         if plan is not None and plan.outlier is not None:
             src["flagged"] = plan.outlier_flag_counts(n)       # rides on the same asynchronous copy as the census
+        if sigma and plan is not None and plan.uncertainty_par is not None:
+            # uncertainty=: copied out of the plan's buffers now (the next launch overwrites them while this one's results
+            # are still in flight), flipped and scaled like the fields; sigma is unsigned, so the sign of fv is taken back
+            su, sv = engine.finish_fields(*plan.uncertainty(n), self._scale, self._dt)
+            src["fsu"], src["fsv"] = su, sv.neg_()
         host = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in src.items()}
         # the copies go down on a stream of their own, behind an event of the compute stream: the next batch's passes
         # start while they run.  (The small kernels above stay on the compute stream: on the side stream too they made
@@ -964,8 +978,8 @@ class OfflinePIV:
         uk, vk = state["host"]["u"].numpy(), state["host"]["v"].numpy()
         return [(uk[i], vk[i]) if state["keep_final"][i] else None for i in range(uk.shape[0])]
 
-    def _post_validate_batch(self, u, v, inv, plan=None):
-        return self._post_collect(self._post_submit(u, v, inv, want_raw=True, plan=plan))
+    def _post_validate_batch(self, u, v, inv, plan=None, sigma=True):
+        return self._post_collect(self._post_submit(u, v, inv, want_raw=True, plan=plan, sigma=sigma))
 
     def _post_pipeline(self, x, y, depth=1, plan=None):
         """The host side of batched() as a pipeline: push(meta, ticket) after every launch returns the finished
@@ -1027,13 +1041,24 @@ class OfflinePIV:
         xs, ys = x * self._scale, y * self._scale
         xs.flags.writeable = False
         ys.flags.writeable = False
+        if "fsu" in state["host"]:
+            # uncertainty=: beside the fields, NaN in the excluded cells too (the kernel wrote them; no fill value)
+            if self.device_out:
+                SU, SV = state["dev"]["fsu"], state["dev"]["fsv"]
+            else:
+                SU, SV = np.array(state["host"]["fsu"].numpy()), np.array(state["host"]["fsv"].numpy())
+            return [(xs, ys, U[k], V[k], SU[k], SV[k]) if keep[k] else None for k in range(keep.size)]
         return [(xs, ys, U[k], V[k]) if keep[k] else None for k in range(keep.size)]
 
-    def _finish(self, uv, x, y, plan=None):
+    def _finish(self, uv, x, y, plan=None, sigma=None):
         """Flip and unit scaling of B:894-898 (numpy, the reference's own expressions); then, with mask=, the fill value
-        into the excluded cells of the plan's last pass."""
+        into the excluded cells of the plan's last pass.  sigma: the raw (su, sv) of uncertainty=, which take the flip and
+        the scaling, no sign and no fill, and follow u, v in the tuple."""
         if uv is None:
             return None
+        if sigma is not None:
+            su, sv = (np.flip(s_, axis=0) * self._scale / self._dt * 1000 for s_ in sigma)
+            return self._finish(uv, x, y, plan=plan) + (su, sv)
         u, v = uv
         u = np.flip(u, axis=0)
         v = -np.flip(v, axis=0)
@@ -1072,16 +1097,20 @@ class OfflinePIV:
         a, b = self._filtered(a, bg_a), self._filtered(b, bg_b)
         plan = self._single_plan(shape)
         u, v, inv = plan.run(self._finished(a, True), self._finished(b, True))
+        sigma = None if self._uncertainty is None else plan.uncertainty(1)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates(shape, w, o)
-        return self._finish(self._post_validate_batch(u, v, inv, plan=plan)[0], x, y, plan=plan)
+        uv = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)[0]     # (sigma: fetched above, finished on the host)
+        if sigma is not None and uv is not None:
+            sigma = tuple(s_[0].cpu().numpy() for s_ in sigma)
+        return self._finish(uv, x, y, plan=plan, sigma=sigma)
 
     def __call__(self) -> Generator:
         if int(self.call_batch) > 1 and len(self._dataset) > 1:
             # the reference hands out FRESH x, y per pair (B:899-900: x * scale makes a new array), which a caller may
             # write into; batched() shares one read-only pair of coordinate arrays per batch, so copy here
-            for _, x, y, u, v in self.batched(int(self.call_batch)):
-                yield x.copy(), y.copy(), u, v
+            for out in self.batched(int(self.call_batch)):      # (i, x, y, u, v), with uncertainty= also su, sv
+                yield (out[1].copy(), out[2].copy()) + out[3:]
             return
         end_time = time()
         for i in range(len(self._dataset)):
@@ -1227,7 +1256,7 @@ class ResidentPIV(OfflinePIV):
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
                  validation_window: int = 3, background=None, outlier=None, depth=None, mask=None,
-                 dewarp=None, equalize=None, prefilter=None) -> None:
+                 dewarp=None, uncertainty=None, equalize=None, prefilter=None) -> None:
         # dewarp (see OfflinePIV): every launch rectifies its pairs into a reused buffer, addressed by their offsets in the
         # caller's stacks (nothing is gathered first, and the caller's frames are never written)
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
@@ -1252,6 +1281,7 @@ class ResidentPIV(OfflinePIV):
         mask = engine.mask_arg(mask)
         if mask is not None and tuple(mask["image"].shape) != tuple(frames_a.shape[1:]):
             raise ValueError(f"mask of shape {tuple(mask['image'].shape)} for frames of shape {tuple(frames_a.shape[1:])}")
+        uncertainty = engine.uncertainty_arg(uncertainty)
         dewarp = engine.dewarp_arg(dewarp)
         if dewarp is not None and "map" in dewarp and tuple(dewarp["map"][0].shape) != tuple(frames_a.shape[1:]):
             raise ValueError(f"dewarp map of shape {tuple(dewarp['map'][0].shape)} for frames of shape "
@@ -1259,7 +1289,8 @@ class ResidentPIV(OfflinePIV):
         device = _require_gpu(frames_a.device)
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
-                         validation_window, bg_arg, outlier, prefilter, depth, equalize, mask, dewarp)
+                         validation_window, bg_arg, outlier, prefilter, depth, equalize, mask, dewarp,
+                         uncertainty)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):
@@ -1371,8 +1402,8 @@ class ResidentPIV(OfflinePIV):
         yield from emit(pipe.flush())
 
     def __call__(self) -> Generator:
-        for _, x, y, u, v in self.batched(1):
-            yield x.copy(), y.copy(), u, v
+        for out in self.batched(1):
+            yield (out[1].copy(), out[2].copy()) + out[3:]
 
 
 class OnlinePIV:

@@ -242,6 +242,9 @@ struct tpiv_plan {
     // geometric mask (tpiv_plan_set_mask); off: nothing is enqueued for it.  mgrid: per pass [N_p], 1 = excluded cell
     bool mask_on = false;
     std::vector<uint8_t*> mgrid;
+    // correlation-statistics uncertainty behind the last pass (tpiv_plan_set_uncertainty); off: nothing is enqueued for it
+    int unc_kind = 0, unc_radius = 3;
+    double *unc_su = nullptr, *unc_sv = nullptr;     // [max_batch, N_last] of the last run
     std::vector<void*> allocs;
     // optional per-kernel timing: events[run][2*slot + {0,1}]
     bool timing = false;
@@ -932,6 +935,104 @@ int tpiv_plan_pass_mask(const tpiv_plan* plan, int pass, uint8_t** grid) {
     return TPIV_OK;
 }
 
+static int run_uncertainty(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov, int n_rows,
+                           int n_cols, const double* u, const double* v, const uint8_t* invalid, const uint8_t* exclude,
+                           int radius, double* su, double* sv, long long* stats, hipStream_t st) {
+    tpiv::UncertaintyParams q{};
+    q.A = a;
+    q.B = b;
+    q.batch = batch;
+    q.H = H;
+    q.W = W;
+    q.ws = ws;
+    q.ov = ov;
+    q.n_rows = n_rows;
+    q.n_cols = n_cols;
+    q.u = u;
+    q.v = v;
+    q.invalid = invalid;
+    q.exclude = exclude;
+    q.radius = radius;
+    q.su = su;
+    q.sv = sv;
+    q.stats = stats;
+    hipError_t he = tpiv::launch_uncertainty(q, st);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_uncertainty");
+}
+
+// the sizes tpiv_uncertainty covers: its integer bounds hold for ws <= 128 and radius <= 4
+static int check_uncertainty(int H, int W, int ws, int ov, int radius) {
+    if (ws < tpiv::UNCERTAINTY_MIN_WS || ws > tpiv::UNCERTAINTY_MAX_WS)
+        return fail(TPIV_EINVAL, "uncertainty: window size must be in 4..128 (got " + std::to_string(ws) + ")");
+    if (ov < 0 || ov >= ws) return fail(TPIV_EINVAL, "uncertainty: overlap must be in 0..ws-1");
+    if (radius < 0 || radius > tpiv::UNCERTAINTY_MAX_RADIUS)
+        return fail(TPIV_EINVAL, "uncertainty: radius must be in 0..4 (got " + std::to_string(radius) + ")");
+    if (H < ws || W < ws) return fail(TPIV_EINVAL, "uncertainty: the frame holds no window");
+    if (H >= (1 << 22) || W >= (1 << 22) || (long long)H * W >= (1LL << 30))
+        return fail(TPIV_EINVAL, "uncertainty: frame too large");      // Q8 coordinates and flat indices in 32 bits
+    return TPIV_OK;
+}
+
+int tpiv_uncertainty(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov, const double* u,
+                     const double* v, const uint8_t* invalid, int radius, double* su, double* sv, long long* stats,
+                     void* stream) {
+    if (batch < 0) return fail(TPIV_EINVAL, "tpiv_uncertainty: negative batch");
+    if (int rc = check_uncertainty(H, W, ws, ov, radius)) return rc;
+    if (batch == 0) return TPIV_OK;
+    if (!a || !b || !u || !v || !su || !sv) return fail(TPIV_EINVAL, "tpiv_uncertainty: null pointer");
+    int nr = 0, nc = 0;
+    field_shape(H, W, ws, ov, &nr, &nc);
+    if ((long long)batch * nr * nc >= (1LL << 31)) return fail(TPIV_EINVAL, "tpiv_uncertainty: batch of fields too large");
+    const size_t cells = (size_t)batch * nr * nc, pixels = (size_t)batch * H * W;
+    struct Span { const char* p; size_t n; };
+    const Span in[5] = {{(const char*)a, pixels}, {(const char*)b, pixels}, {(const char*)u, cells * 8},
+                        {(const char*)v, cells * 8}, {(const char*)invalid, cells}};
+    const Span out[3] = {{(const char*)su, cells * 8}, {(const char*)sv, cells * 8}, {(const char*)stats, cells * 64}};
+    auto overlap = [](const Span& x, const Span& y) { return x.p && y.p && x.p < y.p + y.n && y.p < x.p + x.n; };
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 5; ++j)
+            if (overlap(out[i], in[j])) return fail(TPIV_EINVAL, "tpiv_uncertainty: an output overlaps an input");
+        for (int j = i + 1; j < 3; ++j)
+            if (overlap(out[i], out[j])) return fail(TPIV_EINVAL, "tpiv_uncertainty: two outputs overlap");
+    }
+    return run_uncertainty(a, b, batch, H, W, ws, ov, nr, nc, u, v, invalid, nullptr, radius, su, sv, stats,
+                           (hipStream_t)stream);
+}
+
+int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (kind != 0 && kind != 1)
+        return fail(TPIV_EINVAL, "tpiv_plan_set_uncertainty: kind must be 0 (off) or 1 (correlation statistics)");
+    if (kind == 0) {
+        plan->unc_kind = 0;
+        return TPIV_OK;
+    }
+    const PassGeo& g = plan->geo[plan->n_pass - 1];
+    if (int rc = check_uncertainty(plan->H, plan->W, g.ws, g.ov, radius)) return rc;
+    if (!plan->unc_su) {                             // first time on: the two fields (kept until the plan is destroyed)
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+        const size_t n = (size_t)g.n_rows * g.n_cols * plan->max_batch;
+        double *su = nullptr, *sv = nullptr;
+        if (int rc = plan->alloc(&su, n)) return rc;
+        if (int rc = plan->alloc(&sv, n)) return rc;
+        plan->unc_su = su;
+        plan->unc_sv = sv;
+    }
+    plan->unc_kind = kind;
+    plan->unc_radius = radius;
+    return TPIV_OK;
+}
+
+int tpiv_plan_uncertainty(const tpiv_plan* plan, double** su, double** sv) {
+    if (!plan || !su || !sv) return fail(TPIV_EINVAL, "bad plan / null pointer");
+    if (!plan->unc_kind) return fail(TPIV_EINVAL, "the plan estimates no uncertainty (tpiv_plan_set_uncertainty)");
+    *su = plan->unc_su;
+    *sv = plan->unc_sv;
+    return TPIV_OK;
+}
+
 int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch, double* u, double* v,
                   uint8_t* invalid, void* stream) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
@@ -1008,6 +1109,15 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
                 if (he != hipSuccess) return hip_fail(he, "launch_mask_fields");
             }
         }
+    }
+    if (plan->unc_kind) {    // behind the last pass, its outlier and mask steps and the closing event of its timing slot
+        const PassGeo& g = plan->geo[last];
+        const double* uu = u;
+        const double* vv = v;
+        if (int rc = run_uncertainty(a, b, batch, plan->H, plan->W, g.ws, g.ov, g.n_rows, g.n_cols, uu, vv, invalid,
+                                     plan->mask_on ? plan->mgrid[last] : nullptr, plan->unc_radius, plan->unc_su,
+                                     plan->unc_sv, nullptr, st))
+            return rc;
     }
     if (plan->timing && plan->runs_recorded < 512) plan->runs_recorded++;
     return TPIV_OK;

@@ -236,6 +236,25 @@ constexpr int DEWARP_LINEAR = 0, DEWARP_CUBIC = 1, DEWARP_FRAME_CHUNK = 8;
 hipError_t launch_dewarp(const uint8_t* frames, const long long* src_off, int n, int H, int W, const int32_t* map,
                          const int16_t* table, int interp, int fill, uint8_t* out, hipStream_t stream);
 
+// correlation-statistics uncertainty (uncertainty.hip, defined in include/torchpiv_hip.h: tpiv_uncertainty): one workgroup
+// per window; the two half-shifted patches as int16 and one component's asymmetry contributions as int32 in LDS (150 KB at
+// ws = 128, R = 4), exact 64-bit integer sums, a float64 epilogue in one lane.  batch * n_rows * n_cols < 2^31.
+constexpr int UNCERTAINTY_MIN_WS = 4, UNCERTAINTY_MAX_WS = 128, UNCERTAINTY_MAX_RADIUS = 4;
+struct UncertaintyParams {
+    const uint8_t* A;        // [batch, H, W]
+    const uint8_t* B;
+    int batch, H, W, ws, ov, n_rows, n_cols;
+    const double* u;         // [batch, n_rows, n_cols], pixels from a to b
+    const double* v;
+    const uint8_t* invalid;  // optional [batch, n_rows, n_cols]: non-zero = no estimate (NaN, zero stats row)
+    const uint8_t* exclude;  // optional [n_rows, n_cols], one grid for every pair: the same (a plan's mask grid)
+    int radius;              // 0..UNCERTAINTY_MAX_RADIUS
+    double* su;              // out [batch, n_rows, n_cols]
+    double* sv;
+    long long* stats;        // optional out [batch, n_rows, n_cols, 8]
+};
+hipError_t launch_uncertainty(const UncertaintyParams& p, hipStream_t stream);
+
 hipError_t launch_xcorr(const PassParams& p, int mode, int n_cu, hipStream_t stream);
 // bytes of the tile kernels' work-queue counters (8 x one 64-byte line), and of the slow-item list header behind them
 constexpr size_t TILE_CTR_BYTES = 8 * 16 * sizeof(unsigned), TILE_SLOW_HDR_BYTES = 256;

@@ -284,6 +284,66 @@ def median_test(u, v, inv, threshold=2.0, eps=0.1, min_neighbours=3, want_median
     return (status, mu, mv) if want_medians else status
 
 
+UNCERTAINTY_DEFAULTS = {"kind": "cs", "radius": 3}
+UNCERTAINTY_MAX_RADIUS, UNCERTAINTY_WS = 4, (4, 128)
+
+
+def uncertainty_arg(uncertainty):
+    """The uncertainty= argument of Plan / OfflinePIV / ResidentPIV, checked (no GPU involved): None (no estimate), "cs"
+    (correlation statistics at UNCERTAINTY_DEFAULTS) or a dict with any of kind ("cs") and radius (an integer in 0..4, the
+    reach of the covariance sum in pixels).  Returns None or the full parameter dict; anything else raises ValueError."""
+    if uncertainty is None:
+        return None
+    if isinstance(uncertainty, str):
+        if uncertainty != "cs":
+            raise ValueError(f"uncertainty: None, 'cs' or a dict of {sorted(UNCERTAINTY_DEFAULTS)}, got {uncertainty!r}")
+        return dict(UNCERTAINTY_DEFAULTS)
+    if not isinstance(uncertainty, dict):
+        raise ValueError(f"uncertainty: None, 'cs' or a dict of {sorted(UNCERTAINTY_DEFAULTS)}, "
+                         f"got {type(uncertainty).__name__}")
+    unknown = sorted(set(uncertainty) - set(UNCERTAINTY_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"uncertainty: unknown key(s) {unknown}; known: {sorted(UNCERTAINTY_DEFAULTS)}")
+    par = dict(UNCERTAINTY_DEFAULTS, **uncertainty)
+    if par["kind"] != "cs":
+        raise ValueError(f"uncertainty: kind must be 'cs' (correlation statistics), got {par['kind']!r}")
+    R = par["radius"]
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 0 <= R <= UNCERTAINTY_MAX_RADIUS:
+        raise ValueError(f"uncertainty: radius must be an integer in 0..{UNCERTAINTY_MAX_RADIUS}, got {R!r}")
+    return {"kind": "cs", "radius": int(R)}
+
+
+def uncertainty(a, b, u, v, ws, ov, invalid=None, radius=3, want_stats=False):
+    """Correlation-statistics uncertainty (Wieneke 2015; tpiv_uncertainty) of fields u, v float64 [batch, n_rows, n_cols] (or
+    [n_rows, n_cols]) at geometry (ws, ov) on frames a, b uint8 [batch, H, W] (or [H, W]) on the GPU: the 1-sigma random
+    error of every vector in pixels, NaN where the correlation peak gives none, where u or v is not finite and where
+    invalid (uint8, optional) is non-zero.  Returns (su, sv), with want_stats also the exact integer sums int64
+    [batch, n_rows, n_cols, 8] = C0, S2x, S00x, varx, S2y, S00y, vary, nx + 256 ny.  The inputs are not written."""
+    a, b = _frames(a, b)
+    _need_cuda(u, v, invalid)
+    if u.dtype != torch.float64 or v.dtype != torch.float64 or (invalid is not None and invalid.dtype != torch.uint8):
+        raise TypeError("uncertainty: u, v float64 and invalid uint8")
+    if u.dim() == 2:
+        u, v = u[None], v[None]
+        invalid = None if invalid is None else invalid[None]
+    B, H, W = a.shape
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)):
+        raise ValueError(f"uncertainty: radius must be an integer, got {radius!r}")
+    if isinstance(ws, (int, np.integer)) and isinstance(ov, (int, np.integer)) and 0 <= ov < ws <= min(H, W):
+        nr, nc = (H - ws) // (ws - ov) + 1, (W - ws) // (ws - ov) + 1
+        if tuple(u.shape) != (B, nr, nc) or v.shape != u.shape or (invalid is not None and invalid.shape != u.shape):
+            raise ValueError(f"uncertainty: fields must be [{B}, {nr}, {nc}] for these frames, got {tuple(u.shape)}")
+    u, v = u.contiguous(), v.contiguous()
+    invalid = None if invalid is None else invalid.contiguous()
+    su, sv = torch.empty_like(u), torch.empty_like(v)
+    stats = torch.empty(*u.shape, 8, dtype=torch.int64, device=u.device) if want_stats else None
+    with torch.cuda.device(a.device):
+        check(lib.tpiv_uncertainty(a.data_ptr(), b.data_ptr(), B, H, W, int(ws), int(ov), u.data_ptr(), v.data_ptr(),
+                                   None if invalid is None else invalid.data_ptr(), int(radius), su.data_ptr(),
+                                   sv.data_ptr(), stats.data_ptr() if want_stats else None, _stream()))
+    return (su, sv, stats) if want_stats else (su, sv)
+
+
 def postval(u, v, inv):
     """Device part of the post-validation (PIVbackend.py:884-892) for a batch, IN PLACE on u, v
     (float64 [B, nr, nc]): border interpolation, ring / hole census, fills that do not depend on the
@@ -1180,7 +1240,7 @@ class Plan:
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
 
     def __init__(self, H, W, ws, ov, n_pass=1, mode="CWS", pass_scale=2.0, val_ratio=1.2,
-                 val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None):
+                 val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None, uncertainty=None):
         # outlier: None, "median" or a dict (outlier_arg): the normalized median test after every pass -- flagged vectors of
         # a pass before the last are replaced by their neighbourhood median before the predictor reads them, flagged
         # vectors of the last pass join the invalid mask (tpiv_plan_set_outlier)
@@ -1188,8 +1248,11 @@ class Plan:
         # the threshold are excluded -- zero vectors that are invalid to the predictor and to the median test, valid to the
         # post-validation (tpiv_plan_set_mask).  The plan reads the image and the threshold only: the pixel step
         # (apply_mask) and the fill value are the business of whoever owns the frames and delivers the fields.
+        # uncertainty: None, "cs" or a dict (uncertainty_arg): the correlation-statistics estimate of every returned vector's
+        # random error, behind the last pass on the frames of the run (tpiv_plan_set_uncertainty); read with uncertainty()
         self.outlier = outlier_arg(outlier)
         self.mask = mask_arg(mask)
+        self.uncertainty_par = uncertainty_arg(uncertainty)
         if self.mask is not None and tuple(self.mask["image"].shape) != (H, W):
             raise ValueError(f"mask of shape {tuple(self.mask['image'].shape)} for frames of shape {(H, W)}")
         if not torch.cuda.is_available():
@@ -1218,6 +1281,12 @@ class Plan:
             if self.mask is not None:
                 try:
                     self.set_mask(self.mask["image"], self.mask["threshold"])
+                except Exception:
+                    self.close()
+                    raise
+            if self.uncertainty_par is not None:
+                try:
+                    check(lib.tpiv_plan_set_uncertainty(self._h, 1, self.uncertainty_par["radius"]))
                 except Exception:
                     self.close()
                     raise
@@ -1355,6 +1424,26 @@ class Plan:
         if rc != 0:
             raise _lib.HipError(f"hipMemcpyAsync failed: {rc}")
         return (status & 1).sum(dim=(1, 2), dtype=torch.int32)
+
+    def uncertainty(self, batch):
+        """(su, sv) float64 [batch, n_rows, n_cols] on the device: the uncertainty of the vectors of the last run, in pixels,
+        NaN at its invalid and excluded cells.  Copies, enqueued on the current stream behind the run; no host wait.
+        ValueError for a plan without uncertainty=."""
+        psu, psv = C.c_void_p(), C.c_void_p()
+        check(lib.tpiv_plan_uncertainty(self._h, C.byref(psu), C.byref(psv)))
+        nr, nc = self.out_shape
+        if not 0 <= batch <= self.max_batch:
+            raise ValueError(f"batch {batch} exceeds the plan's max_batch {self.max_batch}")
+        su = torch.empty(batch, nr, nc, dtype=torch.float64, device=self.device)
+        sv = torch.empty_like(su)
+        hip = C.CDLL("libamdhip64.so")
+        with torch.cuda.device(self.device):
+            for dst, src in ((su, psu), (sv, psv)):
+                rc = hip.hipMemcpyAsync(C.c_void_p(dst.data_ptr()), src, C.c_size_t(batch * nr * nc * 8), 3,
+                                        C.c_void_p(_stream()))      # D2D
+                if rc != 0:
+                    raise _lib.HipError(f"hipMemcpyAsync failed: {rc}")
+        return su, sv
 
     def set_mask(self, image, threshold=MASK_DEFAULTS["threshold"]):
         """(Re)computes the plan's grids of excluded cells from a mask image (uint8 [H, W], any device; non-zero = masked)
