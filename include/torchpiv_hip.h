@@ -282,6 +282,84 @@ int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius);
 /* Device pointers to su, sv of the last run, [batch, n_rows, n_cols] of the last pass.  TPIV_EINVAL when it is off. */
 int tpiv_plan_uncertainty(const tpiv_plan* plan, double** su_dev, double** sv_dev);
 
+/* ---- iterative image deformation (extension; the reference shifts windows rigidly) ---------------- */
+
+/* OR-ed into tpiv_deform_warp's interp: every tile takes the per-pixel gather (the same bytes; measurements and tests). */
+#define TPIV_DEFORM_GATHER 0x100
+
+/* Image deformation behind the last pass (Scarano, Meas. Sci. Technol. 13 (2002) R1; predictor smoothing after Schrijer &
+ * Scarano, Exp. Fluids 45 (2008) 927): the field u, v of the last pass, geometry (ws, ov), st = ws - ov, grid n_rows x n_cols
+ * of tpiv_field_shape, window (r, c) at row r st and column c st, becomes a dense half shift; frame a is resampled at -h and
+ * frame b at +h into uint8 frames; tpiv_pass1 measures the residual on them; the sum is the new field.  u runs along x
+ * (columns), v along y (rows), from a to b.  Everything is integer except the last addition, so every implementation of
+ * these lines gives the same bytes.
+ *   Nodes (tpiv_deform_nodes): int16 [batch, n_rows, n_cols, 2], x first, the half shift in Q8.
+ *     A cell is VALID when its invalid byte is 0 and u and v are both finite: q = clamp(rint(w * 128), -16383, 16383) per
+ *     component w (the product is exact, ties to even).  Any other cell: s, k = the sum and the count of q over those of its
+ *     up to 8 neighbours that lie in the grid and are valid; q = floor((2 s + k) / (2 k)) per component, 0 when k == 0 (the
+ *     neighbours are read as a snapshot: substituted values never feed a substitution).  smooth != 0: afterwards the 3 x 3
+ *     binomial [[1,2,1],[2,4,2],[1,2,1]] over the substituted values with edge replicate, out of place, q = (sum + 8) >> 4
+ *     (arithmetic shift).
+ *   Dense half shift of pixel (y, x).  Per axis, shown for rows (n = n_rows): n == 1: r = 0, wy = 0; otherwise
+ *     r = clamp(floor((2 y - (ws - 1)) / (2 st)), 0, n - 2), t = clamp(2 y - (ws - 1) - 2 r st, 0, 2 st),
+ *     wy = (256 t + st) / (2 st) (integer division, 0 .. 256): bilinear between the window centres r st + (ws - 1) / 2,
+ *     constant outside their hull.  h = ((256 - wy) ((256 - wx) n00 + wx n01) + wy ((256 - wx) n10 + wx n11) + 32768) >> 16
+ *     per component (arithmetic shift; node indices r + 1, c + 1 clamped to the grid; |sum| < 2^31 by the node clamp).
+ *   Warp (tpiv_deform_warp): wa[y][x] = frame a sampled at qx = clamp((x << 8) - hx, 0, (W - 1) << 8), qy = clamp((y << 8) -
+ *     hy, 0, (H - 1) << 8); wb[y][x] = frame b at + hx, + hy.  Sampling is tpiv_dewarp's TPIV_DEWARP_LINEAR or
+ *     TPIV_DEWARP_CUBIC -- the same Q8 weights, the same Q10 table int16 [256, 4], the same rounding and clamp, tap indices
+ *     clamped to the frame -- without its outside case: there is no fill.  Out of place: uint8 [batch, H, W] each.
+ *   Combine (tpiv_deform_combine): u = (double)qx * (1.0 / 128) + du (the product is exact: one rounding), v likewise from
+ *     qy and dv, invalid = dval, where du, dv, dval are tpiv_pass1's outputs on (wa, wb) at (ws, ov).  2 h / 256 at a window
+ *     centre is the node itself: the smoothed, quantised predictor is the shift that was applied, so smoothing and
+ *     quantisation cost no accuracy.  The reference's `du > u0` fix-up of the shifted passes (B:236-242) is NOT
+ *     reproduced: the residual is added as measured.
+ * The three entries enqueue only and allocate nothing; batch == 0 succeeds and launches nothing.  TPIV_EINVAL, with nothing
+ * launched: a null pointer (table_dev may be NULL for TPIV_DEWARP_LINEAR, counter_dev always), n_rows or n_cols < 1, ws
+ * outside 2..256, ov outside 0..ws-1, a frame that holds no window, H or W >= 2^22 or H * W >= 2^30 (Q8 coordinates and flat
+ * pixel indices are 32-bit), batch or (H + 31) / 32 above 65535, batch * n_rows * n_cols >= 2^31, an unknown interp, nodes
+ * that are not 4-byte aligned, an output that overlaps an input or another output.
+ * counter_dev (optional): int32 [2] on the device, += the number of 64 x 32 pixel tiles whose source footprints were
+ * sampled from LDS patches, and of those that took the per-pixel gather because a footprint did not fit (a predictor
+ * discontinuity, a huge gradient); both forms give the same bytes. */
+int tpiv_deform_nodes(const double* u_dev, const double* v_dev, const uint8_t* invalid_dev, int batch, int n_rows,
+                      int n_cols, int smooth, int16_t* nodes_dev, void* stream);
+int tpiv_deform_warp(const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H, int W, int ws, int ov,
+                     const int16_t* nodes_dev, const int16_t* table_dev, int interp, uint8_t* wa_dev, uint8_t* wb_dev,
+                     int32_t* counter_dev, void* stream);
+int tpiv_deform_combine(const int16_t* nodes_dev, const double* du_dev, const double* dv_dev, const uint8_t* dval_dev,
+                        int batch, int n_rows, int n_cols, double* u_dev, double* v_dev, uint8_t* invalid_dev, void* stream);
+
+/* Deformation of a plan: iterations 0 = off (every plan's default: tpiv_plan_run enqueues exactly what it does without this
+ * call), 1..8 = that many rounds behind the last pass -- behind its mask and outlier steps and the closing event of its
+ * timing slot (tpiv_plan_get_timing keeps its meaning).  Round k = 1..n: tpiv_deform_nodes on the current u, v, invalid (what
+ * the last pass, or round k - 1, left in the caller's fields), tpiv_deform_warp of the run's frames, the first pass
+ * (tpiv_pass1 at the last pass's geometry with the plan's precision, val_ratio and val_win) on the warped frames,
+ * tpiv_deform_combine into u, v, invalid.  Then, as behind a last pass:
+ *   with tpiv_plan_set_mask: excluded cells read u = v = +0.0 and are valid, so they pull the warp to zero at a wall;
+ *   with tpiv_plan_set_outlier: rounds before the last take the test's "pass before the last" form (a flagged cell gets the
+ *     medians, out of place; its mask byte stays), the last round the "last pass" form (invalid |= flag, u and v untouched);
+ *     the status map of the last pass is then that of the last round's test.  With both, the mask goes in front of the test
+ *     with invalid = 1 and behind it with invalid = 0 and the status map, in every round.
+ * tpiv_plan_set_uncertainty runs behind the rounds, on the original frames and the final fields.  The residual pass records
+ * nothing in the timing slots and leaves tpiv_plan_exact_fallbacks alone (it keeps meaning pass 1).  interp:
+ * TPIV_DEWARP_LINEAR or TPIV_DEWARP_CUBIC; table_dev: the Q10 table (copied into the plan at this call; may be NULL for
+ * linear).  Allocates, at the first call with iterations > 0: the nodes, wa and wb for max_batch pairs, du, dv, dval, the
+ * spare fields of the out-of-place median step, the table, and a larger pass-1 work buffer if the last geometry needs one.
+ * TPIV_EINVAL: iterations outside 0..8, an unknown interp, a missing cubic table, a last-pass geometry tpiv_pass1 refuses, H
+ * or W >= 2^22, H * W >= 2^30. */
+int tpiv_plan_set_deform(tpiv_plan* plan, int iterations, int interp, int smooth, const int16_t* table_dev);
+
+/* Device pointers to what the last round of the last run left: nodes int16 [batch, n_rows, n_cols, 2], wa, wb uint8
+ * [batch, H, W], du, dv float64 and dval uint8 [batch, n_rows, n_cols].  Any pointer argument may be NULL.  TPIV_EINVAL when
+ * the deformation is off. */
+int tpiv_plan_deform_stage(const tpiv_plan* plan, int16_t** nodes_dev, uint8_t** wa_dev, uint8_t** wb_dev, double** du_dev,
+                           double** dv_dev, uint8_t** dval_dev);
+
+/* Milliseconds all rounds of the last run took together (an event pair around them on the run's stream, recorded in every
+ * run of a deforming plan).  Waits for the closing event.  TPIV_EINVAL when the deformation is off or before the first run. */
+int tpiv_plan_deform_ms(tpiv_plan* plan, double* ms);
+
 /* ---- post-validation (B:884-892) ------------------------------------------------- */
 
 /* Device part of the reference's per-pair host post-processing, for a whole batch:

@@ -22,6 +22,7 @@ PREFILTER_NONE, PREFILTER_MIN, PREFILTER_MEAN = 0, 1, 2
 PREFILTERS = {None: PREFILTER_NONE, "min": PREFILTER_MIN, "mean": PREFILTER_MEAN}    # tpiv_prefilter's kinds
 DEWARP_LINEAR, DEWARP_CUBIC = 0, 1
 DEWARP_INTERPS = {"linear": DEWARP_LINEAR, "cubic": DEWARP_CUBIC}                    # tpiv_dewarp's interpolations
+DEFORM_GATHER = 0x100                            # OR-ed into tpiv_deform_warp's interp: the gather form everywhere
 ABI_VERSION = 2
 
 
@@ -84,6 +85,12 @@ SIGNATURES = {
     "tpiv_uncertainty": (C.c_int, [_u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _u8p, _int, _f64p, _f64p, _vp, _vp]),
     "tpiv_plan_set_uncertainty": (C.c_int, [C.c_void_p, _int, _int]),
     "tpiv_plan_uncertainty": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "tpiv_deform_nodes": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _int, _vp, _vp]),
+    "tpiv_deform_warp": (C.c_int, [_u8p, _u8p, _int, _int, _int, _int, _int, _vp, _vp, _int, _u8p, _u8p, _vp, _vp]),
+    "tpiv_deform_combine": (C.c_int, [_vp, _f64p, _f64p, _u8p, _int, _int, _int, _f64p, _f64p, _u8p, _vp]),
+    "tpiv_plan_set_deform": (C.c_int, [C.c_void_p, _int, _int, _int, _vp]),
+    "tpiv_plan_deform_stage": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
+    "tpiv_plan_deform_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "tpiv_postval": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _u8p, _vp, _vp]),
     "tpiv_postval_compact": (C.c_int, [_f64p, _f64p, _u8p, _vp, _int, _int, _int, _vp, _vp, _f64p, _vp, _vp]),
     "tpiv_finish_fields": (C.c_int, [_f64p, _f64p, _int, _int, _int, C.c_double, C.c_double, _f64p, _f64p, _vp]),

@@ -372,7 +372,7 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 depth=None, mask=None, dewarp=None, uncertainty=None, equalize=None, prefilter=None) -> None:
+                 depth=None, mask=None, dewarp=None, uncertainty=None, deform=None, equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -424,6 +424,11 @@ class OfflinePIV:
         # (i, x, y, u, v, su, sv): su, sv are flipped and scaled like u, v (no sign change), and NaN where the last pass's
         # vector was invalid (the delivered value is an interpolation), in mask-excluded cells and where the correlation
         # peak gives no estimate.
+        # deform (extension): None, an integer 1..8 or a dict with any of iterations, interp ("cubic" / "linear") and smooth
+        # -- that many rounds of iterative image deformation behind the last pass (engine.deform_arg, tpiv_plan_set_deform):
+        # both frames are warped by the dense field of the last pass, the first pass measures the residual on the warped
+        # frames and the sum is the new field.  For flows with gradients inside a window.  The tuples delivered are the
+        # same; only the values differ.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
@@ -434,7 +439,8 @@ class OfflinePIV:
         self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
                          engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize),
-                         engine.mask_arg(mask), engine.dewarp_arg(dewarp), engine.uncertainty_arg(uncertainty))
+                         engine.mask_arg(mask), engine.dewarp_arg(dewarp), engine.uncertainty_arg(uncertainty),
+                         engine.deform_arg(deform))
         if not self:
             return
         if self._mask is not None:
@@ -447,7 +453,7 @@ class OfflinePIV:
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                     multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
-                    equalize=None, mask=None, dewarp=None, uncertainty=None):
+                    equalize=None, mask=None, dewarp=None, uncertainty=None, deform=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
         engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's, dewarp: engine.dewarp_arg's,
@@ -465,6 +471,7 @@ class OfflinePIV:
         self._mask = mask
         self._dewarp = dewarp
         self._uncertainty = uncertainty
+        self._deform = deform            # deform=: engine.deform_arg's, handed to every plan
         self._dw_map = None              # dewarp=: the Q8 map on the device, int32 [H, W, 2], once a run needs it
         self._dw_frames = None           # dewarp=: the rectified frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
         self._mask_dev = None            # mask=: the image on the device, uint8 [H, W], once a run needs it
@@ -504,7 +511,7 @@ class OfflinePIV:
         return engine.Plan(H, W, int(self._wind_size), int(self._overlap), n_pass=max(1, int(self._iter)),
                            mode=self._mode, pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio,
                            val_win=self._val_win, device=self._device, precision=self._precision, outlier=self._outlier,
-                           mask=self._mask, uncertainty=self._uncertainty)
+                           mask=self._mask, uncertainty=self._uncertainty, deform=self._deform)
 
     def _get_plan(self, H, W, max_batch=1):
         if (self._plan is None or (self._plan.H, self._plan.W) != (H, W)
@@ -1256,7 +1263,7 @@ class ResidentPIV(OfflinePIV):
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
                  validation_window: int = 3, background=None, outlier=None, depth=None, mask=None,
-                 dewarp=None, uncertainty=None, equalize=None, prefilter=None) -> None:
+                 dewarp=None, uncertainty=None, deform=None, equalize=None, prefilter=None) -> None:
         # dewarp (see OfflinePIV): every launch rectifies its pairs into a reused buffer, addressed by their offsets in the
         # caller's stacks (nothing is gathered first, and the caller's frames are never written)
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
@@ -1282,6 +1289,7 @@ class ResidentPIV(OfflinePIV):
         if mask is not None and tuple(mask["image"].shape) != tuple(frames_a.shape[1:]):
             raise ValueError(f"mask of shape {tuple(mask['image'].shape)} for frames of shape {tuple(frames_a.shape[1:])}")
         uncertainty = engine.uncertainty_arg(uncertainty)
+        deform = engine.deform_arg(deform)
         dewarp = engine.dewarp_arg(dewarp)
         if dewarp is not None and "map" in dewarp and tuple(dewarp["map"][0].shape) != tuple(frames_a.shape[1:]):
             raise ValueError(f"dewarp map of shape {tuple(dewarp['map'][0].shape)} for frames of shape "
@@ -1290,7 +1298,7 @@ class ResidentPIV(OfflinePIV):
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
                          validation_window, bg_arg, outlier, prefilter, depth, equalize, mask, dewarp,
-                         uncertainty)
+                         uncertainty, deform)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):

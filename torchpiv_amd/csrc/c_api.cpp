@@ -245,6 +245,15 @@ struct tpiv_plan {
     // correlation-statistics uncertainty behind the last pass (tpiv_plan_set_uncertainty); off: nothing is enqueued for it
     int unc_kind = 0, unc_radius = 3;
     double *unc_su = nullptr, *unc_sv = nullptr;     // [max_batch, N_last] of the last run
+    // image deformation behind the last pass (tpiv_plan_set_deform); off: nothing is enqueued for it
+    int def_iters = 0, def_interp = 0, def_smooth = 1;
+    int16_t *def_nodes = nullptr, *def_table = nullptr;      // [max_batch, N_last, 2]; the plan's copy of the Q10 table
+    uint8_t *def_wa = nullptr, *def_wb = nullptr;            // [max_batch, H, W]
+    double *def_du = nullptr, *def_dv = nullptr;             // the residual pass, [max_batch, N_last]
+    uint8_t* def_dval = nullptr;
+    double *def_su = nullptr, *def_sv = nullptr;             // a round before the last combines here when the median test is on
+    hipEvent_t def_ev[2] = {nullptr, nullptr};               // around the rounds of a run
+    bool def_ran = false;
     std::vector<void*> allocs;
     // optional per-kernel timing: events[run][2*slot + {0,1}]
     bool timing = false;
@@ -255,6 +264,8 @@ struct tpiv_plan {
         for (void* p : allocs) (void)hipFree(p);
         for (auto& r : events)
             for (hipEvent_t e : r) (void)hipEventDestroy(e);
+        for (hipEvent_t e : def_ev)
+            if (e) (void)hipEventDestroy(e);
     }
     int n_slots() const { return 2 * n_pass - 1; }
     // TPIV_PREC_EXACT: three more events per run inside slot 0 (behind the locating pass, the refinement, the float64 list pass)
@@ -1033,6 +1044,248 @@ int tpiv_plan_uncertainty(const tpiv_plan* plan, double** su, double** sv) {
     return TPIV_OK;
 }
 
+// ---- iterative image deformation (deform.hip) ---------------------------------------------------------------------
+
+namespace {
+struct DSpan { const void* p; size_t n; };
+bool dspans_overlap(const DSpan& x, const DSpan& y) {
+    const char *a = (const char*)x.p, *b = (const char*)y.p;
+    return a && b && x.n && y.n && a < b + y.n && b < a + x.n;
+}
+// no output may overlap an input or another output
+bool deform_aliased(const DSpan* in, int n_in, const DSpan* out, int n_out) {
+    for (int i = 0; i < n_out; ++i) {
+        for (int j = 0; j < n_in; ++j)
+            if (dspans_overlap(out[i], in[j])) return true;
+        for (int j = i + 1; j < n_out; ++j)
+            if (dspans_overlap(out[i], out[j])) return true;
+    }
+    return false;
+}
+int check_deform_grid(const char* who, int batch, int n_rows, int n_cols) {
+    if (batch < 0) return fail(TPIV_EINVAL, std::string(who) + ": negative batch");
+    if (n_rows < 1 || n_cols < 1) return fail(TPIV_EINVAL, std::string(who) + ": empty grid");
+    if (batch > 65535 || (n_rows + 15) / 16 > 65535) return fail(TPIV_EINVAL, std::string(who) + ": batch or grid too large");
+    if ((long long)batch * n_rows * n_cols >= (1LL << 31)) return fail(TPIV_EINVAL, std::string(who) + ": batch of fields too large");
+    return TPIV_OK;
+}
+// the frames and geometries tpiv_deform_warp covers
+int check_deform_frame(int H, int W, int ws, int ov) {
+    if (ws < 2 || ws > 256) return fail(TPIV_EINVAL, "deform: window size must be in 2..256 (got " + std::to_string(ws) + ")");
+    if (ov < 0 || ov >= ws) return fail(TPIV_EINVAL, "deform: overlap must be in 0..ws-1");
+    if (H < ws || W < ws) return fail(TPIV_EINVAL, "deform: the frame holds no window");
+    if (H >= (1 << 22) || W >= (1 << 22) || (long long)H * W >= (1LL << 30))
+        return fail(TPIV_EINVAL, "deform: frame too large");         // Q8 coordinates and flat indices in 32 bits
+    if ((H + 31) / 32 > 65535) return fail(TPIV_EINVAL, "deform: frame too tall");
+    return TPIV_OK;
+}
+}  // namespace
+
+int tpiv_deform_nodes(const double* u, const double* v, const uint8_t* invalid, int batch, int n_rows, int n_cols, int smooth,
+                      int16_t* nodes, void* stream) {
+    if (int rc = check_deform_grid("tpiv_deform_nodes", batch, n_rows, n_cols)) return rc;
+    if (batch == 0) return TPIV_OK;
+    if (!u || !v || !invalid || !nodes) return fail(TPIV_EINVAL, "tpiv_deform_nodes: null pointer");
+    if ((uintptr_t)nodes & 3u) return fail(TPIV_EINVAL, "tpiv_deform_nodes: nodes must be 4-byte aligned");
+    const size_t cells = (size_t)batch * n_rows * n_cols;
+    const DSpan in[3] = {{u, cells * 8}, {v, cells * 8}, {invalid, cells}};
+    const DSpan out[1] = {{nodes, cells * 4}};
+    if (deform_aliased(in, 3, out, 1)) return fail(TPIV_EINVAL, "tpiv_deform_nodes: the nodes overlap an input");
+    HIP_TRY(tpiv::launch_deform_nodes(u, v, invalid, batch, n_rows, n_cols, smooth != 0, nodes, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_deform_warp(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov, const int16_t* nodes,
+                     const int16_t* table, int interp, uint8_t* wa, uint8_t* wb, int32_t* counter, void* stream) {
+    const int kind = interp & ~TPIV_DEFORM_GATHER;
+    if (kind != TPIV_DEWARP_LINEAR && kind != TPIV_DEWARP_CUBIC) return fail(TPIV_EINVAL, "tpiv_deform_warp: unknown interp");
+    if (int rc = check_deform_frame(H, W, ws, ov)) return rc;
+    int nr = 0, nc = 0;
+    field_shape(H, W, ws, ov, &nr, &nc);
+    if (int rc = check_deform_grid("tpiv_deform_warp", batch, nr, nc)) return rc;
+    if (batch == 0) return TPIV_OK;
+    if (!a || !b || !nodes || !wa || !wb || (kind == TPIV_DEWARP_CUBIC && !table))
+        return fail(TPIV_EINVAL, "tpiv_deform_warp: null pointer");
+    if ((uintptr_t)nodes & 3u) return fail(TPIV_EINVAL, "tpiv_deform_warp: nodes must be 4-byte aligned");
+    if (((uintptr_t)table & 7u) || ((uintptr_t)counter & 3u)) return fail(TPIV_EINVAL, "tpiv_deform_warp: misaligned table or counter");
+    const size_t cells = (size_t)batch * nr * nc, pixels = (size_t)batch * H * W;
+    const DSpan in[4] = {{a, pixels}, {b, pixels}, {nodes, cells * 4}, {table, kind == TPIV_DEWARP_CUBIC ? (size_t)2048 : 0}};
+    const DSpan out[3] = {{wa, pixels}, {wb, pixels}, {counter, 8}};
+    if (deform_aliased(in, 4, out, 3)) return fail(TPIV_EINVAL, "tpiv_deform_warp: an output overlaps an input or another output");
+    tpiv::DeformWarpParams q{};
+    q.A = a;
+    q.B = b;
+    q.batch = batch;
+    q.H = H;
+    q.W = W;
+    q.ws = ws;
+    q.ov = ov;
+    q.n_rows = nr;
+    q.n_cols = nc;
+    q.nodes = nodes;
+    q.table = table;
+    q.interp = kind;
+    q.force_gather = (interp & TPIV_DEFORM_GATHER) != 0;
+    q.wa = wa;
+    q.wb = wb;
+    q.counter = counter;
+    HIP_TRY(tpiv::launch_deform_warp(q, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_deform_combine(const int16_t* nodes, const double* du, const double* dv, const uint8_t* dval, int batch, int n_rows,
+                        int n_cols, double* u, double* v, uint8_t* invalid, void* stream) {
+    if (int rc = check_deform_grid("tpiv_deform_combine", batch, n_rows, n_cols)) return rc;
+    if (batch == 0) return TPIV_OK;
+    if (!nodes || !du || !dv || !dval || !u || !v || !invalid) return fail(TPIV_EINVAL, "tpiv_deform_combine: null pointer");
+    if ((uintptr_t)nodes & 3u) return fail(TPIV_EINVAL, "tpiv_deform_combine: nodes must be 4-byte aligned");
+    const size_t cells = (size_t)batch * n_rows * n_cols;
+    const DSpan in[4] = {{nodes, cells * 4}, {du, cells * 8}, {dv, cells * 8}, {dval, cells}};
+    const DSpan out[3] = {{u, cells * 8}, {v, cells * 8}, {invalid, cells}};
+    if (deform_aliased(in, 4, out, 3)) return fail(TPIV_EINVAL, "tpiv_deform_combine: an output overlaps an input or another output");
+    HIP_TRY(tpiv::launch_deform_combine(nodes, du, dv, dval, cells, u, v, invalid, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_plan_set_deform(tpiv_plan* plan, int iterations, int interp, int smooth, const int16_t* table) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (iterations < 0 || iterations > 8) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: iterations must be in 0..8");
+    if (iterations == 0) {
+        plan->def_iters = 0;
+        return TPIV_OK;
+    }
+    if (interp != TPIV_DEWARP_LINEAR && interp != TPIV_DEWARP_CUBIC) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: unknown interp");
+    if (interp == TPIV_DEWARP_CUBIC && !table) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: the cubic interpolation needs its table");
+    const PassGeo& g = plan->geo[plan->n_pass - 1];
+    if (check_window(plan->H, plan->W, g.ws, g.ov, plan->val_win)) {              // what tpiv_pass1 refuses
+        const std::string why = g_err;
+        return fail(TPIV_EINVAL, "tpiv_plan_set_deform: the first pass refuses the last pass's geometry: " + why);
+    }
+    if (int rc = check_deform_frame(plan->H, plan->W, g.ws, g.ov)) return rc;
+    if (int rc = check_deform_grid("tpiv_plan_set_deform", plan->max_batch, g.n_rows, g.n_cols)) return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+    if (!plan->def_nodes) {                          // first time on: the workspace (kept until the plan is destroyed)
+        const size_t n = (size_t)g.n_rows * g.n_cols * plan->max_batch, px = (size_t)plan->H * plan->W * plan->max_batch;
+        int16_t *nodes = nullptr, *tab = nullptr;
+        uint8_t *wa = nullptr, *wb = nullptr, *dval = nullptr;
+        double *du = nullptr, *dv = nullptr, *su = nullptr, *sv = nullptr;
+        int rc = plan->alloc(&nodes, 2 * n);
+        if (!rc) rc = plan->alloc(&tab, 1024);
+        if (!rc) rc = plan->alloc(&wa, px);
+        if (!rc) rc = plan->alloc(&wb, px);
+        if (!rc) rc = plan->alloc(&du, n);
+        if (!rc) rc = plan->alloc(&dv, n);
+        if (!rc) rc = plan->alloc(&dval, n);
+        if (!rc) rc = plan->alloc(&su, n);
+        if (!rc) rc = plan->alloc(&sv, n);
+        if (rc) return rc;                           // (what was allocated stays in plan->allocs and goes with the plan)
+        const size_t need = tpiv::peak_raw_bytes(g.ws, plan->max_batch, g.n_rows * g.n_cols, plan->precision);
+        if (need > plan->peak_raw_bytes) {           // pass 1 at the last geometry needs more than any pass of the plan
+            float* raw = nullptr;
+            if (int rc2 = plan->alloc(&raw, need / sizeof(float) + 64)) return rc2;
+            plan->peak_raw = raw;
+            plan->peak_raw_bytes = need;
+        }
+        for (hipEvent_t& e : plan->def_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        plan->def_table = tab;
+        plan->def_wa = wa;
+        plan->def_wb = wb;
+        plan->def_du = du;
+        plan->def_dv = dv;
+        plan->def_dval = dval;
+        plan->def_su = su;
+        plan->def_sv = sv;
+        plan->def_nodes = nodes;
+    }
+    if (table) HIP_TRY(hipMemcpy(plan->def_table, table, 1024 * sizeof(int16_t), hipMemcpyDeviceToDevice));
+    plan->def_iters = iterations;
+    plan->def_interp = interp;
+    plan->def_smooth = smooth != 0;
+    plan->def_ran = false;
+    return TPIV_OK;
+}
+
+int tpiv_plan_deform_stage(const tpiv_plan* plan, int16_t** nodes, uint8_t** wa, uint8_t** wb, double** du, double** dv,
+                           uint8_t** dval) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!plan->def_iters) return fail(TPIV_EINVAL, "the plan deforms no images (tpiv_plan_set_deform)");
+    if (nodes) *nodes = plan->def_nodes;
+    if (wa) *wa = plan->def_wa;
+    if (wb) *wb = plan->def_wb;
+    if (du) *du = plan->def_du;
+    if (dv) *dv = plan->def_dv;
+    if (dval) *dval = plan->def_dval;
+    return TPIV_OK;
+}
+
+int tpiv_plan_deform_ms(tpiv_plan* plan, double* ms) {
+    if (!plan || !ms) return fail(TPIV_EINVAL, "bad plan / null pointer");
+    if (!plan->def_iters) return fail(TPIV_EINVAL, "the plan deforms no images (tpiv_plan_set_deform)");
+    if (!plan->def_ran) return fail(TPIV_EINVAL, "the plan has not run yet");
+    HIP_TRY(hipEventSynchronize(plan->def_ev[1]));
+    float t = 0.f;
+    HIP_TRY(hipEventElapsedTime(&t, plan->def_ev[0], plan->def_ev[1]));
+    *ms = (double)t;
+    return TPIV_OK;
+}
+
+// the rounds of a deforming plan behind its last pass (tpiv_plan_set_deform has the order of the steps)
+static int run_deform(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch, double* u, double* v, uint8_t* invalid,
+                      void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int last = plan->n_pass - 1;
+    const PassGeo& g = plan->geo[last];
+    const size_t cells = (size_t)batch * g.n_rows * g.n_cols;
+    const bool test = plan->outlier_kind != 0, masked = plan->mask_on;
+    HIP_TRY(hipEventRecord(plan->def_ev[0], st));
+    for (int k = 1; k <= plan->def_iters; ++k) {
+        const bool final = k == plan->def_iters;
+        HIP_TRY(tpiv::launch_deform_nodes(u, v, invalid, batch, g.n_rows, g.n_cols, plan->def_smooth, plan->def_nodes, st));
+        tpiv::DeformWarpParams q{};
+        q.A = a;
+        q.B = b;
+        q.batch = batch;
+        q.H = plan->H;
+        q.W = plan->W;
+        q.ws = g.ws;
+        q.ov = g.ov;
+        q.n_rows = g.n_rows;
+        q.n_cols = g.n_cols;
+        q.nodes = plan->def_nodes;
+        q.table = plan->def_table;
+        q.interp = plan->def_interp;
+        q.wa = plan->def_wa;
+        q.wb = plan->def_wb;
+        HIP_TRY(tpiv::launch_deform_warp(q, st));
+        if (int rc = pass1_impl(plan->def_wa, plan->def_wb, batch, plan->H, plan->W, g.ws, g.ov, plan->val_ratio, plan->val_win,
+                                plan->precision, plan->def_du, plan->def_dv, plan->def_dval, plan->peak_raw,
+                                plan->peak_raw_bytes, nullptr, nullptr, stream))
+            return rc;
+        // with the median test on, the combine writes what the test replaces somewhere else, as the tile kernels of a pass do
+        double* cu = (test && !final) ? plan->def_su : u;
+        double* cv = (test && !final) ? plan->def_sv : v;
+        uint8_t* cval = (test && final) ? plan->raw_val : invalid;
+        HIP_TRY(tpiv::launch_deform_combine(plan->def_nodes, plan->def_du, plan->def_dv, plan->def_dval, cells, cu, cv, cval, st));
+        if (masked)
+            HIP_TRY(tpiv::launch_mask_fields(cu, cv, cval, nullptr, plan->mgrid[last], batch, g.n_rows, g.n_cols, test ? 1 : 0, st));
+        if (test) {
+            if (int rc = run_median_test(cu, cv, cval, batch, g.n_rows, g.n_cols, plan->outlier_threshold, plan->outlier_eps,
+                                         plan->outlier_min, plan->ostatus[last], final ? nullptr : u, final ? nullptr : v, 1,
+                                         final ? invalid : nullptr, st))
+                return rc;
+            if (masked)
+                HIP_TRY(tpiv::launch_mask_fields(u, v, invalid, plan->ostatus[last], plan->mgrid[last], batch, g.n_rows,
+                                                 g.n_cols, 0, st));
+        }
+    }
+    HIP_TRY(hipEventRecord(plan->def_ev[1], st));
+    plan->def_ran = true;
+    return TPIV_OK;
+}
+
 int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch, double* u, double* v,
                   uint8_t* invalid, void* stream) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
@@ -1109,6 +1362,9 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
                 if (he != hipSuccess) return hip_fail(he, "launch_mask_fields");
             }
         }
+    }
+    if (plan->def_iters) {   // behind the last pass, its mask and outlier steps and the closing event of its timing slot
+        if (int rc = run_deform(plan, a, b, batch, u, v, invalid, stream)) return rc;
     }
     if (plan->unc_kind) {    // behind the last pass, its outlier and mask steps and the closing event of its timing slot
         const PassGeo& g = plan->geo[last];

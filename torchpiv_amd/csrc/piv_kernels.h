@@ -255,6 +255,29 @@ struct UncertaintyParams {
 };
 hipError_t launch_uncertainty(const UncertaintyParams& p, hipStream_t stream);
 
+// iterative image deformation (deform.hip, defined in include/torchpiv_hip.h: tpiv_deform_nodes / _warp / _combine).
+// Nodes: int16 [batch, n_rows, n_cols, 2], the Q8 half shift (x first), 4-byte aligned.  The warp kernel owns a tile of
+// 64 x 32 output pixels per workgroup, both frames of a pair; its source footprints come from LDS patches where they fit
+// and from the per-pixel gather where they do not (force_gather != 0: everywhere) -- the same bytes either way.
+// H, W < 2^22, H * W < 2^30 (Q8 coordinates and flat indices in 32 bits); batch and H / 32 at most 65535 (the grid).
+struct DeformWarpParams {
+    const uint8_t* A;        // [batch, H, W]
+    const uint8_t* B;
+    int batch, H, W, ws, ov, n_rows, n_cols;
+    const int16_t* nodes;    // [batch, n_rows, n_cols, 2]
+    const int16_t* table;    // int16 [256, 4], Q10 (read by DEWARP_CUBIC only)
+    int interp;              // DEWARP_LINEAR / DEWARP_CUBIC
+    int force_gather;
+    uint8_t* wa;             // out [batch, H, W]
+    uint8_t* wb;
+    int* counter;            // optional int32 [2]: += tiles sampled from LDS, tiles gathered
+};
+hipError_t launch_deform_nodes(const double* u, const double* v, const uint8_t* invalid, int batch, int n_rows, int n_cols,
+                               int smooth, int16_t* nodes, hipStream_t stream);
+hipError_t launch_deform_warp(const DeformWarpParams& p, hipStream_t stream);
+hipError_t launch_deform_combine(const int16_t* nodes, const double* du, const double* dv, const uint8_t* dval, size_t cells,
+                                 double* u, double* v, uint8_t* invalid, hipStream_t stream);
+
 hipError_t launch_xcorr(const PassParams& p, int mode, int n_cu, hipStream_t stream);
 // bytes of the tile kernels' work-queue counters (8 x one 64-byte line), and of the slow-item list header behind them
 constexpr size_t TILE_CTR_BYTES = 8 * 16 * sizeof(unsigned), TILE_SLOW_HDR_BYTES = 256;

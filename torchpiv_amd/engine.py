@@ -1179,6 +1179,106 @@ def dewarp(frames, map, interp="cubic", fill=0, offsets=None, shape=None, out=No
     return out
 
 
+DEFORM_DEFAULTS = {"iterations": 3, "interp": "cubic", "smooth": True}
+DEFORM_MAX_ITERATIONS = 8
+
+
+def deform_arg(deform):
+    """The deform= argument of Plan / OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None or 0 (off), an
+    integer 1..8 (that many rounds of image deformation behind the last pass at DEFORM_DEFAULTS) or a dict with any of
+    iterations (0..8), interp ("cubic" or "linear") and smooth (bool: the 3 x 3 binomial on the predictor).  Returns None
+    (off) or the full parameter dict; anything else raises ValueError."""
+    if deform is None:
+        return None
+    if isinstance(deform, (bool, np.bool_)):
+        raise ValueError(f"deform: None, an integer 0..{DEFORM_MAX_ITERATIONS} or a dict of {sorted(DEFORM_DEFAULTS)}, got {deform!r}")
+    if isinstance(deform, (int, np.integer)):
+        deform = {"iterations": deform}
+    if not isinstance(deform, dict):
+        raise ValueError(f"deform: None, an integer 0..{DEFORM_MAX_ITERATIONS} or a dict of {sorted(DEFORM_DEFAULTS)}, "
+                         f"got {type(deform).__name__}")
+    unknown = sorted(set(deform) - set(DEFORM_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"deform: unknown key(s) {unknown}; known: {sorted(DEFORM_DEFAULTS)}")
+    par = dict(DEFORM_DEFAULTS, **deform)
+    n = par["iterations"]
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 0 <= n <= DEFORM_MAX_ITERATIONS:
+        raise ValueError(f"deform: iterations must be an integer in 0..{DEFORM_MAX_ITERATIONS}, got {n!r}")
+    if not isinstance(par["interp"], str) or par["interp"] not in _lib.DEWARP_INTERPS:
+        raise ValueError(f"deform: interp must be one of {sorted(_lib.DEWARP_INTERPS)}, got {par['interp']!r}")
+    if not isinstance(par["smooth"], (bool, np.bool_)):
+        raise ValueError(f"deform: smooth must be a bool, got {par['smooth']!r}")
+    if n == 0:
+        return None
+    return {"iterations": int(n), "interp": par["interp"], "smooth": bool(par["smooth"])}
+
+
+def _fields3(who, u, v, inv):
+    _need_cuda(u, v, inv)
+    if u.dtype != torch.float64 or v.dtype != torch.float64 or inv.dtype != torch.uint8:
+        raise TypeError(f"{who}: u, v float64 and invalid uint8")
+    if u.dim() != 3 or u.shape != v.shape or u.shape != inv.shape:
+        raise ValueError(f"{who}: [batch, n_rows, n_cols] tensors of one shape")
+    return u.contiguous(), v.contiguous(), inv.contiguous()
+
+
+def deform_nodes(u, v, inv, smooth=True):
+    """The Q8 half-shift nodes of a field (tpiv_deform_nodes; the definition is in include/torchpiv_hip.h): u, v float64 and
+    inv uint8 [batch, n_rows, n_cols] on the GPU -> int16 [batch, n_rows, n_cols, 2], x first.  Invalid and non-finite cells
+    take the rounded mean of their valid neighbours; smooth: the 3 x 3 binomial afterwards.  The inputs are not written."""
+    u, v, inv = _fields3("deform_nodes", u, v, inv)
+    B, nr, nc = u.shape
+    nodes = torch.empty(B, nr, nc, 2, dtype=torch.int16, device=u.device)
+    with torch.cuda.device(u.device):
+        check(lib.tpiv_deform_nodes(u.data_ptr(), v.data_ptr(), inv.data_ptr(), B, nr, nc, 1 if smooth else 0,
+                                    nodes.data_ptr(), _stream()))
+    return nodes
+
+
+def deform_warp(a, b, nodes, ws, ov, interp="cubic", counter=None, gather=False):
+    """Both frames of every pair warped by the dense half shift between the nodes (tpiv_deform_warp): a, b uint8
+    [batch, H, W] (or [H, W]) on the GPU, nodes int16 [batch, n_rows, n_cols, 2] of the grid of (ws, ov) -> (wa, wb) uint8
+    like the frames, a sampled at -h and b at +h.  counter: an int32 [2] tensor on the device that gains the number of
+    tiles sampled from LDS and of tiles gathered.  gather: the per-pixel gather in every tile (the same bytes)."""
+    a, b = _frames(a, b)
+    _need_cuda(nodes, counter)
+    if not isinstance(interp, str) or interp not in _lib.DEWARP_INTERPS:
+        raise ValueError(f"deform_warp: interp must be one of {sorted(_lib.DEWARP_INTERPS)}, got {interp!r}")
+    B, H, W = a.shape
+    if isinstance(ws, (int, np.integer)) and isinstance(ov, (int, np.integer)) and 0 <= ov < ws <= min(H, W):
+        nr, nc = (H - ws) // (ws - ov) + 1, (W - ws) // (ws - ov) + 1
+        if nodes.dtype != torch.int16 or tuple(nodes.shape) != (B, nr, nc, 2):
+            raise ValueError(f"deform_warp: nodes must be int16 [{B}, {nr}, {nc}, 2] for these frames, got {nodes.dtype} "
+                             f"{tuple(nodes.shape)}")
+    if counter is not None and (counter.dtype != torch.int32 or counter.numel() != 2 or not counter.is_contiguous()):
+        raise ValueError("deform_warp: counter must be a contiguous int32 tensor of 2 elements")
+    nodes = nodes.contiguous()
+    table = _dewarp_table(a.device)
+    wa, wb = torch.empty_like(a), torch.empty_like(b)
+    kind = _lib.DEWARP_INTERPS[interp] | (_lib.DEFORM_GATHER if gather else 0)
+    with torch.cuda.device(a.device):
+        check(lib.tpiv_deform_warp(a.data_ptr(), b.data_ptr(), B, H, W, int(ws), int(ov), nodes.data_ptr(),
+                                   table.data_ptr(), kind, wa.data_ptr(), wb.data_ptr(),
+                                   None if counter is None else counter.data_ptr(), _stream()))
+    return wa, wb
+
+
+def deform_combine(nodes, du, dv, dval):
+    """u = nodes_x / 128 + du, v = nodes_y / 128 + dv (one rounding each), invalid = dval (tpiv_deform_combine): nodes int16
+    [batch, n_rows, n_cols, 2], du, dv float64 and dval uint8 [batch, n_rows, n_cols] on the GPU -> (u, v, invalid)."""
+    du, dv, dval = _fields3("deform_combine", du, dv, dval)
+    _need_cuda(nodes)
+    B, nr, nc = du.shape
+    if nodes.dtype != torch.int16 or tuple(nodes.shape) != (B, nr, nc, 2):
+        raise ValueError(f"deform_combine: nodes must be int16 [{B}, {nr}, {nc}, 2], got {nodes.dtype} {tuple(nodes.shape)}")
+    nodes = nodes.contiguous()
+    u, v, inv = torch.empty_like(du), torch.empty_like(dv), torch.empty_like(dval)
+    with torch.cuda.device(du.device):
+        check(lib.tpiv_deform_combine(nodes.data_ptr(), du.data_ptr(), dv.data_ptr(), dval.data_ptr(), B, nr, nc,
+                                      u.data_ptr(), v.data_ptr(), inv.data_ptr(), _stream()))
+    return u, v, inv
+
+
 DEWARP_FIT_KINDS = {"homography": 4, "poly1": 3, "poly2": 6, "poly3": 10}       # kind -> the fewest points
 
 
@@ -1240,7 +1340,8 @@ class Plan:
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
 
     def __init__(self, H, W, ws, ov, n_pass=1, mode="CWS", pass_scale=2.0, val_ratio=1.2,
-                 val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None, uncertainty=None):
+                 val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None, uncertainty=None,
+                 deform=None):
         # outlier: None, "median" or a dict (outlier_arg): the normalized median test after every pass -- flagged vectors of
         # a pass before the last are replaced by their neighbourhood median before the predictor reads them, flagged
         # vectors of the last pass join the invalid mask (tpiv_plan_set_outlier)
@@ -1250,8 +1351,12 @@ class Plan:
         # (apply_mask) and the fill value are the business of whoever owns the frames and delivers the fields.
         # uncertainty: None, "cs" or a dict (uncertainty_arg): the correlation-statistics estimate of every returned vector's
         # random error, behind the last pass on the frames of the run (tpiv_plan_set_uncertainty); read with uncertainty()
+        # deform: None, an integer or a dict (deform_arg): that many rounds of image deformation behind the last pass -- the
+        # frames warped by the dense field, the first pass on the warped frames, the residual added (tpiv_plan_set_deform);
+        # deform_stage() and deform_ms() read what the last round left and what the rounds cost
         self.outlier = outlier_arg(outlier)
         self.mask = mask_arg(mask)
+        self.deform = deform_arg(deform)
         self.uncertainty_par = uncertainty_arg(uncertainty)
         if self.mask is not None and tuple(self.mask["image"].shape) != (H, W):
             raise ValueError(f"mask of shape {tuple(self.mask['image'].shape)} for frames of shape {(H, W)}")
@@ -1287,6 +1392,15 @@ class Plan:
             if self.uncertainty_par is not None:
                 try:
                     check(lib.tpiv_plan_set_uncertainty(self._h, 1, self.uncertainty_par["radius"]))
+                except Exception:
+                    self.close()
+                    raise
+            if self.deform is not None:
+                try:
+                    cubic = self.deform["interp"] == "cubic"
+                    check(lib.tpiv_plan_set_deform(self._h, self.deform["iterations"], _lib.DEWARP_INTERPS[self.deform["interp"]],
+                                                   1 if self.deform["smooth"] else 0,
+                                                   _dewarp_table(self.device).data_ptr() if cubic else None))
                 except Exception:
                     self.close()
                     raise
@@ -1444,6 +1558,33 @@ class Plan:
                 if rc != 0:
                     raise _lib.HipError(f"hipMemcpyAsync failed: {rc}")
         return su, sv
+
+    def deform_stage(self, batch):
+        """What the last round of the last run left (copies; waits for the device): nodes int16 [batch, n_rows, n_cols, 2],
+        wa, wb uint8 [batch, H, W], du, dv float64 and dval uint8 [batch, n_rows, n_cols].  ValueError for a plan without
+        deform=."""
+        ptr = [C.c_void_p() for _ in range(6)]
+        check(lib.tpiv_plan_deform_stage(self._h, *[C.byref(q) for q in ptr]))
+        if not 0 <= batch <= self.max_batch:
+            raise ValueError(f"batch {batch} exceeds the plan's max_batch {self.max_batch}")
+        nr, nc = self.out_shape
+        dev = self.device
+        nodes = torch.empty(batch, nr, nc, 2, dtype=torch.int16, device=dev)
+        wa = torch.empty(batch, self.H, self.W, dtype=torch.uint8, device=dev)
+        wb = torch.empty_like(wa)
+        du = torch.empty(batch, nr, nc, dtype=torch.float64, device=dev)
+        dv = torch.empty_like(du)
+        dval = torch.empty(batch, nr, nc, dtype=torch.uint8, device=dev)
+        outs = (nodes, wa, wb, du, dv, dval)
+        self._copy_out([(t, q, t.numel() * t.element_size()) for t, q in zip(outs, ptr) if t.numel()])
+        return outs
+
+    def deform_ms(self):
+        """Milliseconds all deformation rounds of the last run took together (waits for them).  ValueError for a plan
+        without deform= or before its first run."""
+        ms = C.c_double()
+        check(lib.tpiv_plan_deform_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def set_mask(self, image, threshold=MASK_DEFAULTS["threshold"]):
         """(Re)computes the plan's grids of excluded cells from a mask image (uint8 [H, W], any device; non-zero = masked)
