@@ -27,8 +27,8 @@ import numpy as np
 F = np.float64
 LD = np.longdouble
 U = 2.0 ** -53
-LEAK = 1e-17                 # build_banded refuses an operator that leaves more than this outside the band (c_api.cpp:351)
-PRED_BW = 65                 # c_api.cpp:289
+LEAK = 1e-17                 # build_banded refuses an operator that leaves more than this outside the band (c_api.cpp)
+PRED_BW = 65                 # c_api.cpp, PRED_BW
 MASKS = ("none", "all", "r05", "r30", "half", "blocks")
 MUTANTS = {
     "a": "the last trip is skipped when the trip count is odd",
@@ -87,7 +87,7 @@ def _passes(cid):
     out, w, o = [], c["ws"], c["ov"]
     for p in range(c["n_pass"]):
         if p:
-            w, o = int(np.floor(w / c["pass_scale"])), int(np.floor(o / c["pass_scale"]))      # c_api.cpp:604-605
+            w, o = int(np.floor(w / c["pass_scale"])), int(np.floor(o / c["pass_scale"]))      # tpiv_plan_create's geometry loop
         nr, nc = engine.field_shape(c["H"], c["W"], w, o)
         x, y = engine.coordinates_1d(c["H"], c["W"], w, o)
         out.append((w, o, nr, nc, x, y))
@@ -297,14 +297,14 @@ def check(mode, ref, outs, first=0):
 
 # ----------------------------------------------------------------------------------------------------- the numpy model
 def band_start(row, bw):
-    """c_api.cpp:291-303."""
+    """c_api.cpp, band_start."""
     nc = row.size
     c = int(np.argmax(np.abs(row)))                    # the first largest entry, like the `>` of the loop
     return min(max(c - bw // 2, 0), nc - bw)
 
 
 def _starts(op, bw):
-    """c_api.cpp:320-331: band starts, monotone in the fine index; the largest entry left outside."""
+    """c_api.cpp, build_banded, `starts`: band starts, monotone in the fine index; the largest entry left outside."""
     st, leak = [], 0.0
     for f in range(op.shape[0]):
         s = band_start(op[f], bw)
@@ -318,7 +318,7 @@ def _starts(op, bw):
 
 
 def _tiles32(op, st, bw):
-    """c_api.cpp:332-348: K, the [nb, K, 32] weight tiles, k0 per block."""
+    """c_api.cpp, build_banded, `tiles32`: K, the [nb, K, 32] weight tiles, k0 per block."""
     nf = op.shape[0]
     nb = (nf + 31) // 32
     k0 = [st[32 * b] for b in range(nb)]
@@ -332,7 +332,7 @@ def _tiles32(op, st, bw):
 
 
 def build_banded(Ay, Ax):
-    """c_api.cpp:316-361."""
+    """c_api.cpp, build_banded."""
     bwy, bwx = min(Ay.shape[1], PRED_BW), min(Ax.shape[1], PRED_BW)
     sy, ly = _starts(Ay, bwy)
     sx, lx = _starts(Ax, bwx)

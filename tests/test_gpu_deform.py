@@ -297,7 +297,7 @@ def mask_image():
     return img
 
 
-def _chain(eng, off, A, B, n, interp, smooth, test, grid):
+def _chain(eng, off, A, B, n, interp, smooth, test, grid, precision="exact"):
     """The rounds as the header prescribes them, from the functions of the function level."""
     u, v, inv = off.run(A, B)
     ws, ov, _, _ = off.geometry[-1]
@@ -306,7 +306,7 @@ def _chain(eng, off, A, B, n, interp, smooth, test, grid):
         final = k == n
         nd = eng.deform_nodes(u, v, inv, smooth=smooth)
         wa, wb = eng.deform_warp(A, B, nd, ws, ov, interp=interp)
-        du, dv, dval = eng.pass1(wa, wb, ws, ov, precision="exact")
+        du, dv, dval = eng.pass1(wa, wb, ws, ov, precision=precision)
         stage = (nd, wa, wb, du, dv, dval)
         cu, cv, cval = eng.deform_combine(nd, du, dv, dval)
         if grid is not None:
@@ -359,6 +359,79 @@ def test_plan_equals_the_unrolled_chain(eng, outlier, mask, n, interp, smooth):
     s1 = on.deform_stage(1)
     assert torch.equal(s1[1], wstage[1][1:2]) and _same(s1[3], wstage[3][1:2])
     off.close()
+    on.close()
+
+
+def _settled(eng, u, v, inv, grid, feeds):
+    """What a plan with mask= and the median test puts behind a pass, from the function level (in place on u, v, inv where
+    it can be).  feeds: the predictor reads the fields next -- flagged vectors are replaced by their medians and excluded
+    cells stay invalid; behind the last pass the flags join the mask and excluded cells end up valid."""
+    eng.mask_fields(u, v, inv, grid, 1)
+    status, mu, mv = eng.median_test(u, v, inv, want_medians=True)
+    flag = (status & 1) != 0
+    if feeds:
+        u, v = torch.where(flag, mu, u), torch.where(flag, mv, v)
+    else:
+        inv = ((inv != 0) | flag).to(torch.uint8)
+    eng.mask_fields(u, v, inv, grid, 1 if feeds else 0, status=status)
+    return u, v, inv, status
+
+
+@pytest.mark.parametrize("mode,precision", [("CWS", "exact"), ("DWS", "fast")])
+def test_three_pass_plan_with_everything_on_equals_the_unrolled_chain(eng, mode, precision):
+    """32/16 -> 16/8 -> 8/4 with outlier=, mask=, deform= and uncertainty= on: the one plan in the suite with a middle
+    pass, which is predicted into, run by the shifted-pass kernel, settled for the predictor and predicted from, and the
+    one where the spare fields of the median step serve two geometries.  Expected: the function level alone."""
+    import types
+    A, B = (t.cuda() for t in scene_pairs(3))
+    m = mask_image()
+    A, B = eng.apply_mask(A, m.cuda()), eng.apply_mask(B, m.cuda())
+    n, interp, smooth = 2, "cubic", True
+    on = eng.Plan(PH, PW, 32, 16, n_pass=3, mode=mode, max_batch=4, precision=precision, outlier="median", mask=m,
+                  deform={"iterations": n}, uncertainty="cs")
+    assert [g[:2] for g in on.geometry] == [(32, 16), (16, 8), (8, 4)]
+    grids = [on.mask_grid(p) for p in range(3)]
+    # the passes
+    fields, status = [], []
+    u, v, inv = eng.pass1(A, B, 32, 16, precision=precision)
+    for p in range(3):
+        if p:
+            ws, ov = on.geometry[p][:2]
+            u, v, inv = eng.iterate(mode, A, B, ws, ov, *on.debug_predict(p, u, v, inv), precision=precision)
+        u, v, inv, st = _settled(eng, u, v, inv, grids[p], feeds=p < 2)
+        fields.append((u, v, inv))
+        status.append(st)
+    n_flag1, n_inv2 = int((status[1] & 1).sum()), int((inv != 0).sum())
+    print(f"{mode} {precision}: excluded at 16/8 {int(grids[1].sum())} of {grids[1].numel()}, flagged at 16/8 {n_flag1}, "
+          f"invalid behind 8/4 {n_inv2}")
+    assert grids[1].any() and not grids[1].all()
+    assert n_flag1 > 0 and n_inv2 > 0
+    # the rounds on what the last pass left, then the estimate on the frames of the run
+    last = types.SimpleNamespace(run=lambda a, b: fields[2], geometry=on.geometry)
+    wu, wv, winv, wstage, wstatus = _chain(eng, last, A, B, n, interp, smooth, True, grids[2], precision=precision)
+    dead = winv | grids[2].to(torch.uint8)[None]
+    wsu, wsv = eng.uncertainty(A, B, wu, wv, 8, 4, invalid=dead, radius=3)
+    status[2] = wstatus
+
+    def check(batch, sl):
+        u, v, inv = on.run(A[sl], B[sl])
+        su, sv = on.uncertainty(batch)
+        stage = on.deform_stage(batch)
+        torch.cuda.synchronize()
+        assert _same(u, wu[sl]) and _same(v, wv[sl]) and torch.equal(inv, winv[sl])
+        for p in range(2):
+            fu, fv, fi = on.pass_fields(p, batch)
+            assert _same(fu, fields[p][0][sl]) and _same(fv, fields[p][1][sl]) and torch.equal(fi, fields[p][2][sl]), p
+        for p in range(3):
+            assert torch.equal(on.outlier_status(p, batch), status[p][sl]), p
+        for got, want in zip(stage, wstage):
+            assert got.dtype == want.dtype and torch.equal(got.view(torch.uint8), want[sl].contiguous().view(torch.uint8))
+        assert _same(su, wsu[sl]) and _same(sv, wsv[sl])
+        assert torch.equal(torch.isnan(su), torch.isnan(wsu[sl])) and torch.isnan(su[dead[sl] != 0]).all()
+
+    check(3, slice(0, 3))
+    assert not _same(wu, fields[2][0])                           # the rounds did something
+    check(1, slice(1, 2))                                        # a smaller batch on the same plan
     on.close()
 
 

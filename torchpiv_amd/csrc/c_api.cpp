@@ -56,6 +56,23 @@ int check_work(const void* work, size_t have, size_t need) {
     return TPIV_OK;
 }
 
+// "No output may overlap an input or another output": 0 = none does, 1 = an output overlaps an input, 2 = two outputs
+// overlap.  A null or empty span overlaps nothing (the only empty span in use is an absent table, whose pointer is null).
+struct Span { const void* p; size_t n; };
+int aliased(const Span* in, int n_in, const Span* out, int n_out) {
+    auto overlap = [](const Span& x, const Span& y) {
+        const char *a = (const char*)x.p, *b = (const char*)y.p;
+        return a && b && x.n && y.n && a < b + y.n && b < a + x.n;
+    };
+    for (int i = 0; i < n_out; ++i) {
+        for (int j = 0; j < n_in; ++j)
+            if (overlap(out[i], in[j])) return 1;
+        for (int j = i + 1; j < n_out; ++j)
+            if (overlap(out[i], out[j])) return 2;
+    }
+    return 0;
+}
+
 // 8/16/32/64: tile kernel (xcorr_tile.hpp); 128 pass 1: xcorr_big.hpp; anything else in 2..256 (and
 // shifted 128x128 passes): generic-size DFT kernel (xcorr_generic.hip)
 bool supported_ws(int ws) { return ws >= 2 && ws <= 256; }
@@ -221,8 +238,7 @@ struct tpiv_plan {
     // device workspace
     std::vector<double*> u, v;           // per pass (all but the last): [max_batch, N_p]
     std::vector<uint8_t*> val;
-    std::vector<double*> Ay, Ax;         // per pass p >= 1: dense operators from pass p-1 to p (debug)
-    // banded form used by tpiv_plan_run (piv_kernels.h: BandedPredictParams)
+    // per pass p >= 1: the spline operators from pass p-1 to p in banded form (piv_kernels.h: BandedPredictParams)
     std::vector<double*> Wy32, Ax32;
     std::vector<int*> k0y32, k0x32;
     std::vector<int> KY, KX;
@@ -297,6 +313,14 @@ struct tpiv_plan {
 };
 
 namespace {
+
+// a plan's workspace lives on the device it was created on: whatever allocates or launches for it checks first
+int check_plan_device(const tpiv_plan* plan) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+    return TPIV_OK;
+}
 
 // band of one operator row: PRED_BW taps around the largest entry (clipped to the matrix); returns
 // the largest magnitude left outside so that the caller can verify the truncation is harmless
@@ -402,17 +426,11 @@ int tpiv_spline_matrix(int nc, const double* xc, int nf, const double* xf, doubl
     return spline_matrix(nc, xc, nf, xf, A);
 }
 
-static int pass1_impl(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
-                      double val_ratio, int val_win, int precision, double* u, double* v, uint8_t* invalid,
-                      void* work, size_t work_bytes, float* dbg_win, float* dbg_corr, void* stream,
-                      hipEvent_t* sub_events = nullptr) {
-    int rc = check_window(H, W, ws, ov, val_win);
-    if (rc) return rc;
-    if (!valid_precision(precision)) return fail(TPIV_EINVAL, "precision must be TPIV_PREC_FAST, TPIV_PREC_REFERENCE, TPIV_PREC_F64 or TPIV_PREC_EXACT");
-    if (batch <= 0) return TPIV_OK;
+// what the first pass and the shifted passes hand their kernels alike; the callers add what is their own
+static tpiv::PassParams pass_params(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
+                                    double val_ratio, int val_win, int precision, double* u, double* v, uint8_t* invalid,
+                                    float* dbg_win, float* dbg_corr) {
     tpiv::PassParams p{};
-    p.dbg_win = dbg_win;
-    p.dbg_corr = dbg_corr;
     p.A = a;
     p.B = b;
     p.batch = batch;
@@ -426,8 +444,22 @@ static int pass1_impl(const uint8_t* a, const uint8_t* b, int batch, int H, int 
     p.val = invalid;
     p.val_ratio = val_ratio;
     p.val_win = val_win;
+    p.dbg_win = dbg_win;
+    p.dbg_corr = dbg_corr;
     p.stamps = g_stamps;
     p.precision = precision;
+    return p;
+}
+
+static int pass1_impl(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
+                      double val_ratio, int val_win, int precision, double* u, double* v, uint8_t* invalid,
+                      void* work, size_t work_bytes, float* dbg_win, float* dbg_corr, void* stream,
+                      hipEvent_t* sub_events = nullptr) {
+    int rc = check_window(H, W, ws, ov, val_win);
+    if (rc) return rc;
+    if (!valid_precision(precision)) return fail(TPIV_EINVAL, "precision must be TPIV_PREC_FAST, TPIV_PREC_REFERENCE, TPIV_PREC_F64 or TPIV_PREC_EXACT");
+    if (batch <= 0) return TPIV_OK;
+    tpiv::PassParams p = pass_params(a, b, batch, H, W, ws, ov, val_ratio, val_win, precision, u, v, invalid, dbg_win, dbg_corr);
     p.sub_events = sub_events;
     rc = check_work(work, work_bytes, tpiv::peak_raw_bytes(ws, batch, p.n_rows * p.n_cols, precision));
     if (rc) return rc;
@@ -496,31 +528,14 @@ static int run_iter(int mode, int precision, const uint8_t* a, const uint8_t* b,
     if (!u0 || !v0) return fail(TPIV_EINVAL, "tpiv_iter: u0 / v0 missing");
     if (!valid_precision(precision)) return fail(TPIV_EINVAL, "precision must be TPIV_PREC_FAST, TPIV_PREC_REFERENCE, TPIV_PREC_F64 or TPIV_PREC_EXACT");
     if (batch <= 0) return TPIV_OK;
-    tpiv::PassParams p{};
-    p.A = a;
-    p.B = b;
-    p.batch = batch;
-    p.H = H;
-    p.W = W;
-    p.ws = ws;
-    p.ov = ov;
-    p.precision = precision;
-    field_shape(H, W, ws, ov, &p.n_rows, &p.n_cols);
+    tpiv::PassParams p = pass_params(a, b, batch, H, W, ws, ov, val_ratio, val_win, precision, u, v, invalid, dbg_win, dbg_corr);
     p.u0 = u0;
     p.v0 = v0;
     p.u2 = u2;
     p.v2 = v2;
     p.pmask = pmask;           // plan path: raw predictor in u0 / v0 + mask (piv_kernels.h)
-    p.u = u;
-    p.v = v;
-    p.val = invalid;
     p.du = du;
     p.dv = dv;
-    p.val_ratio = val_ratio;
-    p.val_win = val_win;
-    p.dbg_win = dbg_win;
-    p.dbg_corr = dbg_corr;
-    p.stamps = g_stamps;
     rc = check_work(work, work_bytes,
                     tpiv::peak_raw_bytes(ws, batch, p.n_rows * p.n_cols, TPIV_PREC_FAST, mode == TPIV_MODE_CWS_FAST));
     if (rc) return rc;
@@ -631,8 +646,6 @@ int tpiv_plan_create(tpiv_plan** out, int H, int W, int ws, int ov, int n_pass, 
         pl->geo.push_back(std::move(g));
     }
     size_t max_fine = 0, max_T = 0;
-    pl->Ay.assign(n_pass, nullptr);
-    pl->Ax.assign(n_pass, nullptr);
     pl->Wy32.assign(n_pass, nullptr);
     pl->Ax32.assign(n_pass, nullptr);
     pl->k0y32.assign(n_pass, nullptr);
@@ -655,20 +668,13 @@ int tpiv_plan_create(tpiv_plan** out, int H, int W, int ws, int ov, int n_pass, 
             std::vector<double> ay((size_t)g.n_rows * c.n_rows), ax((size_t)g.n_cols * c.n_cols);
             rc = spline_matrix(c.n_rows, c.y.data(), g.n_rows, g.y.data(), ay.data());
             if (!rc) rc = spline_matrix(c.n_cols, c.x.data(), g.n_cols, g.x.data(), ax.data());
-            if (!rc) rc = pl->alloc(&pl->Ay[p], ay.size());
-            if (!rc) rc = pl->alloc(&pl->Ax[p], ax.size());
-            if (!rc) {
-                he = hipMemcpy(pl->Ay[p], ay.data(), ay.size() * sizeof(double), hipMemcpyHostToDevice);
-                if (he == hipSuccess)
-                    he = hipMemcpy(pl->Ax[p], ax.data(), ax.size() * sizeof(double), hipMemcpyHostToDevice);
-                if (he != hipSuccess) rc = hip_fail(he, "hipMemcpy(spline operators)");
-            }
             if (!rc) rc = build_banded(pl, p, c.n_rows, c.n_cols, g.n_rows, g.n_cols, ay, ax);
             if (N > max_fine) max_fine = N;
-            const size_t t = (size_t)3 * ((g.n_rows + 31) / 32 * 32) * c.n_cols;     // T1 of the banded path (transposed, padded pitch)
-            const size_t t_dense = (size_t)3 * c.n_rows * g.n_cols;
+            // T1 of the banded predictor: three planes of [coarse columns][fine rows rounded up to 32] per pair.  The row
+            // kernel of predict_mfma.hip stores at cc < ncc, rf < nrfp only, and the column kernel reads each plane through
+            // a buffer descriptor of exactly that size, so no access leaves 3 * roundup32(nrf) * ncc doubles per pair.
+            const size_t t = (size_t)3 * ((g.n_rows + 31) / 32 * 32) * c.n_cols;
             if (t > max_T) max_T = t;
-            if (t_dense > max_T) max_T = t_dense;
         }
     }
     if (rc == TPIV_OK) {
@@ -816,16 +822,10 @@ int tpiv_median_test(const double* u, const double* v, const uint8_t* invalid, i
     if (batch == 0) return TPIV_OK;
     // no output may overlap an input or another output: every decision is taken on the fields as they came in
     const size_t cells = (size_t)batch * n_rows * n_cols;
-    struct Span { const char* p; size_t n; };
-    const Span in[3] = {{(const char*)u, cells * 8}, {(const char*)v, cells * 8}, {(const char*)invalid, cells}};
-    const Span out[3] = {{(const char*)status, cells}, {(const char*)med_u, cells * 8}, {(const char*)med_v, cells * 8}};
-    auto overlap = [](const Span& x, const Span& y) { return x.p && y.p && x.p < y.p + y.n && y.p < x.p + x.n; };
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j)
-            if (overlap(out[i], in[j])) return fail(TPIV_EINVAL, "tpiv_median_test: an output aliases an input");
-        for (int j = i + 1; j < 3; ++j)
-            if (overlap(out[i], out[j])) return fail(TPIV_EINVAL, "tpiv_median_test: two outputs overlap");
-    }
+    const Span in[3] = {{u, cells * 8}, {v, cells * 8}, {invalid, cells}};
+    const Span out[3] = {{status, cells}, {med_u, cells * 8}, {med_v, cells * 8}};
+    if (const int k = aliased(in, 3, out, 3))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_median_test: an output aliases an input" : "tpiv_median_test: two outputs overlap");
     return run_median_test(u, v, invalid, batch, n_rows, n_cols, threshold, eps, min_neighbours, status, med_u, med_v, 0,
                            nullptr, (hipStream_t)stream);
 }
@@ -840,12 +840,10 @@ int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double ep
     if (!(threshold > 0) || !(eps >= 0)) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: threshold must be > 0 and eps >= 0");
     if (min_neighbours < 1 || min_neighbours > 8) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: min_neighbours must be in 1..8");
     if (plan->ostatus.empty()) {                     // first time on: the workspace (kept until the plan is destroyed)
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+        int rc = check_plan_device(plan);
+        if (rc) return rc;
         std::vector<uint8_t*> status(plan->n_pass, nullptr);
         size_t spare = 0;
-        int rc = TPIV_OK;
         for (int p = 0; p < plan->n_pass && !rc; ++p) {
             const size_t N = (size_t)plan->geo[p].n_rows * plan->geo[p].n_cols;
             rc = plan->alloc(&status[p], N * plan->max_batch);
@@ -916,9 +914,7 @@ int tpiv_plan_set_mask(tpiv_plan* plan, const uint8_t* mask, double threshold, v
         return TPIV_OK;
     }
     if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(TPIV_EINVAL, "tpiv_plan_set_mask: threshold must be in [0, 1]");
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+    if (int rc = check_plan_device(plan)) return rc;
     for (const PassGeo& g : plan->geo)
         if (int rc = check_mask_window(plan->H, plan->W, g.ws, g.ov)) return rc;
     if (plan->mgrid.empty()) {                       // first time on: the grids (kept until the plan is destroyed)
@@ -995,17 +991,10 @@ int tpiv_uncertainty(const uint8_t* a, const uint8_t* b, int batch, int H, int W
     field_shape(H, W, ws, ov, &nr, &nc);
     if ((long long)batch * nr * nc >= (1LL << 31)) return fail(TPIV_EINVAL, "tpiv_uncertainty: batch of fields too large");
     const size_t cells = (size_t)batch * nr * nc, pixels = (size_t)batch * H * W;
-    struct Span { const char* p; size_t n; };
-    const Span in[5] = {{(const char*)a, pixels}, {(const char*)b, pixels}, {(const char*)u, cells * 8},
-                        {(const char*)v, cells * 8}, {(const char*)invalid, cells}};
-    const Span out[3] = {{(const char*)su, cells * 8}, {(const char*)sv, cells * 8}, {(const char*)stats, cells * 64}};
-    auto overlap = [](const Span& x, const Span& y) { return x.p && y.p && x.p < y.p + y.n && y.p < x.p + x.n; };
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 5; ++j)
-            if (overlap(out[i], in[j])) return fail(TPIV_EINVAL, "tpiv_uncertainty: an output overlaps an input");
-        for (int j = i + 1; j < 3; ++j)
-            if (overlap(out[i], out[j])) return fail(TPIV_EINVAL, "tpiv_uncertainty: two outputs overlap");
-    }
+    const Span in[5] = {{a, pixels}, {b, pixels}, {u, cells * 8}, {v, cells * 8}, {invalid, cells}};
+    const Span out[3] = {{su, cells * 8}, {sv, cells * 8}, {stats, cells * 64}};
+    if (const int k = aliased(in, 5, out, 3))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_uncertainty: an output overlaps an input" : "tpiv_uncertainty: two outputs overlap");
     return run_uncertainty(a, b, batch, H, W, ws, ov, nr, nc, u, v, invalid, nullptr, radius, su, sv, stats,
                            (hipStream_t)stream);
 }
@@ -1021,9 +1010,7 @@ int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius) {
     const PassGeo& g = plan->geo[plan->n_pass - 1];
     if (int rc = check_uncertainty(plan->H, plan->W, g.ws, g.ov, radius)) return rc;
     if (!plan->unc_su) {                             // first time on: the two fields (kept until the plan is destroyed)
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+        if (int rc = check_plan_device(plan)) return rc;
         const size_t n = (size_t)g.n_rows * g.n_cols * plan->max_batch;
         double *su = nullptr, *sv = nullptr;
         if (int rc = plan->alloc(&su, n)) return rc;
@@ -1047,21 +1034,6 @@ int tpiv_plan_uncertainty(const tpiv_plan* plan, double** su, double** sv) {
 // ---- iterative image deformation (deform.hip) ---------------------------------------------------------------------
 
 namespace {
-struct DSpan { const void* p; size_t n; };
-bool dspans_overlap(const DSpan& x, const DSpan& y) {
-    const char *a = (const char*)x.p, *b = (const char*)y.p;
-    return a && b && x.n && y.n && a < b + y.n && b < a + x.n;
-}
-// no output may overlap an input or another output
-bool deform_aliased(const DSpan* in, int n_in, const DSpan* out, int n_out) {
-    for (int i = 0; i < n_out; ++i) {
-        for (int j = 0; j < n_in; ++j)
-            if (dspans_overlap(out[i], in[j])) return true;
-        for (int j = i + 1; j < n_out; ++j)
-            if (dspans_overlap(out[i], out[j])) return true;
-    }
-    return false;
-}
 int check_deform_grid(const char* who, int batch, int n_rows, int n_cols) {
     if (batch < 0) return fail(TPIV_EINVAL, std::string(who) + ": negative batch");
     if (n_rows < 1 || n_cols < 1) return fail(TPIV_EINVAL, std::string(who) + ": empty grid");
@@ -1088,9 +1060,9 @@ int tpiv_deform_nodes(const double* u, const double* v, const uint8_t* invalid, 
     if (!u || !v || !invalid || !nodes) return fail(TPIV_EINVAL, "tpiv_deform_nodes: null pointer");
     if ((uintptr_t)nodes & 3u) return fail(TPIV_EINVAL, "tpiv_deform_nodes: nodes must be 4-byte aligned");
     const size_t cells = (size_t)batch * n_rows * n_cols;
-    const DSpan in[3] = {{u, cells * 8}, {v, cells * 8}, {invalid, cells}};
-    const DSpan out[1] = {{nodes, cells * 4}};
-    if (deform_aliased(in, 3, out, 1)) return fail(TPIV_EINVAL, "tpiv_deform_nodes: the nodes overlap an input");
+    const Span in[3] = {{u, cells * 8}, {v, cells * 8}, {invalid, cells}};
+    const Span out[1] = {{nodes, cells * 4}};
+    if (aliased(in, 3, out, 1)) return fail(TPIV_EINVAL, "tpiv_deform_nodes: the nodes overlap an input");
     HIP_TRY(tpiv::launch_deform_nodes(u, v, invalid, batch, n_rows, n_cols, smooth != 0, nodes, (hipStream_t)stream));
     return TPIV_OK;
 }
@@ -1109,9 +1081,9 @@ int tpiv_deform_warp(const uint8_t* a, const uint8_t* b, int batch, int H, int W
     if ((uintptr_t)nodes & 3u) return fail(TPIV_EINVAL, "tpiv_deform_warp: nodes must be 4-byte aligned");
     if (((uintptr_t)table & 7u) || ((uintptr_t)counter & 3u)) return fail(TPIV_EINVAL, "tpiv_deform_warp: misaligned table or counter");
     const size_t cells = (size_t)batch * nr * nc, pixels = (size_t)batch * H * W;
-    const DSpan in[4] = {{a, pixels}, {b, pixels}, {nodes, cells * 4}, {table, kind == TPIV_DEWARP_CUBIC ? (size_t)2048 : 0}};
-    const DSpan out[3] = {{wa, pixels}, {wb, pixels}, {counter, 8}};
-    if (deform_aliased(in, 4, out, 3)) return fail(TPIV_EINVAL, "tpiv_deform_warp: an output overlaps an input or another output");
+    const Span in[4] = {{a, pixels}, {b, pixels}, {nodes, cells * 4}, {table, kind == TPIV_DEWARP_CUBIC ? (size_t)2048 : 0}};
+    const Span out[3] = {{wa, pixels}, {wb, pixels}, {counter, 8}};
+    if (aliased(in, 4, out, 3)) return fail(TPIV_EINVAL, "tpiv_deform_warp: an output overlaps an input or another output");
     tpiv::DeformWarpParams q{};
     q.A = a;
     q.B = b;
@@ -1140,9 +1112,9 @@ int tpiv_deform_combine(const int16_t* nodes, const double* du, const double* dv
     if (!nodes || !du || !dv || !dval || !u || !v || !invalid) return fail(TPIV_EINVAL, "tpiv_deform_combine: null pointer");
     if ((uintptr_t)nodes & 3u) return fail(TPIV_EINVAL, "tpiv_deform_combine: nodes must be 4-byte aligned");
     const size_t cells = (size_t)batch * n_rows * n_cols;
-    const DSpan in[4] = {{nodes, cells * 4}, {du, cells * 8}, {dv, cells * 8}, {dval, cells}};
-    const DSpan out[3] = {{u, cells * 8}, {v, cells * 8}, {invalid, cells}};
-    if (deform_aliased(in, 4, out, 3)) return fail(TPIV_EINVAL, "tpiv_deform_combine: an output overlaps an input or another output");
+    const Span in[4] = {{nodes, cells * 4}, {du, cells * 8}, {dv, cells * 8}, {dval, cells}};
+    const Span out[3] = {{u, cells * 8}, {v, cells * 8}, {invalid, cells}};
+    if (aliased(in, 4, out, 3)) return fail(TPIV_EINVAL, "tpiv_deform_combine: an output overlaps an input or another output");
     HIP_TRY(tpiv::launch_deform_combine(nodes, du, dv, dval, cells, u, v, invalid, (hipStream_t)stream));
     return TPIV_OK;
 }
@@ -1163,9 +1135,7 @@ int tpiv_plan_set_deform(tpiv_plan* plan, int iterations, int interp, int smooth
     }
     if (int rc = check_deform_frame(plan->H, plan->W, g.ws, g.ov)) return rc;
     if (int rc = check_deform_grid("tpiv_plan_set_deform", plan->max_batch, g.n_rows, g.n_cols)) return rc;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+    if (int rc = check_plan_device(plan)) return rc;
     if (!plan->def_nodes) {                          // first time on: the workspace (kept until the plan is destroyed)
         const size_t n = (size_t)g.n_rows * g.n_cols * plan->max_batch, px = (size_t)plan->H * plan->W * plan->max_batch;
         int16_t *nodes = nullptr, *tab = nullptr;
@@ -1232,6 +1202,48 @@ int tpiv_plan_deform_ms(tpiv_plan* plan, double* ms) {
     return TPIV_OK;
 }
 
+namespace {
+// What a plan enqueues behind a stage, a pass or a deformation round, at geometry p: the mask step, the median test, the
+// mask step once more on what the test wrote (the header has the order and its reasons, at tpiv_plan_set_outlier,
+// tpiv_plan_set_mask and tpiv_plan_set_deform).  Built before the stage, it also says where the stage writes: with the test
+// on, what the test rewrites goes somewhere else, and the test puts it where the next reader or the caller expects it.
+//   feeds:            another stage reads u, v next: the predictor behind a pass, the next round's nodes behind a round;
+//                     the test then replaces the vectors, and otherwise only flags them in the caller's mask
+//   excluded_invalid: cells that the mask excludes stay invalid in what the stage hands on
+struct Settle {
+    const tpiv_plan* plan;
+    int p;
+    bool test, feeds, excluded_invalid;
+    double *u, *v;              // where the next reader or the caller expects the stage's fields ...
+    uint8_t* invalid;
+    double *wu, *wv;            // ... and where the stage writes them
+    uint8_t* wval;
+
+    Settle(const tpiv_plan* plan_, int p_, bool feeds_, bool excluded_invalid_, double* u_, double* v_, uint8_t* invalid_,
+           double* spare_u, double* spare_v)
+        : plan(plan_), p(p_), test(plan_->outlier_kind != 0), feeds(feeds_), excluded_invalid(excluded_invalid_), u(u_), v(v_),
+          invalid(invalid_), wu(test && feeds ? spare_u : u_), wv(test && feeds ? spare_v : v_),
+          wval(test && !feeds ? plan_->raw_val : invalid_) {}
+
+    int run(int batch, hipStream_t st) const {
+        const PassGeo& g = plan->geo[p];
+        const uint8_t* grid = plan->mask_on ? plan->mgrid[p] : nullptr;
+        auto mask = [&](double* mu, double* mv, uint8_t* mval, uint8_t* status, bool invalid_value) {
+            hipError_t he = tpiv::launch_mask_fields(mu, mv, mval, status, grid, batch, g.n_rows, g.n_cols, invalid_value, st);
+            return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_mask_fields");
+        };
+        if (grid)                   // excluded cells: zero vectors, and always invalid to the test
+            if (int rc = mask(wu, wv, wval, nullptr, test || excluded_invalid)) return rc;
+        if (!test) return TPIV_OK;
+        if (int rc = run_median_test(wu, wv, wval, batch, g.n_rows, g.n_cols, plan->outlier_threshold, plan->outlier_eps,
+                                     plan->outlier_min, plan->ostatus[p], feeds ? u : nullptr, feeds ? v : nullptr, 1,
+                                     feeds ? nullptr : invalid, st))
+            return rc;
+        return grid ? mask(u, v, invalid, plan->ostatus[p], excluded_invalid) : TPIV_OK;
+    }
+};
+}  // namespace
+
 // the rounds of a deforming plan behind its last pass (tpiv_plan_set_deform has the order of the steps)
 static int run_deform(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch, double* u, double* v, uint8_t* invalid,
                       void* stream) {
@@ -1239,10 +1251,10 @@ static int run_deform(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int b
     const int last = plan->n_pass - 1;
     const PassGeo& g = plan->geo[last];
     const size_t cells = (size_t)batch * g.n_rows * g.n_cols;
-    const bool test = plan->outlier_kind != 0, masked = plan->mask_on;
     HIP_TRY(hipEventRecord(plan->def_ev[0], st));
     for (int k = 1; k <= plan->def_iters; ++k) {
-        const bool final = k == plan->def_iters;
+        // excluded cells stay valid behind every round, so that they pull the warp to zero at a wall
+        const Settle settle(plan, last, k < plan->def_iters, false, u, v, invalid, plan->def_su, plan->def_sv);
         HIP_TRY(tpiv::launch_deform_nodes(u, v, invalid, batch, g.n_rows, g.n_cols, plan->def_smooth, plan->def_nodes, st));
         tpiv::DeformWarpParams q{};
         q.A = a;
@@ -1264,22 +1276,9 @@ static int run_deform(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int b
                                 plan->precision, plan->def_du, plan->def_dv, plan->def_dval, plan->peak_raw,
                                 plan->peak_raw_bytes, nullptr, nullptr, stream))
             return rc;
-        // with the median test on, the combine writes what the test replaces somewhere else, as the tile kernels of a pass do
-        double* cu = (test && !final) ? plan->def_su : u;
-        double* cv = (test && !final) ? plan->def_sv : v;
-        uint8_t* cval = (test && final) ? plan->raw_val : invalid;
-        HIP_TRY(tpiv::launch_deform_combine(plan->def_nodes, plan->def_du, plan->def_dv, plan->def_dval, cells, cu, cv, cval, st));
-        if (masked)
-            HIP_TRY(tpiv::launch_mask_fields(cu, cv, cval, nullptr, plan->mgrid[last], batch, g.n_rows, g.n_cols, test ? 1 : 0, st));
-        if (test) {
-            if (int rc = run_median_test(cu, cv, cval, batch, g.n_rows, g.n_cols, plan->outlier_threshold, plan->outlier_eps,
-                                         plan->outlier_min, plan->ostatus[last], final ? nullptr : u, final ? nullptr : v, 1,
-                                         final ? invalid : nullptr, st))
-                return rc;
-            if (masked)
-                HIP_TRY(tpiv::launch_mask_fields(u, v, invalid, plan->ostatus[last], plan->mgrid[last], batch, g.n_rows,
-                                                 g.n_cols, 0, st));
-        }
+        HIP_TRY(tpiv::launch_deform_combine(plan->def_nodes, plan->def_du, plan->def_dv, plan->def_dval, cells, settle.wu,
+                                            settle.wv, settle.wval, st));
+        if (int rc = settle.run(batch, st)) return rc;
     }
     HIP_TRY(hipEventRecord(plan->def_ev[1], st));
     plan->def_ran = true;
@@ -1291,9 +1290,7 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
     if (!plan) return fail(TPIV_EINVAL, "null plan");
     if (batch < 0 || batch > plan->max_batch) return fail(TPIV_EINVAL, "batch exceeds the plan's max_batch");
     if (batch == 0) return TPIV_OK;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != plan->device) return fail(TPIV_EINVAL, "plan was created on another device");
+    if (int rc = check_plan_device(plan)) return rc;
     const int last = plan->n_pass - 1;
     plan->last_batch = batch;
     hipStream_t st = (hipStream_t)stream;
@@ -1303,20 +1300,11 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
     };
     for (int p = 0; p <= last; ++p) {
         const PassGeo& g = plan->geo[p];
-        double* pu = p == last ? u : plan->u[p];
-        double* pv = p == last ? v : plan->v[p];
-        uint8_t* pval = p == last ? invalid : plan->val[p];
-        // with the median test on, the tile kernels write what the test replaces somewhere else and the test writes it
-        // where the next stage reads it: the fields of a pass before the last, the mask of the last pass
-        const bool test = plan->outlier_kind != 0;
-        double *const fu = pu, *const fv = pv;
-        uint8_t* const fval = pval;
-        if (test && p < last) {
-            pu = plan->raw_u;
-            pv = plan->raw_v;
-        } else if (test) {
-            pval = plan->raw_val;
-        }
+        // a pass before the last keeps its fields in the plan for the predictor, to which excluded cells are invalid
+        const Settle settle(plan, p, p < last, p < last, p == last ? u : plan->u[p], p == last ? v : plan->v[p],
+                            p == last ? invalid : plan->val[p], plan->raw_u, plan->raw_v);
+        double *const pu = settle.wu, *const pv = settle.wv;
+        uint8_t* const pval = settle.wval;
         int rc;
         if (p == 0) {
             mark(0, 0);
@@ -1345,23 +1333,8 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
         }
         if (rc) return rc;
         // (what follows goes behind the closing event of the pass's timing slot: the slots keep their meaning)
-        const bool masked = plan->mask_on;
-        if (masked) {    // excluded cells: zero vectors, invalid to the predictor and to the test, valid to the post-validation
-            hipError_t he = tpiv::launch_mask_fields(pu, pv, pval, nullptr, plan->mgrid[p], batch, g.n_rows, g.n_cols,
-                                                     (test || p < last) ? 1 : 0, st);
-            if (he != hipSuccess) return hip_fail(he, "launch_mask_fields");
-        }
-        if (test) {
-            rc = run_median_test(pu, pv, pval, batch, g.n_rows, g.n_cols, plan->outlier_threshold, plan->outlier_eps,
-                                 plan->outlier_min, plan->ostatus[p], p < last ? fu : nullptr, p < last ? fv : nullptr, 1,
-                                 p < last ? nullptr : fval, st);
-            if (rc) return rc;
-            if (masked) {        // once more, on what the test wrote: the pass's fields or the caller's mask, and the status map
-                hipError_t he = tpiv::launch_mask_fields(fu, fv, fval, plan->ostatus[p], plan->mgrid[p], batch, g.n_rows,
-                                                         g.n_cols, p < last ? 1 : 0, st);
-                if (he != hipSuccess) return hip_fail(he, "launch_mask_fields");
-            }
-        }
+        rc = settle.run(batch, st);
+        if (rc) return rc;
     }
     if (plan->def_iters) {   // behind the last pass, its mask and outlier steps and the closing event of its timing slot
         if (int rc = run_deform(plan, a, b, batch, u, v, invalid, stream)) return rc;

@@ -7,6 +7,7 @@ otherwise -- there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -17,6 +18,12 @@ from ._lib import ITER_MODES, MODES, PRECISIONS, check, lib
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+@functools.lru_cache(maxsize=None)
+def _hip():
+    """The HIP runtime itself, opened at its first use: for copies out of arrays that a plan owns (Plan._copy_out)."""
+    return C.CDLL("libamdhip64.so")
 
 
 def _need_cuda(*tensors):
@@ -1376,34 +1383,22 @@ class Plan:
             check(lib.tpiv_plan_create(C.byref(self._h), H, W, ws, ov, n_pass, MODES.get(mode, 0),
                                        float(pass_scale), float(val_ratio), int(val_win),
                                        int(max_batch), prec))
-            if self.outlier is not None:
-                try:
+            try:
+                if self.outlier is not None:
                     check(lib.tpiv_plan_set_outlier(self._h, 1, self.outlier["threshold"], self.outlier["eps"],
                                                     self.outlier["min_neighbours"]))
-                except Exception:
-                    self.close()
-                    raise
-            if self.mask is not None:
-                try:
+                if self.mask is not None:
                     self.set_mask(self.mask["image"], self.mask["threshold"])
-                except Exception:
-                    self.close()
-                    raise
-            if self.uncertainty_par is not None:
-                try:
+                if self.uncertainty_par is not None:
                     check(lib.tpiv_plan_set_uncertainty(self._h, 1, self.uncertainty_par["radius"]))
-                except Exception:
-                    self.close()
-                    raise
-            if self.deform is not None:
-                try:
+                if self.deform is not None:
                     cubic = self.deform["interp"] == "cubic"
                     check(lib.tpiv_plan_set_deform(self._h, self.deform["iterations"], _lib.DEWARP_INTERPS[self.deform["interp"]],
                                                    1 if self.deform["smooth"] else 0,
                                                    _dewarp_table(self.device).data_ptr() if cubic else None))
-                except Exception:
-                    self.close()
-                    raise
+            except Exception:
+                self.close()
+                raise
         self.n_pass = lib.tpiv_plan_n_pass(self._h)
         self.geometry = []
         for p in range(self.n_pass):
@@ -1504,14 +1499,17 @@ class Plan:
             names += [f"pass{p + 1}_predict", f"pass{p + 1}_xcorr"]
         return dict(zip(names, list(arr))), runs.value
 
-    def _copy_out(self, pairs):
-        """Copies of plan-owned device arrays: [(destination tensor, source pointer, bytes)]; waits for the device."""
-        torch.cuda.synchronize(self.device)
-        hip = C.CDLL("libamdhip64.so")
-        for dst, src, nbytes in pairs:
-            rc = hip.hipMemcpy(C.c_void_p(dst.data_ptr()), src, C.c_size_t(nbytes), 3)  # D2D
-            if rc != 0:
-                raise _lib.HipError(f"hipMemcpy failed: {rc}")
+    def _copy_out(self, pairs, sync=True):
+        """Copies of plan-owned device arrays: [(destination tensor, source pointer, bytes)].  sync: waits for the device,
+        then copies; otherwise the copies are enqueued on the current stream, behind the run, and the host does not wait."""
+        if sync:
+            torch.cuda.synchronize(self.device)
+        with torch.cuda.device(self.device):
+            for dst, src, nbytes in pairs:
+                args = (C.c_void_p(dst.data_ptr()), src, C.c_size_t(nbytes), 3)      # 3: device to device
+                rc = _hip().hipMemcpy(*args) if sync else _hip().hipMemcpyAsync(*args, C.c_void_p(_stream()))
+                if rc != 0:
+                    raise _lib.HipError(f"{'hipMemcpy' if sync else 'hipMemcpyAsync'} failed: {rc}")
 
     def pass_fields(self, p, batch):
         """Fields pass p (< n_pass-1) left in the workspace by the last run (copies)."""
@@ -1532,11 +1530,7 @@ class Plan:
         check(lib.tpiv_plan_pass_outliers(self._h, self.n_pass - 1, C.byref(ps)))
         nr, nc = self.out_shape
         status = torch.empty(batch, nr, nc, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = C.CDLL("libamdhip64.so").hipMemcpyAsync(C.c_void_p(status.data_ptr()), ps, C.c_size_t(batch * nr * nc), 3,
-                                                          C.c_void_p(_stream()))      # D2D
-        if rc != 0:
-            raise _lib.HipError(f"hipMemcpyAsync failed: {rc}")
+        self._copy_out(((status, ps, batch * nr * nc),), sync=False)
         return (status & 1).sum(dim=(1, 2), dtype=torch.int32)
 
     def uncertainty(self, batch):
@@ -1550,13 +1544,7 @@ class Plan:
             raise ValueError(f"batch {batch} exceeds the plan's max_batch {self.max_batch}")
         su = torch.empty(batch, nr, nc, dtype=torch.float64, device=self.device)
         sv = torch.empty_like(su)
-        hip = C.CDLL("libamdhip64.so")
-        with torch.cuda.device(self.device):
-            for dst, src in ((su, psu), (sv, psv)):
-                rc = hip.hipMemcpyAsync(C.c_void_p(dst.data_ptr()), src, C.c_size_t(batch * nr * nc * 8), 3,
-                                        C.c_void_p(_stream()))      # D2D
-                if rc != 0:
-                    raise _lib.HipError(f"hipMemcpyAsync failed: {rc}")
+        self._copy_out(((su, psu, batch * nr * nc * 8), (sv, psv, batch * nr * nc * 8)), sync=False)
         return su, sv
 
     def deform_stage(self, batch):
