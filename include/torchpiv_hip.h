@@ -360,6 +360,62 @@ int tpiv_plan_deform_stage(const tpiv_plan* plan, int16_t** nodes_dev, uint8_t**
  * run of a deforming plan).  Waits for the closing event.  TPIV_EINVAL when the deformation is off or before the first run. */
 int tpiv_plan_deform_ms(tpiv_plan* plan, double* ms);
 
+/* ---- ensemble correlation (extension; the reference correlates pair by pair) -------------------------- */
+
+/* Sum-of-correlation PIV (Meinhart, Wereley & Santiago, J. Fluids Eng. 122 (2000) 285): the correlation maps of all pairs
+ * of a recording are added window by window and the peak of the summed map is taken once.  Window sizes 16, 32 and 64 (the
+ * tile kernels), mode 0 (first pass), TPIV_MODE_DWS or TPIV_MODE_CWS; any other size: TPIV_EUNSUPPORTED.
+ *   Map of pair i, window w, C_i[w], float32 [ws, ws] in fftshift layout, RAW -- before any minimum subtraction and before the
+ *   1e-7 of B:381: mode 0: the circular cross-correlation of a / mean(a) - 1 and b / mean(b) - 1 (B:513-514 without the
+ *   pedestal, which is a constant of the map), the ZERO map when the pixel sum of either window is 0; shifted modes: of the
+ *   windows staged at the half shift (u2, v2) exactly as tpiv_iter stages them at TPIV_PREC_FAST (flat-index clamp and
+ *   nearest-sample quirk included), minus their means, not normalised.  u2_dev, v2_dev float64 [n_rows, n_cols]: ONE half
+ *   shift per window for every pair (DWS: integral values); NULL for mode 0.
+ *   tpiv_ensemble_add: acc_dev float32 [n_rows * n_cols, ws, ws] (tpiv_ensemble_bytes bytes, 16-byte aligned, zeroed by the
+ *   caller before the first call) += C_0 + C_1 + ... + C_(batch-1), summed in float32 in ascending pair order by the one
+ *   wavefront that owns the window: no atomics, so the same sequence of calls gives the same bits.  16 x 16, 32 x 32 and
+ *   64 x 64 mode 0 / DWS form T = C_0 + ... + C_(batch-1) first and then acc <- acc + T; 64 x 64 CWS adds pair by pair,
+ *   acc <- (...((acc + C_0) + C_1)...).  batch == 0 succeeds and launches nothing.
+ *   tpiv_ensemble_peaks: M = acc / n_pairs (one float32 division per cell; n_pairs in 1..2^24) through the peak stage of
+ *   every pass -- M - min M + 1e-7, first arg-max, three-point log-Gaussian fit, peak-to-second-peak ratio against val_ratio
+ *   over the val_win neighbourhood, float64 epilogue: correlation_to_displacement (B:360-422) on M - min M.  Mode 0 writes
+ *   the displacement as u, v [n_rows, n_cols]; a shifted mode combines it with the predictor like tpiv_iter, u = 2 u2 + du
+ *   with the fallback to u0 where (du > u0 and rint(u0) > 0) or invalid; u0_dev .. v2_dev are tpiv_predict's outputs for a
+ *   batch of one, du_dev / dv_dev (optional) receive the raw displacement.  No window counts as dead here: a window whose
+ *   every contribution was the zero map has a constant M and comes out invalid with u = v = 0 (mode 0).
+ * work_dev: tpiv_work_bytes(H, W, ws, ov, 1) bytes, for either call.  Both enqueue only and allocate nothing.  TPIV_EINVAL:
+ * a null or misaligned accumulator, missing predictor fields, n_pairs out of range, a work buffer that is too small. */
+size_t tpiv_ensemble_bytes(int H, int W, int ws, int ov);
+int tpiv_ensemble_add(int mode, const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H, int W, int ws, int ov,
+                      const double* u2_dev, const double* v2_dev, float* acc_dev, void* work_dev, size_t work_bytes,
+                      void* stream);
+int tpiv_ensemble_peaks(int mode, const float* acc_dev, long long n_pairs, int H, int W, int ws, int ov,
+                        const double* u0_dev, const double* v0_dev, const double* u2_dev, const double* v2_dev,
+                        double val_ratio, int val_win, double* u_dev, double* v_dev, uint8_t* invalid_dev,
+                        double* du_dev, double* dv_dev, void* work_dev, size_t work_bytes, void* stream);
+
+/* Ensemble correlation of a plan: on != 0 allocates, at the first such call, one accumulator sized for the largest pass, a
+ * batch-1 field per pass and a predictor hand-off of its own (tpiv_plan_run in between disturbs nothing, and runs exactly
+ * as without this call).  TPIV_EUNSUPPORTED when a pass has a window size other than 16, 32, 64 (the message names it);
+ * TPIV_EINVAL on a plan with tpiv_plan_set_uncertainty or tpiv_plan_set_deform on -- and those refuse a plan with this on.
+ * The plan's precision has no effect on these calls: maps are float32, the peak epilogue float64.  Per pass p = 0 .. n_pass - 1:
+ *   tpiv_plan_ensemble_begin(p): zeroes the accumulator; p > 0: runs the plan's banded predictor ONCE, for a batch of one, on
+ *     the ensemble field of pass p - 1 -- one predictor, one mask, one half shift shared by every pair.  TPIV_EINVAL when pass
+ *     p - 1 has not been ended.
+ *   tpiv_plan_ensemble_add: tpiv_ensemble_add of batch <= max_batch pairs at the pass's geometry and mode, any number of times.
+ *   tpiv_plan_ensemble_end: tpiv_ensemble_peaks with the plan's val_ratio / val_win, then the settle step of tpiv_plan_run on
+ *     the batch of one -- tpiv_plan_set_mask and tpiv_plan_set_outlier act on an ensemble field exactly as on a pair's field
+ *     of that pass (a pass before the last: excluded cells invalid, flagged vectors replaced by the medians; last pass:
+ *     excluded cells valid zeros, invalid |= flag).  u_dev, v_dev, invalid_dev [n_rows, n_cols] of that pass receive the
+ *     field; a pass before the last also keeps it in the plan for the next begin.  TPIV_EINVAL with no pair added, or before
+ *     begin.
+ * A failed call changes nothing.  tpiv_plan_ensemble_maps (tests): the accumulator and the pairs added since begin. */
+int tpiv_plan_set_ensemble(tpiv_plan* plan, int on);
+int tpiv_plan_ensemble_begin(tpiv_plan* plan, int pass, void* stream);
+int tpiv_plan_ensemble_add(tpiv_plan* plan, const uint8_t* a_dev, const uint8_t* b_dev, int batch, void* stream);
+int tpiv_plan_ensemble_end(tpiv_plan* plan, double* u_dev, double* v_dev, uint8_t* invalid_dev, void* stream);
+int tpiv_plan_ensemble_maps(tpiv_plan* plan, float** acc_dev, long long* n_pairs);
+
 /* ---- post-validation (B:884-892) ------------------------------------------------- */
 
 /* Device part of the reference's per-pair host post-processing, for a whole batch:

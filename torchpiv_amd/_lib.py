@@ -91,6 +91,15 @@ SIGNATURES = {
     "tpiv_plan_set_deform": (C.c_int, [C.c_void_p, _int, _int, _int, _vp]),
     "tpiv_plan_deform_stage": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
     "tpiv_plan_deform_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "tpiv_ensemble_bytes": (C.c_size_t, [_int, _int, _int, _int]),
+    "tpiv_ensemble_add": (C.c_int, [_int, _u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _f32p, _vp, C.c_size_t, _vp]),
+    "tpiv_ensemble_peaks": (C.c_int, [_int, _f32p, C.c_longlong, _int, _int, _int, _int, _f64p, _f64p, _f64p, _f64p, _dbl, _int,
+                                      _f64p, _f64p, _u8p, _f64p, _f64p, _vp, C.c_size_t, _vp]),
+    "tpiv_plan_set_ensemble": (C.c_int, [C.c_void_p, _int]),
+    "tpiv_plan_ensemble_begin": (C.c_int, [C.c_void_p, _int, _vp]),
+    "tpiv_plan_ensemble_add": (C.c_int, [C.c_void_p, _u8p, _u8p, _int, _vp]),
+    "tpiv_plan_ensemble_end": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _vp]),
+    "tpiv_plan_ensemble_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
     "tpiv_postval": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _u8p, _vp, _vp]),
     "tpiv_postval_compact": (C.c_int, [_f64p, _f64p, _u8p, _vp, _int, _int, _int, _vp, _vp, _f64p, _vp, _vp]),
     "tpiv_finish_fields": (C.c_int, [_f64p, _f64p, _int, _int, _int, C.c_double, C.c_double, _f64p, _f64p, _vp]),

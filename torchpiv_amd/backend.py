@@ -483,6 +483,7 @@ class OfflinePIV:
         self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
         self._bg_frames = None           # ResidentPIV: the frames of a launch minus the background / filtered, uint8 [2, batch, H, W], reused
         self._plan = None
+        self._ens_plan = None            # the plan of ensemble(), made on first use
         self._single_plans = {}          # plans of the one-pair path, per frame shape
         self._reader = None              # the ReadAhead of the latest run over files (closed when that run ended)
         self._stage, self._stage_key = None, None            # pinned staging buffers, kept from call to call
@@ -771,6 +772,107 @@ class OfflinePIV:
             torch.cuda.synchronize(dev)
         return acc[0], acc[1]
 
+    def _ensemble_plan(self, H, W, max_batch):
+        """The plan of ensemble(): this object's passes with ensemble=True, kept like the plan of batched()."""
+        plan = self._ens_plan
+        if plan is None or (plan.H, plan.W) != (H, W) or plan.max_batch < max_batch:
+            if plan is not None:
+                plan.close()
+            plan = self._ens_plan = engine.Plan(
+                H, W, int(self._wind_size), int(self._overlap), n_pass=max(1, int(self._iter)), mode=self._mode,
+                pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio, val_win=self._val_win,
+                device=self._device, precision=self._precision, outlier=self._outlier, mask=self._mask, ensemble=True)
+        return plan
+
+    def _ensemble_check(self):
+        engine.ensemble_check([w for w, _ in engine.pass_sizes(self._wind_size, self._overlap, self._iter, self._iter_scale)],
+                              self._uncertainty, self._deform)
+
+    def _frame_batches(self, idx, batch_size, H, W):
+        """The prepared frames of the pairs idx, batch_size at a time, as (A, B) uint8 [n, H, W] on the device: read through
+        the native read-ahead ring, unpacked on the device and taken through the preparation steps exactly as batched()
+        takes them (tone map, rectification, background, pre-filter, equalize, mask pixels).  Pairs that cannot be decoded
+        or have another frame shape are left out, as compute_background() leaves them out.  The stacks live in buffers
+        of this object that the next batch overwrites: the consumer enqueues its work on the current stream before it
+        asks for the next one."""
+        dev = self._device
+        lut = self._depth_table()
+        deep = lut is not None
+        dewarp = self._dewarp is not None
+        if dewarp:
+            self._dewarp_shape((H, W))
+        bg = self._background((H, W), batch_size)
+        pairs = self._dataset.img_pairs
+        first = self._first_decodable(idx)
+        cap = slot_bytes(H, W, pairs[first[0]] if first is not None else (), deep=deep)
+        stage, raw_dev = self._staging(batch_size, cap)
+        raw_all = raw_dev[0]
+        cur = torch.cuda.current_stream(dev)
+        batches = StagedBatches(idx, pairs, batch_size, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads,
+                                deep=deep)
+        self._reader = batches.reader
+        try:
+            for st in batches:
+                n = len(st.chunk)
+                if n:
+                    raw_d = raw_all[:st.n_files]
+                    raw_d.copy_(stage[st.buf][:st.n_files], non_blocking=True)
+                    if deep:
+                        frames = self._map_staged(raw_d, st, H, W, lut, batch_size)
+                    else:
+                        desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
+                        lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
+                        frames = engine.bmp_unpack(raw_all.view(-1), desc_d, lut_d, H, W, background=None if dewarp else bg)
+                    if dewarp:
+                        frames = self._dewarped(frames, self._scratch("_dw_frames", (2 * batch_size,), H, W, frames.device)[:2 * n])
+                    dst = frames if self._prefilter is None else \
+                        self._scratch("_pf_frames", (2 * batch_size,), H, W, frames.device)[:2 * n]
+                    if (deep or dewarp) and bg is not None:
+                        self._filtered(frames[:n], bg[0], out=dst[:n])
+                        self._filtered(frames[n:], bg[1], out=dst[n:])
+                        frames = dst
+                    else:
+                        frames = self._filtered(frames, None, out=dst)
+                    frames = self._finished(frames, True)
+                    yield frames[:n], frames[n:]
+                    cur.synchronize()           # upload and consumer are through: staging and frame buffers may be refilled
+                batches.release()
+        finally:
+            batches.close()
+            torch.cuda.synchronize(dev)
+
+    def ensemble(self, indices=None, batch_size: int = 32):
+        """Ensemble (sum-of-correlation) PIV over the pairs `indices` (None: all): ONE field (x, y, u, v) from the summed
+        correlation maps of all of them (Meinhart, Wereley & Santiago 2000), for recordings too sparsely seeded for single
+        pairs.  Every pass adds the maps of all pairs window by window and takes the peak of the mean map once; later
+        passes shift every pair's windows by the one predictor of the ensemble field before (engine.Plan.run_ensemble).
+        The frames go through the preparation steps of batched(); a recording on disk is read once per pass.  outlier=
+        and the grid of mask= apply through the plan, pass by pass, as they do to a pair's fields.  The tuple is finished
+        like those of __call__: post-validation (holes filled from their ring), flip, sign, scale / dt -- except that a
+        field without a single invalid vector is delivered as it is (the reference drops such a PAIR, B:300-304; for an
+        ensemble it is the expected result).  None when the post-validation drops the field (a quarter of the cells or
+        more in the ring) or no pair could be read.  Window sizes 16, 32, 64 in every pass (NotImplementedError);
+        ValueError with uncertainty= or deform=.  precision= plays no part: the maps are float32."""
+        self._ensemble_check()
+        idx = list(range(len(self._dataset))) if indices is None else list(indices)
+        first = self._first_decodable(idx) if idx else None
+        if first is None:
+            return None
+        H, W = first[1]
+        batch_size = int(batch_size)
+        plan = self._ensemble_plan(H, W, batch_size)
+        u, v, inv = plan.run_ensemble(lambda: self._frame_batches(idx, batch_size, H, W))
+        return self._ensemble_finish(plan, (H, W), u, v, inv)
+
+    def _ensemble_finish(self, plan, shape, u, v, inv):
+        w, o, _, _ = plan.geometry[-1]
+        x, y = get_coordinates(shape, w, o)
+        if not bool(inv.any()):
+            uv = (u[0].cpu().numpy(), v[0].cpu().numpy())       # nothing to fill, nothing on the border to interpolate
+        else:
+            uv = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)[0]
+        return self._finish(uv, x, y, plan=plan)
+
     def reset_stats(self):
         """Counters of the post-validation: pairs seen, dropped for 'no invalid vector' / 'too many
         false vectors' (decided on the device), finished on the device alone, sent to the host
@@ -821,6 +923,9 @@ class OfflinePIV:
         if self._plan is not None:
             self._plan.close()
             self._plan = None
+        if self._ens_plan is not None:
+            self._ens_plan.close()
+            self._ens_plan = None
         if self._reader is not None:
             self._reader.close()
             self._reader = None
@@ -1408,6 +1513,40 @@ class ResidentPIV(OfflinePIV):
             # host work of the previous batches overlaps this batch's kernels
             yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan)))
         yield from emit(pipe.flush())
+
+    def _frame_batches(self, idx, batch_size, H, W):
+        """The prepared frames of the pairs idx, batch_size at a time, as (A, B) uint8 [n, H, W]: the steps of batched(),
+        into the same reused buffers (the consumer enqueues its work before it asks for the next batch)."""
+        lut = self._depth_table()
+        dbuf = None if lut is None else self._scratch("_depth_frames", (2, batch_size), H, W, self._A.device)
+        bg = self._background((H, W))
+        dw = None if self._dewarp is None else self._scratch("_dw_frames", (2, batch_size), H, W, self._A.device)
+        bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
+        buf = None
+        if bg is not None or self._prefilter is not None \
+                or ((self._equalize is not None or self._zeroes_pixels()) and lut is None and dw is None):
+            buf = self._scratch("_bg_frames", (2, batch_size), H, W, self._A.device)
+        for s in range(0, len(idx), batch_size):
+            chunk = idx[s:s + batch_size]
+            n = len(chunk)
+            A, B, owned = self._select(chunk, lut, out=None if dbuf is None else (dbuf[0, :n], dbuf[1, :n]), dw=dw)
+            out_a, out_b = (None, None) if buf is None else (buf[0, :n], buf[1, :n])
+            fa, fb = self._filtered(A, bg_a, out=out_a), self._filtered(B, bg_b, out=out_b)
+            owned |= fa is not A
+            yield self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b)
+
+    def ensemble(self, indices=None, batch_size: int = 32):
+        """OfflinePIV.ensemble over the resident pairs: one (x, y, u, v) from the summed correlation maps of the pairs
+        `indices` (None: all)."""
+        self._ensemble_check()
+        idx = list(range(len(self))) if indices is None else list(indices)
+        if not idx:
+            return None
+        H, W = self._A.shape[1:]
+        batch_size = int(batch_size)
+        plan = self._ensemble_plan(H, W, batch_size)
+        u, v, inv = plan.run_ensemble(lambda: self._frame_batches(idx, batch_size, H, W))
+        return self._ensemble_finish(plan, (H, W), u, v, inv)
 
     def __call__(self) -> Generator:
         for out in self.batched(1):

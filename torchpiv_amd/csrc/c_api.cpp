@@ -270,6 +270,17 @@ struct tpiv_plan {
     double *def_su = nullptr, *def_sv = nullptr;             // a round before the last combines here when the median test is on
     hipEvent_t def_ev[2] = {nullptr, nullptr};               // around the rounds of a run
     bool def_ran = false;
+    // ensemble correlation (tpiv_plan_set_ensemble); off: nothing below is allocated.  One accumulator sized for the largest
+    // pass; the batch-1 fields of every pass and the shared predictor hand-off of their own, so that tpiv_plan_run in between
+    // disturbs nothing
+    bool ens_on = false;
+    float* ens_acc = nullptr;
+    std::vector<double*> ens_u, ens_v;   // per pass: [N_p], the ensemble field as its settle step left it
+    std::vector<uint8_t*> ens_val;
+    double *ens_u0 = nullptr, *ens_v0 = nullptr;
+    uint8_t* ens_pmask = nullptr;
+    int ens_pass = -1, ens_done = -1;    // the pass between begin and end; the highest pass ended
+    long long ens_pairs = 0;             // pairs added since begin
     std::vector<void*> allocs;
     // optional per-kernel timing: events[run][2*slot + {0,1}]
     bool timing = false;
@@ -1007,6 +1018,7 @@ int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius) {
         plan->unc_kind = 0;
         return TPIV_OK;
     }
+    if (plan->ens_on) return fail(TPIV_EINVAL, "uncertainty= does not combine with ensemble correlation");
     const PassGeo& g = plan->geo[plan->n_pass - 1];
     if (int rc = check_uncertainty(plan->H, plan->W, g.ws, g.ov, radius)) return rc;
     if (!plan->unc_su) {                             // first time on: the two fields (kept until the plan is destroyed)
@@ -1126,6 +1138,7 @@ int tpiv_plan_set_deform(tpiv_plan* plan, int iterations, int interp, int smooth
         plan->def_iters = 0;
         return TPIV_OK;
     }
+    if (plan->ens_on) return fail(TPIV_EINVAL, "deform= does not combine with ensemble correlation");
     if (interp != TPIV_DEWARP_LINEAR && interp != TPIV_DEWARP_CUBIC) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: unknown interp");
     if (interp == TPIV_DEWARP_CUBIC && !table) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: the cubic interpolation needs its table");
     const PassGeo& g = plan->geo[plan->n_pass - 1];
@@ -1349,6 +1362,211 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
             return rc;
     }
     if (plan->timing && plan->runs_recorded < 512) plan->runs_recorded++;
+    return TPIV_OK;
+}
+
+// ---- ensemble correlation -------------------------------------------------------------------------------------------
+
+static int check_ensemble(const char* who, int mode, int H, int W, int ws, int ov, int val_win) {
+    if (mode != 0 && mode != TPIV_MODE_DWS && mode != TPIV_MODE_CWS)
+        return fail(TPIV_EKEY, std::string(who) + ": mode must be 0 (pass 1), TPIV_MODE_DWS or TPIV_MODE_CWS");
+    if (int rc = check_window(H, W, ws, ov, val_win)) return rc;
+    if (!tpiv::ensemble_size(ws))
+        return fail(TPIV_EUNSUPPORTED, std::string(who) + ": ensemble correlation covers window sizes 16, 32 and 64 (got " +
+                                           std::to_string(ws) + ")");
+    return TPIV_OK;
+}
+
+size_t tpiv_ensemble_bytes(int H, int W, int ws, int ov) {
+    if (ov >= ws || ws > H || ws > W || ws <= 0 || ov < 0 || !tpiv::ensemble_size(ws)) return 0;
+    int nr, nc;
+    field_shape(H, W, ws, ov, &nr, &nc);
+    return (size_t)nr * nc * ws * ws * sizeof(float);
+}
+
+static int ensemble_add_impl(int mode, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
+                             const double* u0, const double* v0, const double* u2, const double* v2, const uint8_t* pmask,
+                             float* acc, void* work, size_t work_bytes, void* stream) {
+    if (int rc = check_ensemble("tpiv_ensemble_add", mode, H, W, ws, ov, 0)) return rc;
+    if (batch < 0) return fail(TPIV_EINVAL, "tpiv_ensemble_add: negative batch");
+    if (!acc || ((uintptr_t)acc & 15)) return fail(TPIV_EINVAL, "tpiv_ensemble_add: acc missing or not 16-byte aligned");
+    if (batch == 0) return TPIV_OK;
+    if (!a || !b) return fail(TPIV_EINVAL, "tpiv_ensemble_add: frames missing");
+    if (mode != 0 && !pmask && (!u2 || !v2)) return fail(TPIV_EINVAL, "tpiv_ensemble_add: a shifted pass needs u2 / v2");
+    tpiv::PassParams p = pass_params(a, b, batch, H, W, ws, ov, 1.2, 3, TPIV_PREC_FAST, nullptr, nullptr, nullptr, nullptr, nullptr);
+    p.u0 = u0;
+    p.v0 = v0;
+    p.u2 = u2;
+    p.v2 = v2;
+    p.pmask = pmask;
+    if (int rc = check_work(work, work_bytes, tpiv::ensemble_work_bytes(p.n_rows * p.n_cols))) return rc;
+    p.peak_raw = static_cast<float*>(work);
+    int n_cu;
+    if (int rc = n_cu_of_current_device(&n_cu)) return rc;
+    HIP_TRY(tpiv::launch_ensemble_add(p, mode, acc, n_cu, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+static int ensemble_peaks_impl(int mode, const float* acc, long long n_pairs, int H, int W, int ws, int ov, const double* u0,
+                               const double* v0, const double* u2, const double* v2, const uint8_t* pmask, double val_ratio,
+                               int val_win, double* u, double* v, uint8_t* invalid, double* du, double* dv, void* work,
+                               size_t work_bytes, void* stream) {
+    if (int rc = check_ensemble("tpiv_ensemble_peaks", mode, H, W, ws, ov, val_win)) return rc;
+    if (n_pairs < 1 || n_pairs > (1LL << 24))
+        return fail(TPIV_EINVAL, "tpiv_ensemble_peaks: n_pairs must be in 1..2^24 (no pairs were added?)");
+    if (!acc || ((uintptr_t)acc & 15)) return fail(TPIV_EINVAL, "tpiv_ensemble_peaks: acc missing or not 16-byte aligned");
+    if (!u || !v || !invalid) return fail(TPIV_EINVAL, "tpiv_ensemble_peaks: output missing");
+    if (mode != 0 && (!u0 || !v0 || (!pmask && (!u2 || !v2))))
+        return fail(TPIV_EINVAL, "tpiv_ensemble_peaks: a shifted pass needs u0, v0, u2, v2");
+    tpiv::PassParams p = pass_params(nullptr, nullptr, 1, H, W, ws, ov, val_ratio, val_win, TPIV_PREC_FAST, u, v, invalid, nullptr,
+                                     nullptr);
+    p.u0 = u0;
+    p.v0 = v0;
+    p.u2 = u2;
+    p.v2 = v2;
+    p.pmask = pmask;
+    p.du = mode != 0 ? du : nullptr;
+    p.dv = mode != 0 ? dv : nullptr;
+    if (p.du && !p.dv) return fail(TPIV_EINVAL, "tpiv_ensemble_peaks: du without dv");
+    if (int rc = check_work(work, work_bytes, tpiv::ensemble_work_bytes(p.n_rows * p.n_cols))) return rc;
+    p.peak_raw = static_cast<float*>(work);
+    int n_cu;
+    if (int rc = n_cu_of_current_device(&n_cu)) return rc;
+    HIP_TRY(tpiv::launch_ensemble_peaks(p, mode, acc, n_pairs, n_cu, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_ensemble_add(int mode, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov, const double* u2,
+                      const double* v2, float* acc, void* work, size_t work_bytes, void* stream) {
+    return ensemble_add_impl(mode, a, b, batch, H, W, ws, ov, nullptr, nullptr, u2, v2, nullptr, acc, work, work_bytes, stream);
+}
+
+int tpiv_ensemble_peaks(int mode, const float* acc, long long n_pairs, int H, int W, int ws, int ov, const double* u0,
+                        const double* v0, const double* u2, const double* v2, double val_ratio, int val_win, double* u, double* v,
+                        uint8_t* invalid, double* du, double* dv, void* work, size_t work_bytes, void* stream) {
+    return ensemble_peaks_impl(mode, acc, n_pairs, H, W, ws, ov, u0, v0, u2, v2, nullptr, val_ratio, val_win, u, v, invalid, du,
+                               dv, work, work_bytes, stream);
+}
+
+int tpiv_plan_set_ensemble(tpiv_plan* plan, int on) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!on) {                       // (the workspace stays: a plan frees at its destruction)
+        plan->ens_on = false;
+        plan->ens_pass = plan->ens_done = -1;
+        return TPIV_OK;
+    }
+    if (plan->unc_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with uncertainty=");
+    if (plan->def_iters) return fail(TPIV_EINVAL, "ensemble correlation does not combine with deform=");
+    size_t cells = 0, fine = 0;
+    for (const PassGeo& g : plan->geo) {
+        if (!tpiv::ensemble_size(g.ws))
+            return fail(TPIV_EUNSUPPORTED, "ensemble correlation covers window sizes 16, 32 and 64; this plan has a pass of " +
+                                               std::to_string(g.ws));
+        const size_t N = (size_t)g.n_rows * g.n_cols;
+        cells = std::max(cells, N * g.ws * g.ws);
+        fine = std::max(fine, N);
+    }
+    if (int rc = check_plan_device(plan)) return rc;
+    if (!plan->ens_acc) {
+        if (tpiv::ensemble_work_bytes((int)fine) > plan->peak_raw_bytes)
+            return fail(TPIV_EINVAL, "plan workspace smaller than the ensemble launches need");     // (never: same records)
+        int rc = plan->alloc(&plan->ens_acc, cells);
+        plan->ens_u.assign(plan->n_pass, nullptr);
+        plan->ens_v.assign(plan->n_pass, nullptr);
+        plan->ens_val.assign(plan->n_pass, nullptr);
+        for (int p = 0; p < plan->n_pass && !rc; ++p) {
+            const size_t N = (size_t)plan->geo[p].n_rows * plan->geo[p].n_cols;
+            rc = plan->alloc(&plan->ens_u[p], N);
+            if (!rc) rc = plan->alloc(&plan->ens_v[p], N);
+            if (!rc) rc = plan->alloc(&plan->ens_val[p], N);
+        }
+        if (!rc && plan->n_pass > 1) {
+            rc = plan->alloc(&plan->ens_u0, fine);
+            if (!rc) rc = plan->alloc(&plan->ens_v0, fine);
+            if (!rc) rc = plan->alloc(&plan->ens_pmask, fine);
+        }
+        if (rc) {
+            plan->ens_acc = nullptr;       // (what was allocated stays in allocs and is freed with the plan)
+            return rc;
+        }
+    }
+    plan->ens_on = true;
+    plan->ens_pass = plan->ens_done = -1;
+    plan->ens_pairs = 0;
+    return TPIV_OK;
+}
+
+int tpiv_plan_ensemble_begin(tpiv_plan* plan, int pass, void* stream) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!plan->ens_on) return fail(TPIV_EINVAL, "ensemble correlation is off (tpiv_plan_set_ensemble)");
+    if (pass < 0 || pass >= plan->n_pass) return fail(TPIV_EINVAL, "bad pass index");
+    if (pass > 0 && plan->ens_done < pass - 1)
+        return fail(TPIV_EINVAL, "ensemble pass " + std::to_string(pass) + " begins before pass " + std::to_string(pass - 1) +
+                                     " was ended");
+    if (int rc = check_plan_device(plan)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const PassGeo& g = plan->geo[pass];
+    HIP_TRY(hipMemsetAsync(plan->ens_acc, 0, (size_t)g.n_rows * g.n_cols * g.ws * g.ws * sizeof(float), st));
+    if (pass > 0) {
+        if (int rc = run_banded_predict(plan, pass, 1, plan->ens_u[pass - 1], plan->ens_v[pass - 1], plan->ens_val[pass - 1],
+                                        plan->ens_u0, plan->ens_v0, nullptr, nullptr, st, plan->ens_pmask))
+            return rc;
+    }
+    plan->ens_pass = pass;
+    plan->ens_pairs = 0;
+    return TPIV_OK;
+}
+
+int tpiv_plan_ensemble_add(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch, void* stream) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!plan->ens_on || plan->ens_pass < 0) return fail(TPIV_EINVAL, "tpiv_plan_ensemble_add before tpiv_plan_ensemble_begin");
+    if (batch < 0 || batch > plan->max_batch) return fail(TPIV_EINVAL, "batch exceeds the plan's max_batch");
+    if (batch == 0) return TPIV_OK;
+    if (plan->ens_pairs + batch > (1LL << 24)) return fail(TPIV_EINVAL, "more than 2^24 pairs in one ensemble");
+    if (int rc = check_plan_device(plan)) return rc;
+    const int p = plan->ens_pass;
+    const PassGeo& g = plan->geo[p];
+    if (int rc = ensemble_add_impl(p == 0 ? 0 : plan->mode, a, b, batch, plan->H, plan->W, g.ws, g.ov, plan->ens_u0, plan->ens_v0,
+                                   nullptr, nullptr, p == 0 ? nullptr : plan->ens_pmask, plan->ens_acc, plan->peak_raw,
+                                   plan->peak_raw_bytes, stream))
+        return rc;
+    plan->ens_pairs += batch;
+    return TPIV_OK;
+}
+
+int tpiv_plan_ensemble_end(tpiv_plan* plan, double* u, double* v, uint8_t* invalid, void* stream) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!plan->ens_on || plan->ens_pass < 0) return fail(TPIV_EINVAL, "tpiv_plan_ensemble_end before tpiv_plan_ensemble_begin");
+    if (plan->ens_pairs < 1) return fail(TPIV_EINVAL, "tpiv_plan_ensemble_end: no pairs were added");
+    if (!u || !v || !invalid) return fail(TPIV_EINVAL, "tpiv_plan_ensemble_end: output missing");
+    if (int rc = check_plan_device(plan)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int p = plan->ens_pass, last = plan->n_pass - 1;
+    const PassGeo& g = plan->geo[p];
+    const size_t N = (size_t)g.n_rows * g.n_cols;
+    // as in tpiv_plan_run, on a batch of one: a pass before the last keeps its field in the plan for the next begin
+    const Settle settle(plan, p, p < last, p < last, p == last ? u : plan->ens_u[p], p == last ? v : plan->ens_v[p],
+                        p == last ? invalid : plan->ens_val[p], plan->raw_u, plan->raw_v);
+    if (int rc = ensemble_peaks_impl(p == 0 ? 0 : plan->mode, plan->ens_acc, plan->ens_pairs, plan->H, plan->W, g.ws, g.ov,
+                                     plan->ens_u0, plan->ens_v0, nullptr, nullptr, p == 0 ? nullptr : plan->ens_pmask,
+                                     plan->val_ratio, plan->val_win, settle.wu, settle.wv, settle.wval, nullptr, nullptr,
+                                     plan->peak_raw, plan->peak_raw_bytes, stream))
+        return rc;
+    if (int rc = settle.run(1, st)) return rc;
+    if (p < last) {
+        HIP_TRY(hipMemcpyAsync(u, plan->ens_u[p], N * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(v, plan->ens_v[p], N * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(invalid, plan->ens_val[p], N, hipMemcpyDeviceToDevice, st));
+    }
+    plan->ens_done = p;
+    plan->ens_pass = -1;
+    return TPIV_OK;
+}
+
+int tpiv_plan_ensemble_maps(tpiv_plan* plan, float** acc, long long* n_pairs) {
+    if (!plan || !plan->ens_on) return fail(TPIV_EINVAL, "ensemble correlation is off (tpiv_plan_set_ensemble)");
+    if (acc) *acc = plan->ens_acc;
+    if (n_pairs) *n_pairs = plan->ens_pairs;
     return TPIV_OK;
 }
 

@@ -344,6 +344,13 @@ bool exact_refine_size(int ws);
 size_t exact_fallback_count_offset(int batch, int n_windows);
 // test hook: peak stage + finalize on caller-made maps; planar selects the LDS layout variant of the tile kernel
 hipError_t launch_peaks_from_maps(const PassParams& p, const float* maps, int n_maps, int planar, hipStream_t stream);
+// ensemble correlation (xcorr_ens.hip, defined in include/torchpiv_hip.h: tpiv_ensemble_add / _peaks): window sizes 16, 32, 64;
+// both launches work in PassParams::peak_raw of ensemble_work_bytes(n_windows) bytes
+bool ensemble_size(int ws);
+size_t ensemble_work_bytes(int n_windows);
+hipError_t launch_ensemble_add(const PassParams& p, int mode, float* acc, int n_cu, hipStream_t stream);
+hipError_t launch_ensemble_peaks(const PassParams& p, int mode, const float* acc, long long n_pairs, int n_cu,
+                                 hipStream_t stream);
 hipError_t launch_predict_mfma(const BandedPredictParams& q, hipStream_t stream);
 hipError_t launch_predict(const PredictParams& q, hipStream_t stream);
 

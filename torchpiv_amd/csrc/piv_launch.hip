@@ -34,6 +34,8 @@ hipError_t launch_xcorr_cand_ws128(const PassParams& p, int n_cu, hipStream_t st
 hipError_t launch_exact_refine(const PassParams& p, int n_cu, hipStream_t stream);                    // xcorr_exact.hip
 bool exact_refine_size(int ws);                                                             // every even size 8 ... 128
 hipError_t launch_xcorr_f64_list(const PassParams& p, int n_cu, hipStream_t stream);        // xcorr_f64.hip
+hipError_t launch_xcorr_ens(const PassParams& p, int mode, float* acc, int n_cu, hipStream_t stream);       // xcorr_ens.hip
+hipError_t launch_peak_ens(const PassParams& p, const float* acc, int n_maps, long long n_pairs, hipStream_t stream);
 
 // ---- finalize: sub-pixel fit, validation and multipass combine, one thread per window -----------
 // PIVbackend.py:385-422 (correlation_to_displacement) and B:728-738 / B:800-810 (combine).  Input:
@@ -375,6 +377,45 @@ hipError_t launch_xcorr(const PassParams& p_in, int mode, int n_cu, hipStream_t 
     if (blocks > (size_t)n_cu * 32) blocks = (size_t)n_cu * 32;
     if (f64) hipLaunchKernelGGL(finalize_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
     else hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
+    return hipGetLastError();
+}
+
+// ---- ensemble correlation (xcorr_ens.hip): accumulate raw maps, then one peak stage on the mean map ----------------
+bool ensemble_size(int ws) { return ws == 16 || ws == 32 || ws == 64; }
+// work buffer of both launches: the peak records of ONE field, the tile kernels' item counters behind them
+size_t ensemble_work_bytes(int n_windows) { return work_ctr_offset(1, n_windows) + WORK_CTR_BYTES; }
+
+// acc [N, ws, ws] += the raw maps of the p.batch pairs of p.A / p.B; p.peak_raw: ensemble_work_bytes.  Shifted passes read
+// the predictor (either form of PassParams) by window: one field for every pair.
+hipError_t launch_ensemble_add(const PassParams& p_in, int mode, float* acc, int n_cu, hipStream_t stream) {
+    if (!ensemble_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) return hipErrorInvalidValue;
+    PassParams p = p_in;
+    p.precision = 0;
+    p.list_mode = 0;
+    p.slow_list = nullptr;
+    p.slow_count = nullptr;
+    p.dbg_win = p.dbg_corr = nullptr;
+    p.work_ctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.peak_raw) + work_ctr_offset(1, p.n_rows * p.n_cols));
+    hipError_t e = hipMemsetAsync(p.work_ctr, 0, WORK_CTR_BYTES, stream);
+    if (e != hipSuccess) return e;
+    return launch_xcorr_ens(p, mode, acc, n_cu, stream);
+}
+
+// M = acc / n_pairs through the production peak stage and finalize (batch 1): pass 1 writes du, dv as u, v; a shifted pass
+// combines with the shared predictor like any other (u = 2 u2 + du, fallback to u0)
+hipError_t launch_ensemble_peaks(const PassParams& p_in, int mode, const float* acc, long long n_pairs, int n_cu,
+                                 hipStream_t stream) {
+    if (!ensemble_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) return hipErrorInvalidValue;
+    PassParams p = p_in;
+    p.batch = 1;
+    p.A = p.B = nullptr;           // (finalize: no identical-window comparison -- a sum of maps has no one window pair)
+    p.dbg_win = p.dbg_corr = nullptr;
+    const int N = p.n_rows * p.n_cols;
+    hipError_t e = launch_peak_ens(p, acc, N, n_pairs, stream);
+    if (e != hipSuccess) return e;
+    size_t blocks = ((size_t)N + 255) / 256;
+    if (blocks > (size_t)n_cu * 32) blocks = (size_t)n_cu * 32;
+    hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
     return hipGetLastError();
 }
 

@@ -237,6 +237,114 @@ def debug_peaks(maps: torch.Tensor, val_ratio=1.2, val_win=3, planar=False):
     return u, v, inv
 
 
+ENSEMBLE_SIZES = (16, 32, 64)
+ENSEMBLE_MODES = {0: 0, None: 0, "PASS1": 0, "DWS": _lib.MODE_DWS, "CWS": _lib.MODE_CWS}
+
+
+def ensemble_check(sizes, uncertainty=None, deform=None):
+    """What ensemble correlation refuses, checked without a GPU: the window sizes of every pass must be 16, 32 or 64
+    (NotImplementedError names the size), and it combines with neither uncertainty= nor deform= (ValueError)."""
+    if uncertainty is not None:
+        raise ValueError("ensemble correlation does not combine with uncertainty=")
+    if deform is not None:
+        raise ValueError("ensemble correlation does not combine with deform=")
+    for ws in sizes:
+        if ws not in ENSEMBLE_SIZES:
+            raise NotImplementedError(f"ensemble correlation covers window sizes 16, 32 and 64; a pass of {ws} is not covered")
+
+
+def pass_sizes(ws, ov, n_pass, pass_scale):
+    """[(ws, ov)] of the passes of a plan (PIVbackend.py:856-857: int(x // scale) from pass to pass)."""
+    out = [(int(ws), int(ov))]
+    for _ in range(max(int(n_pass), 1) - 1):
+        w, o = out[-1]
+        out.append((int(w // pass_scale), int(o // pass_scale)))
+    return out
+
+
+def ensemble_mode(mode):
+    try:
+        return ENSEMBLE_MODES[mode]
+    except (KeyError, TypeError):
+        raise KeyError(f"ensemble mode must be 0 / 'PASS1', 'DWS' or 'CWS', got {mode!r}") from None
+
+
+def ensemble_bytes(H, W, ws, ov):
+    """Bytes of the accumulator of (ws, ov) on H x W frames: n_rows * n_cols * ws * ws * 4 (0: not an ensemble geometry)."""
+    return int(lib.tpiv_ensemble_bytes(int(H), int(W), int(ws), int(ov)))
+
+
+def ensemble_add(mode, a, b, ws, ov, acc=None, u2=None, v2=None):
+    """Adds the raw correlation maps of the pairs a, b uint8 [batch, H, W] to acc float32 [n_rows * n_cols, ws, ws]
+    (fftshift layout; None: a fresh zeroed one) and returns acc (tpiv_ensemble_add).  mode 0 / "PASS1": first-pass maps;
+    "DWS" / "CWS": the windows shifted by the half shift u2, v2 float64 [n_rows, n_cols] (or [1, n_rows, n_cols]) -- one
+    shift per window for every pair.  ws in 16, 32, 64 (NotImplementedError otherwise).  Pairs are summed in float32 in
+    ascending order without atomics: the same calls give the same bits."""
+    m = ensemble_mode(mode)
+    a, b = _frames(a, b)
+    B, H, W = a.shape
+    if ws not in ENSEMBLE_SIZES:
+        raise NotImplementedError(f"ensemble correlation covers window sizes 16, 32 and 64 (got {ws})")
+    nr, nc = field_shape(H, W, ws, ov)
+    dev = a.device
+    if acc is None:
+        acc = torch.zeros(nr * nc, ws, ws, dtype=torch.float32, device=dev)
+    else:
+        _need_cuda(acc)
+        if acc.dtype != torch.float32 or tuple(acc.shape) != (nr * nc, ws, ws) or not acc.is_contiguous() or acc.device != dev:
+            raise ValueError(f"ensemble_add: acc must be a contiguous float32 [{nr * nc}, {ws}, {ws}] tensor on the frames' device")
+    if m:
+        if u2 is None or v2 is None:
+            raise ValueError("ensemble_add: a shifted pass needs the half shift u2, v2")
+        _need_cuda(u2, v2)
+        u2, v2 = (t.reshape(nr, nc).contiguous() if t.numel() == nr * nc else t for t in (u2, v2))
+        for t in (u2, v2):
+            if t.dtype != torch.float64 or tuple(t.shape) != (nr, nc) or t.device != dev:
+                raise ValueError(f"ensemble_add: u2, v2 must be float64 [{nr}, {nc}] on the frames' device")
+    with torch.cuda.device(dev):
+        work, nbytes = _work(H, W, ws, ov, 1, dev)
+        check(lib.tpiv_ensemble_add(m, a.data_ptr(), b.data_ptr(), B, H, W, ws, ov, u2.data_ptr() if m else None,
+                                    v2.data_ptr() if m else None, acc.data_ptr(), work.data_ptr(), nbytes, _stream()))
+    return acc
+
+
+def ensemble_peaks(mode, acc, n_pairs, H, W, ws, ov, u0=None, v0=None, u2=None, v2=None, val_ratio=1.2, val_win=3,
+                   want_raw=False):
+    """The field of an accumulator of n_pairs pairs (tpiv_ensemble_peaks): M = acc / n_pairs in float32 through the peak
+    stage of every pass.  Returns u, v float64 and invalid uint8 [1, n_rows, n_cols]; a shifted mode takes the predictor
+    fields u0, v0, u2, v2 of predict() / Plan.debug_predict for a batch of one and combines like iterate(); want_raw adds
+    the raw displacement du, dv of a shifted pass."""
+    m = ensemble_mode(mode)
+    _need_cuda(acc, u0, v0, u2, v2)
+    if ws not in ENSEMBLE_SIZES:
+        raise NotImplementedError(f"ensemble correlation covers window sizes 16, 32 and 64 (got {ws})")
+    nr, nc = field_shape(H, W, ws, ov)
+    dev = acc.device
+    if acc.dtype != torch.float32 or tuple(acc.shape) != (nr * nc, ws, ws) or not acc.is_contiguous():
+        raise ValueError(f"ensemble_peaks: acc must be a contiguous float32 [{nr * nc}, {ws}, {ws}] tensor")
+    pred = [None] * 4
+    if m:
+        if any(t is None for t in (u0, v0, u2, v2)):
+            raise ValueError("ensemble_peaks: a shifted pass needs u0, v0, u2, v2")
+        pred = [t.reshape(nr, nc).contiguous() if t.numel() == nr * nc else t for t in (u0, v0, u2, v2)]
+        for t in pred:
+            if t.dtype != torch.float64 or tuple(t.shape) != (nr, nc) or t.device != dev:
+                raise ValueError(f"ensemble_peaks: predictor fields must be float64 [{nr}, {nc}] on the accumulator's device")
+    u = torch.empty(1, nr, nc, dtype=torch.float64, device=dev)
+    v = torch.empty_like(u)
+    inv = torch.empty(1, nr, nc, dtype=torch.uint8, device=dev)
+    raw = m and want_raw
+    du = torch.empty_like(u) if raw else None
+    dv = torch.empty_like(u) if raw else None
+    with torch.cuda.device(dev):
+        work, nbytes = _work(H, W, ws, ov, 1, dev)
+        check(lib.tpiv_ensemble_peaks(m, acc.data_ptr(), int(n_pairs), H, W, ws, ov, *[t.data_ptr() if m else None for t in pred],
+                                      float(val_ratio), int(val_win), u.data_ptr(), v.data_ptr(), inv.data_ptr(),
+                                      du.data_ptr() if raw else None, dv.data_ptr() if raw else None, work.data_ptr(), nbytes,
+                                      _stream()))
+    return (u, v, inv, du, dv) if raw else (u, v, inv)
+
+
 OUTLIER_DEFAULTS = {"threshold": 2.0, "eps": 0.1, "min_neighbours": 3}
 
 
@@ -1348,7 +1456,7 @@ class Plan:
 
     def __init__(self, H, W, ws, ov, n_pass=1, mode="CWS", pass_scale=2.0, val_ratio=1.2,
                  val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None, uncertainty=None,
-                 deform=None):
+                 deform=None, ensemble=False):
         # outlier: None, "median" or a dict (outlier_arg): the normalized median test after every pass -- flagged vectors of
         # a pass before the last are replaced by their neighbourhood median before the predictor reads them, flagged
         # vectors of the last pass join the invalid mask (tpiv_plan_set_outlier)
@@ -1365,6 +1473,11 @@ class Plan:
         self.mask = mask_arg(mask)
         self.deform = deform_arg(deform)
         self.uncertainty_par = uncertainty_arg(uncertainty)
+        # ensemble: sum-of-correlation passes next to run() -- ensemble_begin / _add / _end, run_ensemble
+        # (tpiv_plan_set_ensemble); window sizes 16, 32, 64 only, and neither uncertainty= nor deform=
+        self.ensemble = bool(ensemble)
+        if self.ensemble:
+            ensemble_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], self.uncertainty_par, self.deform)
         if self.mask is not None and tuple(self.mask["image"].shape) != (H, W):
             raise ValueError(f"mask of shape {tuple(self.mask['image'].shape)} for frames of shape {(H, W)}")
         if not torch.cuda.is_available():
@@ -1396,6 +1509,8 @@ class Plan:
                     check(lib.tpiv_plan_set_deform(self._h, self.deform["iterations"], _lib.DEWARP_INTERPS[self.deform["interp"]],
                                                    1 if self.deform["smooth"] else 0,
                                                    _dewarp_table(self.device).data_ptr() if cubic else None))
+                if self.ensemble:
+                    check(lib.tpiv_plan_set_ensemble(self._h, 1))
             except Exception:
                 self.close()
                 raise
@@ -1448,6 +1563,81 @@ class Plan:
             check(lib.tpiv_plan_run(self._h, a.data_ptr(), b.data_ptr(), B, u.data_ptr(),
                                     v.data_ptr(), inv.data_ptr(), _stream()))
         return u, v, inv
+
+    def ensemble_begin(self, p):
+        """Opens ensemble pass p: zeroes the accumulator and, for p > 0, runs the predictor once on the ensemble field of
+        pass p - 1 (ValueError when that pass has not been ended, or for a plan without ensemble=True)."""
+        with torch.cuda.device(self.device):
+            check(lib.tpiv_plan_ensemble_begin(self._h, int(p), _stream()))
+        self._ens_pass = self._ens_last = int(p)
+
+    def ensemble_add(self, a, b):
+        """Adds the maps of the pairs a, b uint8 [batch <= max_batch, H, W] to the open pass's accumulator."""
+        a, b = _frames(a, b)
+        B = a.shape[0]
+        if a.shape[1] != self.H or a.shape[2] != self.W:
+            raise ValueError("frame shape differs from the plan's")
+        if a.device != self.device or b.device != self.device:
+            raise ValueError(f"frames live on {a.device}, the plan on {self.device}")
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} exceeds the plan's max_batch {self.max_batch}")
+        with torch.cuda.device(self.device):
+            check(lib.tpiv_plan_ensemble_add(self._h, a.data_ptr(), b.data_ptr(), B, _stream()))
+
+    def _ensemble_open(self):
+        if not self.ensemble:
+            raise ValueError("ensemble correlation is off: Plan(..., ensemble=True)")
+        acc, n = C.c_void_p(), C.c_longlong()
+        check(lib.tpiv_plan_ensemble_maps(self._h, C.byref(acc), C.byref(n)))
+        return acc, n.value
+
+    def ensemble_end(self, out=None):
+        """Closes the pass ensemble_begin opened: peak of the mean map, combine with the shared predictor, the plan's settle
+        step (mask=, outlier=).  Returns u, v float64 and invalid uint8 [1, n_rows, n_cols] of that pass.  ValueError
+        before ensemble_begin or with no pair added (the pass stays open)."""
+        p = getattr(self, "_ens_pass", None)
+        if p is None:
+            raise ValueError("ensemble_end before ensemble_begin")
+        _, _, nr, nc = self.geometry[p]
+        if out is None:
+            u = torch.empty(1, nr, nc, dtype=torch.float64, device=self.device)
+            v = torch.empty_like(u)
+            inv = torch.empty(1, nr, nc, dtype=torch.uint8, device=self.device)
+        else:
+            u, v, inv = out
+            for t, dt, name in ((u, torch.float64, "u"), (v, torch.float64, "v"), (inv, torch.uint8, "invalid")):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or not t.is_contiguous() \
+                        or tuple(t.shape) != (1, nr, nc):
+                    raise ValueError(f"out[{name}] must be a contiguous {dt} tensor [1, {nr}, {nc}] on {self.device}")
+        with torch.cuda.device(self.device):
+            check(lib.tpiv_plan_ensemble_end(self._h, u.data_ptr(), v.data_ptr(), inv.data_ptr(), _stream()))
+        self._ens_pass = None
+        return u, v, inv
+
+    def ensemble_maps(self):
+        """(acc float32 [n_rows * n_cols, ws, ws], pairs added): a copy of the accumulator at the geometry of the pass begun
+        last (waits for the device).  Test access."""
+        acc, n = self._ensemble_open()
+        p = getattr(self, "_ens_last", None)
+        if p is None:
+            raise ValueError("ensemble_maps before ensemble_begin")
+        ws, _, nr, nc = self.geometry[p]
+        out = torch.empty(nr * nc, ws, ws, dtype=torch.float32, device=self.device)
+        self._copy_out(((out, acc, out.numel() * 4),))
+        return out, n
+
+    def run_ensemble(self, chunks, out=None):
+        """Every pass of the plan as an ensemble pass.  chunks: a callable that returns a fresh iterator of (a, b) device
+        batches (uint8 [<= max_batch, H, W]); it is called once per pass, so a recording is read once per pass.  Returns
+        u, v, invalid [1, n_rows, n_cols] of the last pass."""
+        self._ensemble_open()
+        res = None
+        for p in range(self.n_pass):
+            self.ensemble_begin(p)
+            for a, b in chunks():
+                self.ensemble_add(a, b)
+            res = self.ensemble_end(out if p == self.n_pass - 1 else None)
+        return res
 
     def kernel_name(self, p):
         """Name of the cross-correlation kernel pass p launches (bench / profile labels)."""
