@@ -416,6 +416,47 @@ int tpiv_plan_ensemble_add(tpiv_plan* plan, const uint8_t* a_dev, const uint8_t*
 int tpiv_plan_ensemble_end(tpiv_plan* plan, double* u_dev, double* v_dev, uint8_t* invalid_dev, void* stream);
 int tpiv_plan_ensemble_maps(tpiv_plan* plan, float** acc_dev, long long* n_pairs);
 
+/* ---- spectrally filtered passes: phase-only and robust phase correlation ----------------------------------------------
+ * (A. Eckstein, P. Vlachos, Digital particle image velocimetry (DPIV) robust phase correlation, Meas. Sci. Technol. 20
+ * (2009) 055401.)  Every pass of a plan with this on takes its peak from a filtered map instead of the plain
+ * cross-correlation.  Take a window pair as the pass stages it -- first pass, DWS or CWS staging, quirks included, exactly
+ * the windows tpiv_debug_pass reports -- call the staged windows wa, wb (ws x ws) and subtract each window's own mean.
+ *   1. P(ky, kx) = conj(F wa) (F wb), F the unnormalised 2-D DFT.  The first pass does NOT divide by the window mean: the
+ *      filter is invariant to a scale factor in either frame.
+ *   2. m = the mean of |P| over all ws^2 bins, tau = floor x m (floor: 2^-20 .. 2^-4, by default 2^-10).
+ *   3. g_x[j] = float32(exp(-(pi d_x / (2 ws))^2 j^2)), j = 0 .. ws/2, and g_y likewise with d_y: evaluated in float64 on
+ *      the host, rounded once.  W(ky, kx) = g_y[|ky~|] g_x[|kx~|] as one float32 product, k~ = k for k <= ws/2 and k - ws
+ *      otherwise.  With d in e^-2 diameters (0 .. 16 pixels) this is the spectrum exp(-pi^2 f^2 d^2 / 4) of the correlation
+ *      of two Gaussian particle images.  TPIV_CORR_PHASE: d_x = d_y = 0, W = 1.
+ *   4. Q = W P / max(|P|, tau), and Q = 0 where |P| = 0.  The floor is what makes the filter well defined: a window with
+ *      periodic content has bins that are exactly 0, and unfloored rounding noise would be normalised to full weight there.
+ *   5. C = fftshift(sum_k Q_k exp(+2 pi i k x / ws)), the UNNORMALISED inverse: a pure circular shift peaks at sum W, and the
+ *      1e-7 of the peak stage keeps the relative size it has in a first-pass map.
+ *   6. The peak stage of every pass follows unchanged: minimum subtraction, + 1e-7, first arg-max, three-point log-Gaussian
+ *      fit, peak-to-second-peak test with the plan's val_ratio / val_win, float64 epilogue; a shifted pass then combines
+ *      with the predictor as tpiv_iter does.
+ *   7. A window whose mean-free energy is 0 in either frame (a zero, masked or constant window) has m = 0: in the first pass
+ *      it is dead exactly as a zero-sum window of the float32 first pass (u = v = 0, valid); in a shifted pass it hands the
+ *      zero map to the peak stage, whose peak ratio makes it invalid.  No NaN comes out of 0 x (1 / tau).  The kernels
+ *      decide this by exact equality of the float32 energy with 0: exact for integer-valued staged windows (first pass,
+ *      DWS, zeroed or masked pixels, constant regions under CWS); a CWS window that is constant only up to the rounding of
+ *      its bilinear samples is not empty -- its map is filtered rounding noise, which the peak ratio has to reject.
+ * tables (host): for pass 0, 1, ... in turn g_y[0 .. ws/2] then g_x[0 .. ws/2] of that pass's window size, n_tables floats
+ * in all; the plan uploads them once.  d_x, d_y and floor are checked against their ranges and floor is what the kernels use;
+ * the weights are the tables' (d_x, d_y are not kept).  A plan whose workspace was sized for float64 records alone
+ * (TPIV_PREC_REFERENCE / _F64 with few windows) gets a larger one here: a filtered pass works in the float32 layout.
+ * tpiv_plan_exact_fallbacks returns TPIV_EINVAL after a filtered run, and tpiv_plan_exact_timing averages over the unfiltered
+ * runs alone.  kind = TPIV_CORR_NONE: off, every pass is byte for byte what it was (tables may be NULL).
+ * TPIV_EUNSUPPORTED, with a message naming the size, when a pass has a window size other than 16, 32 or 64 (multipass modes
+ * of a plan are DWS and CWS; the CWS_Fast iteration has no filtered kernel: tpiv_debug_pass_spec).  TPIV_EINVAL on a plan
+ * with tpiv_plan_set_uncertainty, tpiv_plan_set_deform or tpiv_plan_set_ensemble on -- and those refuse a plan with this on.
+ * The plan's precision has no effect on a filtered pass: the first pass is the float32 spectral kernel -- the exact integer
+ * scheme decides plain correlation sums, not a normalised spectrum.  tpiv_plan_set_mask and tpiv_plan_set_outlier act as
+ * on any plan.  tpiv_plan_kernel_name names the spectral kernels for such a plan.  A failed call changes nothing. */
+enum { TPIV_CORR_NONE = 0, TPIV_CORR_PHASE = 1, TPIV_CORR_RPC = 2 };
+int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double d_x, double d_y, double floor, const float* tables,
+                              size_t n_tables);
+
 /* ---- post-validation (B:884-892) ------------------------------------------------- */
 
 /* Device part of the reference's per-pair host post-processing, for a whole batch:
@@ -636,6 +677,15 @@ int tpiv_debug_pass(int mode, int precision, const uint8_t* a_dev, const uint8_t
                     int ws, int ov, const double* u2_dev, const double* v2_dev, const double* zero_dev,
                     double* u_dev, double* v_dev, uint8_t* invalid_dev,
                     float* win_dev, float* corr_dev, void* work_dev, size_t work_bytes, void* stream);
+
+/* tpiv_debug_pass of a spectrally filtered pass (tpiv_plan_set_correlation): mode 0, TPIV_MODE_DWS or TPIV_MODE_CWS at
+ * ws = 16, 32 or 64 (anything else, TPIV_MODE_CWS_FAST included: TPIV_EUNSUPPORTED); tab_dev = g_y[0 .. ws/2] then
+ * g_x[0 .. ws/2] on the device.  win_dev receives the staged windows (before the mean removal), corr_dev the map the
+ * decisions are taken on, C - min + 1e-7 in fftshift layout. */
+int tpiv_debug_pass_spec(int mode, int kind, double floor, const float* tab_dev, const uint8_t* a_dev, const uint8_t* b_dev,
+                         int batch, int H, int W, int ws, int ov, const double* u2_dev, const double* v2_dev,
+                         const double* zero_dev, double* u_dev, double* v_dev, uint8_t* invalid_dev, float* win_dev,
+                         float* corr_dev, void* work_dev, size_t work_bytes, void* stream);
 
 /* Runs one shifted pass (mode DWS or CWS) from the COMPACT predictor hand-off, exactly as tpiv_plan_run does after its
  * predictor: u_raw_dev, v_raw_dev [batch, n_rows, n_cols] float64 are the raw predictor (before the invalid-zeroing) and

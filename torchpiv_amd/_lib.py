@@ -22,7 +22,9 @@ PREFILTER_NONE, PREFILTER_MIN, PREFILTER_MEAN = 0, 1, 2
 PREFILTERS = {None: PREFILTER_NONE, "min": PREFILTER_MIN, "mean": PREFILTER_MEAN}    # tpiv_prefilter's kinds
 DEWARP_LINEAR, DEWARP_CUBIC = 0, 1
 DEWARP_INTERPS = {"linear": DEWARP_LINEAR, "cubic": DEWARP_CUBIC}                    # tpiv_dewarp's interpolations
-DEFORM_GATHER = 0x100                            # OR-ed into tpiv_deform_warp's interp: the gather form everywhere
+CORR_NONE, CORR_PHASE, CORR_RPC = 0, 1, 2
+CORRELATIONS = {"phase": CORR_PHASE, "rpc": CORR_RPC}                                # tpiv_plan_set_correlation's kinds
+DEFORM_GATHER = 0x100                           # OR-ed into tpiv_deform_warp's interp: the gather form everywhere
 ABI_VERSION = 2
 
 
@@ -100,6 +102,9 @@ SIGNATURES = {
     "tpiv_plan_ensemble_add": (C.c_int, [C.c_void_p, _u8p, _u8p, _int, _vp]),
     "tpiv_plan_ensemble_end": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _vp]),
     "tpiv_plan_ensemble_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
+    "tpiv_plan_set_correlation": (C.c_int, [C.c_void_p, _int, _dbl, _dbl, _dbl, _vp, C.c_size_t]),
+    "tpiv_debug_pass_spec": (C.c_int, [_int, _int, _dbl, _f32p, _u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _f64p,
+                                       _f64p, _f64p, _u8p, _f32p, _f32p, _vp, C.c_size_t, _vp]),
     "tpiv_postval": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _u8p, _vp, _vp]),
     "tpiv_postval_compact": (C.c_int, [_f64p, _f64p, _u8p, _vp, _int, _int, _int, _vp, _vp, _f64p, _vp, _vp]),
     "tpiv_finish_fields": (C.c_int, [_f64p, _f64p, _int, _int, _int, C.c_double, C.c_double, _f64p, _f64p, _vp]),

@@ -281,6 +281,13 @@ struct tpiv_plan {
     uint8_t* ens_pmask = nullptr;
     int ens_pass = -1, ens_done = -1;    // the pass between begin and end; the highest pass ended
     long long ens_pairs = 0;             // pairs added since begin
+    // spectrally filtered passes (tpiv_plan_set_correlation); off: nothing is allocated and every pass is the plain one
+    int corr_kind = 0;
+    double corr_floor = 0.0;
+    std::vector<float*> corr_tab;        // per pass: g_y[0 .. ws/2], then g_x[0 .. ws/2]
+    tpiv::SpecParams spec(int pass) const { return tpiv::SpecParams{corr_tab[pass], (float)corr_floor}; }
+    bool last_filtered = false;          // the last tpiv_plan_run ran filtered passes: its first pass took no exact scheme
+    std::vector<char> sub_recorded;      // per timed run: the three sub-events of the exact first pass were recorded
     std::vector<void*> allocs;
     // optional per-kernel timing: events[run][2*slot + {0,1}]
     bool timing = false;
@@ -465,9 +472,10 @@ static tpiv::PassParams pass_params(const uint8_t* a, const uint8_t* b, int batc
 static int pass1_impl(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
                       double val_ratio, int val_win, int precision, double* u, double* v, uint8_t* invalid,
                       void* work, size_t work_bytes, float* dbg_win, float* dbg_corr, void* stream,
-                      hipEvent_t* sub_events = nullptr) {
+                      hipEvent_t* sub_events = nullptr, const tpiv::SpecParams* spec = nullptr) {
     int rc = check_window(H, W, ws, ov, val_win);
     if (rc) return rc;
+    if (spec) precision = TPIV_PREC_FAST;      // a filtered first pass is the float32 spectral kernel at every precision
     if (!valid_precision(precision)) return fail(TPIV_EINVAL, "precision must be TPIV_PREC_FAST, TPIV_PREC_REFERENCE, TPIV_PREC_F64 or TPIV_PREC_EXACT");
     if (batch <= 0) return TPIV_OK;
     tpiv::PassParams p = pass_params(a, b, batch, H, W, ws, ov, val_ratio, val_win, precision, u, v, invalid, dbg_win, dbg_corr);
@@ -478,7 +486,8 @@ static int pass1_impl(const uint8_t* a, const uint8_t* b, int batch, int H, int 
     int n_cu;
     rc = n_cu_of_current_device(&n_cu);
     if (rc) return rc;
-    HIP_TRY(tpiv::launch_xcorr(p, tpiv::MODE_PASS1, n_cu, (hipStream_t)stream));
+    if (spec) HIP_TRY(tpiv::launch_xcorr_spec(p, tpiv::MODE_PASS1, *spec, n_cu, (hipStream_t)stream));
+    else HIP_TRY(tpiv::launch_xcorr(p, tpiv::MODE_PASS1, n_cu, (hipStream_t)stream));
     return TPIV_OK;
 }
 
@@ -529,7 +538,7 @@ static int run_iter(int mode, int precision, const uint8_t* a, const uint8_t* b,
                     int ov, const double* u0, const double* v0, const double* u2, const double* v2,
                     double val_ratio, int val_win, double* u, double* v, uint8_t* invalid, double* du,
                     double* dv, float* dbg_win, float* dbg_corr, void* work, size_t work_bytes, void* stream,
-                    const uint8_t* pmask = nullptr) {
+                    const uint8_t* pmask = nullptr, const tpiv::SpecParams* spec = nullptr) {
     if (mode != TPIV_MODE_DWS && mode != TPIV_MODE_CWS && mode != TPIV_MODE_CWS_FAST)
         return fail(TPIV_EKEY, "unknown multipass mode");
     int rc = check_window(H, W, ws, ov, val_win);
@@ -554,7 +563,8 @@ static int run_iter(int mode, int precision, const uint8_t* a, const uint8_t* b,
     int n_cu;
     rc = n_cu_of_current_device(&n_cu);
     if (rc) return rc;
-    HIP_TRY(tpiv::launch_xcorr(p, mode, n_cu, (hipStream_t)stream));
+    if (spec) HIP_TRY(tpiv::launch_xcorr_spec(p, mode, *spec, n_cu, (hipStream_t)stream));
+    else HIP_TRY(tpiv::launch_xcorr(p, mode, n_cu, (hipStream_t)stream));
     return TPIV_OK;
 }
 
@@ -577,6 +587,35 @@ int tpiv_debug_pass(int mode, int precision, const uint8_t* a, const uint8_t* b,
     const bool cwsf = mode == TPIV_MODE_CWS_FAST;
     return run_iter(mode, precision, a, b, batch, H, W, ws, ov, cwsf ? u2 : zero, cwsf ? v2 : zero, u2, v2, 1.2, 3, u, v,
                     invalid, nullptr, nullptr, win, corr, work, work_bytes, stream);
+}
+
+static int check_correlation(const char* who, int kind, double dx, double dy, double floor) {
+    if (kind != TPIV_CORR_PHASE && kind != TPIV_CORR_RPC)
+        return fail(TPIV_EINVAL, std::string(who) + ": kind must be TPIV_CORR_NONE, TPIV_CORR_PHASE or TPIV_CORR_RPC");
+    if (!(dx >= 0.0 && dx <= 16.0) || !(dy >= 0.0 && dy <= 16.0))
+        return fail(TPIV_EINVAL, std::string(who) + ": the particle-image diameters must be in 0..16 pixels");
+    if (kind == TPIV_CORR_PHASE && (dx != 0.0 || dy != 0.0))
+        return fail(TPIV_EINVAL, std::string(who) + ": phase-only correlation has diameter 0");
+    if (!(floor >= 0x1p-20 && floor <= 0x1p-4)) return fail(TPIV_EINVAL, std::string(who) + ": floor must be in 2^-20..2^-4");
+    return TPIV_OK;
+}
+
+int tpiv_debug_pass_spec(int mode, int kind, double floor, const float* tab, const uint8_t* a, const uint8_t* b, int batch,
+                         int H, int W, int ws, int ov, const double* u2, const double* v2, const double* zero, double* u,
+                         double* v, uint8_t* invalid, float* win, float* corr, void* work, size_t work_bytes, void* stream) {
+    if (int rc = check_correlation("tpiv_debug_pass_spec", kind, 0.0, 0.0, floor)) return rc;
+    if (mode == TPIV_MODE_CWS_FAST) return fail(TPIV_EUNSUPPORTED, "correlation=: the CWS_Fast iteration has no filtered kernel");
+    if (mode != 0 && mode != TPIV_MODE_DWS && mode != TPIV_MODE_CWS) return fail(TPIV_EKEY, "unknown multipass mode");
+    if (!tpiv::spec_size(ws))
+        return fail(TPIV_EUNSUPPORTED, "correlation=: filtered passes cover window sizes 16, 32 and 64 (got " + std::to_string(ws) + ")");
+    if (!tab) return fail(TPIV_EINVAL, "tpiv_debug_pass_spec: tables missing");
+    const tpiv::SpecParams sp{tab, (float)floor};
+    if (mode == 0)
+        return pass1_impl(a, b, batch, H, W, ws, ov, 1.2, 3, TPIV_PREC_FAST, u, v, invalid, work, work_bytes, win, corr, stream,
+                          nullptr, &sp);
+    if (!zero || !u2 || !v2) return fail(TPIV_EINVAL, "tpiv_debug_pass_spec: shifted passes need u2, v2 and a zero field");
+    return run_iter(mode, TPIV_PREC_FAST, a, b, batch, H, W, ws, ov, zero, zero, u2, v2, 1.2, 3, u, v, invalid, nullptr, nullptr,
+                    win, corr, work, work_bytes, stream, nullptr, &sp);
 }
 
 int tpiv_debug_iter_compact(int mode, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
@@ -736,6 +775,7 @@ const char* tpiv_plan_kernel_name(const tpiv_plan* plan, int pass, char* buf, in
     buf[0] = 0;
     if (!plan || pass < 0 || pass >= plan->n_pass) return buf;
     const int mode = pass == 0 ? (int)tpiv::MODE_PASS1 : plan->mode;
+    if (plan->corr_kind) return tpiv::xcorr_spec_kernel_name(plan->geo[pass].ws, mode, buf, len);
     return tpiv::xcorr_kernel_name(plan->geo[pass].ws, mode, plan->precision, buf, len);
 }
 
@@ -744,6 +784,8 @@ int tpiv_plan_exact_fallbacks(tpiv_plan* plan, long long* n_windows) {
     if (!plan->exact_count)
         return fail(TPIV_EINVAL, "not a TPIV_PREC_EXACT plan with an even first-pass window size from 8 to 128");
     if (plan->last_batch <= 0) return fail(TPIV_EINVAL, "the plan has not run yet");
+    if (plan->last_filtered)
+        return fail(TPIV_EINVAL, "the last run's first pass was a filtered one (tpiv_plan_set_correlation): it takes no exact scheme");
     HIP_TRY(hipDeviceSynchronize());
     unsigned n = 0;
     HIP_TRY(hipMemcpy(&n, plan->exact_count, sizeof(n), hipMemcpyDeviceToHost));
@@ -1019,6 +1061,7 @@ int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius) {
         return TPIV_OK;
     }
     if (plan->ens_on) return fail(TPIV_EINVAL, "uncertainty= does not combine with ensemble correlation");
+    if (plan->corr_kind) return fail(TPIV_EINVAL, "uncertainty= does not combine with correlation=");
     const PassGeo& g = plan->geo[plan->n_pass - 1];
     if (int rc = check_uncertainty(plan->H, plan->W, g.ws, g.ov, radius)) return rc;
     if (!plan->unc_su) {                             // first time on: the two fields (kept until the plan is destroyed)
@@ -1139,6 +1182,7 @@ int tpiv_plan_set_deform(tpiv_plan* plan, int iterations, int interp, int smooth
         return TPIV_OK;
     }
     if (plan->ens_on) return fail(TPIV_EINVAL, "deform= does not combine with ensemble correlation");
+    if (plan->corr_kind) return fail(TPIV_EINVAL, "deform= does not combine with correlation=");
     if (interp != TPIV_DEWARP_LINEAR && interp != TPIV_DEWARP_CUBIC) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: unknown interp");
     if (interp == TPIV_DEWARP_CUBIC && !table) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: the cubic interpolation needs its table");
     const PassGeo& g = plan->geo[plan->n_pass - 1];
@@ -1319,13 +1363,15 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
         double *const pu = settle.wu, *const pv = settle.wv;
         uint8_t* const pval = settle.wval;
         int rc;
+        const tpiv::SpecParams sp = plan->corr_kind ? plan->spec(p) : tpiv::SpecParams{};
+        const tpiv::SpecParams* const spec = plan->corr_kind ? &sp : nullptr;
         if (p == 0) {
             mark(0, 0);
             rc = pass1_impl(a, b, batch, plan->H, plan->W, g.ws, g.ov, plan->val_ratio, plan->val_win,
                             plan->precision, pu, pv, pval, plan->peak_raw, plan->peak_raw_bytes, nullptr, nullptr,
-                            stream, plan->sub_events());
+                            stream, spec ? nullptr : plan->sub_events(), spec);
             mark(0, 1);
-            if (!rc && plan->exact_count) {
+            if (!rc && plan->exact_count && !spec) {
                 const size_t off = tpiv::exact_fallback_count_offset(batch, g.n_rows * g.n_cols);
                 HIP_TRY(hipMemcpyAsync(plan->exact_count, reinterpret_cast<const char*>(plan->peak_raw) + off,
                                        sizeof(unsigned), hipMemcpyDeviceToDevice, st));
@@ -1341,7 +1387,7 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
             if (!rc)
                 rc = run_iter(plan->mode, plan->precision, a, b, batch, plan->H, plan->W, g.ws, g.ov, plan->u0, plan->v0,
                               nullptr, nullptr, plan->val_ratio, plan->val_win, pu, pv, pval, nullptr,
-                              nullptr, nullptr, nullptr, plan->peak_raw, plan->peak_raw_bytes, stream, plan->pmask);
+                              nullptr, nullptr, nullptr, plan->peak_raw, plan->peak_raw_bytes, stream, plan->pmask, spec);
             mark(2 * p, 1);
         }
         if (rc) return rc;
@@ -1361,7 +1407,66 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
                                      plan->unc_sv, nullptr, st))
             return rc;
     }
-    if (plan->timing && plan->runs_recorded < 512) plan->runs_recorded++;
+    plan->last_filtered = plan->corr_kind != 0;
+    if (plan->timing && plan->runs_recorded < 512) {
+        if (plan->sub_recorded.size() <= plan->runs_recorded) plan->sub_recorded.resize(plan->runs_recorded + 1, 0);
+        plan->sub_recorded[plan->runs_recorded] = plan->exact_count != nullptr && !plan->last_filtered;
+        plan->runs_recorded++;
+    }
+    return TPIV_OK;
+}
+
+// ---- spectrally filtered passes -------------------------------------------------------------------------------------
+
+int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double dx, double dy, double floor, const float* tables,
+                              size_t n_tables) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (kind == TPIV_CORR_NONE) {
+        plan->corr_kind = 0;
+        return TPIV_OK;
+    }
+    if (int rc = check_correlation("tpiv_plan_set_correlation", kind, dx, dy, floor)) return rc;
+    if (plan->unc_kind) return fail(TPIV_EINVAL, "correlation= does not combine with uncertainty=");
+    if (plan->def_iters) return fail(TPIV_EINVAL, "correlation= does not combine with deform=");
+    if (plan->ens_on) return fail(TPIV_EINVAL, "correlation= does not combine with ensemble correlation");
+    size_t need = 0;
+    for (const PassGeo& g : plan->geo) {
+        if (!tpiv::spec_size(g.ws))
+            return fail(TPIV_EUNSUPPORTED, "correlation=: filtered passes cover window sizes 16, 32 and 64; this plan has a pass of " +
+                                               std::to_string(g.ws));
+        need += 2 * (size_t)(g.ws / 2 + 1);
+    }
+    if (!tables || n_tables != need)
+        return fail(TPIV_EINVAL, "tpiv_plan_set_correlation: tables must hold g_y and g_x of every pass, " + std::to_string(need) +
+                                     " floats in all");
+    if (int rc = check_plan_device(plan)) return rc;
+    // a filtered pass works in the float32 tile layout (records, item counters) whatever the plan's precision: a plan whose
+    // workspace was sized for float64 records alone gets a larger one (the old one is freed with the plan)
+    size_t raw = 0;
+    for (const PassGeo& g : plan->geo)
+        raw = std::max(raw, tpiv::peak_raw_bytes(g.ws, plan->max_batch, g.n_rows * g.n_cols, TPIV_PREC_FAST));
+    float* grown = nullptr;
+    if (raw > plan->peak_raw_bytes)
+        if (int rc = plan->alloc(&grown, raw / sizeof(float) + 64)) return rc;
+    if (plan->corr_tab.empty()) {                    // first time on (kept until the plan is destroyed)
+        std::vector<float*> tabs(plan->n_pass, nullptr);
+        for (int p = 0; p < plan->n_pass; ++p)
+            if (int rc = plan->alloc(&tabs[p], 2 * (size_t)(plan->geo[p].ws / 2 + 1))) return rc;
+        plan->corr_tab = std::move(tabs);
+    }
+    HIP_TRY(hipDeviceSynchronize());                 // no run in flight reads the tables while they change
+    size_t off = 0;
+    for (int p = 0; p < plan->n_pass; ++p) {
+        const size_t n = 2 * (size_t)(plan->geo[p].ws / 2 + 1);
+        HIP_TRY(hipMemcpy(plan->corr_tab[p], tables + off, n * sizeof(float), hipMemcpyHostToDevice));
+        off += n;
+    }
+    if (grown) {
+        plan->peak_raw = grown;
+        plan->peak_raw_bytes = raw;
+    }
+    plan->corr_kind = kind;
+    plan->corr_floor = floor;
     return TPIV_OK;
 }
 
@@ -1457,6 +1562,7 @@ int tpiv_plan_set_ensemble(tpiv_plan* plan, int on) {
     }
     if (plan->unc_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with uncertainty=");
     if (plan->def_iters) return fail(TPIV_EINVAL, "ensemble correlation does not combine with deform=");
+    if (plan->corr_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with correlation=");
     size_t cells = 0, fine = 0;
     for (const PassGeo& g : plan->geo) {
         if (!tpiv::ensemble_size(g.ws))
@@ -1937,14 +2043,17 @@ int tpiv_plan_get_timing(tpiv_plan* plan, double* avg_ms, int n_slots, int* n_ru
     if (n)
         for (int s = 0; s < n_slots; ++s) avg_ms[s] /= (double)n;
     for (double& m : plan->exact_ms) m = 0.0;
-    if (plan->exact_count && n) {
+    size_t n_sub = 0;                    // runs whose first pass was the exact scheme (a filtered run records no sub-events)
+    for (size_t r = 0; r < n; ++r) n_sub += r < plan->sub_recorded.size() && plan->sub_recorded[r];
+    if (plan->exact_count && n_sub) {
         for (size_t r = 0; r < n; ++r) {
+            if (!plan->sub_recorded[r]) continue;
             const hipEvent_t* sub = plan->events[r].data() + 2 * n_slots;
             const hipEvent_t chain[5] = {plan->events[r][0], sub[0], sub[1], sub[2], plan->events[r][1]};
             for (int s = 0; s < 4; ++s) {
                 float ms = 0.f;
                 HIP_TRY(hipEventElapsedTime(&ms, chain[s], chain[s + 1]));
-                plan->exact_ms[s] += ms / (double)n;
+                plan->exact_ms[s] += ms / (double)n_sub;
             }
         }
     }

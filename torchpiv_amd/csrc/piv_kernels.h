@@ -351,6 +351,16 @@ size_t ensemble_work_bytes(int n_windows);
 hipError_t launch_ensemble_add(const PassParams& p, int mode, float* acc, int n_cu, hipStream_t stream);
 hipError_t launch_ensemble_peaks(const PassParams& p, int mode, const float* acc, long long n_pairs, int n_cu,
                                  hipStream_t stream);
+// spectrally filtered passes (xcorr_spec.hip, defined in include/torchpiv_hip.h: tpiv_plan_set_correlation): window sizes 16,
+// 32 and 64, pass 1 / DWS / CWS.  The filter travels as a second kernel argument: PassParams keeps its layout.
+struct SpecParams {
+    const float* tab;        // device: g_y[0 .. ws/2], then g_x[0 .. ws/2] (all ones: phase-only correlation)
+    float floor;             // tau = floor x mean |P|
+};
+bool spec_size(int ws);
+// the pass with its finalize step; p.peak_raw: peak_raw_bytes(ws, batch, n_windows, 0)
+hipError_t launch_xcorr_spec(const PassParams& p, int mode, const SpecParams& s, int n_cu, hipStream_t stream);
+const char* xcorr_spec_kernel_name(int ws, int mode, char* buf, int len);
 hipError_t launch_predict_mfma(const BandedPredictParams& q, hipStream_t stream);
 hipError_t launch_predict(const PredictParams& q, hipStream_t stream);
 

@@ -36,6 +36,9 @@ bool exact_refine_size(int ws);                                                 
 hipError_t launch_xcorr_f64_list(const PassParams& p, int n_cu, hipStream_t stream);        // xcorr_f64.hip
 hipError_t launch_xcorr_ens(const PassParams& p, int mode, float* acc, int n_cu, hipStream_t stream);       // xcorr_ens.hip
 hipError_t launch_peak_ens(const PassParams& p, const float* acc, int n_maps, long long n_pairs, hipStream_t stream);
+hipError_t launch_xcorr_spec_tile(const PassParams& p, int mode, const SpecParams& s, int n_cu, hipStream_t stream);   // xcorr_spec.hip
+int spec_occ(int ws, int mode);
+bool spec_planar(int ws, int mode);
 
 // ---- finalize: sub-pixel fit, validation and multipass combine, one thread per window -----------
 // PIVbackend.py:385-422 (correlation_to_displacement) and B:728-738 / B:800-810 (combine).  Input:
@@ -414,6 +417,37 @@ hipError_t launch_ensemble_peaks(const PassParams& p_in, int mode, const float* 
     hipError_t e = launch_peak_ens(p, acc, N, n_pairs, stream);
     if (e != hipSuccess) return e;
     size_t blocks = ((size_t)N + 255) / 256;
+    if (blocks > (size_t)n_cu * 32) blocks = (size_t)n_cu * 32;
+    hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
+    return hipGetLastError();
+}
+
+// ---- spectrally filtered passes (xcorr_spec.hip): phase-only / robust phase correlation -----------------------------
+bool spec_size(int ws) { return ws == 16 || ws == 32 || ws == 64; }
+
+const char* xcorr_spec_kernel_name(int ws, int mode, char* buf, int len) {
+    if (!spec_size(ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) snprintf(buf, len, "%s", "");
+    else snprintf(buf, len, "xcorr_spec_kernel<%d, %d, %d, %s>", ws, mode, spec_occ(ws, mode), spec_planar(ws, mode) ? "true" : "false");
+    return buf;
+}
+
+// one filtered pass: the spectral tile kernel, then the finalize step of every float32 pass (pass 1 writes du, dv as u, v; a
+// shifted pass combines with the predictor).  The workspace is the plain tile kernels': records, item counters behind them.
+hipError_t launch_xcorr_spec(const PassParams& p_in, int mode, const SpecParams& s, int n_cu, hipStream_t stream) {
+    if (!spec_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS) || s.tab == nullptr)
+        return hipErrorInvalidValue;
+    PassParams p = p_in;
+    p.precision = 0;
+    p.list_mode = 0;
+    p.slow_list = nullptr;
+    p.slow_count = nullptr;
+    p.work_ctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.peak_raw) + work_ctr_offset(p.batch, p.n_rows * p.n_cols));
+    hipError_t e = hipMemsetAsync(p.work_ctr, 0, WORK_CTR_BYTES, stream);
+    if (e != hipSuccess) return e;
+    e = launch_xcorr_spec_tile(p, mode, s, n_cu, stream);
+    if (e != hipSuccess) return e;
+    const size_t total = (size_t)p.batch * p.n_rows * p.n_cols;
+    size_t blocks = (total + 255) / 256;
     if (blocks > (size_t)n_cu * 32) blocks = (size_t)n_cu * 32;
     hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
     return hipGetLastError();

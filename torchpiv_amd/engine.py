@@ -190,14 +190,19 @@ def iterate_compact(mode, a, b, ws, ov, u_raw, v_raw, mask, val_ratio=1.2, val_w
     return u, v, inv
 
 
-def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference"):
+def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference", correlation=None):
     """Test hook: one pass plus the staged windows and the correlation maps (shifted passes at
     `precision`: "reference" = the reference's operation order, bit-identical windows).  Pass 1
     (mode 0) runs the float32 kernel, or with precision="exact" the exact first pass, whose maps
     are those of its float32 locating kernel -- the map every decision is taken on, also for the
     windows that then go to the float64 transform.  "CWS_Fast" takes u2, v2 as its predictor u0, v0 (the windows are
-    resampled by -/+ u0 / 2 inside themselves); DWS / CWS return u = 2 u2 + du where valid, 0 where invalid."""
+    resampled by -/+ u0 / 2 inside themselves); DWS / CWS return u = 2 u2 + du where valid, 0 where invalid.
+    correlation (correlation_arg): the spectrally filtered pass instead (tpiv_debug_pass_spec; `precision` has no effect on
+    it) -- the windows as staged, before the mean removal, and the filtered map the decisions are taken on."""
     prec = _precision(precision)
+    corr_par = correlation_arg(correlation)
+    if corr_par is not None:
+        correlation_check([ws], mode if isinstance(mode, str) else None)
     a, b = _frames(a, b)
     B, H, W = a.shape
     nr, nc = field_shape(H, W, ws, ov)
@@ -210,6 +215,18 @@ def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference"):
     corr = torch.empty(B, N, ws, ws, dtype=torch.float32, device=dev)
     m = 0 if mode in (0, None, "PASS1") else ITER_MODES[mode]
     zero = torch.zeros(B, nr, nc, dtype=torch.float64, device=dev) if m else None
+    if corr_par is not None:
+        tab = torch.from_numpy(correlation_tables(corr_par, [ws])).to(dev)
+        with torch.cuda.device(dev):
+            work, nbytes = _work(H, W, ws, ov, B, dev)
+            check(lib.tpiv_debug_pass_spec(m, _lib.CORRELATIONS[corr_par["kind"]], corr_par["floor"], tab.data_ptr(),
+                                           a.data_ptr(), b.data_ptr(), B, H, W, ws, ov,
+                                           u2.contiguous().data_ptr() if u2 is not None else None,
+                                           v2.contiguous().data_ptr() if v2 is not None else None,
+                                           zero.data_ptr() if zero is not None else None,
+                                           u.data_ptr(), v.data_ptr(), inv.data_ptr(), win.data_ptr(),
+                                           corr.data_ptr(), work.data_ptr(), nbytes, _stream()))
+        return u, v, inv, win, corr
     with torch.cuda.device(dev):
         work, nbytes = _work(H, W, ws, ov, B, dev)
         check(lib.tpiv_debug_pass(m, prec, a.data_ptr(), b.data_ptr(), B, H, W, ws, ov,
@@ -251,6 +268,89 @@ def ensemble_check(sizes, uncertainty=None, deform=None):
     for ws in sizes:
         if ws not in ENSEMBLE_SIZES:
             raise NotImplementedError(f"ensemble correlation covers window sizes 16, 32 and 64; a pass of {ws} is not covered")
+
+
+CORRELATION_SIZES = (16, 32, 64)
+CORRELATION_DEFAULTS = {"kind": "rpc", "diameter": 2.8, "floor": 2.0 ** -10}
+CORRELATION_MAX_DIAMETER, CORRELATION_FLOOR_MIN, CORRELATION_FLOOR_MAX = 16.0, 2.0 ** -20, 2.0 ** -4
+
+
+def correlation_arg(correlation):
+    """The correlation= argument of Plan / OfflinePIV / ResidentPIV / run_folder / debug_pass, checked (no GPU involved):
+    None (the plain cross-correlation), "phase" (phase-only correlation), "rpc" (robust phase correlation at the default
+    particle-image diameter 2.8) or a dict with any of CORRELATION_DEFAULTS' keys -- diameter: the e^-2 diameter in pixels,
+    one number or (d_x, d_y), 0..16; floor: 2^-20..2^-4 (include/torchpiv_hip.h: tpiv_plan_set_correlation has the
+    definition).  Returns None or {"kind", "dx", "dy", "floor"}; "phase" has dx = dy = 0.  ValueError for anything else."""
+    if correlation is None:
+        return None
+    if isinstance(correlation, dict) and set(correlation) == {"kind", "dx", "dy", "floor"}:      # this function's own result
+        correlation = dict({"kind": correlation["kind"], "floor": correlation["floor"]},
+                           **({} if correlation["kind"] == "phase" else {"diameter": (correlation["dx"], correlation["dy"])}))
+    form = f"correlation: None, 'phase', 'rpc' or a dict of {sorted(CORRELATION_DEFAULTS)}"
+    if isinstance(correlation, str):
+        if correlation not in _lib.CORRELATIONS:
+            raise ValueError(f"{form}, got {correlation!r}")
+        correlation = {"kind": correlation}
+    if not isinstance(correlation, dict):
+        raise ValueError(f"{form}, got {type(correlation).__name__}")
+    unknown = sorted(set(correlation) - set(CORRELATION_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"correlation: unknown key(s) {unknown}; known: {sorted(CORRELATION_DEFAULTS)}")
+    par = dict(CORRELATION_DEFAULTS, **correlation)
+    if not isinstance(par["kind"], str) or par["kind"] not in _lib.CORRELATIONS:
+        raise ValueError(f"correlation: kind must be one of {sorted(_lib.CORRELATIONS)}, got {par['kind']!r}")
+    if par["kind"] == "phase":
+        if "diameter" in correlation and correlation["diameter"] not in (0, 0.0, (0, 0), (0.0, 0.0)):
+            raise ValueError("correlation: 'phase' has no diameter (it is 'rpc' at diameter 0)")
+        d = (0.0, 0.0)
+    else:
+        d = par["diameter"]
+        if isinstance(d, (tuple, list)):
+            if len(d) != 2:
+                raise ValueError(f"correlation: diameter must be a number or (d_x, d_y), got {d!r}")
+        else:
+            d = (d, d)
+    try:
+        if any(isinstance(q, (bool, np.bool_)) for q in d):
+            raise TypeError
+        dx, dy = float(d[0]), float(d[1])
+        floor = float(par["floor"])
+    except (TypeError, ValueError):
+        raise ValueError(f"correlation: diameter and floor must be numbers, got {par['diameter']!r}, {par['floor']!r}") from None
+    for q in (dx, dy):
+        if not 0.0 <= q <= CORRELATION_MAX_DIAMETER:
+            raise ValueError(f"correlation: diameter must be in 0..{CORRELATION_MAX_DIAMETER:g} pixels, got {q!r}")
+    if not CORRELATION_FLOOR_MIN <= floor <= CORRELATION_FLOOR_MAX:
+        raise ValueError(f"correlation: floor must be in 2^-20..2^-4, got {floor!r}")
+    return {"kind": par["kind"], "dx": dx, "dy": dy, "floor": floor}
+
+
+def correlation_check(sizes, mode=None, uncertainty=None, deform=None, ensemble=False):
+    """What correlation= refuses, checked without a GPU: it combines with neither uncertainty= nor deform= nor ensemble
+    correlation (ValueError), the window size of every pass must be 16, 32 or 64 and the mode must not be CWS_Fast
+    (NotImplementedError names it)."""
+    if uncertainty is not None:
+        raise ValueError("correlation= does not combine with uncertainty=")
+    if deform is not None:
+        raise ValueError("correlation= does not combine with deform=")
+    if ensemble:
+        raise ValueError("correlation= does not combine with ensemble correlation")
+    if mode == "CWS_Fast":
+        raise NotImplementedError("correlation=: the CWS_Fast iteration has no filtered kernel")
+    for ws in sizes:
+        if ws not in CORRELATION_SIZES:
+            raise NotImplementedError(f"correlation=: filtered passes cover window sizes 16, 32 and 64; a pass of {ws} is not covered")
+
+
+def correlation_tables(par, sizes):
+    """float32 [sum over the passes of 2 (ws/2 + 1)]: g_y[0 .. ws/2] then g_x[0 .. ws/2] per pass, g[j] =
+    float32(exp(-(pi d / (2 ws))^2 j^2)) evaluated in float64 and rounded once."""
+    out = []
+    for ws in sizes:
+        j = np.arange(ws // 2 + 1, dtype=np.float64)
+        for d in (par["dy"], par["dx"]):
+            out.append(np.exp(-(np.pi * d / (2.0 * ws)) ** 2 * j * j).astype(np.float32))
+    return np.ascontiguousarray(np.concatenate(out))
 
 
 def pass_sizes(ws, ov, n_pass, pass_scale):
@@ -1456,7 +1556,7 @@ class Plan:
 
     def __init__(self, H, W, ws, ov, n_pass=1, mode="CWS", pass_scale=2.0, val_ratio=1.2,
                  val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None, uncertainty=None,
-                 deform=None, ensemble=False):
+                 deform=None, ensemble=False, correlation=None):
         # outlier: None, "median" or a dict (outlier_arg): the normalized median test after every pass -- flagged vectors of
         # a pass before the last are replaced by their neighbourhood median before the predictor reads them, flagged
         # vectors of the last pass join the invalid mask (tpiv_plan_set_outlier)
@@ -1478,6 +1578,13 @@ class Plan:
         self.ensemble = bool(ensemble)
         if self.ensemble:
             ensemble_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], self.uncertainty_par, self.deform)
+        # correlation: None, "phase", "rpc" or a dict (correlation_arg): every pass takes its peak from the phase-only /
+        # robust-phase-correlation map instead of the plain cross-correlation (tpiv_plan_set_correlation); window sizes 16,
+        # 32, 64 only, neither uncertainty= nor deform= nor ensemble=, and `precision` has no effect on such a plan
+        self.correlation = correlation_arg(correlation)
+        if self.correlation is not None:
+            correlation_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], mode, self.uncertainty_par, self.deform,
+                              self.ensemble)
         if self.mask is not None and tuple(self.mask["image"].shape) != (H, W):
             raise ValueError(f"mask of shape {tuple(self.mask['image'].shape)} for frames of shape {(H, W)}")
         if not torch.cuda.is_available():
@@ -1511,6 +1618,8 @@ class Plan:
                                                    _dewarp_table(self.device).data_ptr() if cubic else None))
                 if self.ensemble:
                     check(lib.tpiv_plan_set_ensemble(self._h, 1))
+                if self.correlation is not None:
+                    self.set_correlation(self.correlation)
             except Exception:
                 self.close()
                 raise
@@ -1529,6 +1638,24 @@ class Plan:
             self._h = C.c_void_p()
 
     __del__ = close
+
+    def set_correlation(self, correlation):
+        """Switches the plan's passes to the filtered map (correlation_arg's forms; None: back to the plain
+        cross-correlation).  The tables are built here and uploaded once (tpiv_plan_set_correlation)."""
+        par = correlation_arg(correlation)
+        with torch.cuda.device(self.device):
+            if par is None:
+                check(lib.tpiv_plan_set_correlation(self._h, _lib.CORR_NONE, 0.0, 0.0, 0.0, None, 0))
+            else:
+                sizes = []
+                for p in range(lib.tpiv_plan_n_pass(self._h)):
+                    w = C.c_int()
+                    check(lib.tpiv_plan_pass_geometry(self._h, p, C.byref(w), None, None, None))
+                    sizes.append(w.value)
+                tab = correlation_tables(par, sizes)
+                check(lib.tpiv_plan_set_correlation(self._h, _lib.CORRELATIONS[par["kind"]], par["dx"], par["dy"], par["floor"],
+                                                    tab.ctypes.data, tab.size))
+        self.correlation = par
 
     @property
     def out_shape(self):
