@@ -457,6 +457,52 @@ enum { TPIV_CORR_NONE = 0, TPIV_CORR_PHASE = 1, TPIV_CORR_RPC = 2 };
 int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double d_x, double d_y, double floor, const float* tables,
                               size_t n_tables);
 
+/* ---- weighted interrogation windows ------------------------------------------------------------------------------------
+ * Every pass of a plan with this on multiplies its windows by a separable weight in front of the transform; the top-hat
+ * window of the plain passes has a sinc-shaped frequency response with negative lobes (F. Schrijer, F. Scarano, Effect of
+ * predictor-corrector filtering on the stability and spatial resolution of iterative PIV interrogation, Exp. Fluids 45
+ * (2008) 927), a Gaussian weight a positive one and a smaller effective footprint.  Take a window pair as the pass stages
+ * it -- first pass, DWS or CWS staging, quirks included, exactly the windows tpiv_debug_pass reports -- and call the staged
+ * windows wa, wb (ws x ws, float32).
+ *   1. W(y, x) = g_y[y] g_x[x], one float32 product; both tables have ws entries and are strictly positive.
+ *      TPIV_WEIGHT_GAUSSIAN: g[i] = float32(exp(-t^2 / (2 sigma^2))), t = (2 i - (ws - 1)) / ws, evaluated in float64 on the
+ *      host and rounded once; sigma is relative to the half window, 0.2 <= sigma <= 4 (sigma_x for g_x, sigma_y for g_y).
+ *      TPIV_WEIGHT_UNIFORM: g = 1, the top-hat window through the weighted kernels.
+ *   2. a' = wa - mean(wa), the plain mean: exactly 0 for a constant integer-valued window.
+ *   3. mu = sum W a' / sum W, the W-weighted mean of the remainder: the weighted signal has no DC, or the map would carry
+ *      the pedestal W * W centred at zero displacement.
+ *   4. x_a = W (a' - mu); in the first pass x_a is additionally divided by mean(wa), which keeps the scale of the plain first
+ *      pass (B:513-514), so the peak stage's 1e-7 keeps its relative size.  The shifted passes divide by nothing.  x_b
+ *      likewise.
+ *   5. C = fftshift of the circular cross-correlation of x_a and x_b, as every float32 pass forms it.  The peak stage of
+ *      every pass follows unchanged: minimum subtraction, + 1e-7, first arg-max, three-point log-Gaussian fit,
+ *      peak-to-second-peak test with the plan's val_ratio / val_win, float64 epilogue; a shifted pass then combines with the
+ *      predictor as tpiv_iter does.
+ *   6. A window whose energy sum x^2 is exactly 0 in float32 in either frame (a zero, masked or constant window) is handled
+ *      as rule 7 of tpiv_plan_set_correlation has it: in the first pass it is dead (u = v = 0, valid), as is a first-pass
+ *      window whose pixel sum is 0; in a shifted pass it hands the zero map to the peak stage, whose peak ratio makes it
+ *      invalid.  No NaN.  A CWS window that is constant only up to the rounding of its bilinear samples is not empty: its
+ *      map is rounding noise, which the peak ratio has to reject.
+ *   7. The bias of the weighted correlation toward zero displacement (the envelope W * W) is NOT corrected, as the reference
+ *      does not correct the top-hat's triangle; it vanishes as the residual does under predictor passes and
+ *      tpiv_plan_set_deform.
+ * tables (host): for pass 0, 1, ... in turn g_y[0 .. ws-1] then g_x[0 .. ws-1] of that pass's window size, n_tables floats
+ * in all; the plan uploads them once.  The weights are the tables' (sigma_x, sigma_y are checked against their range and not
+ * kept).  kind = TPIV_WEIGHT_NONE: off, every pass is byte for byte what it was (tables may be NULL).
+ * TPIV_EINVAL: a table entry that is not finite or not in (0, 1], a uniform table that is not all ones, sigma out of range, a
+ * wrong n_tables.  TPIV_EUNSUPPORTED, with a message naming the size, when a pass has a window size other than 16, 32 or 64
+ * (multipass modes of a plan are DWS and CWS; the CWS_Fast iteration has no weighted kernel: tpiv_debug_pass_weighted).
+ * TPIV_EINVAL on a plan with tpiv_plan_set_uncertainty (its estimator sums over a top-hat window), tpiv_plan_set_ensemble or
+ * tpiv_plan_set_correlation on -- and those refuse a plan with this on.  It combines with tpiv_plan_set_deform, in either
+ * order of the two calls: the residual pass of every round is the weighted first pass at the last pass's geometry with that
+ * pass's tables.  The plan's precision has no effect on a weighted pass (float32 kernel, float64 epilogue); a plan whose
+ * workspace was sized for float64 records alone gets a larger one here.  tpiv_plan_exact_fallbacks returns TPIV_EINVAL after
+ * a weighted run, and tpiv_plan_exact_timing averages over the other runs alone.  tpiv_plan_set_mask and
+ * tpiv_plan_set_outlier act as on any plan.  tpiv_plan_kernel_name names the weighted kernels for such a plan.  A failed
+ * call changes nothing. */
+enum { TPIV_WEIGHT_NONE = 0, TPIV_WEIGHT_UNIFORM = 1, TPIV_WEIGHT_GAUSSIAN = 2 };
+int tpiv_plan_set_weighting(tpiv_plan* plan, int kind, double sigma_x, double sigma_y, const float* tables, size_t n_tables);
+
 /* ---- post-validation (B:884-892) ------------------------------------------------- */
 
 /* Device part of the reference's per-pair host post-processing, for a whole batch:
@@ -686,6 +732,15 @@ int tpiv_debug_pass_spec(int mode, int kind, double floor, const float* tab_dev,
                          int batch, int H, int W, int ws, int ov, const double* u2_dev, const double* v2_dev,
                          const double* zero_dev, double* u_dev, double* v_dev, uint8_t* invalid_dev, float* win_dev,
                          float* corr_dev, void* work_dev, size_t work_bytes, void* stream);
+
+/* tpiv_debug_pass of a weighted pass (tpiv_plan_set_weighting): mode 0, TPIV_MODE_DWS or TPIV_MODE_CWS at ws = 16, 32 or 64
+ * (anything else, TPIV_MODE_CWS_FAST included: TPIV_EUNSUPPORTED); tab_dev = g_y[0 .. ws-1] then g_x[0 .. ws-1] on the
+ * device.  win_dev receives the staged windows (before step 2), corr_dev the map the decisions are taken on, C - min + 1e-7
+ * in fftshift layout. */
+int tpiv_debug_pass_weighted(int mode, const float* tab_dev, const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H,
+                             int W, int ws, int ov, const double* u2_dev, const double* v2_dev, const double* zero_dev,
+                             double* u_dev, double* v_dev, uint8_t* invalid_dev, float* win_dev, float* corr_dev,
+                             void* work_dev, size_t work_bytes, void* stream);
 
 /* Runs one shifted pass (mode DWS or CWS) from the COMPACT predictor hand-off, exactly as tpiv_plan_run does after its
  * predictor: u_raw_dev, v_raw_dev [batch, n_rows, n_cols] float64 are the raw predictor (before the invalid-zeroing) and

@@ -24,6 +24,8 @@ DEWARP_LINEAR, DEWARP_CUBIC = 0, 1
 DEWARP_INTERPS = {"linear": DEWARP_LINEAR, "cubic": DEWARP_CUBIC}                    # tpiv_dewarp's interpolations
 CORR_NONE, CORR_PHASE, CORR_RPC = 0, 1, 2
 CORRELATIONS = {"phase": CORR_PHASE, "rpc": CORR_RPC}                                # tpiv_plan_set_correlation's kinds
+WEIGHT_NONE, WEIGHT_UNIFORM, WEIGHT_GAUSSIAN = 0, 1, 2
+WEIGHTINGS = {"uniform": WEIGHT_UNIFORM, "gaussian": WEIGHT_GAUSSIAN}                # tpiv_plan_set_weighting's kinds
 DEFORM_GATHER = 0x100                           # OR-ed into tpiv_deform_warp's interp: the gather form everywhere
 ABI_VERSION = 2
 
@@ -105,6 +107,9 @@ SIGNATURES = {
     "tpiv_plan_set_correlation": (C.c_int, [C.c_void_p, _int, _dbl, _dbl, _dbl, _vp, C.c_size_t]),
     "tpiv_debug_pass_spec": (C.c_int, [_int, _int, _dbl, _f32p, _u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _f64p,
                                        _f64p, _f64p, _u8p, _f32p, _f32p, _vp, C.c_size_t, _vp]),
+    "tpiv_plan_set_weighting": (C.c_int, [C.c_void_p, _int, _dbl, _dbl, _vp, C.c_size_t]),
+    "tpiv_debug_pass_weighted": (C.c_int, [_int, _f32p, _u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _f64p,
+                                           _f64p, _f64p, _u8p, _f32p, _f32p, _vp, C.c_size_t, _vp]),
     "tpiv_postval": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _u8p, _vp, _vp]),
     "tpiv_postval_compact": (C.c_int, [_f64p, _f64p, _u8p, _vp, _int, _int, _int, _vp, _vp, _f64p, _vp, _vp]),
     "tpiv_finish_fields": (C.c_int, [_f64p, _f64p, _int, _int, _int, C.c_double, C.c_double, _f64p, _f64p, _vp]),

@@ -372,8 +372,8 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 depth=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, equalize=None,
-                 prefilter=None) -> None:
+                 depth=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None,
+                 equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -437,10 +437,22 @@ class OfflinePIV:
         # banding -- that competes with the particle peak.  Window sizes 16, 32 and 64 in every pass (NotImplementedError
         # otherwise); combines with neither uncertainty= nor deform= nor ensemble() (ValueError); precision= has no effect
         # on a filtered pass.  The tuples delivered are the same; only the values differ.
+        # weighting (extension): None, "gaussian", "uniform" or a dict with any of kind and sigma (one number or (sigma_x,
+        # sigma_y), relative to the half window, 0.2..4; default 0.4) -- every pass multiplies its interrogation windows by a
+        # separable weight in front of the transform (engine.weighting_arg, tpiv_plan_set_weighting).  A Gaussian weight
+        # has a positive frequency response and a smaller effective footprint than the top-hat window: a large window at
+        # high overlap then resolves what a small one resolves and keeps the large window's robustness; the standard
+        # companion of deform=, whose residual passes are weighted too.  The bias of the weighted correlation toward zero
+        # displacement is not corrected (it vanishes as the residual does under predictor passes and deform=).  Window sizes
+        # 16, 32 and 64 in every pass (NotImplementedError otherwise); combines with neither uncertainty= nor correlation=
+        # nor ensemble() (ValueError); precision= has no effect on a weighted pass.  The tuples delivered are the same; only
+        # the values differ.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         correlation = self._correlation_arg(correlation, wind_size, overlap, multipass, multipass_scale, multipass_mode,
                                             uncertainty, deform)
+        weighting = self._weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode,
+                                        uncertainty, correlation)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
         depth = engine.depth_arg(depth)
         dataset = PIVDataset(folder, file_fmt, folder_mode, deep=depth is not None,
@@ -450,7 +462,7 @@ class OfflinePIV:
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
                          engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize),
                          engine.mask_arg(mask), engine.dewarp_arg(dewarp), engine.uncertainty_arg(uncertainty),
-                         engine.deform_arg(deform), correlation)
+                         engine.deform_arg(deform), correlation, weighting)
         if not self:
             return
         if self._mask is not None:
@@ -463,7 +475,7 @@ class OfflinePIV:
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                     multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
-                    equalize=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None):
+                    equalize=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
         engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's, dewarp: engine.dewarp_arg's,
@@ -483,6 +495,7 @@ class OfflinePIV:
         self._uncertainty = uncertainty
         self._deform = deform            # deform=: engine.deform_arg's, handed to every plan
         self._correlation = correlation  # correlation=: engine.correlation_arg's, handed to every plan but ensemble()'s
+        self._weighting = weighting      # weighting=: engine.weighting_arg's, handed to every plan but ensemble()'s
         self._dw_map = None              # dewarp=: the Q8 map on the device, int32 [H, W, 2], once a run needs it
         self._dw_frames = None           # dewarp=: the rectified frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
         self._mask_dev = None            # mask=: the image on the device, uint8 [H, W], once a run needs it
@@ -515,6 +528,15 @@ class OfflinePIV:
             engine.correlation_check(sizes, multipass_mode, engine.uncertainty_arg(uncertainty), engine.deform_arg(deform))
         return par
 
+    @staticmethod
+    def _weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode, uncertainty, correlation):
+        """weighting= of either constructor, checked with what it refuses (no GPU involved): engine.weighting_arg's."""
+        par = engine.weighting_arg(weighting)
+        if par is not None:
+            sizes = [w for w, _ in engine.pass_sizes(wind_size, overlap, multipass, multipass_scale)]
+            engine.weighting_check(sizes, multipass_mode, engine.uncertainty_arg(uncertainty), False, correlation)
+        return par
+
     def _first_decodable(self, idx):
         """(pair id, frame shape) of the first pair of `idx` that decodes, None without one."""
         for i in idx:
@@ -533,7 +555,7 @@ class OfflinePIV:
                            mode=self._mode, pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio,
                            val_win=self._val_win, device=self._device, precision=self._precision, outlier=self._outlier,
                            mask=self._mask, uncertainty=self._uncertainty, deform=self._deform,
-                           correlation=self._correlation)
+                           correlation=self._correlation, weighting=self._weighting)
 
     def _get_plan(self, H, W, max_batch=1):
         if (self._plan is None or (self._plan.H, self._plan.W) != (H, W)
@@ -808,6 +830,8 @@ class OfflinePIV:
     def _ensemble_check(self):
         if self._correlation is not None:
             raise ValueError("ensemble correlation does not combine with correlation=")
+        if self._weighting is not None:
+            raise ValueError("ensemble correlation does not combine with weighting=")
         engine.ensemble_check([w for w, _ in engine.pass_sizes(self._wind_size, self._overlap, self._iter, self._iter_scale)],
                               self._uncertainty, self._deform)
 
@@ -1391,7 +1415,8 @@ class ResidentPIV(OfflinePIV):
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
                  validation_window: int = 3, background=None, outlier=None, depth=None, mask=None,
-                 dewarp=None, uncertainty=None, deform=None, correlation=None, equalize=None, prefilter=None) -> None:
+                 dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None, equalize=None,
+                 prefilter=None) -> None:
         # dewarp (see OfflinePIV): every launch rectifies its pairs into a reused buffer, addressed by their offsets in the
         # caller's stacks (nothing is gathered first, and the caller's frames are never written)
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
@@ -1420,6 +1445,8 @@ class ResidentPIV(OfflinePIV):
         deform = engine.deform_arg(deform)
         correlation = self._correlation_arg(correlation, wind_size, overlap, multipass, multipass_scale, multipass_mode,
                                             uncertainty, deform)
+        weighting = self._weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode,
+                                        uncertainty, correlation)
         dewarp = engine.dewarp_arg(dewarp)
         if dewarp is not None and "map" in dewarp and tuple(dewarp["map"][0].shape) != tuple(frames_a.shape[1:]):
             raise ValueError(f"dewarp map of shape {tuple(dewarp['map'][0].shape)} for frames of shape "
@@ -1428,7 +1455,7 @@ class ResidentPIV(OfflinePIV):
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
                          validation_window, bg_arg, outlier, prefilter, depth, equalize, mask, dewarp,
-                         uncertainty, deform, correlation)
+                         uncertainty, deform, correlation, weighting)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):

@@ -286,7 +286,10 @@ struct tpiv_plan {
     double corr_floor = 0.0;
     std::vector<float*> corr_tab;        // per pass: g_y[0 .. ws/2], then g_x[0 .. ws/2]
     tpiv::SpecParams spec(int pass) const { return tpiv::SpecParams{corr_tab[pass], (float)corr_floor}; }
-    bool last_filtered = false;          // the last tpiv_plan_run ran filtered passes: its first pass took no exact scheme
+    // weighted interrogation windows (tpiv_plan_set_weighting); off: nothing is allocated and every pass is the plain one
+    int wt_kind = 0;
+    std::vector<float*> wt_tab;          // per pass: g_y[0 .. ws-1], then g_x[0 .. ws-1]
+    bool last_filtered = false;          // the last tpiv_plan_run ran filtered or weighted passes: its first pass took no exact scheme
     std::vector<char> sub_recorded;      // per timed run: the three sub-events of the exact first pass were recorded
     std::vector<void*> allocs;
     // optional per-kernel timing: events[run][2*slot + {0,1}]
@@ -472,10 +475,11 @@ static tpiv::PassParams pass_params(const uint8_t* a, const uint8_t* b, int batc
 static int pass1_impl(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
                       double val_ratio, int val_win, int precision, double* u, double* v, uint8_t* invalid,
                       void* work, size_t work_bytes, float* dbg_win, float* dbg_corr, void* stream,
-                      hipEvent_t* sub_events = nullptr, const tpiv::SpecParams* spec = nullptr) {
+                      hipEvent_t* sub_events = nullptr, const tpiv::SpecParams* spec = nullptr,
+                      const tpiv::WinParams* win = nullptr) {
     int rc = check_window(H, W, ws, ov, val_win);
     if (rc) return rc;
-    if (spec) precision = TPIV_PREC_FAST;      // a filtered first pass is the float32 spectral kernel at every precision
+    if (spec || win) precision = TPIV_PREC_FAST;      // a filtered or weighted first pass is a float32 kernel at every precision
     if (!valid_precision(precision)) return fail(TPIV_EINVAL, "precision must be TPIV_PREC_FAST, TPIV_PREC_REFERENCE, TPIV_PREC_F64 or TPIV_PREC_EXACT");
     if (batch <= 0) return TPIV_OK;
     tpiv::PassParams p = pass_params(a, b, batch, H, W, ws, ov, val_ratio, val_win, precision, u, v, invalid, dbg_win, dbg_corr);
@@ -486,7 +490,8 @@ static int pass1_impl(const uint8_t* a, const uint8_t* b, int batch, int H, int 
     int n_cu;
     rc = n_cu_of_current_device(&n_cu);
     if (rc) return rc;
-    if (spec) HIP_TRY(tpiv::launch_xcorr_spec(p, tpiv::MODE_PASS1, *spec, n_cu, (hipStream_t)stream));
+    if (win) HIP_TRY(tpiv::launch_xcorr_win(p, tpiv::MODE_PASS1, *win, n_cu, (hipStream_t)stream));
+    else if (spec) HIP_TRY(tpiv::launch_xcorr_spec(p, tpiv::MODE_PASS1, *spec, n_cu, (hipStream_t)stream));
     else HIP_TRY(tpiv::launch_xcorr(p, tpiv::MODE_PASS1, n_cu, (hipStream_t)stream));
     return TPIV_OK;
 }
@@ -538,7 +543,8 @@ static int run_iter(int mode, int precision, const uint8_t* a, const uint8_t* b,
                     int ov, const double* u0, const double* v0, const double* u2, const double* v2,
                     double val_ratio, int val_win, double* u, double* v, uint8_t* invalid, double* du,
                     double* dv, float* dbg_win, float* dbg_corr, void* work, size_t work_bytes, void* stream,
-                    const uint8_t* pmask = nullptr, const tpiv::SpecParams* spec = nullptr) {
+                    const uint8_t* pmask = nullptr, const tpiv::SpecParams* spec = nullptr,
+                    const tpiv::WinParams* win = nullptr) {
     if (mode != TPIV_MODE_DWS && mode != TPIV_MODE_CWS && mode != TPIV_MODE_CWS_FAST)
         return fail(TPIV_EKEY, "unknown multipass mode");
     int rc = check_window(H, W, ws, ov, val_win);
@@ -563,7 +569,8 @@ static int run_iter(int mode, int precision, const uint8_t* a, const uint8_t* b,
     int n_cu;
     rc = n_cu_of_current_device(&n_cu);
     if (rc) return rc;
-    if (spec) HIP_TRY(tpiv::launch_xcorr_spec(p, mode, *spec, n_cu, (hipStream_t)stream));
+    if (win) HIP_TRY(tpiv::launch_xcorr_win(p, mode, *win, n_cu, (hipStream_t)stream));
+    else if (spec) HIP_TRY(tpiv::launch_xcorr_spec(p, mode, *spec, n_cu, (hipStream_t)stream));
     else HIP_TRY(tpiv::launch_xcorr(p, mode, n_cu, (hipStream_t)stream));
     return TPIV_OK;
 }
@@ -616,6 +623,23 @@ int tpiv_debug_pass_spec(int mode, int kind, double floor, const float* tab, con
     if (!zero || !u2 || !v2) return fail(TPIV_EINVAL, "tpiv_debug_pass_spec: shifted passes need u2, v2 and a zero field");
     return run_iter(mode, TPIV_PREC_FAST, a, b, batch, H, W, ws, ov, zero, zero, u2, v2, 1.2, 3, u, v, invalid, nullptr, nullptr,
                     win, corr, work, work_bytes, stream, nullptr, &sp);
+}
+
+int tpiv_debug_pass_weighted(int mode, const float* tab, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws,
+                             int ov, const double* u2, const double* v2, const double* zero, double* u, double* v,
+                             uint8_t* invalid, float* win, float* corr, void* work, size_t work_bytes, void* stream) {
+    if (mode == TPIV_MODE_CWS_FAST) return fail(TPIV_EUNSUPPORTED, "weighting=: the CWS_Fast iteration has no weighted kernel");
+    if (mode != 0 && mode != TPIV_MODE_DWS && mode != TPIV_MODE_CWS) return fail(TPIV_EKEY, "unknown multipass mode");
+    if (!tpiv::win_size(ws))
+        return fail(TPIV_EUNSUPPORTED, "weighting=: weighted passes cover window sizes 16, 32 and 64 (got " + std::to_string(ws) + ")");
+    if (!tab) return fail(TPIV_EINVAL, "tpiv_debug_pass_weighted: tables missing");
+    const tpiv::WinParams wp{tab};
+    if (mode == 0)
+        return pass1_impl(a, b, batch, H, W, ws, ov, 1.2, 3, TPIV_PREC_FAST, u, v, invalid, work, work_bytes, win, corr, stream,
+                          nullptr, nullptr, &wp);
+    if (!zero || !u2 || !v2) return fail(TPIV_EINVAL, "tpiv_debug_pass_weighted: shifted passes need u2, v2 and a zero field");
+    return run_iter(mode, TPIV_PREC_FAST, a, b, batch, H, W, ws, ov, zero, zero, u2, v2, 1.2, 3, u, v, invalid, nullptr, nullptr,
+                    win, corr, work, work_bytes, stream, nullptr, nullptr, &wp);
 }
 
 int tpiv_debug_iter_compact(int mode, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov,
@@ -775,6 +799,7 @@ const char* tpiv_plan_kernel_name(const tpiv_plan* plan, int pass, char* buf, in
     buf[0] = 0;
     if (!plan || pass < 0 || pass >= plan->n_pass) return buf;
     const int mode = pass == 0 ? (int)tpiv::MODE_PASS1 : plan->mode;
+    if (plan->wt_kind) return tpiv::xcorr_win_kernel_name(plan->geo[pass].ws, mode, buf, len);
     if (plan->corr_kind) return tpiv::xcorr_spec_kernel_name(plan->geo[pass].ws, mode, buf, len);
     return tpiv::xcorr_kernel_name(plan->geo[pass].ws, mode, plan->precision, buf, len);
 }
@@ -785,7 +810,7 @@ int tpiv_plan_exact_fallbacks(tpiv_plan* plan, long long* n_windows) {
         return fail(TPIV_EINVAL, "not a TPIV_PREC_EXACT plan with an even first-pass window size from 8 to 128");
     if (plan->last_batch <= 0) return fail(TPIV_EINVAL, "the plan has not run yet");
     if (plan->last_filtered)
-        return fail(TPIV_EINVAL, "the last run's first pass was a filtered one (tpiv_plan_set_correlation): it takes no exact scheme");
+        return fail(TPIV_EINVAL, "the last run's first pass was a filtered or weighted one (tpiv_plan_set_correlation, tpiv_plan_set_weighting): it takes no exact scheme");
     HIP_TRY(hipDeviceSynchronize());
     unsigned n = 0;
     HIP_TRY(hipMemcpy(&n, plan->exact_count, sizeof(n), hipMemcpyDeviceToHost));
@@ -1062,6 +1087,7 @@ int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius) {
     }
     if (plan->ens_on) return fail(TPIV_EINVAL, "uncertainty= does not combine with ensemble correlation");
     if (plan->corr_kind) return fail(TPIV_EINVAL, "uncertainty= does not combine with correlation=");
+    if (plan->wt_kind) return fail(TPIV_EINVAL, "uncertainty= does not combine with weighting= (its estimator sums over a top-hat window)");
     const PassGeo& g = plan->geo[plan->n_pass - 1];
     if (int rc = check_uncertainty(plan->H, plan->W, g.ws, g.ov, radius)) return rc;
     if (!plan->unc_su) {                             // first time on: the two fields (kept until the plan is destroyed)
@@ -1309,6 +1335,8 @@ static int run_deform(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int b
     const PassGeo& g = plan->geo[last];
     const size_t cells = (size_t)batch * g.n_rows * g.n_cols;
     HIP_TRY(hipEventRecord(plan->def_ev[0], st));
+    // a weighted plan's residual pass is the weighted first pass with the last pass's tables
+    const tpiv::WinParams wp{plan->wt_kind ? plan->wt_tab[last] : nullptr};
     for (int k = 1; k <= plan->def_iters; ++k) {
         // excluded cells stay valid behind every round, so that they pull the warp to zero at a wall
         const Settle settle(plan, last, k < plan->def_iters, false, u, v, invalid, plan->def_su, plan->def_sv);
@@ -1331,7 +1359,7 @@ static int run_deform(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int b
         HIP_TRY(tpiv::launch_deform_warp(q, st));
         if (int rc = pass1_impl(plan->def_wa, plan->def_wb, batch, plan->H, plan->W, g.ws, g.ov, plan->val_ratio, plan->val_win,
                                 plan->precision, plan->def_du, plan->def_dv, plan->def_dval, plan->peak_raw,
-                                plan->peak_raw_bytes, nullptr, nullptr, stream))
+                                plan->peak_raw_bytes, nullptr, nullptr, stream, nullptr, nullptr, plan->wt_kind ? &wp : nullptr))
             return rc;
         HIP_TRY(tpiv::launch_deform_combine(plan->def_nodes, plan->def_du, plan->def_dv, plan->def_dval, cells, settle.wu,
                                             settle.wv, settle.wval, st));
@@ -1365,13 +1393,15 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
         int rc;
         const tpiv::SpecParams sp = plan->corr_kind ? plan->spec(p) : tpiv::SpecParams{};
         const tpiv::SpecParams* const spec = plan->corr_kind ? &sp : nullptr;
+        const tpiv::WinParams wp{plan->wt_kind ? plan->wt_tab[p] : nullptr};
+        const tpiv::WinParams* const win = plan->wt_kind ? &wp : nullptr;
         if (p == 0) {
             mark(0, 0);
             rc = pass1_impl(a, b, batch, plan->H, plan->W, g.ws, g.ov, plan->val_ratio, plan->val_win,
                             plan->precision, pu, pv, pval, plan->peak_raw, plan->peak_raw_bytes, nullptr, nullptr,
-                            stream, spec ? nullptr : plan->sub_events(), spec);
+                            stream, spec || win ? nullptr : plan->sub_events(), spec, win);
             mark(0, 1);
-            if (!rc && plan->exact_count && !spec) {
+            if (!rc && plan->exact_count && !spec && !win) {
                 const size_t off = tpiv::exact_fallback_count_offset(batch, g.n_rows * g.n_cols);
                 HIP_TRY(hipMemcpyAsync(plan->exact_count, reinterpret_cast<const char*>(plan->peak_raw) + off,
                                        sizeof(unsigned), hipMemcpyDeviceToDevice, st));
@@ -1387,7 +1417,7 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
             if (!rc)
                 rc = run_iter(plan->mode, plan->precision, a, b, batch, plan->H, plan->W, g.ws, g.ov, plan->u0, plan->v0,
                               nullptr, nullptr, plan->val_ratio, plan->val_win, pu, pv, pval, nullptr,
-                              nullptr, nullptr, nullptr, plan->peak_raw, plan->peak_raw_bytes, stream, plan->pmask, spec);
+                              nullptr, nullptr, nullptr, plan->peak_raw, plan->peak_raw_bytes, stream, plan->pmask, spec, win);
             mark(2 * p, 1);
         }
         if (rc) return rc;
@@ -1407,7 +1437,7 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
                                      plan->unc_sv, nullptr, st))
             return rc;
     }
-    plan->last_filtered = plan->corr_kind != 0;
+    plan->last_filtered = plan->corr_kind != 0 || plan->wt_kind != 0;
     if (plan->timing && plan->runs_recorded < 512) {
         if (plan->sub_recorded.size() <= plan->runs_recorded) plan->sub_recorded.resize(plan->runs_recorded + 1, 0);
         plan->sub_recorded[plan->runs_recorded] = plan->exact_count != nullptr && !plan->last_filtered;
@@ -1429,6 +1459,7 @@ int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double dx, double dy, d
     if (plan->unc_kind) return fail(TPIV_EINVAL, "correlation= does not combine with uncertainty=");
     if (plan->def_iters) return fail(TPIV_EINVAL, "correlation= does not combine with deform=");
     if (plan->ens_on) return fail(TPIV_EINVAL, "correlation= does not combine with ensemble correlation");
+    if (plan->wt_kind) return fail(TPIV_EINVAL, "correlation= does not combine with weighting=");
     size_t need = 0;
     for (const PassGeo& g : plan->geo) {
         if (!tpiv::spec_size(g.ws))
@@ -1467,6 +1498,67 @@ int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double dx, double dy, d
     }
     plan->corr_kind = kind;
     plan->corr_floor = floor;
+    return TPIV_OK;
+}
+
+// ---- weighted interrogation windows ---------------------------------------------------------------------------------
+
+int tpiv_plan_set_weighting(tpiv_plan* plan, int kind, double sigma_x, double sigma_y, const float* tables, size_t n_tables) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (kind == TPIV_WEIGHT_NONE) {
+        plan->wt_kind = 0;
+        return TPIV_OK;
+    }
+    if (kind != TPIV_WEIGHT_UNIFORM && kind != TPIV_WEIGHT_GAUSSIAN)
+        return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: kind must be TPIV_WEIGHT_NONE, TPIV_WEIGHT_UNIFORM or TPIV_WEIGHT_GAUSSIAN");
+    if (kind == TPIV_WEIGHT_GAUSSIAN && (!(sigma_x >= 0.2 && sigma_x <= 4.0) || !(sigma_y >= 0.2 && sigma_y <= 4.0)))
+        return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: sigma must be in 0.2..4 (relative to the half window)");
+    if (plan->unc_kind) return fail(TPIV_EINVAL, "weighting= does not combine with uncertainty= (its estimator sums over a top-hat window)");
+    if (plan->ens_on) return fail(TPIV_EINVAL, "weighting= does not combine with ensemble correlation");
+    if (plan->corr_kind) return fail(TPIV_EINVAL, "weighting= does not combine with correlation=");
+    size_t need = 0;
+    for (const PassGeo& g : plan->geo) {
+        if (!tpiv::win_size(g.ws))
+            return fail(TPIV_EUNSUPPORTED, "weighting=: weighted passes cover window sizes 16, 32 and 64; this plan has a pass of " +
+                                               std::to_string(g.ws));
+        need += 2 * (size_t)g.ws;
+    }
+    if (!tables || n_tables != need)
+        return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: tables must hold g_y and g_x of every pass, " + std::to_string(need) +
+                                     " floats in all");
+    for (size_t i = 0; i < need; ++i)
+        if (!(tables[i] > 0.0f && tables[i] <= 1.0f))       // (also refuses NaN)
+            return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: every table entry must be finite and in (0, 1]");
+    if (kind == TPIV_WEIGHT_UNIFORM)
+        for (size_t i = 0; i < need; ++i)
+            if (tables[i] != 1.0f) return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: the uniform weight's tables are all ones");
+    if (int rc = check_plan_device(plan)) return rc;
+    // a weighted pass works in the float32 tile layout (records, item counters) whatever the plan's precision: a plan whose
+    // workspace was sized for float64 records alone gets a larger one (the old one is freed with the plan)
+    size_t raw = 0;
+    for (const PassGeo& g : plan->geo)
+        raw = std::max(raw, tpiv::peak_raw_bytes(g.ws, plan->max_batch, g.n_rows * g.n_cols, TPIV_PREC_FAST));
+    float* grown = nullptr;
+    if (raw > plan->peak_raw_bytes)
+        if (int rc = plan->alloc(&grown, raw / sizeof(float) + 64)) return rc;
+    if (plan->wt_tab.empty()) {                      // first time on (kept until the plan is destroyed)
+        std::vector<float*> tabs(plan->n_pass, nullptr);
+        for (int p = 0; p < plan->n_pass; ++p)
+            if (int rc = plan->alloc(&tabs[p], 2 * (size_t)plan->geo[p].ws)) return rc;
+        plan->wt_tab = std::move(tabs);
+    }
+    HIP_TRY(hipDeviceSynchronize());                 // no run in flight reads the tables while they change
+    size_t off = 0;
+    for (int p = 0; p < plan->n_pass; ++p) {
+        const size_t n = 2 * (size_t)plan->geo[p].ws;
+        HIP_TRY(hipMemcpy(plan->wt_tab[p], tables + off, n * sizeof(float), hipMemcpyHostToDevice));
+        off += n;
+    }
+    if (grown) {
+        plan->peak_raw = grown;
+        plan->peak_raw_bytes = raw;
+    }
+    plan->wt_kind = kind;
     return TPIV_OK;
 }
 
@@ -1563,6 +1655,7 @@ int tpiv_plan_set_ensemble(tpiv_plan* plan, int on) {
     if (plan->unc_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with uncertainty=");
     if (plan->def_iters) return fail(TPIV_EINVAL, "ensemble correlation does not combine with deform=");
     if (plan->corr_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with correlation=");
+    if (plan->wt_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with weighting=");
     size_t cells = 0, fine = 0;
     for (const PassGeo& g : plan->geo) {
         if (!tpiv::ensemble_size(g.ws))

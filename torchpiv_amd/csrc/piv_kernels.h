@@ -361,6 +361,15 @@ bool spec_size(int ws);
 // the pass with its finalize step; p.peak_raw: peak_raw_bytes(ws, batch, n_windows, 0)
 hipError_t launch_xcorr_spec(const PassParams& p, int mode, const SpecParams& s, int n_cu, hipStream_t stream);
 const char* xcorr_spec_kernel_name(int ws, int mode, char* buf, int len);
+// weighted interrogation windows (xcorr_win.hip, defined in include/torchpiv_hip.h: tpiv_plan_set_weighting): window sizes 16,
+// 32 and 64, pass 1 / DWS / CWS.  The tables travel as a second kernel argument: PassParams keeps its layout.
+struct WinParams {
+    const float* tab;        // device: g_y[0 .. ws-1], then g_x[0 .. ws-1] (all ones: the top-hat through these kernels)
+};
+bool win_size(int ws);
+// the pass with its finalize step; p.peak_raw: peak_raw_bytes(ws, batch, n_windows, 0)
+hipError_t launch_xcorr_win(const PassParams& p, int mode, const WinParams& s, int n_cu, hipStream_t stream);
+const char* xcorr_win_kernel_name(int ws, int mode, char* buf, int len);
 hipError_t launch_predict_mfma(const BandedPredictParams& q, hipStream_t stream);
 hipError_t launch_predict(const PredictParams& q, hipStream_t stream);
 

@@ -39,6 +39,9 @@ hipError_t launch_peak_ens(const PassParams& p, const float* acc, int n_maps, lo
 hipError_t launch_xcorr_spec_tile(const PassParams& p, int mode, const SpecParams& s, int n_cu, hipStream_t stream);   // xcorr_spec.hip
 int spec_occ(int ws, int mode);
 bool spec_planar(int ws, int mode);
+hipError_t launch_xcorr_win_tile(const PassParams& p, int mode, const WinParams& s, int n_cu, hipStream_t stream);     // xcorr_win.hip
+int win_occ(int ws, int mode);
+bool win_planar(int ws, int mode);
 
 // ---- finalize: sub-pixel fit, validation and multipass combine, one thread per window -----------
 // PIVbackend.py:385-422 (correlation_to_displacement) and B:728-738 / B:800-810 (combine).  Input:
@@ -445,6 +448,37 @@ hipError_t launch_xcorr_spec(const PassParams& p_in, int mode, const SpecParams&
     hipError_t e = hipMemsetAsync(p.work_ctr, 0, WORK_CTR_BYTES, stream);
     if (e != hipSuccess) return e;
     e = launch_xcorr_spec_tile(p, mode, s, n_cu, stream);
+    if (e != hipSuccess) return e;
+    const size_t total = (size_t)p.batch * p.n_rows * p.n_cols;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > (size_t)n_cu * 32) blocks = (size_t)n_cu * 32;
+    hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
+    return hipGetLastError();
+}
+
+// ---- weighted interrogation windows (xcorr_win.hip) -------------------------------------------------------------------
+bool win_size(int ws) { return ws == 16 || ws == 32 || ws == 64; }
+
+const char* xcorr_win_kernel_name(int ws, int mode, char* buf, int len) {
+    if (!win_size(ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) snprintf(buf, len, "%s", "");
+    else snprintf(buf, len, "xcorr_win_kernel<%d, %d, %d, %s>", ws, mode, win_occ(ws, mode), win_planar(ws, mode) ? "true" : "false");
+    return buf;
+}
+
+// one weighted pass: the weighted tile kernel, then the finalize step of every float32 pass (pass 1 writes du, dv as u, v; a
+// shifted pass combines with the predictor).  The workspace is the plain tile kernels': records, item counters behind them.
+hipError_t launch_xcorr_win(const PassParams& p_in, int mode, const WinParams& s, int n_cu, hipStream_t stream) {
+    if (!win_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS) || s.tab == nullptr)
+        return hipErrorInvalidValue;
+    PassParams p = p_in;
+    p.precision = 0;
+    p.list_mode = 0;
+    p.slow_list = nullptr;
+    p.slow_count = nullptr;
+    p.work_ctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.peak_raw) + work_ctr_offset(p.batch, p.n_rows * p.n_cols));
+    hipError_t e = hipMemsetAsync(p.work_ctr, 0, WORK_CTR_BYTES, stream);
+    if (e != hipSuccess) return e;
+    e = launch_xcorr_win_tile(p, mode, s, n_cu, stream);
     if (e != hipSuccess) return e;
     const size_t total = (size_t)p.batch * p.n_rows * p.n_cols;
     size_t blocks = (total + 255) / 256;

@@ -190,7 +190,7 @@ def iterate_compact(mode, a, b, ws, ov, u_raw, v_raw, mask, val_ratio=1.2, val_w
     return u, v, inv
 
 
-def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference", correlation=None):
+def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference", weighting=None, correlation=None):
     """Test hook: one pass plus the staged windows and the correlation maps (shifted passes at
     `precision`: "reference" = the reference's operation order, bit-identical windows).  Pass 1
     (mode 0) runs the float32 kernel, or with precision="exact" the exact first pass, whose maps
@@ -198,11 +198,16 @@ def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference", corr
     windows that then go to the float64 transform.  "CWS_Fast" takes u2, v2 as its predictor u0, v0 (the windows are
     resampled by -/+ u0 / 2 inside themselves); DWS / CWS return u = 2 u2 + du where valid, 0 where invalid.
     correlation (correlation_arg): the spectrally filtered pass instead (tpiv_debug_pass_spec; `precision` has no effect on
-    it) -- the windows as staged, before the mean removal, and the filtered map the decisions are taken on."""
+    it) -- the windows as staged, before the mean removal, and the filtered map the decisions are taken on.
+    weighting (weighting_arg): the weighted pass instead (tpiv_debug_pass_weighted; `precision` has no effect on it) -- the
+    windows as staged, before the weighting, and the map the decisions are taken on."""
     prec = _precision(precision)
     corr_par = correlation_arg(correlation)
     if corr_par is not None:
         correlation_check([ws], mode if isinstance(mode, str) else None)
+    wt_par = weighting_arg(weighting)
+    if wt_par is not None:
+        weighting_check([ws], mode if isinstance(mode, str) else None, correlation=corr_par)
     a, b = _frames(a, b)
     B, H, W = a.shape
     nr, nc = field_shape(H, W, ws, ov)
@@ -215,6 +220,17 @@ def debug_pass(mode, a, b, ws, ov, u2=None, v2=None, precision="reference", corr
     corr = torch.empty(B, N, ws, ws, dtype=torch.float32, device=dev)
     m = 0 if mode in (0, None, "PASS1") else ITER_MODES[mode]
     zero = torch.zeros(B, nr, nc, dtype=torch.float64, device=dev) if m else None
+    if wt_par is not None:
+        tab = torch.from_numpy(weighting_tables(wt_par, [ws])).to(dev)
+        with torch.cuda.device(dev):
+            work, nbytes = _work(H, W, ws, ov, B, dev)
+            check(lib.tpiv_debug_pass_weighted(m, tab.data_ptr(), a.data_ptr(), b.data_ptr(), B, H, W, ws, ov,
+                                               u2.contiguous().data_ptr() if u2 is not None else None,
+                                               v2.contiguous().data_ptr() if v2 is not None else None,
+                                               zero.data_ptr() if zero is not None else None,
+                                               u.data_ptr(), v.data_ptr(), inv.data_ptr(), win.data_ptr(),
+                                               corr.data_ptr(), work.data_ptr(), nbytes, _stream()))
+        return u, v, inv, win, corr
     if corr_par is not None:
         tab = torch.from_numpy(correlation_tables(corr_par, [ws])).to(dev)
         with torch.cuda.device(dev):
@@ -350,6 +366,87 @@ def correlation_tables(par, sizes):
         j = np.arange(ws // 2 + 1, dtype=np.float64)
         for d in (par["dy"], par["dx"]):
             out.append(np.exp(-(np.pi * d / (2.0 * ws)) ** 2 * j * j).astype(np.float32))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+WEIGHTING_SIZES = (16, 32, 64)
+WEIGHTING_DEFAULTS = {"kind": "gaussian", "sigma": 0.4}
+WEIGHTING_SIGMA_MIN, WEIGHTING_SIGMA_MAX = 0.2, 4.0
+
+
+def weighting_arg(weighting):
+    """The weighting= argument of Plan / OfflinePIV / ResidentPIV / run_folder / debug_pass, checked (no GPU involved):
+    None (the top-hat window of the plain passes), "gaussian" (at the default sigma 0.4), "uniform" (the top-hat window
+    through the weighted kernels) or a dict with any of WEIGHTING_DEFAULTS' keys -- sigma: relative to the half window, one
+    number or (sigma_x, sigma_y), 0.2..4 (include/torchpiv_hip.h: tpiv_plan_set_weighting has the definition).  Returns None
+    or {"kind", "sx", "sy"}; "uniform" has no sigma (sx = sy = 0).  ValueError for anything else."""
+    if weighting is None:
+        return None
+    if isinstance(weighting, dict) and set(weighting) == {"kind", "sx", "sy"}:       # this function's own result
+        weighting = dict({"kind": weighting["kind"]},
+                         **({} if weighting["kind"] == "uniform" else {"sigma": (weighting["sx"], weighting["sy"])}))
+    form = f"weighting: None, 'gaussian', 'uniform' or a dict of {sorted(WEIGHTING_DEFAULTS)}"
+    if isinstance(weighting, str):
+        if weighting not in _lib.WEIGHTINGS:
+            raise ValueError(f"{form}, got {weighting!r}")
+        weighting = {"kind": weighting}
+    if not isinstance(weighting, dict):
+        raise ValueError(f"{form}, got {type(weighting).__name__}")
+    unknown = sorted(set(weighting) - set(WEIGHTING_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"weighting: unknown key(s) {unknown}; known: {sorted(WEIGHTING_DEFAULTS)}")
+    par = dict(WEIGHTING_DEFAULTS, **weighting)
+    if not isinstance(par["kind"], str) or par["kind"] not in _lib.WEIGHTINGS:
+        raise ValueError(f"weighting: kind must be one of {sorted(_lib.WEIGHTINGS)}, got {par['kind']!r}")
+    if par["kind"] == "uniform":
+        if "sigma" in weighting:
+            raise ValueError("weighting: 'uniform' has no sigma")
+        return {"kind": "uniform", "sx": 0.0, "sy": 0.0}
+    s = par["sigma"]
+    if isinstance(s, (tuple, list)):
+        if len(s) != 2:
+            raise ValueError(f"weighting: sigma must be a number or (sigma_x, sigma_y), got {s!r}")
+    else:
+        s = (s, s)
+    try:
+        if any(isinstance(q, (bool, np.bool_)) for q in s):
+            raise TypeError
+        sx, sy = float(s[0]), float(s[1])
+    except (TypeError, ValueError):
+        raise ValueError(f"weighting: sigma must be a number or a pair of numbers, got {par['sigma']!r}") from None
+    for q in (sx, sy):
+        if not WEIGHTING_SIGMA_MIN <= q <= WEIGHTING_SIGMA_MAX:          # (NaN fails both comparisons)
+            raise ValueError(f"weighting: sigma must be in {WEIGHTING_SIGMA_MIN:g}..{WEIGHTING_SIGMA_MAX:g} "
+                             f"(relative to the half window), got {q!r}")
+    return {"kind": "gaussian", "sx": sx, "sy": sy}
+
+
+def weighting_check(sizes, mode=None, uncertainty=None, ensemble=False, correlation=None):
+    """What weighting= refuses, checked without a GPU: it combines with neither uncertainty= (its estimator sums over a
+    top-hat window) nor ensemble correlation nor correlation= (ValueError), the window size of every pass must be 16, 32 or
+    64 and the mode must not be CWS_Fast (NotImplementedError names it).  It does combine with deform=."""
+    if uncertainty is not None:
+        raise ValueError("weighting= does not combine with uncertainty= (its estimator sums over a top-hat window)")
+    if ensemble:
+        raise ValueError("weighting= does not combine with ensemble correlation")
+    if correlation is not None:
+        raise ValueError("weighting= does not combine with correlation=")
+    if mode == "CWS_Fast":
+        raise NotImplementedError("weighting=: the CWS_Fast iteration has no weighted kernel")
+    for ws in sizes:
+        if ws not in WEIGHTING_SIZES:
+            raise NotImplementedError(f"weighting=: weighted passes cover window sizes 16, 32 and 64; a pass of {ws} is not covered")
+
+
+def weighting_tables(par, sizes):
+    """float32 [sum over the passes of 2 ws]: g_y[0 .. ws-1] then g_x[0 .. ws-1] per pass; "gaussian": g[i] =
+    float32(exp(-t^2 / (2 sigma^2))), t = (2 i - (ws - 1)) / ws, evaluated in float64 and rounded once; "uniform": ones."""
+    out = []
+    for ws in sizes:
+        t = (2.0 * np.arange(ws, dtype=np.float64) - (ws - 1)) / ws
+        for s in (par["sy"], par["sx"]):
+            out.append(np.ones(ws, np.float32) if par["kind"] == "uniform"
+                       else np.exp(-t * t / (2.0 * s * s)).astype(np.float32))
     return np.ascontiguousarray(np.concatenate(out))
 
 
@@ -1556,7 +1653,7 @@ class Plan:
 
     def __init__(self, H, W, ws, ov, n_pass=1, mode="CWS", pass_scale=2.0, val_ratio=1.2,
                  val_win=3, max_batch=1, device=None, precision="exact", outlier=None, mask=None, uncertainty=None,
-                 deform=None, ensemble=False, correlation=None):
+                 deform=None, ensemble=False, weighting=None, correlation=None):
         # outlier: None, "median" or a dict (outlier_arg): the normalized median test after every pass -- flagged vectors of
         # a pass before the last are replaced by their neighbourhood median before the predictor reads them, flagged
         # vectors of the last pass join the invalid mask (tpiv_plan_set_outlier)
@@ -1585,6 +1682,14 @@ class Plan:
         if self.correlation is not None:
             correlation_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], mode, self.uncertainty_par, self.deform,
                               self.ensemble)
+        # weighting: None, "gaussian", "uniform" or a dict (weighting_arg): every pass multiplies its windows by a separable
+        # weight in front of the transform (tpiv_plan_set_weighting); window sizes 16, 32, 64 only, neither uncertainty= nor
+        # ensemble= nor correlation=; combines with deform= (the residual passes are weighted too), and `precision` has no
+        # effect on such a plan
+        self.weighting = weighting_arg(weighting)
+        if self.weighting is not None:
+            weighting_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], mode, self.uncertainty_par, self.ensemble,
+                            self.correlation)
         if self.mask is not None and tuple(self.mask["image"].shape) != (H, W):
             raise ValueError(f"mask of shape {tuple(self.mask['image'].shape)} for frames of shape {(H, W)}")
         if not torch.cuda.is_available():
@@ -1620,6 +1725,8 @@ class Plan:
                     check(lib.tpiv_plan_set_ensemble(self._h, 1))
                 if self.correlation is not None:
                     self.set_correlation(self.correlation)
+                if self.weighting is not None:
+                    self.set_weighting(self.weighting)
             except Exception:
                 self.close()
                 raise
@@ -1656,6 +1763,24 @@ class Plan:
                 check(lib.tpiv_plan_set_correlation(self._h, _lib.CORRELATIONS[par["kind"]], par["dx"], par["dy"], par["floor"],
                                                     tab.ctypes.data, tab.size))
         self.correlation = par
+
+    def set_weighting(self, weighting):
+        """Switches the plan's passes to weighted windows (weighting_arg's forms; None: back to the plain passes).  The
+        tables are built here and uploaded once (tpiv_plan_set_weighting)."""
+        par = weighting_arg(weighting)
+        with torch.cuda.device(self.device):
+            if par is None:
+                check(lib.tpiv_plan_set_weighting(self._h, _lib.WEIGHT_NONE, 0.0, 0.0, None, 0))
+            else:
+                sizes = []
+                for p in range(lib.tpiv_plan_n_pass(self._h)):
+                    w = C.c_int()
+                    check(lib.tpiv_plan_pass_geometry(self._h, p, C.byref(w), None, None, None))
+                    sizes.append(w.value)
+                tab = weighting_tables(par, sizes)
+                check(lib.tpiv_plan_set_weighting(self._h, _lib.WEIGHTINGS[par["kind"]], par["sx"], par["sy"],
+                                                  tab.ctypes.data, tab.size))
+        self.weighting = par
 
     @property
     def out_shape(self):
