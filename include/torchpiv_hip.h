@@ -237,6 +237,74 @@ int tpiv_plan_set_mask(tpiv_plan* plan, const uint8_t* mask_dev, double threshol
 /* Device pointer to the grid of pass `pass`, uint8 [n_rows, n_cols], 1 = excluded.  TPIV_EINVAL when the mask is off. */
 int tpiv_plan_pass_mask(const tpiv_plan* plan, int pass, uint8_t** grid_dev);
 
+/* ---- per-pair masks of moving bodies (extension; the reference has none) ------------------------- */
+
+enum tpiv_dynmask_kind {
+    TPIV_DYNMASK_BRIGHT = 0, /* a lit body: core where the whole neighbourhood is >= level */
+    TPIV_DYNMASK_DARK = 1    /* a shadow: core where the whole neighbourhood is <= level */
+};
+
+/* Segments one mask per pair from the frames a_dev, b_dev [n, H, W] uint8 themselves, in integer arithmetic (every
+ * implementation of these lines gives the same bytes).  size = 2 r + 1 odd in 3..63, level in 0..255, grow >= 0 with
+ * r + grow <= 31.  N_q(y, x) is the (2 q + 1) x (2 q + 1) square around a pixel clipped to the image (no padding value), as
+ * in tpiv_prefilter.  Per frame g:
+ *   BRIGHT: core(y, x) = [min over N_r(y, x) of g >= level]
+ *   DARK:   core(y, x) = [max over N_r(y, x) of g <= level]
+ *   obj(y, x) = [core is set somewhere in N_(r + grow)(y, x)]
+ * -- the morphological opening of {g >= level} ({g <= level}) by the size x size square, grown by `grow`: anything
+ * narrower than size in either direction vanishes, what survives comes back at full width.
+ *   masks_dev[f] = obj(a[f]) | obj(b[f]) | (static_dev != 0), bytes 0 / 1, [n, H, W]; static_dev [H, W] uint8 or NULL.
+ * work_dev: at least tpiv_dynamic_mask_work_bytes(n, H, W) bytes on the device (0 for a shape the call refuses);
+ * afterwards it holds the union of both frames' cores, one byte (0x00 / 0xFF) per pixel and pair.  masks_dev and work_dev
+ * overlap neither each other nor an input; the inputs are not written.  TPIV_EINVAL for a bad kind, size, level, grow or
+ * shape (n < 0, H or W outside 1..2^28, H above 65535 * 64), a null pointer or such an overlap: decided on the host, nothing is launched then.
+ * n == 0 succeeds and launches nothing.  Enqueues two kernels; allocates nothing and never synchronises. */
+size_t tpiv_dynamic_mask_work_bytes(int n, int H, int W);
+int tpiv_dynamic_mask(const uint8_t* a_dev, const uint8_t* b_dev, int n, int H, int W, int kind, int size, int level,
+                      int grow, const uint8_t* static_dev, uint8_t* masks_dev, void* work_dev, void* stream);
+
+/* tpiv_apply_mask with mask f for frame f: out_dev[f][p] = masks_dev[f][p] != 0 ? 0 : frames_dev[f][p], all [n, pixels]
+ * uint8.  out_dev may be frames_dev itself; a partial overlap, or any overlap of out_dev with the masks, is TPIV_EINVAL,
+ * like a null pointer, n < 0 or pixels < 1.  n == 0 succeeds and launches nothing.  Enqueues only; allocates nothing. */
+int tpiv_apply_mask_pairs(const uint8_t* frames_dev, int n, long long pixels, const uint8_t* masks_dev, uint8_t* out_dev,
+                          void* stream);
+
+/* tpiv_mask_coverage for n masks masks_dev [n, H, W]: count_dev [n, n_rows, n_cols] int32, count[f][i][j] = the non-zero
+ * bytes of mask f inside window (i, j).  Any ws in 8..256 and any overlap, like the static one.  n == 0 succeeds and
+ * launches nothing.  Enqueues only; allocates nothing. */
+int tpiv_mask_coverage_pairs(const uint8_t* masks_dev, int n, int H, int W, int ws, int ov, int32_t* count_dev,
+                             void* stream);
+
+/* tpiv_mask_fields with one grid per pair: wherever grids_dev [batch, n_rows, n_cols] uint8 is non-zero, the same cell of
+ * the same pair reads u = v = +0.0, invalid = invalid_value (0 or 1) and status = 2 (status_dev not NULL).  Every other cell
+ * is untouched.  batch == 0 succeeds and launches nothing.  Enqueues only; allocates nothing. */
+int tpiv_mask_fields_pairs(double* u_dev, double* v_dev, uint8_t* invalid_dev, uint8_t* status_dev,
+                           const uint8_t* grids_dev, int batch, int n_rows, int n_cols, int invalid_value, void* stream);
+
+/* Per-pair grids of a plan.  on != 0 allocates, at this call (the first such call), one uint8 [max_batch, n_rows, n_cols]
+ * grid per pass; on == 0 switches them off again.  TPIV_EINVAL for a plan with tpiv_plan_set_ensemble on (and
+ * tpiv_plan_set_ensemble refuses a plan with these grids on); a pass with a window size outside 8..256 is refused as
+ * tpiv_plan_set_mask refuses it.  tpiv_plan_run is not affected. */
+int tpiv_plan_set_pair_masks(tpiv_plan* plan, int on);
+
+/* tpiv_plan_run with one mask per pair, masks_dev [batch, H, W] uint8 (non-zero = masked; the device reads them
+ * when the enqueued work runs, so they stay valid until then).  First, for every
+ * pass with (ws, ov), one tpiv_mask_coverage_pairs-like launch writes the plan's grids of this batch: cell (i, j) of pair f
+ * is EXCLUDED if and only if count[f][i][j] > limit, limit = (int)(threshold * (double)(ws * ws)) -- tpiv_plan_set_mask's
+ * rule, threshold in [0, 1].  Then everything tpiv_plan_run enqueues, with pair f's grid wherever a plan with a static
+ * mask reads its one grid: the mask steps behind every pass and every deformation round, with and without the median
+ * test (tpiv_mask_fields_pairs in the place of tpiv_mask_fields), and the grid the uncertainty kernel reads.  A static mask
+ * set with tpiv_plan_set_mask is superseded for this run (callers OR the static image into masks_dev) and applies again to
+ * the next tpiv_plan_run.  The plan does not touch the frames: the pixel step is tpiv_apply_mask_pairs, the caller's.
+ * TPIV_EINVAL without tpiv_plan_set_pair_masks, for a bad threshold or batch, or a null mask pointer.  Enqueues only;
+ * allocates nothing. */
+int tpiv_plan_run_masked(tpiv_plan* plan, const uint8_t* a_dev, const uint8_t* b_dev, const uint8_t* masks_dev,
+                         double threshold, int batch, double* u_dev, double* v_dev, uint8_t* invalid_dev, void* stream);
+
+/* Device pointer to the grids of pass `pass` that the last tpiv_plan_run_masked used, uint8 [batch, n_rows, n_cols] of that
+ * run, 1 = excluded.  TPIV_EINVAL when the per-pair grids are off. */
+int tpiv_plan_pass_pair_mask(const tpiv_plan* plan, int pass, uint8_t** grid_dev);
+
 /* ---- per-vector uncertainty (extension; the reference has none) ---------------------------------- */
 
 /* Correlation-statistics uncertainty (B. Wieneke, Meas. Sci. Technol. 26 (2015) 074002): the 1-sigma random error, in

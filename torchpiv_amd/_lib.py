@@ -26,6 +26,8 @@ CORR_NONE, CORR_PHASE, CORR_RPC = 0, 1, 2
 CORRELATIONS = {"phase": CORR_PHASE, "rpc": CORR_RPC}                                # tpiv_plan_set_correlation's kinds
 WEIGHT_NONE, WEIGHT_UNIFORM, WEIGHT_GAUSSIAN = 0, 1, 2
 WEIGHTINGS = {"uniform": WEIGHT_UNIFORM, "gaussian": WEIGHT_GAUSSIAN}                # tpiv_plan_set_weighting's kinds
+DYNMASK_BRIGHT, DYNMASK_DARK = 0, 1
+DYNMASKS = {"bright": DYNMASK_BRIGHT, "dark": DYNMASK_DARK}                          # tpiv_dynamic_mask's kinds
 DEFORM_GATHER = 0x100                           # OR-ed into tpiv_deform_warp's interp: the gather form everywhere
 ABI_VERSION = 2
 
@@ -86,6 +88,14 @@ SIGNATURES = {
     "tpiv_mask_fields": (C.c_int, [_f64p, _f64p, _u8p, _u8p, _u8p, _int, _int, _int, _int, _vp]),
     "tpiv_plan_set_mask": (C.c_int, [C.c_void_p, _u8p, _dbl, _vp]),
     "tpiv_plan_pass_mask": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p)]),
+    "tpiv_dynamic_mask_work_bytes": (C.c_size_t, [_int, _int, _int]),
+    "tpiv_dynamic_mask": (C.c_int, [_u8p, _u8p, _int, _int, _int, _int, _int, _int, _int, _u8p, _u8p, _vp, _vp]),
+    "tpiv_apply_mask_pairs": (C.c_int, [_u8p, _int, C.c_longlong, _u8p, _u8p, _vp]),
+    "tpiv_mask_coverage_pairs": (C.c_int, [_u8p, _int, _int, _int, _int, _int, _vp, _vp]),
+    "tpiv_mask_fields_pairs": (C.c_int, [_f64p, _f64p, _u8p, _u8p, _u8p, _int, _int, _int, _int, _vp]),
+    "tpiv_plan_set_pair_masks": (C.c_int, [C.c_void_p, _int]),
+    "tpiv_plan_run_masked": (C.c_int, [C.c_void_p, _u8p, _u8p, _u8p, _dbl, _int, _f64p, _f64p, _u8p, _vp]),
+    "tpiv_plan_pass_pair_mask": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p)]),
     "tpiv_uncertainty": (C.c_int, [_u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _u8p, _int, _f64p, _f64p, _vp, _vp]),
     "tpiv_plan_set_uncertainty": (C.c_int, [C.c_void_p, _int, _int]),
     "tpiv_plan_uncertainty": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),

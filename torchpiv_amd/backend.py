@@ -373,7 +373,7 @@ class OfflinePIV:
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
                  depth=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None,
-                 equalize=None, prefilter=None) -> None:
+                 dynamic_mask=None, equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -447,12 +447,23 @@ class OfflinePIV:
         # 16, 32 and 64 in every pass (NotImplementedError otherwise); combines with neither uncertainty= nor correlation=
         # nor ensemble() (ValueError); precision= has no effect on a weighted pass.  The tuples delivered are the same; only
         # the values differ.
+        # dynamic_mask (extension): None or a dict (engine.dynamic_mask_arg) -- one mask per PAIR, for bodies that move: a
+        # wing, a swimmer, a piston, a free surface, their shadows.  {"kind": "bright" | "dark", "size", "level", "grow"}: the
+        # mask is segmented on the device from the pair's own frames (tpiv_dynamic_mask: the opening of {frame >= level} /
+        # {frame <= level} by the size x size square, grown by `grow`, of both frames), read behind the background and in
+        # front of the pre-filter: tone map, dewarp, background, segment, pre-filter and cap, equalize, mask pixels.  The
+        # windows of every pass whose share of masked pixels exceeds the threshold are excluded pair by pair
+        # (tpiv_plan_run_masked) with everything mask= says about excluded cells; the delivered fields carry `fill` there and
+        # pair_mask(i) shows the mask pair i gets.  threshold / pixels / fill go into this dict when mask= is None; with
+        # mask= its image is OR-ed into every pair's mask and its three values apply.  ensemble() is refused (ValueError).
+        # The form {"stack": masks [N, H, W]} is ResidentPIV's.
         if precision not in PRECISIONS:
             raise KeyError(precision)
         correlation = self._correlation_arg(correlation, wind_size, overlap, multipass, multipass_scale, multipass_mode,
                                             uncertainty, deform)
         weighting = self._weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode,
                                         uncertainty, correlation)
+        dynamic_mask = engine.dynamic_mask_arg(dynamic_mask, mask, stack=False)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
         depth = engine.depth_arg(depth)
         dataset = PIVDataset(folder, file_fmt, folder_mode, deep=depth is not None,
@@ -462,7 +473,7 @@ class OfflinePIV:
                          multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
                          engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize),
                          engine.mask_arg(mask), engine.dewarp_arg(dewarp), engine.uncertainty_arg(uncertainty),
-                         engine.deform_arg(deform), correlation, weighting)
+                         engine.deform_arg(deform), correlation, weighting, dynamic_mask)
         if not self:
             return
         if self._mask is not None:
@@ -475,7 +486,8 @@ class OfflinePIV:
 
     def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
                     multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
-                    equalize=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None):
+                    equalize=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None,
+                    dynamic_mask=None):
         """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
         run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
         engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's, dewarp: engine.dewarp_arg's,
@@ -496,6 +508,11 @@ class OfflinePIV:
         self._deform = deform            # deform=: engine.deform_arg's, handed to every plan
         self._correlation = correlation  # correlation=: engine.correlation_arg's, handed to every plan but ensemble()'s
         self._weighting = weighting      # weighting=: engine.weighting_arg's, handed to every plan but ensemble()'s
+        self._dynmask = dynamic_mask     # dynamic_mask=: engine.dynamic_mask_arg's (threshold, pixels and fill included)
+        self._dm_masks = None            # dynamic_mask=: the masks of a launch, uint8 [batch, H, W], reused
+        self._dm_work = None             # dynamic_mask=: the segmentation's workspace, kept from launch to launch
+        self._dm_frames = None           # dynamic_mask=: a caller's frames minus the background, uint8 [2, batch, H, W], reused
+        self._dm_stack = None            # dynamic_mask={"stack"}: the caller's masks with mask='s image, on the device
         self._dw_map = None              # dewarp=: the Q8 map on the device, int32 [H, W, 2], once a run needs it
         self._dw_frames = None           # dewarp=: the rectified frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
         self._mask_dev = None            # mask=: the image on the device, uint8 [H, W], once a run needs it
@@ -626,7 +643,8 @@ class OfflinePIV:
         over x).  owned: x is memory this object made -- an upload, a reused buffer, a gathered copy -- and a step writes
         in place; a caller's tensor is never written: the first step that runs writes into out (None: a fresh tensor),
         and what it wrote is owned.  The one place that decides between in place and copy."""
-        for on, step in ((self._equalize is not None, self._equalized), (self._zeroes_pixels(), self._masked)):
+        for on, step in ((self._equalize is not None, self._equalized),
+                         (self._zeroes_pixels() and self._dynmask is None, self._masked)):
             if on:
                 x = step(x, out=x if owned else out)
                 owned = True
@@ -651,16 +669,117 @@ class OfflinePIV:
             raise ValueError(f"mask of shape {got} for frames of shape {tuple(shape)}")
 
     def _zeroes_pixels(self):
+        if self._dynmask is not None:
+            return self._dynmask["pixels"] == "zero"
         return self._mask is not None and self._mask["pixels"] == "zero"
+
+    def _static_image(self, shape, device):
+        """The image of mask= on `device` (uint8 [H, W]; it goes there once), None without mask=."""
+        if self._mask is None:
+            return None
+        self._mask_shape(shape)
+        img = self._mask_dev
+        if img is None or img.device != device:
+            img = self._mask_dev = self._mask["image"].to(device).contiguous()
+        return img
+
+    def _pair_masks(self, A, B, ids):
+        """dynamic_mask=: the masks uint8 [n, H, W] of the pairs whose frames A, B [n, H, W] are (behind the background, in
+        front of the pre-filter), mask='s image included: one tpiv_dynamic_mask call into a buffer kept from launch to
+        launch, or the pairs `ids` of the caller's stack."""
+        dm = self._dynmask
+        n, H, W = (int(s_) for s_ in A.shape)
+        static = self._static_image((H, W), A.device)
+        if "stack" in dm:
+            st = self._dm_stack
+            if st is None or st.device != A.device:
+                st = (dm["stack"].to(A.device) != 0)
+                if static is not None:
+                    st |= static != 0
+                st = self._dm_stack = st.to(torch.uint8).contiguous()
+            ids = list(ids)
+            if ids == list(range(ids[0], ids[0] + n)):
+                return st[ids[0]:ids[0] + n]
+            return st.index_select(0, torch.tensor(ids, dtype=torch.int64, device=A.device))
+        masks = self._scratch("_dm_masks", (n,), H, W, A.device)[:n]
+        work = self._dm_work
+        if work is None or work.numel() < n * H * W or work.device != A.device:
+            work = self._dm_work = torch.empty(n * H * W, dtype=torch.uint8, device=A.device)
+        return engine.dynamic_mask(A, B, dm["kind"], dm["size"], dm["level"], dm["grow"], static=static, out=masks, work=work)
+
+    def _pair_chain(self, A, B, bg_a, bg_b, owned, out_a=None, out_b=None, ids=None, masks_only=False):
+        """dynamic_mask=: the frames A, B (uint8 [n, H, W] or [H, W]) of the pairs `ids` from the background on -- background,
+        segment, pre-filter and cap, equalize, mask pixels -- as (A, B, masks), each [n, H, W].  bg_a, bg_b: what is still to
+        be subtracted (None: nothing, or done).  The subtraction runs on its own here, where prefilter= otherwise fuses it
+        (the same bytes), because the segmentation reads its result.  owned / out_a, out_b: as in _finished -- a caller's
+        frames are never written: the first step that runs writes elsewhere."""
+        if A.dim() == 2:
+            A, B = A[None], B[None]
+            out_a, out_b = (None if o is None else o[None] if o.dim() == 2 else o for o in (out_a, out_b))
+        n, H, W = (int(s_) for s_ in A.shape)
+        if bg_a is not None:
+            if owned:
+                dst_a, dst_b = A, B
+            else:                       # (not out_a: the pre-filter, a stencil, writes there next)
+                buf = self._scratch("_dm_frames", (2, n), H, W, A.device)
+                dst_a, dst_b = buf[0, :n], buf[1, :n]
+            A, B = engine.subtract_background(A, bg_a, out=dst_a), engine.subtract_background(B, bg_b, out=dst_b)
+            owned = True
+        masks = self._pair_masks(A, B, ids)
+        if masks_only:
+            return None, None, masks
+        fa, fb = self._filtered(A, None, out=out_a), self._filtered(B, None, out=out_b)
+        owned |= fa is not A
+        fa, fb = self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b)
+        owned |= self._equalize is not None
+        if self._zeroes_pixels():
+            fa = engine.apply_mask_pairs(fa, masks, out=fa if owned else out_a)
+            fb = engine.apply_mask_pairs(fb, masks, out=fb if owned else out_b)
+        return fa, fb, masks
+
+    def _run_masked(self, plan, fa, fb, masks):
+        """dynamic_mask=: the passes on prepared frames with their masks; (u, v, inv, excluded) with excluded bool
+        [n, n_rows, n_cols], the excluded cells of every pair in the orientation of the delivered fields (a copy, enqueued
+        behind the run: the next launch overwrites the plan's grids)."""
+        u, v, inv = plan.run_masked(fa, fb, masks, self._dynmask["threshold"])
+        excluded = torch.flip(plan.pair_mask_grid(plan.n_pass - 1, int(u.shape[0]), sync=False), dims=(1,))
+        return u, v, inv, excluded
+
+    def _load_pair(self, i):
+        """(a, b, bg_a, bg_b, owned) for pair i alone: its uint8 frames on the device behind tone map and rectification,
+        what is to be subtracted from them, and whether they are memory of this object.  None for an undecodable pair."""
+        a, b = self._dataset[i]
+        if a is None or b is None:
+            return None
+        a = a.to(self._device, non_blocking=True)
+        b = b.to(self._device, non_blocking=True)
+        shape = (int(a.shape[-2]), int(a.shape[-1]))
+        lut = self._depth_table()
+        if lut is not None:                             # uint16 as decoded -> uint8, right after the upload
+            a, b = engine.depth_map(a, lut), engine.depth_map(b, lut)
+        if self._dewarp is not None:                    # rectified next, into the reused buffer (stream order keeps a
+            self._dewarp_shape(shape)                   # launch's passes ahead of the next write into it)
+            buf = self._scratch("_dw_frames", (2,), shape[0], shape[1], a.device)
+            a, b = self._dewarped(a, buf[0]), self._dewarped(b, buf[1])
+        bg = self._background(shape)
+        bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
+        return a, b, bg_a, bg_b, True
+
+    def pair_mask(self, i):
+        """uint8 [H, W] numpy, 0 / 1: the mask pair i gets under dynamic_mask=, mask='s image included -- for tuning size
+        and level.  None without the keyword or for a pair that cannot be decoded."""
+        if self._dynmask is None:
+            return None
+        got = self._load_pair(int(i))
+        if got is None:
+            return None
+        a, b, bg_a, bg_b, owned = got
+        return self._pair_chain(a, b, bg_a, bg_b, owned, ids=[int(i)], masks_only=True)[2][0].cpu().numpy()
 
     def _masked(self, frames, out=None):
         """uint8 frames [n, H, W] or [H, W] through the pixel step of mask= (one tpiv_apply_mask call), into out (None: a
         fresh tensor; _finished chooses).  The image goes to the device once."""
-        self._mask_shape(frames.shape[-2:])
-        img = self._mask_dev
-        if img is None or img.device != frames.device:
-            img = self._mask_dev = self._mask["image"].to(frames.device).contiguous()
-        return engine.apply_mask(frames, img, out=out)
+        return engine.apply_mask(frames, self._static_image(frames.shape[-2:], frames.device), out=out)
 
     def _dewarp_shape(self, shape):
         """ValueError unless a map given as coordinate arrays has the frame shape (None: not known)."""
@@ -828,6 +947,8 @@ class OfflinePIV:
         return plan
 
     def _ensemble_check(self):
+        if self._dynmask is not None:
+            raise ValueError("ensemble correlation does not combine with dynamic_mask=")
         if self._correlation is not None:
             raise ValueError("ensemble correlation does not combine with correlation=")
         if self._weighting is not None:
@@ -984,7 +1105,7 @@ class OfflinePIV:
 
     RING_CAP = 256           # ring / hole cells per pair (batch average) that ride on the first, asynchronous copy
 
-    def _post_submit(self, u, v, inv, want_raw=False, plan=None, sigma=True):
+    def _post_submit(self, u, v, inv, want_raw=False, plan=None, sigma=True, excluded=None):
         """Device half of B:884-898 for a batch of final fields (u, v float64 [n, nr, nc], modified in
         place; inv uint8): tpiv_postval (NaN-out, border interpolation, census, triangulation-free fills),
         tpiv_postval_compact (the ring points with their values and the hole cells of the pairs that need Qhull, cut out
@@ -1004,6 +1125,8 @@ class OfflinePIV:
                "hole_rc": hole_rc[:cap_h], "fu": fu, "fv": fv}
         if want_raw:
             src["u"], src["v"] = u, v
+        if excluded is not None:                                # dynamic_mask=: where _finish_batch puts the fill value
+            src["excluded"] = excluded
         if plan is not None and plan.outlier is not None:
             src["flagged"] = plan.outlier_flag_counts(n)       # rides on the same asynchronous copy as the census
         if sigma and plan is not None and plan.uncertainty_par is not None:
@@ -1188,7 +1311,18 @@ class OfflinePIV:
             U, V = state["dev"]["fu"], state["dev"]["fv"]           # rows of the batch's device stacks (views)
         else:
             U, V = np.array(state["host"]["fu"].numpy()), np.array(state["host"]["fv"].numpy())
-        if self._mask is not None and plan is not None:
+        if "excluded" in state["host"]:
+            # dynamic_mask=: the fill value into every pair's own excluded cells, after flip and scale (the grids came
+            # flipped; mask='s image is part of every pair's mask)
+            if self.device_out:
+                ex = state["dev"]["excluded"]
+                U.masked_fill_(ex, self._dynmask["fill"])
+                V.masked_fill_(ex, self._dynmask["fill"])
+            else:
+                ex = state["host"]["excluded"].numpy()
+                U[ex] = self._dynmask["fill"]
+                V[ex] = self._dynmask["fill"]
+        elif self._mask is not None and plan is not None:
             # mask=: the fill value into the excluded cells of every pair, after flip and scale (the grid is flipped too)
             grid = self._fill_grid(plan)
             if self.device_out:
@@ -1209,7 +1343,7 @@ class OfflinePIV:
             return [(xs, ys, U[k], V[k], SU[k], SV[k]) if keep[k] else None for k in range(keep.size)]
         return [(xs, ys, U[k], V[k]) if keep[k] else None for k in range(keep.size)]
 
-    def _finish(self, uv, x, y, plan=None, sigma=None):
+    def _finish(self, uv, x, y, plan=None, sigma=None, excluded=None):
         """Flip and unit scaling of B:894-898 (numpy, the reference's own expressions); then, with mask=, the fill value
         into the excluded cells of the plan's last pass.  sigma: the raw (su, sv) of uncertainty=, which take the flip and
         the scaling, no sign and no fill, and follow u, v in the tuple."""
@@ -1217,13 +1351,16 @@ class OfflinePIV:
             return None
         if sigma is not None:
             su, sv = (np.flip(s_, axis=0) * self._scale / self._dt * 1000 for s_ in sigma)
-            return self._finish(uv, x, y, plan=plan) + (su, sv)
+            return self._finish(uv, x, y, plan=plan, excluded=excluded) + (su, sv)
         u, v = uv
         u = np.flip(u, axis=0)
         v = -np.flip(v, axis=0)
         u = u * self._scale / self._dt * 1000
         v = v * self._scale / self._dt * 1000
-        if self._mask is not None and plan is not None:
+        if excluded is not None:                        # dynamic_mask=: this pair's own grid (bool numpy, flipped)
+            u[excluded] = self._dynmask["fill"]
+            v[excluded] = self._dynmask["fill"]
+        elif self._mask is not None and plan is not None:
             grid = self._fill_grid(plan)[0]
             u[grid] = self._mask["fill"]
             v[grid] = self._mask["fill"]
@@ -1237,32 +1374,28 @@ class OfflinePIV:
     def _one(self, i):
         """Pair i alone: decode on the host, one launch per pass, post-validation, flip / scale (B:868-898).
         None for an undecodable or dropped pair.  Plans of this path are kept per frame shape."""
-        a, b = self._dataset[i]
-        if a is None or b is None:
+        got = self._load_pair(i)
+        if got is None:
             return None
-        a = a.to(self._device, non_blocking=True)
-        b = b.to(self._device, non_blocking=True)
+        a, b, bg_a, bg_b, _ = got
         shape = (int(a.shape[-2]), int(a.shape[-1]))
-        lut = self._depth_table()
-        if lut is not None:                             # uint16 as decoded -> uint8, right after the upload
-            a, b = engine.depth_map(a, lut), engine.depth_map(b, lut)
-        if self._dewarp is not None:                    # rectified next, into the reused buffer (stream order keeps a
-            self._dewarp_shape(shape)                   # launch's passes ahead of the next write into it)
-            buf = self._scratch("_dw_frames", (2,), shape[0], shape[1], a.device)
-            a, b = self._dewarped(a, buf[0]), self._dewarped(b, buf[1])
-        bg = self._background(shape)
-        bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
-        # one launch per frame and step; in place from equalize on: the upload and what the steps made are this object's
-        a, b = self._filtered(a, bg_a), self._filtered(b, bg_b)
         plan = self._single_plan(shape)
-        u, v, inv = plan.run(self._finished(a, True), self._finished(b, True))
+        excluded = None
+        if self._dynmask is not None:
+            fa, fb, masks = self._pair_chain(a, b, bg_a, bg_b, True, ids=[i])
+            u, v, inv, excluded = self._run_masked(plan, fa, fb, masks)
+            excluded = excluded[0].cpu().numpy()
+        else:
+            # one launch per frame and step; in place from equalize on: the upload and what the steps made are this object's
+            a, b = self._filtered(a, bg_a), self._filtered(b, bg_b)
+            u, v, inv = plan.run(self._finished(a, True), self._finished(b, True))
         sigma = None if self._uncertainty is None else plan.uncertainty(1)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates(shape, w, o)
         uv = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)[0]     # (sigma: fetched above, finished on the host)
         if sigma is not None and uv is not None:
             sigma = tuple(s_[0].cpu().numpy() for s_ in sigma)
-        return self._finish(uv, x, y, plan=plan, sigma=sigma)
+        return self._finish(uv, x, y, plan=plan, sigma=sigma, excluded=excluded)
 
     def __call__(self) -> Generator:
         if int(self.call_batch) > 1 and len(self._dataset) > 1:
@@ -1378,19 +1511,27 @@ class OfflinePIV:
                     # next batch's filter), the subtraction alone goes in place
                     dst = frames if self._prefilter is None else \
                         self._scratch("_pf_frames", (2 * batch_size,), H, W, frames.device)[:2 * n]
-                    if (deep or dewarp) and bg is not None:
-                        # per stack: the tone map subtracted nothing, and neither did an unpack in front of dewarp=
-                        self._filtered(frames[:n], bg[0], out=dst[:n])
-                        self._filtered(frames[n:], bg[1], out=dst[n:])
-                        frames = dst
+                    if self._dynmask is not None:
+                        # per stack, with the segmentation between the background and the filter
+                        todo = bg if (deep or dewarp) and bg is not None else (None, None)
+                        fa, fb, masks = self._pair_chain(frames[:n], frames[n:], todo[0], todo[1], True, dst[:n], dst[n:],
+                                                         ids=st.chunk)
+                        u, v, inv, excluded = self._run_masked(plan, fa, fb, masks)
+                        ticket = self._post_submit(u, v, inv, plan=plan, excluded=excluded)
                     else:
-                        # one launch over the stack (the unpack subtracted already)
-                        frames = self._filtered(frames, None, out=dst)
-                    # one call per step over the stack, in place: the unpack, the tone map or the filter wrote it into
-                    # memory of this object
-                    frames = self._finished(frames, True)
-                    u, v, inv = plan.run(frames[:n], frames[n:])
-                    ticket = self._post_submit(u, v, inv, plan=plan)
+                        if (deep or dewarp) and bg is not None:
+                            # per stack: the tone map subtracted nothing, and neither did an unpack in front of dewarp=
+                            self._filtered(frames[:n], bg[0], out=dst[:n])
+                            self._filtered(frames[n:], bg[1], out=dst[n:])
+                            frames = dst
+                        else:
+                            # one launch over the stack (the unpack subtracted already)
+                            frames = self._filtered(frames, None, out=dst)
+                        # one call per step over the stack, in place: the unpack, the tone map or the filter wrote it into
+                        # memory of this object
+                        frames = self._finished(frames, True)
+                        u, v, inv = plan.run(frames[:n], frames[n:])
+                        ticket = self._post_submit(u, v, inv, plan=plan)
                 let_go(release)
                 release = (up,)
                 # the host work of the PREVIOUS batches runs while the GPU works on this one
@@ -1415,8 +1556,8 @@ class ResidentPIV(OfflinePIV):
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
                  validation_window: int = 3, background=None, outlier=None, depth=None, mask=None,
-                 dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None, equalize=None,
-                 prefilter=None) -> None:
+                 dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None, dynamic_mask=None,
+                 equalize=None, prefilter=None) -> None:
         # dewarp (see OfflinePIV): every launch rectifies its pairs into a reused buffer, addressed by their offsets in the
         # caller's stacks (nothing is gathered first, and the caller's frames are never written)
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
@@ -1447,6 +1588,11 @@ class ResidentPIV(OfflinePIV):
                                             uncertainty, deform)
         weighting = self._weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode,
                                         uncertainty, correlation)
+        dynamic_mask = engine.dynamic_mask_arg(dynamic_mask, mask)
+        if dynamic_mask is not None and "stack" in dynamic_mask \
+                and tuple(dynamic_mask["stack"].shape) != tuple(frames_a.shape):
+            raise ValueError(f"dynamic_mask: a stack of shape {tuple(dynamic_mask['stack'].shape)} for frames of shape "
+                             f"{tuple(frames_a.shape)}")
         dewarp = engine.dewarp_arg(dewarp)
         if dewarp is not None and "map" in dewarp and tuple(dewarp["map"][0].shape) != tuple(frames_a.shape[1:]):
             raise ValueError(f"dewarp map of shape {tuple(dewarp['map'][0].shape)} for frames of shape "
@@ -1455,7 +1601,7 @@ class ResidentPIV(OfflinePIV):
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
                          multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
                          validation_window, bg_arg, outlier, prefilter, depth, equalize, mask, dewarp,
-                         uncertainty, deform, correlation, weighting)
+                         uncertainty, deform, correlation, weighting, dynamic_mask)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):
@@ -1496,6 +1642,14 @@ class ResidentPIV(OfflinePIV):
             return self._A[chunk[0]:chunk[0] + n], self._B[chunk[0]:chunk[0] + n], False
         sel = torch.tensor(chunk, dtype=torch.int64, device=self._device)
         return self._A.index_select(0, sel), self._B.index_select(0, sel), True
+
+    def _load_pair(self, i):
+        H, W = self._A.shape[1:]
+        dw = None if self._dewarp is None else self._scratch("_dw_frames", (2, 1), H, W, self._A.device)
+        A, B, owned = self._select([i], self._depth_table(), dw=dw)
+        bg = self._background((H, W))
+        bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
+        return A, B, bg_a, bg_b, owned
 
     def compute_background(self, indices=None, batch_size=None):
         """(bg_a, bg_b): the per-pixel minimum of the resident a frames and of the b frames (of the pairs `indices`;
@@ -1559,6 +1713,11 @@ class ResidentPIV(OfflinePIV):
             # one launch per frame stack and step.  The background and the filter write the reused buffer (stream order
             # keeps a launch's passes ahead of the next launch's writes into the same memory), and so does the first later
             # step that meets the caller's frames; everything else goes in place
+            if self._dynmask is not None:
+                fa, fb, masks = self._pair_chain(A, B, bg_a, bg_b, owned, out_a, out_b, ids=chunk)
+                u, v, inv, excluded = self._run_masked(plan, fa, fb, masks)
+                yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan, excluded=excluded)))
+                continue
             fa, fb = self._filtered(A, bg_a, out=out_a), self._filtered(B, bg_b, out=out_b)
             owned |= fa is not A
             u, v, inv = plan.run(self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b))

@@ -258,6 +258,11 @@ struct tpiv_plan {
     // geometric mask (tpiv_plan_set_mask); off: nothing is enqueued for it.  mgrid: per pass [N_p], 1 = excluded cell
     bool mask_on = false;
     std::vector<uint8_t*> mgrid;
+    // per-pair masks (tpiv_plan_set_pair_masks); off: nothing below is allocated.  pgrid: per pass [max_batch, N_p], what the
+    // last tpiv_plan_run_masked computed; pair_run: set while that call enqueues, so that the settle steps and the
+    // uncertainty kernel read pgrid instead of mgrid
+    bool pair_on = false, pair_run = false;
+    std::vector<uint8_t*> pgrid;
     // correlation-statistics uncertainty behind the last pass (tpiv_plan_set_uncertainty); off: nothing is enqueued for it
     int unc_kind = 0, unc_radius = 3;
     double *unc_su = nullptr, *unc_sv = nullptr;     // [max_batch, N_last] of the last run
@@ -1020,9 +1025,100 @@ int tpiv_plan_pass_mask(const tpiv_plan* plan, int pass, uint8_t** grid) {
     return TPIV_OK;
 }
 
+int tpiv_apply_mask_pairs(const uint8_t* frames, int n, long long pixels, const uint8_t* masks, uint8_t* out, void* stream) {
+    if (n < 0 || pixels <= 0) return fail(TPIV_EINVAL, "tpiv_apply_mask_pairs: bad shape");
+    if (n == 0) return TPIV_OK;
+    if (!frames || !masks || !out) return fail(TPIV_EINVAL, "tpiv_apply_mask_pairs: null pointer");
+    const size_t bytes = (size_t)n * pixels;
+    if (out != frames && out < frames + bytes && frames < out + bytes)
+        return fail(TPIV_EINVAL, "tpiv_apply_mask_pairs: out overlaps frames without being frames");
+    if (out < masks + bytes && masks < out + bytes) return fail(TPIV_EINVAL, "tpiv_apply_mask_pairs: out overlaps the masks");
+    HIP_TRY(tpiv::launch_apply_mask_pairs(frames, n, pixels, masks, out, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_mask_coverage_pairs(const uint8_t* masks, int n, int H, int W, int ws, int ov, int32_t* count, void* stream) {
+    if (n < 0) return fail(TPIV_EINVAL, "tpiv_mask_coverage_pairs: bad shape");
+    if (int rc = check_mask_window(H, W, ws, ov)) return rc;
+    if (n == 0) return TPIV_OK;
+    if (!masks || !count) return fail(TPIV_EINVAL, "tpiv_mask_coverage_pairs: null pointer");
+    int nr = 0, nc = 0;
+    field_shape(H, W, ws, ov, &nr, &nc);
+    HIP_TRY(tpiv::launch_mask_coverage_pairs(masks, n, H, W, ws, ov, nr, nc, count, nullptr, 0, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_mask_fields_pairs(double* u, double* v, uint8_t* invalid, uint8_t* status, const uint8_t* grids, int batch,
+                           int n_rows, int n_cols, int invalid_value, void* stream) {
+    if (batch < 0 || n_rows < 1 || n_cols < 1) return fail(TPIV_EINVAL, "tpiv_mask_fields_pairs: empty grid");
+    if (invalid_value != 0 && invalid_value != 1)
+        return fail(TPIV_EINVAL, "tpiv_mask_fields_pairs: invalid_value must be 0 or 1");
+    if ((long long)n_rows * n_cols >= (1LL << 31)) return fail(TPIV_EUNSUPPORTED, "field too large");
+    if (batch == 0) return TPIV_OK;
+    if (!u || !v || !invalid || !grids) return fail(TPIV_EINVAL, "tpiv_mask_fields_pairs: null pointer");
+    HIP_TRY(tpiv::launch_mask_fields_pairs(u, v, invalid, status, grids, batch, n_rows, n_cols, invalid_value,
+                                           (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+size_t tpiv_dynamic_mask_work_bytes(int n, int H, int W) {
+    if (n <= 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28)) return 0;
+    return (size_t)n * H * W;
+}
+
+int tpiv_dynamic_mask(const uint8_t* a, const uint8_t* b, int n, int H, int W, int kind, int size, int level, int grow,
+                      const uint8_t* fixed, uint8_t* masks, void* work, void* stream) {
+    if (n < 0 || H <= 0 || W <= 0 || H > (1 << 28) || W > (1 << 28)) return fail(TPIV_EINVAL, "tpiv_dynamic_mask: bad shape");
+    if ((H + tpiv::PREFILTER_TILE_ROWS - 1) / tpiv::PREFILTER_TILE_ROWS > 65535)
+        return fail(TPIV_EINVAL, "tpiv_dynamic_mask: more than 65535 tile rows");
+    if (kind != TPIV_DYNMASK_BRIGHT && kind != TPIV_DYNMASK_DARK)
+        return fail(TPIV_EINVAL, "tpiv_dynamic_mask: kind must be TPIV_DYNMASK_BRIGHT or TPIV_DYNMASK_DARK");
+    if (size < 3 || size > 63 || size % 2 == 0) return fail(TPIV_EINVAL, "tpiv_dynamic_mask: size must be odd and in 3..63");
+    if (level < 0 || level > 255) return fail(TPIV_EINVAL, "tpiv_dynamic_mask: level must be in 0..255");
+    if (grow < 0 || size / 2 + grow > 31) return fail(TPIV_EINVAL, "tpiv_dynamic_mask: grow must be >= 0 with size / 2 + grow <= 31");
+    if (n == 0) return TPIV_OK;
+    if (!a || !b || !masks || !work) return fail(TPIV_EINVAL, "tpiv_dynamic_mask: null pointer");
+    const size_t bytes = (size_t)n * H * W, image = (size_t)H * W;
+    uint8_t* core = static_cast<uint8_t*>(work);
+    auto overlaps = [](const uint8_t* x, size_t nx, const uint8_t* y, size_t ny) { return x < y + ny && y < x + nx; };
+    if (overlaps(masks, bytes, a, bytes) || overlaps(masks, bytes, b, bytes) || overlaps(core, bytes, a, bytes) ||
+        overlaps(core, bytes, b, bytes) || overlaps(core, bytes, masks, bytes) ||
+        (fixed && (overlaps(masks, bytes, fixed, image) || overlaps(core, bytes, fixed, image))))
+        return fail(TPIV_EINVAL, "tpiv_dynamic_mask: the masks and the workspace overlap neither each other nor an input");
+    HIP_TRY(tpiv::launch_dynamic_mask(a, b, n, H, W, kind, size, level, grow, fixed, masks, core, (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_plan_set_pair_masks(tpiv_plan* plan, int on) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!on) {
+        plan->pair_on = false;
+        return TPIV_OK;
+    }
+    if (plan->ens_on) return fail(TPIV_EINVAL, "per-pair masks do not combine with ensemble correlation");
+    if (int rc = check_plan_device(plan)) return rc;
+    for (const PassGeo& g : plan->geo)
+        if (int rc = check_mask_window(plan->H, plan->W, g.ws, g.ov)) return rc;
+    if (plan->pgrid.empty()) {                       // first time on: the grids (kept until the plan is destroyed)
+        std::vector<uint8_t*> grids(plan->n_pass, nullptr);
+        for (int p = 0; p < plan->n_pass; ++p)
+            if (int rc = plan->alloc(&grids[p], (size_t)plan->geo[p].n_rows * plan->geo[p].n_cols * plan->max_batch)) return rc;
+        plan->pgrid = std::move(grids);
+    }
+    plan->pair_on = true;
+    return TPIV_OK;
+}
+
+int tpiv_plan_pass_pair_mask(const tpiv_plan* plan, int pass, uint8_t** grid) {
+    if (!plan || !grid || pass < 0 || pass >= plan->n_pass) return fail(TPIV_EINVAL, "bad plan / pass index");
+    if (!plan->pair_on) return fail(TPIV_EINVAL, "the plan has no per-pair masks (tpiv_plan_set_pair_masks)");
+    *grid = plan->pgrid[pass];
+    return TPIV_OK;
+}
+
 static int run_uncertainty(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov, int n_rows,
                            int n_cols, const double* u, const double* v, const uint8_t* invalid, const uint8_t* exclude,
-                           int radius, double* su, double* sv, long long* stats, hipStream_t st) {
+                           int radius, double* su, double* sv, long long* stats, hipStream_t st, bool exclude_pairs = false) {
     tpiv::UncertaintyParams q{};
     q.A = a;
     q.B = b;
@@ -1037,6 +1133,7 @@ static int run_uncertainty(const uint8_t* a, const uint8_t* b, int batch, int H,
     q.v = v;
     q.invalid = invalid;
     q.exclude = exclude;
+    q.exclude_stride = exclude_pairs ? n_rows * n_cols : 0;
     q.radius = radius;
     q.su = su;
     q.sv = sv;
@@ -1310,9 +1407,13 @@ struct Settle {
 
     int run(int batch, hipStream_t st) const {
         const PassGeo& g = plan->geo[p];
-        const uint8_t* grid = plan->mask_on ? plan->mgrid[p] : nullptr;
+        const bool pairs = plan->pair_run;      // a masked run: one grid per pair in the place of the static one
+        const uint8_t* grid = pairs ? plan->pgrid[p] : plan->mask_on ? plan->mgrid[p] : nullptr;
         auto mask = [&](double* mu, double* mv, uint8_t* mval, uint8_t* status, bool invalid_value) {
-            hipError_t he = tpiv::launch_mask_fields(mu, mv, mval, status, grid, batch, g.n_rows, g.n_cols, invalid_value, st);
+            hipError_t he = pairs ? tpiv::launch_mask_fields_pairs(mu, mv, mval, status, grid, batch, g.n_rows, g.n_cols,
+                                                                   invalid_value, st)
+                                  : tpiv::launch_mask_fields(mu, mv, mval, status, grid, batch, g.n_rows, g.n_cols,
+                                                             invalid_value, st);
             return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_mask_fields");
         };
         if (grid)                   // excluded cells: zero vectors, and always invalid to the test
@@ -1433,8 +1534,10 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
         const double* uu = u;
         const double* vv = v;
         if (int rc = run_uncertainty(a, b, batch, plan->H, plan->W, g.ws, g.ov, g.n_rows, g.n_cols, uu, vv, invalid,
-                                     plan->mask_on ? plan->mgrid[last] : nullptr, plan->unc_radius, plan->unc_su,
-                                     plan->unc_sv, nullptr, st))
+                                     plan->pair_run  ? plan->pgrid[last]
+                                     : plan->mask_on ? plan->mgrid[last]
+                                                     : nullptr,
+                                     plan->unc_radius, plan->unc_su, plan->unc_sv, nullptr, st, plan->pair_run))
             return rc;
     }
     plan->last_filtered = plan->corr_kind != 0 || plan->wt_kind != 0;
@@ -1444,6 +1547,27 @@ int tpiv_plan_run(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, int batch
         plan->runs_recorded++;
     }
     return TPIV_OK;
+}
+
+int tpiv_plan_run_masked(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, const uint8_t* masks, double threshold,
+                         int batch, double* u, double* v, uint8_t* invalid, void* stream) {
+    if (!plan) return fail(TPIV_EINVAL, "null plan");
+    if (!plan->pair_on) return fail(TPIV_EINVAL, "the plan has no per-pair masks (tpiv_plan_set_pair_masks)");
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(TPIV_EINVAL, "tpiv_plan_run_masked: threshold must be in [0, 1]");
+    if (batch < 0 || batch > plan->max_batch) return fail(TPIV_EINVAL, "batch exceeds the plan's max_batch");
+    if (batch == 0) return TPIV_OK;
+    if (!masks) return fail(TPIV_EINVAL, "tpiv_plan_run_masked: null pointer");
+    if (int rc = check_plan_device(plan)) return rc;
+    for (int p = 0; p < plan->n_pass; ++p) {
+        const PassGeo& g = plan->geo[p];
+        const int limit = (int)(threshold * (double)(g.ws * g.ws));       // tpiv_plan_set_mask's rule
+        HIP_TRY(tpiv::launch_mask_coverage_pairs(masks, batch, plan->H, plan->W, g.ws, g.ov, g.n_rows, g.n_cols, nullptr,
+                                                 plan->pgrid[p], limit, (hipStream_t)stream));
+    }
+    plan->pair_run = true;
+    const int rc = tpiv_plan_run(plan, a, b, batch, u, v, invalid, stream);
+    plan->pair_run = false;
+    return rc;
 }
 
 // ---- spectrally filtered passes -------------------------------------------------------------------------------------
@@ -1656,6 +1780,7 @@ int tpiv_plan_set_ensemble(tpiv_plan* plan, int on) {
     if (plan->def_iters) return fail(TPIV_EINVAL, "ensemble correlation does not combine with deform=");
     if (plan->corr_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with correlation=");
     if (plan->wt_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with weighting=");
+    if (plan->pair_on) return fail(TPIV_EINVAL, "ensemble correlation does not combine with per-pair masks");
     size_t cells = 0, fine = 0;
     for (const PassGeo& g : plan->geo) {
         if (!tpiv::ensemble_size(g.ws))

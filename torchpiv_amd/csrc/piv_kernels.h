@@ -227,6 +227,20 @@ hipError_t launch_mask_coverage(const uint8_t* mask, int H, int W, int ws, int o
                                 uint8_t* grid, int limit, hipStream_t stream);
 hipError_t launch_mask_fields(double* u, double* v, uint8_t* invalid, uint8_t* status, const uint8_t* grid, int batch,
                               int n_rows, int n_cols, int invalid_value, hipStream_t stream);
+// the per-pair forms: masks [n, pixels] (mask f for frame f), count and grid [n, n_rows, n_cols], grids [batch, n_rows, n_cols]
+hipError_t launch_apply_mask_pairs(const uint8_t* frames, int n, long long pixels, const uint8_t* masks, uint8_t* out,
+                                   hipStream_t stream);
+hipError_t launch_mask_coverage_pairs(const uint8_t* masks, int n, int H, int W, int ws, int ov, int n_rows, int n_cols,
+                                      int32_t* count, uint8_t* grid, int limit, hipStream_t stream);
+hipError_t launch_mask_fields_pairs(double* u, double* v, uint8_t* invalid, uint8_t* status, const uint8_t* grids, int batch,
+                                    int n_rows, int n_cols, int invalid_value, hipStream_t stream);
+
+// per-pair masks of moving bodies (dynmask.hip, defined in include/torchpiv_hip.h: tpiv_dynamic_mask): an erosion kernel
+// (core = erode(a) | erode(b) into `core`, [n, H, W] bytes of the caller's workspace) and a dilation kernel
+// (out = dilate(core) | fixed != 0), both on the tiles of the pre-filter.  out and core overlap neither each other nor an input.
+constexpr int DYNMASK_BRIGHT = 0, DYNMASK_DARK = 1;
+hipError_t launch_dynamic_mask(const uint8_t* a, const uint8_t* b, int n, int H, int W, int kind, int size, int level,
+                               int grow, const uint8_t* fixed, uint8_t* out, uint8_t* core, hipStream_t stream);
 
 // geometric rectification (dewarp.hip, defined in include/torchpiv_hip.h): out[f] = frame f (at element offset src_off[f] on
 // the device, nullptr: f * H * W) sampled through map int32 [H, W, 2] (signed Q8, x first), bilinear or Catmull-Rom with the
@@ -248,6 +262,7 @@ struct UncertaintyParams {
     const double* v;
     const uint8_t* invalid;  // optional [batch, n_rows, n_cols]: non-zero = no estimate (NaN, zero stats row)
     const uint8_t* exclude;  // optional [n_rows, n_cols], one grid for every pair: the same (a plan's mask grid)
+    int exclude_stride;      // 0: that one grid; n_rows * n_cols: a grid per pair (a plan's per-pair grids)
     int radius;              // 0..UNCERTAINTY_MAX_RADIUS
     double* su;              // out [batch, n_rows, n_cols]
     double* sv;

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kMaxThreads) void uncertainty_kernel(UncertaintyPar
 
     // (uniform over the workgroup: every lane reads the same three values)
     const double u = p.u[item], v = p.v[item];
-    const bool off = (p.invalid && p.invalid[item] != 0) || (p.exclude && p.exclude[cell] != 0) ||
+    const bool off = (p.invalid && p.invalid[item] != 0) || (p.exclude && p.exclude[(size_t)pair * p.exclude_stride + cell] != 0) ||
                      !(fabs(u) < __longlong_as_double(0x7ff0000000000000LL)) ||
                      !(fabs(v) < __longlong_as_double(0x7ff0000000000000LL));
     if (off) {

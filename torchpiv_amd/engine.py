@@ -895,7 +895,171 @@ def mask_fields(u, v, inv, grid, invalid_value, status=None):
     return (u, v, inv) if status is None else (u, v, inv, status)
 
 
-PREFILTER_KEYS = ("kind", "size", "cap")
+DYNMASK_KINDS = ("bright", "dark")
+DYNMASK_KEYS = ("kind", "size", "level", "grow", "stack", "threshold", "pixels", "fill")
+
+
+def dynamic_mask_arg(dynamic_mask, mask=None, stack=True):
+    """The dynamic_mask= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved).  None: no per-pair
+    mask.  {"kind": "bright" | "dark", "size": k, "level": L, "grow": g}: one mask per pair segmented on the device from the
+    frames themselves (tpiv_dynamic_mask: k odd in 3..63, L an integer in 0..255, g >= 0, default 0, with k // 2 + g <= 31).
+    {"stack": uint8 or bool [N, H, W]}: one mask per pair from the caller, non-zero = masked (stack=False: this form is
+    refused, for the classes whose frames do not come with an index the caller knows).  threshold, pixels and fill -- as
+    in mask_arg, with its defaults -- are accepted in the dict only when mask= (`mask`: as given or as mask_arg returned
+    it) is None; with mask= given, its image is OR-ed into every pair's mask and its three values apply.  Returns None or
+    a dict with "threshold", "pixels", "fill" and either "kind", "size", "level", "grow" (ints but for kind) or "stack" (a
+    contiguous uint8 tensor); anything else raises ValueError."""
+    if dynamic_mask is None:
+        return None
+    if not isinstance(dynamic_mask, dict):
+        raise ValueError(f"dynamic_mask: None or a dict of {list(DYNMASK_KEYS)}, got {type(dynamic_mask).__name__}")
+    unknown = sorted(set(dynamic_mask) - set(DYNMASK_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"dynamic_mask: unknown key(s) {unknown}; known: {list(DYNMASK_KEYS)}")
+    static = mask_arg(mask)                          # (what mask_arg returned passes through it unchanged)
+    shared = [k for k in ("threshold", "pixels", "fill") if k in dynamic_mask]
+    if static is not None and shared:
+        raise ValueError(f"dynamic_mask: {shared} are given with mask= when both keywords are used, not here")
+    probe = mask_arg(dict({"image": np.zeros((1, 1), np.uint8)}, **{k: dynamic_mask[k] for k in shared}))
+    out = {k: (static if static is not None else probe)[k] for k in ("threshold", "pixels", "fill")}
+
+    def integer(x):
+        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+    if "stack" in dynamic_mask:
+        extra = sorted(set(dynamic_mask) & {"kind", "size", "level", "grow"})
+        if extra:
+            raise ValueError(f"dynamic_mask: 'stack' gives the masks; {extra} belong to the segmented form")
+        if not stack:
+            raise ValueError("dynamic_mask: the 'stack' form is for ResidentPIV, whose pairs the caller indexes; a run "
+                             "over files takes the segmented form")
+        st = dynamic_mask["stack"]
+        if isinstance(st, np.ndarray):
+            if st.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"dynamic_mask: a uint8 or bool stack, got {st.dtype}")
+            st = torch.from_numpy(np.ascontiguousarray(st))
+        elif not isinstance(st, torch.Tensor):
+            raise ValueError(f"dynamic_mask: stack must be a uint8 or bool numpy array or tensor [N, H, W], got "
+                             f"{type(st).__name__}")
+        elif st.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"dynamic_mask: a uint8 or bool stack, got {st.dtype}")
+        if st.dim() != 3 or st.numel() == 0:
+            raise ValueError(f"dynamic_mask: a stack [N, H, W], got shape {tuple(st.shape)}")
+        out["stack"] = st.to(torch.uint8).contiguous()
+        return out
+    missing = [k for k in ("kind", "size", "level") if k not in dynamic_mask]
+    if missing:
+        raise ValueError(f"dynamic_mask: the dict needs {missing} (or a 'stack')")
+    kind, size, level, grow = (dynamic_mask["kind"], dynamic_mask["size"], dynamic_mask["level"], dynamic_mask.get("grow", 0))
+    if not isinstance(kind, str) or kind not in DYNMASK_KINDS:
+        raise ValueError(f"dynamic_mask: kind must be 'bright' or 'dark', got {kind!r}")
+    if not (integer(size) and 3 <= size <= 63 and size % 2 == 1):
+        raise ValueError(f"dynamic_mask: size must be an odd integer in 3..63, got {size!r}")
+    if not (integer(level) and 0 <= level <= 255):
+        raise ValueError(f"dynamic_mask: level must be an integer in 0..255, got {level!r}")
+    if not (integer(grow) and grow >= 0 and size // 2 + grow <= 31):
+        raise ValueError(f"dynamic_mask: grow must be an integer >= 0 with size // 2 + grow <= 31, got {grow!r}")
+    out.update(kind=kind, size=int(size), level=int(level), grow=int(grow))
+    return out
+
+
+def dynamic_mask(a, b, kind, size, level, grow=0, static=None, out=None, work=None):
+    """One mask per pair, uint8 [n, H, W] of bytes 0 / 1, segmented from the frames a, b uint8 [n, H, W] or [H, W] on the
+    device (tpiv_dynamic_mask: an erosion and a dilation kernel; the definition is in include/torchpiv_hip.h): the
+    opening by the size x size square of {frame >= level} ("bright") or {frame <= level} ("dark"), grown by `grow`, of
+    both frames, OR-ed with static (uint8 [H, W], non-zero = masked; None: nothing).  The frames may be any view (one that
+    is not contiguous is copied first).  out: a contiguous uint8 tensor [n, H, W] that overlaps no input; None: a fresh
+    one.  work: a uint8 workspace of at least n * H * W bytes to reuse from call to call (None: a fresh one)."""
+    par = dynamic_mask_arg({"kind": kind, "size": size, "level": level, "grow": grow})
+    _need_cuda(a, b, static, out, work)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() not in (2, 3) or a.shape != b.shape \
+            or a.device != b.device:
+        raise ValueError("dynamic_mask: a, b must be uint8 tensors [n, H, W] or [H, W] of one shape on one device")
+    fa, fb = (t if t.is_contiguous() else t.contiguous() for t in (a, b))
+    if fa.dim() == 2:
+        fa, fb = fa[None], fb[None]
+    n, H, W = (int(s) for s in fa.shape)
+    if static is not None:
+        _mask_image(static, H, W, fa.device, "dynamic_mask")
+    if out is None:
+        out = torch.empty(n, H, W, dtype=torch.uint8, device=fa.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous() or out.device != fa.device:
+        raise ValueError("dynamic_mask: out must be a contiguous uint8 [n, H, W] tensor on the frames' device")
+    need = n * H * W
+    if work is None:
+        work = torch.empty(max(need, 16), dtype=torch.uint8, device=fa.device)
+    elif work.dtype != torch.uint8 or work.dim() != 1 or not work.is_contiguous() or work.device != fa.device \
+            or work.numel() < need:
+        raise ValueError(f"dynamic_mask: work must be a contiguous uint8 vector of at least {need} bytes on the frames' device")
+    with torch.cuda.device(fa.device):
+        check(lib.tpiv_dynamic_mask(fa.data_ptr(), fb.data_ptr(), n, H, W, _lib.DYNMASKS[par["kind"]], par["size"],
+                                    par["level"], par["grow"], None if static is None else static.data_ptr(),
+                                    out.data_ptr(), work.data_ptr(), _stream()))
+    return out
+
+
+def _mask_stack(masks, f, name):
+    _need_cuda(masks)
+    if masks.dtype != torch.uint8 or masks.shape != f.shape or not masks.is_contiguous() or masks.device != f.device:
+        raise ValueError(f"{name}: masks must be a contiguous uint8 tensor of the frames' shape [n, H, W] on their device")
+
+
+def apply_mask_pairs(frames, masks, out=None):
+    """masks != 0 ? 0 : frames for uint8 frames [n, H, W] on the device and one mask per frame, uint8 [n, H, W] (any
+    non-zero byte masks).  out: frames itself (in place) or memory that overlaps neither; None: a fresh tensor
+    (tpiv_apply_mask_pairs)."""
+    f, H, W = _images(frames, "apply_mask_pairs")
+    if frames.dim() != 3:
+        raise ValueError("apply_mask_pairs: frames must be a contiguous uint8 tensor [n, H, W]")
+    _need_cuda(out)
+    _mask_stack(masks, f, "apply_mask_pairs")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or not out.is_contiguous() or out.device != f.device:
+        raise ValueError("apply_mask_pairs: out must be a contiguous uint8 tensor of the frames' shape and device")
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_apply_mask_pairs(f.data_ptr(), f.shape[0], H * W, masks.data_ptr(), out.data_ptr(), _stream()))
+    return out
+
+
+def mask_coverage_pairs(masks, ws, ov):
+    """int32 [n, n_rows, n_cols]: the masked (non-zero) pixels of every mask of masks uint8 [n, H, W] (on the device)
+    inside every window of the (ws, ov) grid of field_shape (tpiv_mask_coverage_pairs)."""
+    _need_cuda(masks)
+    if masks.dim() != 3 or masks.dtype != torch.uint8 or not masks.is_contiguous():
+        raise ValueError("mask_coverage_pairs: masks must be a contiguous uint8 [n, H, W] tensor")
+    n, H, W = (int(s) for s in masks.shape)
+    nr, nc = C.c_int(), C.c_int()
+    check(lib.tpiv_field_shape(H, W, int(ws), int(ov), C.byref(nr), C.byref(nc)))
+    count = torch.empty(n, max(nr.value, 0), max(nc.value, 0), dtype=torch.int32, device=masks.device)
+    with torch.cuda.device(masks.device):
+        check(lib.tpiv_mask_coverage_pairs(masks.data_ptr(), n, H, W, int(ws), int(ov), count.data_ptr(), _stream()))
+    return count
+
+
+def mask_fields_pairs(u, v, inv, grids, invalid_value, status=None):
+    """mask_fields with one grid per pair: grids uint8 or bool [batch, n_rows, n_cols], the fields' shape
+    (tpiv_mask_fields_pairs).  IN PLACE; returns (u, v, inv) or (u, v, inv, status)."""
+    _need_cuda(u, v, inv, grids, status)
+    if u.dtype != torch.float64 or v.dtype != torch.float64 or inv.dtype != torch.uint8:
+        raise TypeError("mask_fields_pairs: u, v float64 and invalid uint8")
+    if not (u.is_contiguous() and v.is_contiguous() and inv.is_contiguous()) or u.dim() != 3 \
+            or u.shape != v.shape or u.shape != inv.shape:
+        raise ValueError("mask_fields_pairs: contiguous [batch, n_rows, n_cols] tensors of one shape")
+    B, nr, nc = u.shape
+    if grids.dtype not in (torch.uint8, torch.bool) or grids.shape != u.shape or grids.device != u.device:
+        raise ValueError("mask_fields_pairs: grids must be a uint8 or bool tensor of the fields' shape on their device")
+    g = grids.to(torch.uint8).contiguous()
+    if status is not None and (status.dtype != torch.uint8 or status.shape != u.shape or not status.is_contiguous()
+                               or status.device != u.device):
+        raise ValueError("mask_fields_pairs: status must be a contiguous uint8 tensor of the fields' shape and device")
+    with torch.cuda.device(u.device):
+        check(lib.tpiv_mask_fields_pairs(u.data_ptr(), v.data_ptr(), inv.data_ptr(),
+                                         None if status is None else status.data_ptr(), g.data_ptr(), B, nr, nc,
+                                         int(invalid_value), _stream()))
+    return (u, v, inv) if status is None else (u, v, inv, status)
+
+
+PREFILTER_KEYS =("kind", "size", "cap")
 
 
 def prefilter_arg(prefilter):
@@ -1730,6 +1894,7 @@ class Plan:
             except Exception:
                 self.close()
                 raise
+        self._pair_masks = False         # the per-pair grids, switched on by the first run_masked
         self.n_pass = lib.tpiv_plan_n_pass(self._h)
         self.geometry = []
         for p in range(self.n_pass):
@@ -1789,6 +1954,9 @@ class Plan:
     def run(self, a, b, out=None):
         """a, b uint8 [batch, H, W] (or [H, W]) on the plan's device.  Returns u, v float64 and
         invalid uint8, [batch, n_rows, n_cols] of the last pass (async on the current stream)."""
+        return self._run(a, b, out)
+
+    def _run(self, a, b, out, masks=None, threshold=0.0):
         a, b = _frames(a, b)
         B = a.shape[0]
         if a.shape[1] != self.H or a.shape[2] != self.W:
@@ -1812,9 +1980,49 @@ class Plan:
                 if not t.is_contiguous() or t.dim() != 3 or t.shape[0] < B or tuple(t.shape[1:]) != (nr, nc):
                     raise ValueError(f"out[{name}] must be contiguous [>= {B}, {nr}, {nc}], got {tuple(t.shape)}")
         with torch.cuda.device(self.device):
-            check(lib.tpiv_plan_run(self._h, a.data_ptr(), b.data_ptr(), B, u.data_ptr(),
-                                    v.data_ptr(), inv.data_ptr(), _stream()))
+            if masks is None:
+                check(lib.tpiv_plan_run(self._h, a.data_ptr(), b.data_ptr(), B, u.data_ptr(),
+                                        v.data_ptr(), inv.data_ptr(), _stream()))
+            else:
+                check(lib.tpiv_plan_run_masked(self._h, a.data_ptr(), b.data_ptr(), masks.data_ptr(), float(threshold), B,
+                                               u.data_ptr(), v.data_ptr(), inv.data_ptr(), _stream()))
         return u, v, inv
+
+    def run_masked(self, a, b, masks, threshold=MASK_DEFAULTS["threshold"], out=None):
+        """run() with one mask per pair: masks uint8 [batch, H, W] (or [H, W]) on the plan's device, non-zero = masked.
+        The cells of every pass whose share of masked pixels exceeds the threshold are excluded pair by pair, exactly as
+        a static mask excludes them for every pair (tpiv_plan_run_masked); a static mask of the plan is superseded for
+        this run -- OR its image into masks.  The frames are not touched (apply_mask_pairs is the pixel step).  Switches
+        the plan's per-pair grids on at first use (ValueError for a plan with ensemble=True); pair_mask_grid() reads them."""
+        _need_cuda(masks)
+        if masks.dtype != torch.uint8:
+            raise TypeError("masks must be uint8")
+        m = masks[None] if masks.dim() == 2 else masks
+        if m.dim() != 3 or tuple(m.shape[1:]) != (self.H, self.W) or m.device != self.device:
+            raise ValueError(f"masks must be [batch, {self.H}, {self.W}] on {self.device}, got {tuple(masks.shape)} on "
+                             f"{masks.device}")
+        a3 = a[None] if a.dim() == 2 else a
+        if m.shape[0] != a3.shape[0]:
+            raise ValueError(f"{m.shape[0]} masks for {a3.shape[0]} pairs")
+        if not self._pair_masks:
+            with torch.cuda.device(self.device):
+                check(lib.tpiv_plan_set_pair_masks(self._h, 1))
+            self._pair_masks = True
+        return self._run(a, b, out, m.contiguous(), threshold)
+
+    def pair_mask_grid(self, p, batch, sync=True):
+        """bool [batch, n_rows, n_cols] on the device: the excluded cells of pass p for every pair of the last run_masked,
+        unflipped; a copy (sync=False: enqueued on the current stream behind the run, no host wait).  ValueError before
+        the first run_masked."""
+        pg = C.c_void_p()
+        check(lib.tpiv_plan_pass_pair_mask(self._h, p, C.byref(pg)))
+        if not 0 <= batch <= self.max_batch:
+            raise ValueError(f"batch {batch} exceeds the plan's max_batch {self.max_batch}")
+        _, _, nr, nc = self.geometry[p]
+        grid = torch.empty(batch, nr, nc, dtype=torch.uint8, device=self.device)
+        if batch:
+            self._copy_out(((grid, pg, batch * nr * nc),), sync=sync)
+        return grid != 0
 
     def ensemble_begin(self, p):
         """Opens ensemble pass p: zeroes the accumulator and, for p > 0, runs the predictor once on the ensemble field of

@@ -237,7 +237,8 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
                folder_mode: str = "pairs", save_opt: str = "Dont save", save_dir: str = "Out",
                batch_size: int = 32, on_pair=None, distributed: bool = False, stats_on_device: bool = True,
                precision: str = "exact", streaming_stats: bool = False, background=None, outlier=None, depth=None,
-               mask=None, dewarp=None, deform=None, correlation=None, weighting=None, equalize=None, prefilter=None):
+               mask=None, dewarp=None, deform=None, correlation=None, weighting=None, dynamic_mask=None, equalize=None,
+               prefilter=None):
     """Process a folder like PIVWorker.run.  save_opt: "Dont save" | "Save all binary" |
     "Save all text" | "Save statistics" (anything but "Dont save" also writes the statistics table).
     streaming_stats: running accumulators instead of the stacked fields (EnsembleStats(streaming=True): O(1) memory in
@@ -261,6 +262,9 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
     diameter and floor; engine.correlation_arg); per pair, so sharded runs need nothing more.
     weighting: the weighted interrogation windows of OfflinePIV (None, "gaussian", "uniform" or a dict with kind and sigma;
     engine.weighting_arg); per pair, so sharded runs need nothing more.
+    dynamic_mask: the per-pair masks of OfflinePIV, segmented on the device from every pair's own frames (None or a dict with
+    kind, size, level and optionally grow, threshold, pixels, fill; engine.dynamic_mask_arg); per pair, so sharded runs need
+    nothing more.  The statistics take the delivered fields as they are, as for mask=.
     depth: the tone map of deep (10..16-bit) files of OfflinePIV (None, "auto" or a dict, engine.depth_arg); with
     distributed=True every rank takes "auto"'s histogram over the sample of the whole dataset, not of its shard, so all
     ranks use the same range.
@@ -270,7 +274,7 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
                      multipass_mode=multipass_mode, dt=dt, scale=scale, multipass_scale=multipass_scale,
                      folder_mode=folder_mode, precision=precision, background=background, outlier=outlier, prefilter=prefilter,
                      depth=depth, equalize=equalize, mask=mask, dewarp=dewarp, deform=deform,
-                     correlation=correlation, weighting=weighting)
+                     correlation=correlation, weighting=weighting, dynamic_mask=dynamic_mask)
     if len(piv) == 0:
         return None, 0
     rank, world = 0, 1
