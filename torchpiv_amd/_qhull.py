@@ -11,6 +11,8 @@ triangulation itself.  `qhull_fill` runs the SAME triangulation (scipy.spatial.D
 point order -- and with it the same tie-break on the co-circular diamonds of a lattice) and evaluates it with the
 arithmetic of scipy's _interpnd.pyx spelled out in numpy: bit-identical results (tests/test_host_logic.py compares the
 two on random hole patterns), a tenth of the time."""
+import weakref
+
 import numpy as np
 
 
@@ -31,7 +33,9 @@ def _diamond_fill(tri, points, values, targets):
     barycentric coordinates are (1/2, 1/2, 0) exactly (lattice coordinates: the 2 x 2 inverse has entries 0, +-1/2, +-1): the
     value is 0.5 a + 0.5 b of the diagonal's ends.  So only the DIAGONAL has to be read off the triangulation: no barycentric
     transforms (one LAPACK call per simplex), no simplex walk.  Returns None when a target is not such a hole or the diagonal
-    cannot be read (the caller then takes the general path)."""
+    cannot be read (the caller then takes the general path).  The general path accumulates from 0.0 and adds the third
+    vertex's 0 * value, so a sum of zeros comes out as +0.0 there whatever the signs of the ends: hence the `+ 0.0` here
+    (-0.0 + 0.0 = +0.0; every other sum is left as it is)."""
     pts = np.asarray(points, dtype=np.int64)
     tg = np.asarray(targets, dtype=np.int64)
     n = pts.shape[0]
@@ -60,7 +64,7 @@ def _diamond_fill(tri, points, values, targets):
         return None
     a = np.where(ns, iN, iW)
     b = np.where(ns, iS, iE)
-    return 0.5 * values[a] + 0.5 * values[b]
+    return (0.5 * values[a] + 0.5 * values[b]) + 0.0
 
 
 def qhull_fill(points, values, targets, diamonds=True):
@@ -150,11 +154,23 @@ def _job_bytes(part):
     return sum(a.nbytes for job in part for a in job)
 
 
+class PipelineOwner:
+    """The name of one pipeline in a FillWorkers pool.  The pool refers to it weakly: when a pipeline goes away with
+    batches in flight (a generator closed early), nobody is left to collect its tickets, and the pool drops them."""
+    __slots__ = ("__weakref__",)
+
+
+_GONE = object()                 # the owner of a ticket whose PipelineOwner no longer exists
+
+
 class FillWorkers:
     """`n` worker processes behind one duplex pipe each.  Unlike multiprocessing.Pool there are no handler threads in the
     calling process (they compete with it for the GIL: an asynchronous Pool.map made the whole generator slower) and the
     exchange is split: submit(jobs) hands the jobs of a batch out and returns at once, collect(ticket) reads the answers --
     the caller launches the next batch and finishes the previous one in between (backend.OfflinePIV._post_pipeline).
+    Several pipelines may share one pool (all batched() generators of an OfflinePIV do): each names itself as the `owner`
+    of its tickets (a PipelineOwner, or any other value compared with ==), and what one owner forgets
+    (collect(..., forget_older=True)) is its own.
     Messages beyond LIGHT bytes could fill a pipe while its reader is itself blocked writing, so a batch that holds one is
     exchanged on the spot, one message per worker at a time (send to all, then read from all: no cycle of blocked writers)."""
     LIGHT = 24 * 1024            # bytes per message that may stay in flight (two batches outstanding: well inside a socket buffer)
@@ -172,6 +188,7 @@ class FillWorkers:
             self.procs.append(p)
         self.n = n
         self._order, self._parts, self._ready = [], {}, {}      # tickets in flight (oldest first), their message counts, answers read early
+        self._owner = {}                                        # ticket -> owner, until the ticket is collected or forgotten
 
     def _recv(self, w):
         try:
@@ -185,9 +202,22 @@ class FillWorkers:
             t = self._order.pop(0)
             self._ready[t] = [s for w in range(self._parts.pop(t)) for s in self._recv(w)]
 
-    def submit(self, jobs):
-        """Ticket for collect(): the jobs cut into one run per worker (the order of the jobs is the order of the answers)."""
+    def _who(self, t):
+        o = self._owner.get(t)
+        if isinstance(o, weakref.ref):
+            o = o()
+            return _GONE if o is None else o
+        return o
+
+    def _forget(self, t):
+        del self._ready[t]
+        self._owner.pop(t, None)
+
+    def submit(self, jobs, owner=None):
+        """Ticket for collect(): the jobs cut into one run per worker (the order of the jobs is the order of the answers).
+        owner: names the submitting pipeline (see collect)."""
         t = self._next = getattr(self, "_next", 0) + 1
+        self._owner[t] = weakref.ref(owner) if isinstance(owner, PipelineOwner) else owner
         per = max(1, -(-len(jobs) // self.n))
         parts = [jobs[k:k + per] for k in range(0, len(jobs), per)]
         if all(_job_bytes(p_) <= self.LIGHT for p_ in parts):
@@ -209,14 +239,19 @@ class FillWorkers:
         self._ready[t] = out
         return t
 
-    def collect(self, ticket, forget_older=False):
-        """The answers of `ticket`.  forget_older: answers of earlier tickets that nobody collected (a generator abandoned with
-        batches in flight) are dropped -- for callers that collect in the order they submit."""
+    def collect(self, ticket, forget_older=False, owner=None):
+        """The answers of `ticket`.  forget_older: answers of earlier tickets OF THIS OWNER that nobody collected (a generator
+        abandoned with batches in flight) are dropped -- for callers that collect in the order they submit.  Tickets of
+        other owners stay: their pipelines are still to collect them.  (Answers whose PipelineOwner is gone go too.)"""
+        if ticket not in self._owner or self._who(ticket) != owner:
+            raise KeyError(f"ticket {ticket} is not one of this owner's outstanding tickets")
         if ticket not in self._ready:
             self._drain(ticket)
-        if forget_older:
-            for t in [t for t in self._ready if t < ticket]:
-                del self._ready[t]
+        for t in [t for t in self._ready if t != ticket]:
+            who = self._who(t)
+            if who is _GONE or (forget_older and t < ticket and who == owner):
+                self._forget(t)
+        self._owner.pop(ticket, None)
         return self._ready.pop(ticket)
 
     def terminate(self):

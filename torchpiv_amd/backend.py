@@ -26,7 +26,7 @@ import torch
 
 from . import engine
 from ._lib import PRECISIONS
-from ._qhull import blas_one_thread, qhull_fill, qhull_fill_many      # numpy/scipy-only module: the fill worker processes import nothing else
+from ._qhull import PipelineOwner, blas_one_thread, qhull_fill, qhull_fill_many      # numpy/scipy-only module: the fill worker processes import nothing else
 from .io import PIVDataset, StagedBatches, ToTensor, natural_keys, slot_bytes  # noqa: F401  (re-exported like the reference)
 
 
@@ -1154,11 +1154,12 @@ class OfflinePIV:
         #  the full lists serve the overflow path)
         return done, host, (src, ring_rc, ring_uv, hole_rc, u, v)
 
-    def _post_extract(self, ticket):
+    def _post_extract(self, ticket, owner=None):
         """Host half, first stage: drop decisions from the census; the pairs that hold an ambiguous or wide hole
         (counted) arrive with their ring points, values and hole cells already cut out (tpiv_postval_compact) and go to
         the triangulation -- in worker processes when fill_workers > 0: the jobs are handed out here and the answers read
         by _post_complete, so whatever the caller does in between (the next launch, the batch before) overlaps them.
+        owner: names the pipeline these jobs belong to in the pool that all pipelines of this object share.
         Returns the state _post_complete takes."""
         done, host, keep_alive = ticket
         done.synchronize()
@@ -1199,7 +1200,7 @@ class OfflinePIV:
                 # (round 5: own worker processes behind pipes.  multiprocessing.Pool.map was synchronous here -- with map_async
                 #  the pool's handler threads compete with this thread for the GIL and the whole host side got slower,
                 #  6.5 k -> 4.8 k pairs/s -- and a batch of 64 pairs waited 2-4 ms for its triangulations)
-                state["pending"] = (pool, pool.submit(jobs))
+                state["pending"] = (pool, pool.submit(jobs, owner=owner), owner)
             else:
                 with blas_one_thread():
                     state["sols"] = qhull_fill_many(jobs)
@@ -1211,8 +1212,8 @@ class OfflinePIV:
         per-pair keep flags (False: dropped)."""
         keep, need, host = state["keep"].copy(), state["need"], state["host"]
         if "pending" in state:
-            pool, t_ = state.pop("pending")
-            state["sols"] = pool.collect(t_, forget_older=True)
+            pool, t_, owner = state.pop("pending")
+            state["sols"] = pool.collect(t_, forget_older=True, owner=owner)      # (older tickets of this pipeline only)
         if need.size:
             st = self.stats
             fu, fv = host["fu"].numpy(), host["fv"].numpy()
@@ -1271,6 +1272,7 @@ class OfflinePIV:
         depth 2: a batch's upload (longer than its passes) then overlaps the passes of the batch before instead of being
         waited for.  flush() drains."""
         waiting, extracted = [], []
+        owner = PipelineOwner()          # this pipeline's name in the fill-worker pool (shared with every other generator)
 
         def step(drain=False):
             # the census of the next batch first: it waits for the GPU, and behind that wait its triangulations go to the
@@ -1279,7 +1281,7 @@ class OfflinePIV:
             out = []
             if waiting:
                 meta, ticket = waiting.pop(0)
-                extracted.append((meta, self._post_extract(ticket) if ticket is not None else None))
+                extracted.append((meta, self._post_extract(ticket, owner) if ticket is not None else None))
             if extracted and (len(extracted) > 1 or (drain and not waiting)):
                 meta, state = extracted.pop(0)
                 out.append((meta, self._finish_batch(self._post_complete(state), x, y, plan) if state is not None else []))
