@@ -1,6 +1,6 @@
 """Do two builds of the library produce the same BITS?  (development aid for changes that must not move a result)
    python tools/dev/ab_bits.py dump out.npz     (with TPIV_LIB=<build>)      -> fields of a fixed set of plans on seeded frames
-   python tools/dev/ab_bits.py cmp a.npz b.npz                               -> per-plan count of differing words"""
+   python tools/dev/ab_bits.py cmp a.npz b.npz                               -> per-array count of differing bytes"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
@@ -12,11 +12,22 @@ CASES = [  # (H, W, ws, passes, mode, precision, kind, noise)
     (512, 512, 64, 1, "CWS", "fast", "wavy", 30.0), (256, 256, 32, 1, "CWS", "fast", "noise", 0.0),
     (512, 512, 48, 2, "CWS", "fast", "wavy", 2.0),
 ]
+# the variant kernels (xcorr_variant.hpp), each chain in DWS and in CWS: 64 -> 32 -> 16 runs the pass-1 instance of 64 and the
+# shifted instances of 32 and 16, 64 -> 64 the shifted instances of 64, and one single-pass plan each the pass-1 instances of
+# 32 and 16
+VARIANTS = {"phase": {"correlation": "phase"}, "rpc": {"correlation": "rpc"}, "gauss": {"weighting": "gaussian"},
+            "ens": {"ensemble": True}}
+CHAINS = [(64, 3, 2.0), (64, 2, 1.0), (32, 1, 2.0), (16, 1, 2.0)]      # (first window size, passes, pass_scale)
+V_H = V_W = 512
 
 if sys.argv[1] == "dump":
     import torch
     from torchpiv_amd import engine, synth
     out = {}
+
+    def put(tag, u, v, inv):
+        out["u" + tag], out["v" + tag], out["m" + tag] = u.cpu().numpy(), v.cpu().numpy(), inv.cpu().numpy()
+
     for i, (H, W, ws, n_pass, mode, prec, kind, noise) in enumerate(CASES):
         try:
             A, B = synth.make_batch(3, H, W, device="cuda", kind=kind, noise=noise)
@@ -25,18 +36,47 @@ if sys.argv[1] == "dump":
             A = torch.randint(0, 256, (3, H, W), dtype=torch.uint8, device="cuda", generator=g)
             B = torch.randint(0, 256, (3, H, W), dtype=torch.uint8, device="cuda", generator=g)
         plan = engine.Plan(H, W, ws, ws // 2, n_pass=n_pass, mode=mode, max_batch=3, precision=prec)
-        u, v, inv = plan.run(A, B)
+        put(str(i), *plan.run(A, B))
         torch.cuda.synchronize()
-        out[f"u{i}"], out[f"v{i}"], out[f"m{i}"] = u.cpu().numpy(), v.cpu().numpy(), inv.cpu().numpy()
+        plan.close()
+    A, B = synth.make_batch(3, V_H, V_W, device="cuda", kind="wavy", noise=2.0)
+    A2, B2 = synth.make_batch(3, V_H, V_W, device="cuda", kind="wavy", noise=5.0)      # the second ensemble_add
+    A[0, :96, :96] = 0                                              # empty windows: zeroed in one frame, constant in both
+    A[1, 128:224, 128:224] = 9
+    B[1, 128:224, 128:224] = 9
+    n_plans = len(CASES)
+    for name, kw in VARIANTS.items():
+        for ws, n_pass, scale in CHAINS:
+            for mode in ("DWS", "CWS"):
+                if n_pass == 1 and mode == "DWS":
+                    continue                                        # a single pass has no shifted pass: one plan is enough
+                tag = f"_{name}_{ws}x{n_pass}s{scale:g}_{mode}"
+                plan = engine.Plan(V_H, V_W, ws, ws // 2, n_pass=n_pass, mode=mode, max_batch=3, precision="fast", pass_scale=scale,
+                                   **kw)
+                if name == "ens":
+                    for p in range(n_pass):
+                        plan.ensemble_begin(p)
+                        plan.ensemble_add(A, B)
+                        plan.ensemble_add(A2, B2)
+                        put(f"{tag}_p{p}", *plan.ensemble_end())
+                    out["acc" + tag] = plan.ensemble_maps()[0].cpu().numpy()      # of the last pass
+                else:
+                    put(tag, *plan.run(A, B))
+                torch.cuda.synchronize()
+                plan.close()
+                n_plans += 1
     np.savez(sys.argv[2], **out)
-    print("dumped", len(CASES), "plans to", sys.argv[2], "with", os.environ.get("TPIV_LIB", "the in-tree library"))
+    print("dumped", n_plans, "plans,", len(out), "arrays to", sys.argv[2], "with", os.environ.get("TPIV_LIB", "the in-tree library"))
 else:
     a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
-    bad = 0
-    for i, c in enumerate(CASES):
-        d = [int((a[k + str(i)].view(np.uint8) != b[k + str(i)].view(np.uint8)).reshape(-1).sum()) for k in "uvm"]
-        n = a["u" + str(i)].size
-        bad += sum(d)
-        print(c, "differing bytes u/v/mask:", d, "of", n, "vectors", "nan:", int(np.isnan(a["u" + str(i)]).sum()))
-    print("IDENTICAL" if bad == 0 else "DIFFERENT")
+    bad = sorted(set(a.files) ^ set(b.files))
+    if bad:
+        print("arrays in one dump only:", bad)
+    for k in sorted(set(a.files) & set(b.files)):
+        x, y = a[k], b[k]
+        d = x.size if x.shape != y.shape or x.dtype != y.dtype else int((x.view(np.uint8) != y.view(np.uint8)).sum())
+        if d:
+            bad.append(k)
+        print(f"{k:28s} differing bytes: {d} of {x.nbytes}  nan: {int(np.isnan(x).sum())}")
+    print("IDENTICAL" if not bad else "DIFFERENT")
     sys.exit(1 if bad else 0)

@@ -1570,6 +1570,41 @@ int tpiv_plan_run_masked(tpiv_plan* plan, const uint8_t* a, const uint8_t* b, co
     return rc;
 }
 
+// ---- spectrally filtered passes and weighted windows: what their two setters share -----------------------------------
+
+// The last step of tpiv_plan_set_correlation / _set_weighting, behind every refusal that needs no device.  Such a pass works in
+// the float32 tile layout (records, item counters) whatever the plan's precision: a plan whose workspace was sized for
+// float64 records alone gets a larger one (the old one is freed with the plan).  tabs (the plan's per-pass device tables,
+// floats_of(ws) floats each) are allocated the first time and kept until the plan is destroyed; tables: all of them, pass
+// after pass, on the host.  The plan's workspace changes only when everything else has succeeded.
+static int install_pass_tables(tpiv_plan* plan, std::vector<float*>& tabs, const float* tables, size_t (*floats_of)(int ws)) {
+    if (int rc = check_plan_device(plan)) return rc;
+    size_t raw = 0;
+    for (const PassGeo& g : plan->geo)
+        raw = std::max(raw, tpiv::peak_raw_bytes(g.ws, plan->max_batch, g.n_rows * g.n_cols, TPIV_PREC_FAST));
+    float* grown = nullptr;
+    if (raw > plan->peak_raw_bytes)
+        if (int rc = plan->alloc(&grown, raw / sizeof(float) + 64)) return rc;
+    if (tabs.empty()) {
+        std::vector<float*> fresh(plan->n_pass, nullptr);
+        for (int p = 0; p < plan->n_pass; ++p)
+            if (int rc = plan->alloc(&fresh[p], floats_of(plan->geo[p].ws))) return rc;
+        tabs = std::move(fresh);
+    }
+    HIP_TRY(hipDeviceSynchronize());                 // no run in flight reads the tables while they change
+    size_t off = 0;
+    for (int p = 0; p < plan->n_pass; ++p) {
+        const size_t n = floats_of(plan->geo[p].ws);
+        HIP_TRY(hipMemcpy(tabs[p], tables + off, n * sizeof(float), hipMemcpyHostToDevice));
+        off += n;
+    }
+    if (grown) {
+        plan->peak_raw = grown;
+        plan->peak_raw_bytes = raw;
+    }
+    return TPIV_OK;
+}
+
 // ---- spectrally filtered passes -------------------------------------------------------------------------------------
 
 int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double dx, double dy, double floor, const float* tables,
@@ -1594,32 +1629,7 @@ int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double dx, double dy, d
     if (!tables || n_tables != need)
         return fail(TPIV_EINVAL, "tpiv_plan_set_correlation: tables must hold g_y and g_x of every pass, " + std::to_string(need) +
                                      " floats in all");
-    if (int rc = check_plan_device(plan)) return rc;
-    // a filtered pass works in the float32 tile layout (records, item counters) whatever the plan's precision: a plan whose
-    // workspace was sized for float64 records alone gets a larger one (the old one is freed with the plan)
-    size_t raw = 0;
-    for (const PassGeo& g : plan->geo)
-        raw = std::max(raw, tpiv::peak_raw_bytes(g.ws, plan->max_batch, g.n_rows * g.n_cols, TPIV_PREC_FAST));
-    float* grown = nullptr;
-    if (raw > plan->peak_raw_bytes)
-        if (int rc = plan->alloc(&grown, raw / sizeof(float) + 64)) return rc;
-    if (plan->corr_tab.empty()) {                    // first time on (kept until the plan is destroyed)
-        std::vector<float*> tabs(plan->n_pass, nullptr);
-        for (int p = 0; p < plan->n_pass; ++p)
-            if (int rc = plan->alloc(&tabs[p], 2 * (size_t)(plan->geo[p].ws / 2 + 1))) return rc;
-        plan->corr_tab = std::move(tabs);
-    }
-    HIP_TRY(hipDeviceSynchronize());                 // no run in flight reads the tables while they change
-    size_t off = 0;
-    for (int p = 0; p < plan->n_pass; ++p) {
-        const size_t n = 2 * (size_t)(plan->geo[p].ws / 2 + 1);
-        HIP_TRY(hipMemcpy(plan->corr_tab[p], tables + off, n * sizeof(float), hipMemcpyHostToDevice));
-        off += n;
-    }
-    if (grown) {
-        plan->peak_raw = grown;
-        plan->peak_raw_bytes = raw;
-    }
+    if (int rc = install_pass_tables(plan, plan->corr_tab, tables, [](int ws) { return 2 * (size_t)(ws / 2 + 1); })) return rc;
     plan->corr_kind = kind;
     plan->corr_floor = floor;
     return TPIV_OK;
@@ -1656,32 +1666,7 @@ int tpiv_plan_set_weighting(tpiv_plan* plan, int kind, double sigma_x, double si
     if (kind == TPIV_WEIGHT_UNIFORM)
         for (size_t i = 0; i < need; ++i)
             if (tables[i] != 1.0f) return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: the uniform weight's tables are all ones");
-    if (int rc = check_plan_device(plan)) return rc;
-    // a weighted pass works in the float32 tile layout (records, item counters) whatever the plan's precision: a plan whose
-    // workspace was sized for float64 records alone gets a larger one (the old one is freed with the plan)
-    size_t raw = 0;
-    for (const PassGeo& g : plan->geo)
-        raw = std::max(raw, tpiv::peak_raw_bytes(g.ws, plan->max_batch, g.n_rows * g.n_cols, TPIV_PREC_FAST));
-    float* grown = nullptr;
-    if (raw > plan->peak_raw_bytes)
-        if (int rc = plan->alloc(&grown, raw / sizeof(float) + 64)) return rc;
-    if (plan->wt_tab.empty()) {                      // first time on (kept until the plan is destroyed)
-        std::vector<float*> tabs(plan->n_pass, nullptr);
-        for (int p = 0; p < plan->n_pass; ++p)
-            if (int rc = plan->alloc(&tabs[p], 2 * (size_t)plan->geo[p].ws)) return rc;
-        plan->wt_tab = std::move(tabs);
-    }
-    HIP_TRY(hipDeviceSynchronize());                 // no run in flight reads the tables while they change
-    size_t off = 0;
-    for (int p = 0; p < plan->n_pass; ++p) {
-        const size_t n = 2 * (size_t)plan->geo[p].ws;
-        HIP_TRY(hipMemcpy(plan->wt_tab[p], tables + off, n * sizeof(float), hipMemcpyHostToDevice));
-        off += n;
-    }
-    if (grown) {
-        plan->peak_raw = grown;
-        plan->peak_raw_bytes = raw;
-    }
+    if (int rc = install_pass_tables(plan, plan->wt_tab, tables, [](int ws) { return 2 * (size_t)ws; })) return rc;
     plan->wt_kind = kind;
     return TPIV_OK;
 }

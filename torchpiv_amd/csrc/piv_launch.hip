@@ -387,14 +387,17 @@ hipError_t launch_xcorr(const PassParams& p_in, int mode, int n_cu, hipStream_t 
 }
 
 // ---- ensemble correlation (xcorr_ens.hip): accumulate raw maps, then one peak stage on the mean map ----------------
-bool ensemble_size(int ws) { return ws == 16 || ws == 32 || ws == 64; }
+// the window sizes and modes of the variant units (ensemble, spectral, weighted: xcorr_variant.hpp)
+static bool variant_size(int ws) { return ws == 16 || ws == 32 || ws == 64; }
+static bool variant_mode(int mode) { return mode == MODE_PASS1 || mode == MODE_DWS || mode == MODE_CWS; }
+bool ensemble_size(int ws) { return variant_size(ws); }
 // work buffer of both launches: the peak records of ONE field, the tile kernels' item counters behind them
 size_t ensemble_work_bytes(int n_windows) { return work_ctr_offset(1, n_windows) + WORK_CTR_BYTES; }
 
 // acc [N, ws, ws] += the raw maps of the p.batch pairs of p.A / p.B; p.peak_raw: ensemble_work_bytes.  Shifted passes read
 // the predictor (either form of PassParams) by window: one field for every pair.
 hipError_t launch_ensemble_add(const PassParams& p_in, int mode, float* acc, int n_cu, hipStream_t stream) {
-    if (!ensemble_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) return hipErrorInvalidValue;
+    if (!variant_size(p_in.ws) || !variant_mode(mode)) return hipErrorInvalidValue;
     PassParams p = p_in;
     p.precision = 0;
     p.list_mode = 0;
@@ -411,7 +414,7 @@ hipError_t launch_ensemble_add(const PassParams& p_in, int mode, float* acc, int
 // combines with the shared predictor like any other (u = 2 u2 + du, fallback to u0)
 hipError_t launch_ensemble_peaks(const PassParams& p_in, int mode, const float* acc, long long n_pairs, int n_cu,
                                  hipStream_t stream) {
-    if (!ensemble_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) return hipErrorInvalidValue;
+    if (!variant_size(p_in.ws) || !variant_mode(mode)) return hipErrorInvalidValue;
     PassParams p = p_in;
     p.batch = 1;
     p.A = p.B = nullptr;           // (finalize: no identical-window comparison -- a sum of maps has no one window pair)
@@ -425,51 +428,28 @@ hipError_t launch_ensemble_peaks(const PassParams& p_in, int mode, const float* 
     return hipGetLastError();
 }
 
-// ---- spectrally filtered passes (xcorr_spec.hip): phase-only / robust phase correlation -----------------------------
-bool spec_size(int ws) { return ws == 16 || ws == 32 || ws == 64; }
+// ---- spectrally filtered passes (xcorr_spec.hip) and weighted interrogation windows (xcorr_win.hip) ------------------
+bool spec_size(int ws) { return variant_size(ws); }
+bool win_size(int ws) { return variant_size(ws); }
 
+static const char* variant_kernel_name(const char* stem, int ws, int mode, int occ, bool planar, char* buf, int len) {
+    if (!variant_size(ws) || !variant_mode(mode)) snprintf(buf, len, "%s", "");
+    else snprintf(buf, len, "%s<%d, %d, %d, %s>", stem, ws, mode, occ, planar ? "true" : "false");
+    return buf;
+}
 const char* xcorr_spec_kernel_name(int ws, int mode, char* buf, int len) {
-    if (!spec_size(ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) snprintf(buf, len, "%s", "");
-    else snprintf(buf, len, "xcorr_spec_kernel<%d, %d, %d, %s>", ws, mode, spec_occ(ws, mode), spec_planar(ws, mode) ? "true" : "false");
-    return buf;
+    return variant_kernel_name("xcorr_spec_kernel", ws, mode, spec_occ(ws, mode), spec_planar(ws, mode), buf, len);
 }
-
-// one filtered pass: the spectral tile kernel, then the finalize step of every float32 pass (pass 1 writes du, dv as u, v; a
-// shifted pass combines with the predictor).  The workspace is the plain tile kernels': records, item counters behind them.
-hipError_t launch_xcorr_spec(const PassParams& p_in, int mode, const SpecParams& s, int n_cu, hipStream_t stream) {
-    if (!spec_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS) || s.tab == nullptr)
-        return hipErrorInvalidValue;
-    PassParams p = p_in;
-    p.precision = 0;
-    p.list_mode = 0;
-    p.slow_list = nullptr;
-    p.slow_count = nullptr;
-    p.work_ctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.peak_raw) + work_ctr_offset(p.batch, p.n_rows * p.n_cols));
-    hipError_t e = hipMemsetAsync(p.work_ctr, 0, WORK_CTR_BYTES, stream);
-    if (e != hipSuccess) return e;
-    e = launch_xcorr_spec_tile(p, mode, s, n_cu, stream);
-    if (e != hipSuccess) return e;
-    const size_t total = (size_t)p.batch * p.n_rows * p.n_cols;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > (size_t)n_cu * 32) blocks = (size_t)n_cu * 32;
-    hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
-    return hipGetLastError();
-}
-
-// ---- weighted interrogation windows (xcorr_win.hip) -------------------------------------------------------------------
-bool win_size(int ws) { return ws == 16 || ws == 32 || ws == 64; }
-
 const char* xcorr_win_kernel_name(int ws, int mode, char* buf, int len) {
-    if (!win_size(ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS)) snprintf(buf, len, "%s", "");
-    else snprintf(buf, len, "xcorr_win_kernel<%d, %d, %d, %s>", ws, mode, win_occ(ws, mode), win_planar(ws, mode) ? "true" : "false");
-    return buf;
+    return variant_kernel_name("xcorr_win_kernel", ws, mode, win_occ(ws, mode), win_planar(ws, mode), buf, len);
 }
 
-// one weighted pass: the weighted tile kernel, then the finalize step of every float32 pass (pass 1 writes du, dv as u, v; a
-// shifted pass combines with the predictor).  The workspace is the plain tile kernels': records, item counters behind them.
-hipError_t launch_xcorr_win(const PassParams& p_in, int mode, const WinParams& s, int n_cu, hipStream_t stream) {
-    if (!win_size(p_in.ws) || (mode != MODE_PASS1 && mode != MODE_DWS && mode != MODE_CWS) || s.tab == nullptr)
-        return hipErrorInvalidValue;
+// one filtered or weighted pass: tile_launch(p) runs the unit's tile kernel, then the finalize step of every float32 pass
+// (pass 1 writes du, dv as u, v; a shifted pass combines with the predictor).  The workspace is the plain tile kernels':
+// records, item counters behind them.
+template <class TileLaunch>
+static hipError_t launch_variant_pass(const PassParams& p_in, int mode, int n_cu, hipStream_t stream, TileLaunch tile_launch) {
+    if (!variant_size(p_in.ws) || !variant_mode(mode)) return hipErrorInvalidValue;
     PassParams p = p_in;
     p.precision = 0;
     p.list_mode = 0;
@@ -478,13 +458,25 @@ hipError_t launch_xcorr_win(const PassParams& p_in, int mode, const WinParams& s
     p.work_ctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(p.peak_raw) + work_ctr_offset(p.batch, p.n_rows * p.n_cols));
     hipError_t e = hipMemsetAsync(p.work_ctr, 0, WORK_CTR_BYTES, stream);
     if (e != hipSuccess) return e;
-    e = launch_xcorr_win_tile(p, mode, s, n_cu, stream);
+    e = tile_launch(p);
     if (e != hipSuccess) return e;
     const size_t total = (size_t)p.batch * p.n_rows * p.n_cols;
     size_t blocks = (total + 255) / 256;
     if (blocks > (size_t)n_cu * 32) blocks = (size_t)n_cu * 32;
     hipLaunchKernelGGL(finalize_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, mode);
     return hipGetLastError();
+}
+
+hipError_t launch_xcorr_spec(const PassParams& p_in, int mode, const SpecParams& s, int n_cu, hipStream_t stream) {
+    if (s.tab == nullptr) return hipErrorInvalidValue;
+    return launch_variant_pass(p_in, mode, n_cu, stream,
+                               [&](const PassParams& p) { return launch_xcorr_spec_tile(p, mode, s, n_cu, stream); });
+}
+
+hipError_t launch_xcorr_win(const PassParams& p_in, int mode, const WinParams& s, int n_cu, hipStream_t stream) {
+    if (s.tab == nullptr) return hipErrorInvalidValue;
+    return launch_variant_pass(p_in, mode, n_cu, stream,
+                               [&](const PassParams& p) { return launch_xcorr_win_tile(p, mode, s, n_cu, stream); });
 }
 
 // ----------------------------------------------------------------------------

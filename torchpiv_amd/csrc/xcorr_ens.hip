@@ -2,8 +2,9 @@
 // (Meinhart, Wereley & Santiago, J. Fluids Eng. 122 (2000) 285: add the correlation maps of all pairs of a recording
 // window by window and take the peak of the summed map once.)
 //
-// Same staging, in-register transforms and transposes as xcorr_tile_body (xcorr_tile.hpp, fast operation order); the peak
-// stage is replaced by an epilogue that adds the raw map into acc float32 [N, ws, ws], fftshift layout:
+// Same staging, in-register transforms and transposes as xcorr_tile_body (xcorr_tile.hpp, fast operation order), with the
+// inverse_rows, pass_shift and dispatch of xcorr_variant.hpp; the work loop is this unit's own, and the peak stage is
+// replaced by an epilogue that adds the raw map into acc float32 [N, ws, ws], fftshift layout:
 //   * a work item is a window GROUP (64 / WS windows), not a (pair, group): the wavefront that takes a group owns its
 //     accumulator rows for the whole launch and loops over the pairs of the launch in ascending order.  No atomics, one
 //     owner per cell: the same sequence of launches gives the same bits.
@@ -15,8 +16,7 @@
 //   * raw map: what peak_analysis would receive, with the constant factor of the fast shifted order (1/4 n^2, a power of
 //     two) applied -- before any minimum subtraction and before the 1e-7.  A pass-1 window whose pixel sum is 0 in either
 //     frame is transformed as zeros (ka = kb = 0 below) and so contributes the zero map.
-// The production instances of xcorr_tile.hpp are not touched: this body is separate.
-#include "xcorr_tile.hpp"
+#include "xcorr_variant.hpp"
 
 namespace tpiv {
 
@@ -69,19 +69,6 @@ __device__ __forceinline__ void xcorr_ens_body(const PassParams& p, float* __res
         g.fidx = (size_t)g.win;
         return g;
     };
-    auto shift_of = [&](const ItemGeom& g, float& vx, float& vy) TPIV_LAMBDA_INLINE {
-        if constexpr (MODE == MODE_PASS1) {
-            vx = 0.f;
-            vy = 0.f;
-        } else if constexpr (MODE == MODE_CWS) {
-            pred_half_shift_cws_f32(p, g.fidx, vx, vy);
-        } else {
-            double sx, sy;
-            pred_half_shift<MODE>(p, g.fidx, sx, sy);
-            vx = (float)sx;
-            vy = (float)sy;
-        }
-    };
 
     int item = q_take(q_issue());
     if (item >= hi) return;
@@ -93,14 +80,12 @@ __device__ __forceinline__ void xcorr_ens_body(const PassParams& p, float* __res
     {
         const int l0 = fresh_lane();
         const ItemGeom g0 = geom_of(item, 0, l0 / WS);
-        shift_of(g0, vx, vy);
+        pass_shift<MODE>(p, g0, vx, vy);
         issue_rows<WS, MODE, FAST>(p, g0, l0 % WS, vx, vy, raw, coff);
     }
 
     constexpr bool FASTN = MODE != MODE_PASS1;
     constexpr bool NOSWAP = WS == 64 && MODE != MODE_DWS;
-    auto up_sign = []() TPIV_LAMBDA_INLINE { return fresh_lane() >= 32 ? 0x80000000u : 0u; };
-    auto sflip = [](float v, unsigned sg) TPIV_LAMBDA_INLINE { return __uint_as_float(__float_as_uint(v) ^ sg); };
     constexpr float END_SCALE = FASTN ? 0.25f / (float)(WS * WS) : 1.0f;      // a power of two: exact
 
     // the lane's accumulator row (fftshift layout), or nullptr for the idle window slots of the last group
@@ -145,7 +130,7 @@ __device__ __forceinline__ void xcorr_ens_body(const PassParams& p, float* __res
             const int npr = last ? 0 : pr + 1;
             const ItemGeom gnext = geom_of(nit, npr, w);
             float nvx, nvy;
-            shift_of(gnext, nvx, nvy);
+            pass_shift<MODE>(p, gnext, nvx, nvy);
 
             cf x[WS];
             float sa, sb;
@@ -201,97 +186,9 @@ __device__ __forceinline__ void xcorr_ens_body(const PassParams& p, float* __res
             transpose_tile<WS, PLANAR, NOSWAP>(x, tile, fresh_lane());
             fft_inreg<WS, 1>(x, tw);
 
-            constexpr bool HALF_INV = PLANAR && (WS == 32 || WS == 64);
             float crow[WS];
-            auto cross = [&](cf zk, cf zm, float two) TPIV_LAMBDA_INLINE {
-                const float a_ = zk.x, b_ = zk.y, c_ = zm.x, d_ = zm.y;
-                cf pr_;
-                pr_.x = (a_ * d_ + b_ * c_) * two;
-                pr_.y = (c_ * c_ - a_ * a_) + (d_ * d_ - b_ * b_);
-                return pr_;
-            };
-            if constexpr (HALF_INV) {
-                constexpr int M = WS / 2;
-                cf h[M];
-                {
-                    const int lane_c = fresh_lane();
-                    const int r_c = lane_c % WS;
-                    const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
-                    const float two_odd = (NOSWAP && (lane_c & 31) != 0) ? -2.0f : 2.0f;
-                    cf pc[M + 1];
-                    static_for<0, M + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
-                        constexpr int ky = decltype(kc)::value;
-                        constexpr int nky = (WS - ky) % WS;
-                        const cf z2 = x[FFT_POS<nky, WS>];
-                        cf m1;
-                        m1.x = __shfl(z2.x, partner, 64);
-                        m1.y = __shfl(z2.y, partner, 64);
-                        pc[ky] = cross(x[FFT_POS<ky, WS>], m1, (ky & 1) ? two_odd : 2.0f);
-                    });
-                    const bool odd = r_c > M;
-                    const float fs = (r_c == 0 || r_c == M) ? 1.0f : 0.0f;
-                    static_for<0, M>([&](auto kc) TPIV_LAMBDA_INLINE {
-                        constexpr int k = decltype(kc)::value;
-                        cf pr_;
-                        pr_.x = __shfl(pc[M - k].x, partner, 64);
-                        pr_.y = __shfl(pc[M - k].y, partner, 64);
-                        const cf s{pc[k].x + pr_.x, pc[k].y - pr_.y};
-                        const cf tt = twmul<k, WS, -1>(cf{pc[k].x - pr_.x, pc[k].y + pr_.y});
-                        h[k].x = odd ? tt.x : __builtin_fmaf(-fs, tt.y, s.x);
-                        h[k].y = odd ? tt.y : __builtin_fmaf(fs, tt.x, s.y);
-                    });
-                }
-                fft_inreg<M, -1>(h, tw);
-                cf hs[M + 1], z[M];
-                transpose_half_pairs<WS, PLANAR>(h, hs, tile, fresh_lane());
-                c2r_inreg<WS>(hs, z);
-                static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
-                    constexpr int x_ = decltype(xc)::value;
-                    crow[x_] = (x_ & 1) ? z[FFT_POS<x_ / 2, M>].y : z[FFT_POS<x_ / 2, M>].x;
-                });
-            } else {
-                {
-                    const int lane_c = fresh_lane();
-                    const int r_c = lane_c % WS;
-                    const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
-                    const float two_odd = (NOSWAP && (lane_c & 31) != 0) ? -2.0f : 2.0f;
-                    static_for<0, WS / 2 + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
-                        constexpr int ky = decltype(kc)::value;
-                        constexpr int nky = (WS - ky) % WS;
-                        constexpr int p1 = FFT_POS<ky, WS>, p2 = FFT_POS<nky, WS>;
-                        const float two = (ky & 1) ? two_odd : 2.0f;
-                        const cf z1 = x[p1];
-                        if constexpr (ky == nky) {
-                            cf m1;
-                            m1.x = __shfl(z1.x, partner, 64);
-                            m1.y = __shfl(z1.y, partner, 64);
-                            x[p1] = cross(z1, m1, two);
-                        } else {
-                            const cf z2 = x[p2];
-                            cf m1, m2;
-                            m1.x = __shfl(z2.x, partner, 64);
-                            m1.y = __shfl(z2.y, partner, 64);
-                            m2.x = __shfl(z1.x, partner, 64);
-                            m2.y = __shfl(z1.y, partner, 64);
-                            x[p1] = cross(z1, m1, two);
-                            x[p2] = cross(z2, m2, two);
-                        }
-                    });
-                }
-                cf t[WS];
-                static_for<0, WS>([&](auto kc) TPIV_LAMBDA_INLINE {
-                    constexpr int ky = decltype(kc)::value;
-                    t[ky] = x[FFT_POS<ky, WS>];
-                });
-                fft_inreg<WS, -1>(t, tw);
-                cf hs[WS / 2 + 1], z[WS / 2];
-                transpose_half<WS, PLANAR>(t, hs, tile, fresh_lane());
-                c2r_inreg<WS>(hs, z);
-                static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
-                    constexpr int x_ = decltype(xc)::value;
-                    crow[x_] = (x_ & 1) ? z[FFT_POS<x_ / 2, WS / 2>].y : z[FFT_POS<x_ / 2, WS / 2>].x;
-                });
-            }
+            inverse_rows<WS, PLANAR, NOSWAP, false>(x, tile, tw, CrossPlain{},
+                                                    [](auto&, int) TPIV_LAMBDA_INLINE { return false; }, crow);      // no filter
             wave_sync();                                  // tile reads done: the next step's staging may use it
 
             if constexpr (WS > 32) {
@@ -354,24 +251,11 @@ static hipError_t launch_ens(const PassParams& p_in, float* acc, int n_cu, hipSt
     return hipGetLastError();
 }
 
-template <int WS>
-static hipError_t launch_ens_ws(const PassParams& p, int mode, float* acc, int n_cu, hipStream_t stream) {
-    switch (mode) {
-        case MODE_PASS1: return launch_ens<WS, MODE_PASS1>(p, acc, n_cu, stream);
-        case MODE_DWS: return launch_ens<WS, MODE_DWS>(p, acc, n_cu, stream);
-        case MODE_CWS: return launch_ens<WS, MODE_CWS>(p, acc, n_cu, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
 // acc [N, ws, ws] += the raw maps of p.batch pairs; p.work_ctr zeroed by the caller (piv_launch.hip: launch_ensemble_add)
 hipError_t launch_xcorr_ens(const PassParams& p, int mode, float* acc, int n_cu, hipStream_t stream) {
-    switch (p.ws) {
-        case 16: return launch_ens_ws<16>(p, mode, acc, n_cu, stream);
-        case 32: return launch_ens_ws<32>(p, mode, acc, n_cu, stream);
-        case 64: return launch_ens_ws<64>(p, mode, acc, n_cu, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return for_ws_mode(p.ws, mode, hipErrorInvalidValue, [&](auto w, auto m) {
+        return launch_ens<decltype(w)::value, decltype(m)::value>(p, acc, n_cu, stream);
+    });
 }
 
 // ---- peak stage on accumulated maps: M = acc / n (one float32 division per cell), then peak_analysis as in production

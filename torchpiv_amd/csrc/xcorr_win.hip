@@ -18,8 +18,9 @@
 //     is constant only up to the rounding of its bilinear samples is NOT empty (as in xcorr_spec.hip).
 // Every 64x64 instance runs the swap-free first transposition: the weighting is a multiply per sample here, so the sign
 // rides on its constants in the DWS instance too.
-// The production instances of xcorr_tile.hpp and the spectral ones of xcorr_spec.hip are not touched: this body is separate.
-#include "xcorr_tile.hpp"
+// inverse_rows, pass_shift, up_sign / sflip and the dispatch come from xcorr_variant.hpp, which also says why the work loop
+// is this unit's own text.
+#include "xcorr_variant.hpp"
 
 namespace tpiv {
 
@@ -83,19 +84,6 @@ __device__ __forceinline__ void xcorr_win_body(const PassParams& p, const WinPar
         g.fidx = (size_t)g.pair * N + g.win;
         return g;
     };
-    auto shift_of = [&](const ItemGeom& g, float& vx, float& vy) TPIV_LAMBDA_INLINE {
-        if constexpr (MODE == MODE_PASS1) {
-            vx = 0.f;
-            vy = 0.f;
-        } else if constexpr (MODE == MODE_CWS) {
-            pred_half_shift_cws_f32(p, g.fidx, vx, vy);
-        } else {
-            double sx, sy;
-            pred_half_shift<MODE>(p, g.fidx, sx, sy);
-            vx = (float)sx;
-            vy = (float)sy;
-        }
-    };
 
     int item = q_take(q_issue());
     if (item >= hi) return;
@@ -109,7 +97,7 @@ __device__ __forceinline__ void xcorr_win_body(const PassParams& p, const WinPar
     {
         const int l0 = fresh_lane();
         gcur = geom_of(item, l0 / WS);
-        shift_of(gcur, vx, vy);
+        pass_shift<MODE>(p, gcur, vx, vy);
         issue_rows<WS, MODE, FAST>(p, gcur, l0 % WS, vx, vy, raw, coff);
     }
 
@@ -123,8 +111,6 @@ __device__ __forceinline__ void xcorr_win_body(const PassParams& p, const WinPar
         const float sy = grp_sum<WS>(gyr), sx = grp_sum<WS>(gxt[r0]);
         inv_sw = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / (sy * sx))));
     }
-    auto up_sign = []() TPIV_LAMBDA_INLINE { return fresh_lane() >= 32 ? 0x80000000u : 0u; };
-    auto sflip = [](float v, unsigned sg) TPIV_LAMBDA_INLINE { return __uint_as_float(__float_as_uint(v) ^ sg); };
 
     for (int nnitem; item < hi; item = nitem, nitem = nnitem) {
         const unsigned q_raw = q_issue();
@@ -137,7 +123,7 @@ __device__ __forceinline__ void xcorr_win_body(const PassParams& p, const WinPar
         const int nit = nitem < hi ? nitem : item;
         const ItemGeom gnext = geom_of(nit, w);
         float nvx, nvy;
-        shift_of(gnext, nvx, nvy);
+        pass_shift<MODE>(p, gnext, nvx, nvy);
 
         cf x[WS];
         float sa, sb;
@@ -212,98 +198,9 @@ __device__ __forceinline__ void xcorr_win_body(const PassParams& p, const WinPar
         transpose_tile<WS, PLANAR, NOSWAP>(x, tile, fresh_lane());
         fft_inreg<WS, 1>(x, tw);
 
-        constexpr bool HALF_INV = PLANAR && (WS == 32 || WS == 64);
         float crow[WS];
-        // 4 P = conj(2A) (2B) of the packed transform Z = A + iB, as xcorr_tile_body forms it: with zk = Z(k) = a + ib and
-        // zm = Z(-k) = c + id,  re = 2 (a d + b c),  im = (c^2 - a^2) + (d^2 - b^2).  two (+-2): the sign the swap-free 64x64
-        // transposition leaves on the odd bins of exactly one of zk, zm (`two_odd` of xcorr_tile_body).
-        auto cross = [&](cf zk, cf zm, float two) TPIV_LAMBDA_INLINE {
-            const float a_ = zk.x, b_ = zk.y, c_ = zm.x, d_ = zm.y;
-            cf pr_;
-            pr_.x = (a_ * d_ + b_ * c_) * two;
-            pr_.y = (c_ * c_ - a_ * a_) + (d_ * d_ - b_ * b_);
-            return pr_;
-        };
-        if constexpr (HALF_INV) {
-            constexpr int M = WS / 2;
-            cf h[M];
-            {
-                const int lane_c = fresh_lane();
-                const int r_c = lane_c % WS;
-                const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
-                const float two_odd = (NOSWAP && (lane_c & 31) != 0) ? -2.0f : 2.0f;
-                cf pc[M + 1];
-                static_for<0, M + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
-                    constexpr int ky = decltype(kc)::value;
-                    constexpr int nky = (WS - ky) % WS;
-                    const cf z2 = x[FFT_POS<nky, WS>];
-                    cf m1;
-                    m1.x = __shfl(z2.x, partner, 64);
-                    m1.y = __shfl(z2.y, partner, 64);
-                    pc[ky] = cross(x[FFT_POS<ky, WS>], m1, (ky & 1) ? two_odd : 2.0f);
-                });
-                const bool odd = r_c > M;
-                const float fs = (r_c == 0 || r_c == M) ? 1.0f : 0.0f;
-                static_for<0, M>([&](auto kc) TPIV_LAMBDA_INLINE {
-                    constexpr int k = decltype(kc)::value;
-                    cf pr_;
-                    pr_.x = __shfl(pc[M - k].x, partner, 64);
-                    pr_.y = __shfl(pc[M - k].y, partner, 64);
-                    const cf sm{pc[k].x + pr_.x, pc[k].y - pr_.y};
-                    const cf tt = twmul<k, WS, -1>(cf{pc[k].x - pr_.x, pc[k].y + pr_.y});
-                    h[k].x = odd ? tt.x : __builtin_fmaf(-fs, tt.y, sm.x);
-                    h[k].y = odd ? tt.y : __builtin_fmaf(fs, tt.x, sm.y);
-                });
-            }
-            fft_inreg<M, -1>(h, tw);
-            cf hs[M + 1], z[M];
-            transpose_half_pairs<WS, PLANAR>(h, hs, tile, fresh_lane());
-            c2r_inreg<WS>(hs, z);
-            static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
-                constexpr int x_ = decltype(xc)::value;
-                const float c_ = (x_ & 1) ? z[FFT_POS<x_ / 2, M>].y : z[FFT_POS<x_ / 2, M>].x;
-                crow[x_] = zero ? 0.0f : c_;
-            });
-        } else {
-            cf t[WS];
-            {
-                const int lane_c = fresh_lane();
-                const int r_c = lane_c % WS;
-                const int partner = (lane_c - r_c) + ((WS - r_c) % WS);
-                const float two_odd = (NOSWAP && (lane_c & 31) != 0) ? -2.0f : 2.0f;
-                static_for<0, WS / 2 + 1>([&](auto kc) TPIV_LAMBDA_INLINE {
-                    constexpr int ky = decltype(kc)::value;
-                    constexpr int nky = (WS - ky) % WS;
-                    constexpr int p1 = FFT_POS<ky, WS>, p2 = FFT_POS<nky, WS>;
-                    const float two = (ky & 1) ? two_odd : 2.0f;
-                    const cf z1 = x[p1];
-                    if constexpr (ky == nky) {
-                        cf m1;
-                        m1.x = __shfl(z1.x, partner, 64);
-                        m1.y = __shfl(z1.y, partner, 64);
-                        t[ky] = cross(z1, m1, two);
-                    } else {
-                        const cf z2 = x[p2];
-                        cf m1, m2;
-                        m1.x = __shfl(z2.x, partner, 64);
-                        m1.y = __shfl(z2.y, partner, 64);
-                        m2.x = __shfl(z1.x, partner, 64);
-                        m2.y = __shfl(z1.y, partner, 64);
-                        t[ky] = cross(z1, m1, two);
-                        t[nky] = cross(z2, m2, two);
-                    }
-                });
-            }
-            fft_inreg<WS, -1>(t, tw);
-            cf hs[WS / 2 + 1], z[WS / 2];
-            transpose_half<WS, PLANAR>(t, hs, tile, fresh_lane());
-            c2r_inreg<WS>(hs, z);
-            static_for<0, WS>([&](auto xc) TPIV_LAMBDA_INLINE {
-                constexpr int x_ = decltype(xc)::value;
-                const float c_ = (x_ & 1) ? z[FFT_POS<x_ / 2, WS / 2>].y : z[FFT_POS<x_ / 2, WS / 2>].x;
-                crow[x_] = zero ? 0.0f : c_;
-            });
-        }
+        inverse_rows<WS, PLANAR, NOSWAP, true>(x, tile, tw, CrossPlain{},
+                                               [&](auto&, int) TPIV_LAMBDA_INLINE { return zero; }, crow);      // no filter
         wave_sync();                                  // tile reads done: it becomes the map
 
         if constexpr (WS > 32) {
@@ -353,45 +250,16 @@ struct WinCfg {
     static constexpr bool PLANAR = WS == 16 ? false : (WS == 32 ? true : MODE != MODE_CWS);
 };
 
-int win_occ(int ws, int mode) {
-    switch (ws) {
-        case 16: return mode == MODE_CWS ? WinCfg<16, MODE_CWS>::OCC : (mode == MODE_DWS ? WinCfg<16, MODE_DWS>::OCC : WinCfg<16, MODE_PASS1>::OCC);
-        case 32: return mode == MODE_CWS ? WinCfg<32, MODE_CWS>::OCC : (mode == MODE_DWS ? WinCfg<32, MODE_DWS>::OCC : WinCfg<32, MODE_PASS1>::OCC);
-        case 64: return mode == MODE_CWS ? WinCfg<64, MODE_CWS>::OCC : (mode == MODE_DWS ? WinCfg<64, MODE_DWS>::OCC : WinCfg<64, MODE_PASS1>::OCC);
-        default: return 0;
-    }
-}
-bool win_planar(int ws, int mode) { return ws == 32 || (ws == 64 && mode != MODE_CWS); }
-
-template <int WS, int MODE>
-static hipError_t launch_win(const PassParams& p_in, const WinParams& s, int n_cu, hipStream_t stream) {
-    using C = WinCfg<WS, MODE>;
-    static_assert(C::PLANAR == (WS == 32 || (WS == 64 && MODE != MODE_CWS)), "win_planar names the layout");
-    PassParams p = p_in;
-    const unsigned blocks = tile_grid<WS>(p, n_cu);
-    if (blocks == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((xcorr_win_kernel<WS, MODE, C::OCC, C::PLANAR>), dim3(blocks), dim3(64), 0, stream, p, s);
-    return hipGetLastError();
-}
-
-template <int WS>
-static hipError_t launch_win_ws(const PassParams& p, int mode, const WinParams& s, int n_cu, hipStream_t stream) {
-    switch (mode) {
-        case MODE_PASS1: return launch_win<WS, MODE_PASS1>(p, s, n_cu, stream);
-        case MODE_DWS: return launch_win<WS, MODE_DWS>(p, s, n_cu, stream);
-        case MODE_CWS: return launch_win<WS, MODE_CWS>(p, s, n_cu, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
+int win_occ(int ws, int mode) { return cfg_occ<WinCfg>(ws, mode); }
+bool win_planar(int ws, int mode) { return cfg_planar<WinCfg>(ws, mode); }
 
 // one weighted pass up to its peak records; p.work_ctr zeroed by the caller (piv_launch.hip: launch_xcorr_win)
 hipError_t launch_xcorr_win_tile(const PassParams& p, int mode, const WinParams& s, int n_cu, hipStream_t stream) {
-    switch (p.ws) {
-        case 16: return launch_win_ws<16>(p, mode, s, n_cu, stream);
-        case 32: return launch_win_ws<32>(p, mode, s, n_cu, stream);
-        case 64: return launch_win_ws<64>(p, mode, s, n_cu, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return for_ws_mode(p.ws, mode, hipErrorInvalidValue, [&](auto w, auto m) {
+        constexpr int WS = decltype(w)::value, MODE = decltype(m)::value;
+        using C = WinCfg<WS, MODE>;
+        return launch_variant_tile<WS>(xcorr_win_kernel<WS, MODE, C::OCC, C::PLANAR>, p, s, n_cu, stream);
+    });
 }
 
 }  // namespace tpiv
