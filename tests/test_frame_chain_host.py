@@ -61,10 +61,12 @@ def stand_ins(monkeypatch):
 
 
 def _object(prefilter=None, equalize=None, mask=None):
-    from torchpiv_amd import backend, engine
+    from torchpiv_amd import backend, engine, options
     piv = backend.ResidentPIV.__new__(backend.ResidentPIV)
-    piv._init_state(CPU, range(N), None, 32, 16, 1, "CWS", 1, 1.0, 2.0, "exact", 1.2, 3, None, None,
-                    engine.prefilter_arg(prefilter), None, engine.equalize_arg(equalize), engine.mask_arg(mask))
+    run = dict(wind_size=32, overlap=16, multipass=1, multipass_mode="CWS", dt=1, scale=1.0, multipass_scale=2.0,
+               precision="exact", validation_ratio=1.2, validation_window=3)
+    piv._init_state(CPU, range(N), None, run, options.Options(prefilter=engine.prefilter_arg(prefilter),
+                                                              equalize=engine.equalize_arg(equalize), mask=engine.mask_arg(mask)))
     return piv
 
 

@@ -380,3 +380,62 @@ def test_sharded_generator_rehearsal_two_ranks_one_gpu():
     assert line["config"]["gathered_on_rank0"] == line["config"]["yielded_total"] > 0
     assert line["host"]["host_cpu_s_per_pair"] > 0 and line["host"]["budget_per_rank"]["ranks_on_node"] == 2
     assert sum(rk["post_validation"]["pairs"] for rk in line["distributed"]["ranks"]) == 2 * 16 * 4
+
+
+# (subject: the setter called, other: the feature the plan already has, tpiv_last_error's text) -- what the setters of the
+# C ABI refuse to combine
+REFUSED_PAIRS = [
+    ("uncertainty", "ensemble", "uncertainty= does not combine with ensemble correlation"),
+    ("uncertainty", "correlation", "uncertainty= does not combine with correlation="),
+    ("uncertainty", "weighting", "uncertainty= does not combine with weighting= (its estimator sums over a top-hat window)"),
+    ("deform", "ensemble", "deform= does not combine with ensemble correlation"),
+    ("deform", "correlation", "deform= does not combine with correlation="),
+    ("correlation", "uncertainty", "correlation= does not combine with uncertainty="),
+    ("correlation", "deform", "correlation= does not combine with deform="),
+    ("correlation", "ensemble", "correlation= does not combine with ensemble correlation"),
+    ("correlation", "weighting", "correlation= does not combine with weighting="),
+    ("weighting", "uncertainty", "weighting= does not combine with uncertainty= (its estimator sums over a top-hat window)"),
+    ("weighting", "ensemble", "weighting= does not combine with ensemble correlation"),
+    ("weighting", "correlation", "weighting= does not combine with correlation="),
+    ("ensemble", "uncertainty", "ensemble correlation does not combine with uncertainty="),
+    ("ensemble", "deform", "ensemble correlation does not combine with deform="),
+    ("ensemble", "correlation", "ensemble correlation does not combine with correlation="),
+    ("ensemble", "weighting", "ensemble correlation does not combine with weighting="),
+    ("ensemble", "pair_masks", "ensemble correlation does not combine with per-pair masks"),
+    ("pair_masks", "ensemble", "per-pair masks do not combine with ensemble correlation"),
+]
+
+
+@pytest.mark.gpu
+def test_plan_setters_refuse_what_does_not_combine():
+    """Every ordered pair of features a plan refuses, at the C ABI: with the other feature switched on the way callers
+    switch it on, the subject's setter returns TPIV_EINVAL with its message, and the plan still runs a pair.  The smallest
+    plan all six features accept: 64 x 64 frames, 16 x 16 windows at overlap 8, one pass, one pair."""
+    from torchpiv_amd import _lib, engine, synth
+    L, (H, W, ws, ov) = _lib.lib, (64, 64, 16, 8)
+    a, b = (t.cuda() for t in synth.make_pair(H, W, 3, kind="wavy", noise=1.0))
+    on = {"uncertainty": {"uncertainty": "cs"}, "deform": {"deform": 1}, "ensemble": {"ensemble": True},
+          "correlation": {"correlation": "rpc"}, "weighting": {"weighting": "gaussian"}, "pair_masks": {}}
+    ctab = engine.correlation_tables(engine.correlation_arg("rpc"), [ws])
+    wtab = engine.weighting_tables(engine.weighting_arg("gaussian"), [ws])
+    setters = {"uncertainty": lambda h: L.tpiv_plan_set_uncertainty(h, 1, 3),
+               "deform": lambda h: L.tpiv_plan_set_deform(h, 1, _lib.DEWARP_LINEAR, 1, None),
+               "correlation": lambda h: L.tpiv_plan_set_correlation(h, _lib.CORR_RPC, 2.8, 2.8, 2.0 ** -10, ctab.ctypes.data, ctab.size),
+               "weighting": lambda h: L.tpiv_plan_set_weighting(h, _lib.WEIGHT_GAUSSIAN, 0.4, 0.4, wtab.ctypes.data, wtab.size),
+               "ensemble": lambda h: L.tpiv_plan_set_ensemble(h, 1),
+               "pair_masks": lambda h: L.tpiv_plan_set_pair_masks(h, 1)}
+    for subject, other, message in REFUSED_PAIRS:
+        plan = engine.Plan(H, W, ws, ov, n_pass=1, max_batch=1, device="cuda:0", precision="fast", **on[other])
+        if other == "pair_masks":
+            plan.run_masked(a, b, torch.zeros(1, H, W, dtype=torch.uint8, device="cuda:0"))
+        assert setters[subject](plan._h) == _lib.EINVAL, (subject, other)
+        assert L.tpiv_last_error().decode() == message
+        u, v, inv = plan.run(a, b)
+        assert bool(torch.isfinite(u).all()) and bool(torch.isfinite(v).all()), (subject, other)
+        plan.close()
+    # and the pair that does combine still switches on, in either order
+    plan = engine.Plan(H, W, ws, ov, n_pass=1, max_batch=1, device="cuda:0", precision="fast", weighting="gaussian", deform=1)
+    assert setters["deform"](plan._h) == _lib.OK and setters["weighting"](plan._h) == _lib.OK
+    u, v, inv = plan.run(a, b)
+    assert bool(torch.isfinite(u).all()) and bool(torch.isfinite(v).all())
+    plan.close()

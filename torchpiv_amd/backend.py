@@ -24,10 +24,11 @@ from typing import Generator
 import numpy as np
 import torch
 
-from . import engine
+from . import engine, options
 from ._lib import PRECISIONS
 from ._qhull import PipelineOwner, blas_one_thread, qhull_fill, qhull_fill_many      # numpy/scipy-only module: the fill worker processes import nothing else
 from .io import PIVDataset, StagedBatches, ToTensor, natural_keys, slot_bytes  # noqa: F401  (re-exported like the reference)
+from .options import background_arg as _background_arg
 
 
 # ----------------------------------------------------------------------------------------
@@ -325,38 +326,6 @@ def free_cuda_memory():
 # ----------------------------------------------------------------------------------------
 # the generator API (B:824-903)
 # ----------------------------------------------------------------------------------------
-def _background_arg(background, shape=None):
-    """The background= argument of OfflinePIV / ResidentPIV, checked: None, "min", or a pair of uint8 images [H, W] as
-    torch tensors (one image given for both frames of a pair, or a pair (bg_a, bg_b); numpy arrays or tensors).  shape:
-    the frame shape the images must have (None: not known, e.g. an empty folder).  Anything else raises ValueError."""
-    if background is None:
-        return None
-    if isinstance(background, str):
-        if background != "min":
-            raise ValueError(f"background: None, 'min', a uint8 image [H, W] or a pair of them, got {background!r}")
-        return "min"
-    imgs = list(background) if isinstance(background, (tuple, list)) else [background, background]
-    if len(imgs) != 2:
-        raise ValueError(f"background: a pair (bg_a, bg_b) holds two images, got {len(imgs)}")
-    out = []
-    for im in imgs:
-        if isinstance(im, np.ndarray):
-            if im.dtype != np.uint8:
-                raise ValueError(f"background: uint8 images, got {im.dtype}")
-            im = torch.from_numpy(np.ascontiguousarray(im))
-        elif not isinstance(im, torch.Tensor):
-            raise ValueError(f"background: a uint8 numpy array or tensor [H, W], got {type(im).__name__}")
-        elif im.dtype != torch.uint8:
-            raise ValueError(f"background: uint8 images, got {im.dtype}")
-        if im.dim() != 2:
-            raise ValueError(f"background: images [H, W], got shape {tuple(im.shape)}")
-        out.append(im)
-    if out[0].shape != out[1].shape or (shape is not None and tuple(out[0].shape) != tuple(shape)):
-        raise ValueError(f"background: images of the frame shape {None if shape is None else tuple(shape)}, got "
-                         f"{tuple(out[0].shape)} and {tuple(out[1].shape)}")
-    return out
-
-
 class OfflinePIV:
     """for x, y, u, v in OfflinePIV(folder, device, file_fmt, wind_size, overlap, ...)(): ...
 
@@ -459,21 +428,17 @@ class OfflinePIV:
         # The form {"stack": masks [N, H, W]} is ResidentPIV's.
         if precision not in PRECISIONS:
             raise KeyError(precision)
-        correlation = self._correlation_arg(correlation, wind_size, overlap, multipass, multipass_scale, multipass_mode,
-                                            uncertainty, deform)
-        weighting = self._weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode,
-                                        uncertainty, correlation)
-        dynamic_mask = engine.dynamic_mask_arg(dynamic_mask, mask, stack=False)
+        run = dict(wind_size=wind_size, overlap=overlap, multipass=multipass, multipass_mode=multipass_mode, dt=dt,
+                   scale=scale, multipass_scale=multipass_scale, precision=precision, validation_ratio=validation_ratio,
+                   validation_window=validation_window)
+        opts = options.parse_options(run, stack=False, background=background, outlier=outlier, prefilter=prefilter,
+                                     depth=depth, equalize=equalize, mask=mask, dewarp=dewarp, uncertainty=uncertainty,
+                                     deform=deform, correlation=correlation, weighting=weighting, dynamic_mask=dynamic_mask)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
-        depth = engine.depth_arg(depth)
-        dataset = PIVDataset(folder, file_fmt, folder_mode, deep=depth is not None,
-                             transform=ToTensor(dtype=torch.uint8 if depth is None else torch.uint16))
+        dataset = PIVDataset(folder, file_fmt, folder_mode, deep=opts.depth is not None,
+                             transform=ToTensor(dtype=torch.uint8 if opts.depth is None else torch.uint16))
         iter_function = IterModMap.functions[multipass_mode]            # KeyError like B:850
-        self._init_state(device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
-                         multipass_scale, precision, validation_ratio, validation_window, _background_arg(background),
-                         engine.outlier_arg(outlier), engine.prefilter_arg(prefilter), depth, engine.equalize_arg(equalize),
-                         engine.mask_arg(mask), engine.dewarp_arg(dewarp), engine.uncertainty_arg(uncertainty),
-                         engine.deform_arg(deform), correlation, weighting, dynamic_mask)
+        self._init_state(device, dataset, iter_function, run, opts)
         if not self:
             return
         if self._mask is not None:
@@ -484,31 +449,24 @@ class OfflinePIV:
             _background_arg(background, self.frame_shape())
         _require_gpu(self._device)
 
-    def _init_state(self, device, dataset, iter_function, wind_size, overlap, multipass, multipass_mode, dt, scale,
-                    multipass_scale, precision, validation_ratio, validation_window, bg_arg, outlier, prefilter=None, depth=None,
-                    equalize=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None,
-                    dynamic_mask=None):
-        """Every attribute of an object, for both constructors (which check their arguments, each in its own order): the
-        run parameters as checked (bg_arg: _background_arg's, outlier: engine.outlier_arg's, prefilter:
-        engine.prefilter_arg's, depth: engine.depth_arg's, equalize: engine.equalize_arg's, mask: engine.mask_arg's, dewarp: engine.dewarp_arg's,
-        uncertainty: engine.uncertainty_arg's) and the state that the methods build up, empty."""
+    def _init_state(self, device, dataset, iter_function, run, opts):
+        """Every attribute of an object, for both constructors: the run parameters (run: a dict of wind_size, overlap,
+        multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio and validation_window), the
+        twelve keywords as options.parse_options checked them (opts: an options.Options record), and the state that the methods
+        build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
-        self._wind_size, self._overlap, self._dt = wind_size, overlap, dt
-        self._iter, self._iter_scale, self._scale = multipass, multipass_scale, scale
-        self._mode, self._precision = multipass_mode, precision
-        self._val_ratio, self._val_win = float(validation_ratio), int(validation_window)
-        self._bg_arg = bg_arg
-        self._outlier = outlier
-        self._prefilter = prefilter
-        self._depth = depth
-        self._equalize = equalize
-        self._mask = mask
-        self._dewarp = dewarp
-        self._uncertainty = uncertainty
-        self._deform = deform            # deform=: engine.deform_arg's, handed to every plan
-        self._correlation = correlation  # correlation=: engine.correlation_arg's, handed to every plan but ensemble()'s
-        self._weighting = weighting      # weighting=: engine.weighting_arg's, handed to every plan but ensemble()'s
-        self._dynmask = dynamic_mask     # dynamic_mask=: engine.dynamic_mask_arg's (threshold, pixels and fill included)
+        self._wind_size, self._overlap, self._dt = run["wind_size"], run["overlap"], run["dt"]
+        self._iter, self._iter_scale, self._scale = run["multipass"], run["multipass_scale"], run["scale"]
+        self._mode, self._precision = run["multipass_mode"], run["precision"]
+        self._val_ratio, self._val_win = float(run["validation_ratio"]), int(run["validation_window"])
+        self._bg_arg = opts.background
+        self._outlier, self._prefilter, self._equalize = opts.outlier, opts.prefilter, opts.equalize
+        self._mask, self._dewarp, self._uncertainty = opts.mask, opts.dewarp, opts.uncertainty
+        self._depth = depth = opts.depth
+        self._deform = opts.deform            # handed to every plan
+        self._correlation = opts.correlation  # handed to every plan but ensemble()'s
+        self._weighting = opts.weighting      # handed to every plan but ensemble()'s
+        self._dynmask = opts.dynamic_mask     # (threshold, pixels and fill included)
         self._dm_masks = None            # dynamic_mask=: the masks of a launch, uint8 [batch, H, W], reused
         self._dm_work = None             # dynamic_mask=: the segmentation's workspace, kept from launch to launch
         self._dm_frames = None           # dynamic_mask=: a caller's frames minus the background, uint8 [2, batch, H, W], reused
@@ -536,24 +494,6 @@ class OfflinePIV:
     def __len__(self) -> int:
         return len(self._dataset)
 
-    @staticmethod
-    def _correlation_arg(correlation, wind_size, overlap, multipass, multipass_scale, multipass_mode, uncertainty, deform):
-        """correlation= of either constructor, checked with what it refuses (no GPU involved): engine.correlation_arg's."""
-        par = engine.correlation_arg(correlation)
-        if par is not None:
-            sizes = [w for w, _ in engine.pass_sizes(wind_size, overlap, multipass, multipass_scale)]
-            engine.correlation_check(sizes, multipass_mode, engine.uncertainty_arg(uncertainty), engine.deform_arg(deform))
-        return par
-
-    @staticmethod
-    def _weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode, uncertainty, correlation):
-        """weighting= of either constructor, checked with what it refuses (no GPU involved): engine.weighting_arg's."""
-        par = engine.weighting_arg(weighting)
-        if par is not None:
-            sizes = [w for w, _ in engine.pass_sizes(wind_size, overlap, multipass, multipass_scale)]
-            engine.weighting_check(sizes, multipass_mode, engine.uncertainty_arg(uncertainty), False, correlation)
-        return par
-
     def _first_decodable(self, idx):
         """(pair id, frame shape) of the first pair of `idx` that decodes, None without one."""
         for i in idx:
@@ -567,12 +507,16 @@ class OfflinePIV:
         first = self._first_decodable(range(len(self._dataset)))
         return None if first is None else first[1]
 
-    def _new_plan(self, H, W, max_batch):
+    def _make_plan(self, H, W, max_batch, **features):
+        """A plan of this object's passes, outlier= and mask=, with the features the caller names."""
         return engine.Plan(H, W, int(self._wind_size), int(self._overlap), n_pass=max(1, int(self._iter)),
                            mode=self._mode, pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio,
                            val_win=self._val_win, device=self._device, precision=self._precision, outlier=self._outlier,
-                           mask=self._mask, uncertainty=self._uncertainty, deform=self._deform,
-                           correlation=self._correlation, weighting=self._weighting)
+                           mask=self._mask, **features)
+
+    def _new_plan(self, H, W, max_batch):
+        return self._make_plan(H, W, max_batch, uncertainty=self._uncertainty, deform=self._deform,
+                               correlation=self._correlation, weighting=self._weighting)
 
     def _get_plan(self, H, W, max_batch=1):
         if (self._plan is None or (self._plan.H, self._plan.W) != (H, W)
@@ -664,9 +608,7 @@ class OfflinePIV:
 
     def _mask_shape(self, shape):
         """ValueError unless the mask image has the frame shape (None: not known, e.g. an undecodable folder)."""
-        got = tuple(self._mask["image"].shape)
-        if shape is not None and got != tuple(shape):
-            raise ValueError(f"mask of shape {got} for frames of shape {tuple(shape)}")
+        options.mask_shape(self._mask, shape)
 
     def _zeroes_pixels(self):
         if self._dynmask is not None:
@@ -783,8 +725,7 @@ class OfflinePIV:
 
     def _dewarp_shape(self, shape):
         """ValueError unless a map given as coordinate arrays has the frame shape (None: not known)."""
-        if shape is not None and "map" in self._dewarp and tuple(self._dewarp["map"][0].shape) != tuple(shape):
-            raise ValueError(f"dewarp map of shape {tuple(self._dewarp['map'][0].shape)} for frames of shape {tuple(shape)}")
+        options.dewarp_shape(self._dewarp, shape)
 
     def _dewarp_map(self, shape, device):
         """The Q8 map of dewarp= for frames of `shape` on `device` (int32 [H, W, 2]): built on the host, checked and
@@ -940,21 +881,13 @@ class OfflinePIV:
         if plan is None or (plan.H, plan.W) != (H, W) or plan.max_batch < max_batch:
             if plan is not None:
                 plan.close()
-            plan = self._ens_plan = engine.Plan(
-                H, W, int(self._wind_size), int(self._overlap), n_pass=max(1, int(self._iter)), mode=self._mode,
-                pass_scale=self._iter_scale, max_batch=max_batch, val_ratio=self._val_ratio, val_win=self._val_win,
-                device=self._device, precision=self._precision, outlier=self._outlier, mask=self._mask, ensemble=True)
+            plan = self._ens_plan = self._make_plan(H, W, max_batch, ensemble=True)
         return plan
 
     def _ensemble_check(self):
-        if self._dynmask is not None:
-            raise ValueError("ensemble correlation does not combine with dynamic_mask=")
-        if self._correlation is not None:
-            raise ValueError("ensemble correlation does not combine with correlation=")
-        if self._weighting is not None:
-            raise ValueError("ensemble correlation does not combine with weighting=")
-        engine.ensemble_check([w for w, _ in engine.pass_sizes(self._wind_size, self._overlap, self._iter, self._iter_scale)],
-                              self._uncertainty, self._deform)
+        options.refuse("ensemble", dict(dynamic_mask=self._dynmask, correlation=self._correlation, weighting=self._weighting,
+                                        uncertainty=self._uncertainty, deform=self._deform),
+                       [w for w, _ in engine.pass_sizes(self._wind_size, self._overlap, self._iter, self._iter_scale)])
 
     def _frame_batches(self, idx, batch_size, H, W):
         """The prepared frames of the pairs idx, batch_size at a time, as (A, B) uint8 [n, H, W] on the device: read through
@@ -1577,33 +1510,14 @@ class ResidentPIV(OfflinePIV):
                              "ResidentPIV: with depth=, two uint16 tensors [n, H, W] of one shape")
         if precision not in PRECISIONS:
             raise KeyError(precision)
-        bg_arg = _background_arg(background, frames_a.shape[1:])
-        outlier = engine.outlier_arg(outlier)
-        prefilter = engine.prefilter_arg(prefilter)
-        equalize = engine.equalize_arg(equalize)
-        mask = engine.mask_arg(mask)
-        if mask is not None and tuple(mask["image"].shape) != tuple(frames_a.shape[1:]):
-            raise ValueError(f"mask of shape {tuple(mask['image'].shape)} for frames of shape {tuple(frames_a.shape[1:])}")
-        uncertainty = engine.uncertainty_arg(uncertainty)
-        deform = engine.deform_arg(deform)
-        correlation = self._correlation_arg(correlation, wind_size, overlap, multipass, multipass_scale, multipass_mode,
-                                            uncertainty, deform)
-        weighting = self._weighting_arg(weighting, wind_size, overlap, multipass, multipass_scale, multipass_mode,
-                                        uncertainty, correlation)
-        dynamic_mask = engine.dynamic_mask_arg(dynamic_mask, mask)
-        if dynamic_mask is not None and "stack" in dynamic_mask \
-                and tuple(dynamic_mask["stack"].shape) != tuple(frames_a.shape):
-            raise ValueError(f"dynamic_mask: a stack of shape {tuple(dynamic_mask['stack'].shape)} for frames of shape "
-                             f"{tuple(frames_a.shape)}")
-        dewarp = engine.dewarp_arg(dewarp)
-        if dewarp is not None and "map" in dewarp and tuple(dewarp["map"][0].shape) != tuple(frames_a.shape[1:]):
-            raise ValueError(f"dewarp map of shape {tuple(dewarp['map'][0].shape)} for frames of shape "
-                             f"{tuple(frames_a.shape[1:])}")
+        run = dict(wind_size=wind_size, overlap=overlap, multipass=multipass, multipass_mode=multipass_mode, dt=dt,
+                   scale=scale, multipass_scale=multipass_scale, precision=precision, validation_ratio=validation_ratio,
+                   validation_window=validation_window)
+        opts = options.parse_options(run, frames_a.shape, background=background, outlier=outlier, prefilter=prefilter,
+                                     depth=depth, equalize=equalize, mask=mask, dewarp=dewarp, uncertainty=uncertainty,
+                                     deform=deform, correlation=correlation, weighting=weighting, dynamic_mask=dynamic_mask)
         device = _require_gpu(frames_a.device)
-        self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], wind_size, overlap,
-                         multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio,
-                         validation_window, bg_arg, outlier, prefilter, depth, equalize, mask, dewarp,
-                         uncertainty, deform, correlation, weighting, dynamic_mask)
+        self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], run, opts)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
     def frame_shape(self):

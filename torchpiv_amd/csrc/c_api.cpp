@@ -348,6 +348,39 @@ int check_plan_device(const tpiv_plan* plan) {
     return TPIV_OK;
 }
 
+// The feature pairs a plan refuses: every setter that switches a feature on walks its rows, in this order, against what the
+// plan already has (refuse_combination).  The guard of direct users of the C ABI; the Python layer refuses the same pairs
+// before it gets here (torchpiv_amd/options.py: EXCLUSIONS).
+enum Feature { F_PAIR_MASKS, F_UNCERTAINTY, F_DEFORM, F_CORRELATION, F_WEIGHTING, F_ENSEMBLE };
+#define HAS(field) [](const tpiv_plan* p) { return bool(p->field); }
+const struct Refusal { Feature subject; bool (*on)(const tpiv_plan*); const char* msg; } REFUSALS[] = {
+    {F_PAIR_MASKS, HAS(ens_on), "per-pair masks do not combine with ensemble correlation"},
+    {F_UNCERTAINTY, HAS(ens_on), "uncertainty= does not combine with ensemble correlation"},
+    {F_UNCERTAINTY, HAS(corr_kind), "uncertainty= does not combine with correlation="},
+    {F_UNCERTAINTY, HAS(wt_kind), "uncertainty= does not combine with weighting= (its estimator sums over a top-hat window)"},
+    {F_DEFORM, HAS(ens_on), "deform= does not combine with ensemble correlation"},
+    {F_DEFORM, HAS(corr_kind), "deform= does not combine with correlation="},
+    {F_CORRELATION, HAS(unc_kind), "correlation= does not combine with uncertainty="},
+    {F_CORRELATION, HAS(def_iters), "correlation= does not combine with deform="},
+    {F_CORRELATION, HAS(ens_on), "correlation= does not combine with ensemble correlation"},
+    {F_CORRELATION, HAS(wt_kind), "correlation= does not combine with weighting="},
+    {F_WEIGHTING, HAS(unc_kind), "weighting= does not combine with uncertainty= (its estimator sums over a top-hat window)"},
+    {F_WEIGHTING, HAS(ens_on), "weighting= does not combine with ensemble correlation"},
+    {F_WEIGHTING, HAS(corr_kind), "weighting= does not combine with correlation="},
+    {F_ENSEMBLE, HAS(unc_kind), "ensemble correlation does not combine with uncertainty="},
+    {F_ENSEMBLE, HAS(def_iters), "ensemble correlation does not combine with deform="},
+    {F_ENSEMBLE, HAS(corr_kind), "ensemble correlation does not combine with correlation="},
+    {F_ENSEMBLE, HAS(wt_kind), "ensemble correlation does not combine with weighting="},
+    {F_ENSEMBLE, HAS(pair_on), "ensemble correlation does not combine with per-pair masks"},
+};
+#undef HAS
+
+int refuse_combination(const tpiv_plan* plan, Feature subject) {
+    for (const Refusal& r : REFUSALS)
+        if (r.subject == subject && r.on(plan)) return fail(TPIV_EINVAL, r.msg);
+    return TPIV_OK;
+}
+
 // band of one operator row: PRED_BW taps around the largest entry (clipped to the matrix); returns
 // the largest magnitude left outside so that the caller can verify the truncation is harmless
 constexpr int PRED_BW = 65;
@@ -1095,7 +1128,7 @@ int tpiv_plan_set_pair_masks(tpiv_plan* plan, int on) {
         plan->pair_on = false;
         return TPIV_OK;
     }
-    if (plan->ens_on) return fail(TPIV_EINVAL, "per-pair masks do not combine with ensemble correlation");
+    if (int rc = refuse_combination(plan, F_PAIR_MASKS)) return rc;
     if (int rc = check_plan_device(plan)) return rc;
     for (const PassGeo& g : plan->geo)
         if (int rc = check_mask_window(plan->H, plan->W, g.ws, g.ov)) return rc;
@@ -1182,9 +1215,7 @@ int tpiv_plan_set_uncertainty(tpiv_plan* plan, int kind, int radius) {
         plan->unc_kind = 0;
         return TPIV_OK;
     }
-    if (plan->ens_on) return fail(TPIV_EINVAL, "uncertainty= does not combine with ensemble correlation");
-    if (plan->corr_kind) return fail(TPIV_EINVAL, "uncertainty= does not combine with correlation=");
-    if (plan->wt_kind) return fail(TPIV_EINVAL, "uncertainty= does not combine with weighting= (its estimator sums over a top-hat window)");
+    if (int rc = refuse_combination(plan, F_UNCERTAINTY)) return rc;
     const PassGeo& g = plan->geo[plan->n_pass - 1];
     if (int rc = check_uncertainty(plan->H, plan->W, g.ws, g.ov, radius)) return rc;
     if (!plan->unc_su) {                             // first time on: the two fields (kept until the plan is destroyed)
@@ -1304,8 +1335,7 @@ int tpiv_plan_set_deform(tpiv_plan* plan, int iterations, int interp, int smooth
         plan->def_iters = 0;
         return TPIV_OK;
     }
-    if (plan->ens_on) return fail(TPIV_EINVAL, "deform= does not combine with ensemble correlation");
-    if (plan->corr_kind) return fail(TPIV_EINVAL, "deform= does not combine with correlation=");
+    if (int rc = refuse_combination(plan, F_DEFORM)) return rc;
     if (interp != TPIV_DEWARP_LINEAR && interp != TPIV_DEWARP_CUBIC) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: unknown interp");
     if (interp == TPIV_DEWARP_CUBIC && !table) return fail(TPIV_EINVAL, "tpiv_plan_set_deform: the cubic interpolation needs its table");
     const PassGeo& g = plan->geo[plan->n_pass - 1];
@@ -1615,10 +1645,7 @@ int tpiv_plan_set_correlation(tpiv_plan* plan, int kind, double dx, double dy, d
         return TPIV_OK;
     }
     if (int rc = check_correlation("tpiv_plan_set_correlation", kind, dx, dy, floor)) return rc;
-    if (plan->unc_kind) return fail(TPIV_EINVAL, "correlation= does not combine with uncertainty=");
-    if (plan->def_iters) return fail(TPIV_EINVAL, "correlation= does not combine with deform=");
-    if (plan->ens_on) return fail(TPIV_EINVAL, "correlation= does not combine with ensemble correlation");
-    if (plan->wt_kind) return fail(TPIV_EINVAL, "correlation= does not combine with weighting=");
+    if (int rc = refuse_combination(plan, F_CORRELATION)) return rc;
     size_t need = 0;
     for (const PassGeo& g : plan->geo) {
         if (!tpiv::spec_size(g.ws))
@@ -1647,9 +1674,7 @@ int tpiv_plan_set_weighting(tpiv_plan* plan, int kind, double sigma_x, double si
         return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: kind must be TPIV_WEIGHT_NONE, TPIV_WEIGHT_UNIFORM or TPIV_WEIGHT_GAUSSIAN");
     if (kind == TPIV_WEIGHT_GAUSSIAN && (!(sigma_x >= 0.2 && sigma_x <= 4.0) || !(sigma_y >= 0.2 && sigma_y <= 4.0)))
         return fail(TPIV_EINVAL, "tpiv_plan_set_weighting: sigma must be in 0.2..4 (relative to the half window)");
-    if (plan->unc_kind) return fail(TPIV_EINVAL, "weighting= does not combine with uncertainty= (its estimator sums over a top-hat window)");
-    if (plan->ens_on) return fail(TPIV_EINVAL, "weighting= does not combine with ensemble correlation");
-    if (plan->corr_kind) return fail(TPIV_EINVAL, "weighting= does not combine with correlation=");
+    if (int rc = refuse_combination(plan, F_WEIGHTING)) return rc;
     size_t need = 0;
     for (const PassGeo& g : plan->geo) {
         if (!tpiv::win_size(g.ws))
@@ -1761,11 +1786,7 @@ int tpiv_plan_set_ensemble(tpiv_plan* plan, int on) {
         plan->ens_pass = plan->ens_done = -1;
         return TPIV_OK;
     }
-    if (plan->unc_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with uncertainty=");
-    if (plan->def_iters) return fail(TPIV_EINVAL, "ensemble correlation does not combine with deform=");
-    if (plan->corr_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with correlation=");
-    if (plan->wt_kind) return fail(TPIV_EINVAL, "ensemble correlation does not combine with weighting=");
-    if (plan->pair_on) return fail(TPIV_EINVAL, "ensemble correlation does not combine with per-pair masks");
+    if (int rc = refuse_combination(plan, F_ENSEMBLE)) return rc;
     size_t cells = 0, fine = 0;
     for (const PassGeo& g : plan->geo) {
         if (!tpiv::ensemble_size(g.ws))

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import ITER_MODES, MODES, PRECISIONS, check, lib
+from .options import *  # noqa: F401,F403  (the keyword parsers, their constants and checks live there; engine.X keeps working)
 
 
 def _stream() -> int:
@@ -270,92 +271,7 @@ def debug_peaks(maps: torch.Tensor, val_ratio=1.2, val_win=3, planar=False):
     return u, v, inv
 
 
-ENSEMBLE_SIZES = (16, 32, 64)
 ENSEMBLE_MODES = {0: 0, None: 0, "PASS1": 0, "DWS": _lib.MODE_DWS, "CWS": _lib.MODE_CWS}
-
-
-def ensemble_check(sizes, uncertainty=None, deform=None):
-    """What ensemble correlation refuses, checked without a GPU: the window sizes of every pass must be 16, 32 or 64
-    (NotImplementedError names the size), and it combines with neither uncertainty= nor deform= (ValueError)."""
-    if uncertainty is not None:
-        raise ValueError("ensemble correlation does not combine with uncertainty=")
-    if deform is not None:
-        raise ValueError("ensemble correlation does not combine with deform=")
-    for ws in sizes:
-        if ws not in ENSEMBLE_SIZES:
-            raise NotImplementedError(f"ensemble correlation covers window sizes 16, 32 and 64; a pass of {ws} is not covered")
-
-
-CORRELATION_SIZES = (16, 32, 64)
-CORRELATION_DEFAULTS = {"kind": "rpc", "diameter": 2.8, "floor": 2.0 ** -10}
-CORRELATION_MAX_DIAMETER, CORRELATION_FLOOR_MIN, CORRELATION_FLOOR_MAX = 16.0, 2.0 ** -20, 2.0 ** -4
-
-
-def correlation_arg(correlation):
-    """The correlation= argument of Plan / OfflinePIV / ResidentPIV / run_folder / debug_pass, checked (no GPU involved):
-    None (the plain cross-correlation), "phase" (phase-only correlation), "rpc" (robust phase correlation at the default
-    particle-image diameter 2.8) or a dict with any of CORRELATION_DEFAULTS' keys -- diameter: the e^-2 diameter in pixels,
-    one number or (d_x, d_y), 0..16; floor: 2^-20..2^-4 (include/torchpiv_hip.h: tpiv_plan_set_correlation has the
-    definition).  Returns None or {"kind", "dx", "dy", "floor"}; "phase" has dx = dy = 0.  ValueError for anything else."""
-    if correlation is None:
-        return None
-    if isinstance(correlation, dict) and set(correlation) == {"kind", "dx", "dy", "floor"}:      # this function's own result
-        correlation = dict({"kind": correlation["kind"], "floor": correlation["floor"]},
-                           **({} if correlation["kind"] == "phase" else {"diameter": (correlation["dx"], correlation["dy"])}))
-    form = f"correlation: None, 'phase', 'rpc' or a dict of {sorted(CORRELATION_DEFAULTS)}"
-    if isinstance(correlation, str):
-        if correlation not in _lib.CORRELATIONS:
-            raise ValueError(f"{form}, got {correlation!r}")
-        correlation = {"kind": correlation}
-    if not isinstance(correlation, dict):
-        raise ValueError(f"{form}, got {type(correlation).__name__}")
-    unknown = sorted(set(correlation) - set(CORRELATION_DEFAULTS), key=str)
-    if unknown:
-        raise ValueError(f"correlation: unknown key(s) {unknown}; known: {sorted(CORRELATION_DEFAULTS)}")
-    par = dict(CORRELATION_DEFAULTS, **correlation)
-    if not isinstance(par["kind"], str) or par["kind"] not in _lib.CORRELATIONS:
-        raise ValueError(f"correlation: kind must be one of {sorted(_lib.CORRELATIONS)}, got {par['kind']!r}")
-    if par["kind"] == "phase":
-        if "diameter" in correlation and correlation["diameter"] not in (0, 0.0, (0, 0), (0.0, 0.0)):
-            raise ValueError("correlation: 'phase' has no diameter (it is 'rpc' at diameter 0)")
-        d = (0.0, 0.0)
-    else:
-        d = par["diameter"]
-        if isinstance(d, (tuple, list)):
-            if len(d) != 2:
-                raise ValueError(f"correlation: diameter must be a number or (d_x, d_y), got {d!r}")
-        else:
-            d = (d, d)
-    try:
-        if any(isinstance(q, (bool, np.bool_)) for q in d):
-            raise TypeError
-        dx, dy = float(d[0]), float(d[1])
-        floor = float(par["floor"])
-    except (TypeError, ValueError):
-        raise ValueError(f"correlation: diameter and floor must be numbers, got {par['diameter']!r}, {par['floor']!r}") from None
-    for q in (dx, dy):
-        if not 0.0 <= q <= CORRELATION_MAX_DIAMETER:
-            raise ValueError(f"correlation: diameter must be in 0..{CORRELATION_MAX_DIAMETER:g} pixels, got {q!r}")
-    if not CORRELATION_FLOOR_MIN <= floor <= CORRELATION_FLOOR_MAX:
-        raise ValueError(f"correlation: floor must be in 2^-20..2^-4, got {floor!r}")
-    return {"kind": par["kind"], "dx": dx, "dy": dy, "floor": floor}
-
-
-def correlation_check(sizes, mode=None, uncertainty=None, deform=None, ensemble=False):
-    """What correlation= refuses, checked without a GPU: it combines with neither uncertainty= nor deform= nor ensemble
-    correlation (ValueError), the window size of every pass must be 16, 32 or 64 and the mode must not be CWS_Fast
-    (NotImplementedError names it)."""
-    if uncertainty is not None:
-        raise ValueError("correlation= does not combine with uncertainty=")
-    if deform is not None:
-        raise ValueError("correlation= does not combine with deform=")
-    if ensemble:
-        raise ValueError("correlation= does not combine with ensemble correlation")
-    if mode == "CWS_Fast":
-        raise NotImplementedError("correlation=: the CWS_Fast iteration has no filtered kernel")
-    for ws in sizes:
-        if ws not in CORRELATION_SIZES:
-            raise NotImplementedError(f"correlation=: filtered passes cover window sizes 16, 32 and 64; a pass of {ws} is not covered")
 
 
 def correlation_tables(par, sizes):
@@ -369,75 +285,6 @@ def correlation_tables(par, sizes):
     return np.ascontiguousarray(np.concatenate(out))
 
 
-WEIGHTING_SIZES = (16, 32, 64)
-WEIGHTING_DEFAULTS = {"kind": "gaussian", "sigma": 0.4}
-WEIGHTING_SIGMA_MIN, WEIGHTING_SIGMA_MAX = 0.2, 4.0
-
-
-def weighting_arg(weighting):
-    """The weighting= argument of Plan / OfflinePIV / ResidentPIV / run_folder / debug_pass, checked (no GPU involved):
-    None (the top-hat window of the plain passes), "gaussian" (at the default sigma 0.4), "uniform" (the top-hat window
-    through the weighted kernels) or a dict with any of WEIGHTING_DEFAULTS' keys -- sigma: relative to the half window, one
-    number or (sigma_x, sigma_y), 0.2..4 (include/torchpiv_hip.h: tpiv_plan_set_weighting has the definition).  Returns None
-    or {"kind", "sx", "sy"}; "uniform" has no sigma (sx = sy = 0).  ValueError for anything else."""
-    if weighting is None:
-        return None
-    if isinstance(weighting, dict) and set(weighting) == {"kind", "sx", "sy"}:       # this function's own result
-        weighting = dict({"kind": weighting["kind"]},
-                         **({} if weighting["kind"] == "uniform" else {"sigma": (weighting["sx"], weighting["sy"])}))
-    form = f"weighting: None, 'gaussian', 'uniform' or a dict of {sorted(WEIGHTING_DEFAULTS)}"
-    if isinstance(weighting, str):
-        if weighting not in _lib.WEIGHTINGS:
-            raise ValueError(f"{form}, got {weighting!r}")
-        weighting = {"kind": weighting}
-    if not isinstance(weighting, dict):
-        raise ValueError(f"{form}, got {type(weighting).__name__}")
-    unknown = sorted(set(weighting) - set(WEIGHTING_DEFAULTS), key=str)
-    if unknown:
-        raise ValueError(f"weighting: unknown key(s) {unknown}; known: {sorted(WEIGHTING_DEFAULTS)}")
-    par = dict(WEIGHTING_DEFAULTS, **weighting)
-    if not isinstance(par["kind"], str) or par["kind"] not in _lib.WEIGHTINGS:
-        raise ValueError(f"weighting: kind must be one of {sorted(_lib.WEIGHTINGS)}, got {par['kind']!r}")
-    if par["kind"] == "uniform":
-        if "sigma" in weighting:
-            raise ValueError("weighting: 'uniform' has no sigma")
-        return {"kind": "uniform", "sx": 0.0, "sy": 0.0}
-    s = par["sigma"]
-    if isinstance(s, (tuple, list)):
-        if len(s) != 2:
-            raise ValueError(f"weighting: sigma must be a number or (sigma_x, sigma_y), got {s!r}")
-    else:
-        s = (s, s)
-    try:
-        if any(isinstance(q, (bool, np.bool_)) for q in s):
-            raise TypeError
-        sx, sy = float(s[0]), float(s[1])
-    except (TypeError, ValueError):
-        raise ValueError(f"weighting: sigma must be a number or a pair of numbers, got {par['sigma']!r}") from None
-    for q in (sx, sy):
-        if not WEIGHTING_SIGMA_MIN <= q <= WEIGHTING_SIGMA_MAX:          # (NaN fails both comparisons)
-            raise ValueError(f"weighting: sigma must be in {WEIGHTING_SIGMA_MIN:g}..{WEIGHTING_SIGMA_MAX:g} "
-                             f"(relative to the half window), got {q!r}")
-    return {"kind": "gaussian", "sx": sx, "sy": sy}
-
-
-def weighting_check(sizes, mode=None, uncertainty=None, ensemble=False, correlation=None):
-    """What weighting= refuses, checked without a GPU: it combines with neither uncertainty= (its estimator sums over a
-    top-hat window) nor ensemble correlation nor correlation= (ValueError), the window size of every pass must be 16, 32 or
-    64 and the mode must not be CWS_Fast (NotImplementedError names it).  It does combine with deform=."""
-    if uncertainty is not None:
-        raise ValueError("weighting= does not combine with uncertainty= (its estimator sums over a top-hat window)")
-    if ensemble:
-        raise ValueError("weighting= does not combine with ensemble correlation")
-    if correlation is not None:
-        raise ValueError("weighting= does not combine with correlation=")
-    if mode == "CWS_Fast":
-        raise NotImplementedError("weighting=: the CWS_Fast iteration has no weighted kernel")
-    for ws in sizes:
-        if ws not in WEIGHTING_SIZES:
-            raise NotImplementedError(f"weighting=: weighted passes cover window sizes 16, 32 and 64; a pass of {ws} is not covered")
-
-
 def weighting_tables(par, sizes):
     """float32 [sum over the passes of 2 ws]: g_y[0 .. ws-1] then g_x[0 .. ws-1] per pass; "gaussian": g[i] =
     float32(exp(-t^2 / (2 sigma^2))), t = (2 i - (ws - 1)) / ws, evaluated in float64 and rounded once; "uniform": ones."""
@@ -448,15 +295,6 @@ def weighting_tables(par, sizes):
             out.append(np.ones(ws, np.float32) if par["kind"] == "uniform"
                        else np.exp(-t * t / (2.0 * s * s)).astype(np.float32))
     return np.ascontiguousarray(np.concatenate(out))
-
-
-def pass_sizes(ws, ov, n_pass, pass_scale):
-    """[(ws, ov)] of the passes of a plan (PIVbackend.py:856-857: int(x // scale) from pass to pass)."""
-    out = [(int(ws), int(ov))]
-    for _ in range(max(int(n_pass), 1) - 1):
-        w, o = out[-1]
-        out.append((int(w // pass_scale), int(o // pass_scale)))
-    return out
 
 
 def ensemble_mode(mode):
@@ -542,38 +380,6 @@ def ensemble_peaks(mode, acc, n_pairs, H, W, ws, ov, u0=None, v0=None, u2=None, 
     return (u, v, inv, du, dv) if raw else (u, v, inv)
 
 
-OUTLIER_DEFAULTS = {"threshold": 2.0, "eps": 0.1, "min_neighbours": 3}
-
-
-def outlier_arg(outlier):
-    """The outlier= argument of Plan / OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no test),
-    "median" (the normalized median test at OUTLIER_DEFAULTS) or a dict with any of threshold (> 0), eps (>= 0, pixels)
-    and min_neighbours (1..8).  Returns None or the full parameter dict; anything else raises ValueError."""
-    if outlier is None:
-        return None
-    if isinstance(outlier, str):
-        if outlier != "median":
-            raise ValueError(f"outlier: None, 'median' or a dict of {sorted(OUTLIER_DEFAULTS)}, got {outlier!r}")
-        return dict(OUTLIER_DEFAULTS)
-    if not isinstance(outlier, dict):
-        raise ValueError(f"outlier: None, 'median' or a dict of {sorted(OUTLIER_DEFAULTS)}, got {type(outlier).__name__}")
-    unknown = sorted(set(outlier) - set(OUTLIER_DEFAULTS), key=str)
-    if unknown:
-        raise ValueError(f"outlier: unknown key(s) {unknown}; known: {sorted(OUTLIER_DEFAULTS)}")
-    par = dict(OUTLIER_DEFAULTS, **outlier)
-    try:
-        thr, eps, mn = float(par["threshold"]), float(par["eps"]), par["min_neighbours"]
-    except (TypeError, ValueError):
-        raise ValueError(f"outlier: threshold and eps must be numbers, got {outlier!r}") from None
-    if not thr > 0 or thr == float("inf"):
-        raise ValueError(f"outlier: threshold must be a finite number > 0, got {par['threshold']!r}")
-    if not eps >= 0 or eps == float("inf"):
-        raise ValueError(f"outlier: eps must be a finite number >= 0, got {par['eps']!r}")
-    if isinstance(mn, bool) or not isinstance(mn, (int, np.integer)) or not 1 <= mn <= 8:
-        raise ValueError(f"outlier: min_neighbours must be an integer in 1..8, got {mn!r}")
-    return {"threshold": thr, "eps": eps, "min_neighbours": int(mn)}
-
-
 def median_test(u, v, inv, threshold=2.0, eps=0.1, min_neighbours=3, want_medians=False):
     """Normalized median test (Westerweel & Scarano 2005; tpiv_median_test) on fields u, v float64 and the mask inv uint8,
     [batch, n_rows, n_cols] on the GPU.  Returns status uint8 (bit 0: flagged, bit 1: invalid on input), with
@@ -594,35 +400,6 @@ def median_test(u, v, inv, threshold=2.0, eps=0.1, min_neighbours=3, want_median
                                    par["min_neighbours"], status.data_ptr(), mu.data_ptr() if want_medians else None,
                                    mv.data_ptr() if want_medians else None, _stream()))
     return (status, mu, mv) if want_medians else status
-
-
-UNCERTAINTY_DEFAULTS = {"kind": "cs", "radius": 3}
-UNCERTAINTY_MAX_RADIUS, UNCERTAINTY_WS = 4, (4, 128)
-
-
-def uncertainty_arg(uncertainty):
-    """The uncertainty= argument of Plan / OfflinePIV / ResidentPIV, checked (no GPU involved): None (no estimate), "cs"
-    (correlation statistics at UNCERTAINTY_DEFAULTS) or a dict with any of kind ("cs") and radius (an integer in 0..4, the
-    reach of the covariance sum in pixels).  Returns None or the full parameter dict; anything else raises ValueError."""
-    if uncertainty is None:
-        return None
-    if isinstance(uncertainty, str):
-        if uncertainty != "cs":
-            raise ValueError(f"uncertainty: None, 'cs' or a dict of {sorted(UNCERTAINTY_DEFAULTS)}, got {uncertainty!r}")
-        return dict(UNCERTAINTY_DEFAULTS)
-    if not isinstance(uncertainty, dict):
-        raise ValueError(f"uncertainty: None, 'cs' or a dict of {sorted(UNCERTAINTY_DEFAULTS)}, "
-                         f"got {type(uncertainty).__name__}")
-    unknown = sorted(set(uncertainty) - set(UNCERTAINTY_DEFAULTS), key=str)
-    if unknown:
-        raise ValueError(f"uncertainty: unknown key(s) {unknown}; known: {sorted(UNCERTAINTY_DEFAULTS)}")
-    par = dict(UNCERTAINTY_DEFAULTS, **uncertainty)
-    if par["kind"] != "cs":
-        raise ValueError(f"uncertainty: kind must be 'cs' (correlation statistics), got {par['kind']!r}")
-    R = par["radius"]
-    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 0 <= R <= UNCERTAINTY_MAX_RADIUS:
-        raise ValueError(f"uncertainty: radius must be an integer in 0..{UNCERTAINTY_MAX_RADIUS}, got {R!r}")
-    return {"kind": "cs", "radius": int(R)}
 
 
 def uncertainty(a, b, u, v, ws, ov, invalid=None, radius=3, want_stats=False):
@@ -790,50 +567,6 @@ def subtract_background(frames, bg, out=None):
     return out
 
 
-MASK_KEYS = ("image", "threshold", "pixels", "fill")
-MASK_DEFAULTS = {"threshold": 0.5, "pixels": "zero", "fill": 0.0}
-
-
-def mask_arg(mask):
-    """The mask= argument of Plan / OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no mask), an
-    image -- uint8 or bool [H, W], numpy array or tensor, non-zero = masked -- or a dict with that image under "image" and
-    any of threshold (a number in [0, 1]: the share of masked pixels above which a window is excluded), pixels ("zero":
-    masked pixels are set to 0 in both frames before the passes, "keep": the frames stay as they are) and fill (any
-    float, NaN allowed: the value delivered at excluded cells).  Returns None or {"image": contiguous uint8 tensor [H, W],
-    "threshold": float, "pixels": str, "fill": float}; anything else raises ValueError."""
-    if mask is None:
-        return None
-    if not isinstance(mask, dict):
-        mask = {"image": mask}
-    unknown = sorted(set(mask) - set(MASK_KEYS), key=str)
-    if unknown:
-        raise ValueError(f"mask: unknown key(s) {unknown}; known: {list(MASK_KEYS)}")
-    if "image" not in mask:
-        raise ValueError("mask: the dict needs an 'image' (uint8 or bool [H, W])")
-    im = mask["image"]
-    if isinstance(im, np.ndarray):
-        if im.dtype not in (np.uint8, np.bool_):
-            raise ValueError(f"mask: a uint8 or bool image, got {im.dtype}")
-        im = torch.from_numpy(np.ascontiguousarray(im))
-    elif not isinstance(im, torch.Tensor):
-        raise ValueError(f"mask: a uint8 or bool numpy array or tensor [H, W], got {type(im).__name__}")
-    elif im.dtype not in (torch.uint8, torch.bool):
-        raise ValueError(f"mask: a uint8 or bool image, got {im.dtype}")
-    if im.dim() != 2 or im.numel() == 0:
-        raise ValueError(f"mask: an image [H, W], got shape {tuple(im.shape)}")
-    im = im.to(torch.uint8).contiguous()             # (True -> 1; a uint8 image keeps its bytes: any non-zero one masks)
-    par = dict(MASK_DEFAULTS, **{k: v for k, v in mask.items() if k != "image"})
-    thr, fill = par["threshold"], par["fill"]
-    if isinstance(thr, (bool, np.bool_)) or not isinstance(thr, (int, float, np.integer, np.floating)) \
-            or not 0 <= thr <= 1:                                       # (a NaN fails the comparison)
-        raise ValueError(f"mask: threshold must be a number in [0, 1], got {thr!r}")
-    if not isinstance(par["pixels"], str) or par["pixels"] not in ("zero", "keep"):
-        raise ValueError(f"mask: pixels must be 'zero' or 'keep', got {par['pixels']!r}")
-    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, (int, float, np.integer, np.floating)):
-        raise ValueError(f"mask: fill must be a float (NaN allowed), got {fill!r}")
-    return {"image": im, "threshold": float(thr), "pixels": par["pixels"], "fill": float(fill)}
-
-
 def _mask_image(mask, H, W, device, name):
     _need_cuda(mask)
     if mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or not mask.is_contiguous() or mask.device != device:
@@ -893,73 +626,6 @@ def mask_fields(u, v, inv, grid, invalid_value, status=None):
         check(lib.tpiv_mask_fields(u.data_ptr(), v.data_ptr(), inv.data_ptr(), None if status is None else status.data_ptr(),
                                    g.data_ptr(), B, nr, nc, int(invalid_value), _stream()))
     return (u, v, inv) if status is None else (u, v, inv, status)
-
-
-DYNMASK_KINDS = ("bright", "dark")
-DYNMASK_KEYS = ("kind", "size", "level", "grow", "stack", "threshold", "pixels", "fill")
-
-
-def dynamic_mask_arg(dynamic_mask, mask=None, stack=True):
-    """The dynamic_mask= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved).  None: no per-pair
-    mask.  {"kind": "bright" | "dark", "size": k, "level": L, "grow": g}: one mask per pair segmented on the device from the
-    frames themselves (tpiv_dynamic_mask: k odd in 3..63, L an integer in 0..255, g >= 0, default 0, with k // 2 + g <= 31).
-    {"stack": uint8 or bool [N, H, W]}: one mask per pair from the caller, non-zero = masked (stack=False: this form is
-    refused, for the classes whose frames do not come with an index the caller knows).  threshold, pixels and fill -- as
-    in mask_arg, with its defaults -- are accepted in the dict only when mask= (`mask`: as given or as mask_arg returned
-    it) is None; with mask= given, its image is OR-ed into every pair's mask and its three values apply.  Returns None or
-    a dict with "threshold", "pixels", "fill" and either "kind", "size", "level", "grow" (ints but for kind) or "stack" (a
-    contiguous uint8 tensor); anything else raises ValueError."""
-    if dynamic_mask is None:
-        return None
-    if not isinstance(dynamic_mask, dict):
-        raise ValueError(f"dynamic_mask: None or a dict of {list(DYNMASK_KEYS)}, got {type(dynamic_mask).__name__}")
-    unknown = sorted(set(dynamic_mask) - set(DYNMASK_KEYS), key=str)
-    if unknown:
-        raise ValueError(f"dynamic_mask: unknown key(s) {unknown}; known: {list(DYNMASK_KEYS)}")
-    static = mask_arg(mask)                          # (what mask_arg returned passes through it unchanged)
-    shared = [k for k in ("threshold", "pixels", "fill") if k in dynamic_mask]
-    if static is not None and shared:
-        raise ValueError(f"dynamic_mask: {shared} are given with mask= when both keywords are used, not here")
-    probe = mask_arg(dict({"image": np.zeros((1, 1), np.uint8)}, **{k: dynamic_mask[k] for k in shared}))
-    out = {k: (static if static is not None else probe)[k] for k in ("threshold", "pixels", "fill")}
-
-    def integer(x):
-        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
-    if "stack" in dynamic_mask:
-        extra = sorted(set(dynamic_mask) & {"kind", "size", "level", "grow"})
-        if extra:
-            raise ValueError(f"dynamic_mask: 'stack' gives the masks; {extra} belong to the segmented form")
-        if not stack:
-            raise ValueError("dynamic_mask: the 'stack' form is for ResidentPIV, whose pairs the caller indexes; a run "
-                             "over files takes the segmented form")
-        st = dynamic_mask["stack"]
-        if isinstance(st, np.ndarray):
-            if st.dtype not in (np.uint8, np.bool_):
-                raise ValueError(f"dynamic_mask: a uint8 or bool stack, got {st.dtype}")
-            st = torch.from_numpy(np.ascontiguousarray(st))
-        elif not isinstance(st, torch.Tensor):
-            raise ValueError(f"dynamic_mask: stack must be a uint8 or bool numpy array or tensor [N, H, W], got "
-                             f"{type(st).__name__}")
-        elif st.dtype not in (torch.uint8, torch.bool):
-            raise ValueError(f"dynamic_mask: a uint8 or bool stack, got {st.dtype}")
-        if st.dim() != 3 or st.numel() == 0:
-            raise ValueError(f"dynamic_mask: a stack [N, H, W], got shape {tuple(st.shape)}")
-        out["stack"] = st.to(torch.uint8).contiguous()
-        return out
-    missing = [k for k in ("kind", "size", "level") if k not in dynamic_mask]
-    if missing:
-        raise ValueError(f"dynamic_mask: the dict needs {missing} (or a 'stack')")
-    kind, size, level, grow = (dynamic_mask["kind"], dynamic_mask["size"], dynamic_mask["level"], dynamic_mask.get("grow", 0))
-    if not isinstance(kind, str) or kind not in DYNMASK_KINDS:
-        raise ValueError(f"dynamic_mask: kind must be 'bright' or 'dark', got {kind!r}")
-    if not (integer(size) and 3 <= size <= 63 and size % 2 == 1):
-        raise ValueError(f"dynamic_mask: size must be an odd integer in 3..63, got {size!r}")
-    if not (integer(level) and 0 <= level <= 255):
-        raise ValueError(f"dynamic_mask: level must be an integer in 0..255, got {level!r}")
-    if not (integer(grow) and grow >= 0 and size // 2 + grow <= 31):
-        raise ValueError(f"dynamic_mask: grow must be an integer >= 0 with size // 2 + grow <= 31, got {grow!r}")
-    out.update(kind=kind, size=int(size), level=int(level), grow=int(grow))
-    return out
 
 
 def dynamic_mask(a, b, kind, size, level, grow=0, static=None, out=None, work=None):
@@ -1059,42 +725,6 @@ def mask_fields_pairs(u, v, inv, grids, invalid_value, status=None):
     return (u, v, inv) if status is None else (u, v, inv, status)
 
 
-PREFILTER_KEYS =("kind", "size", "cap")
-
-
-def prefilter_arg(prefilter):
-    """The prefilter= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no filter) or a
-    dict with kind ("min": sliding-minimum subtraction, "mean": local-mean high-pass, None: capping only), size (odd, 3..63;
-    required with a kind) and optionally cap (1..255).  Returns None or {"kind", "size", "cap"} with ints (size None
-    without a kind, cap None without capping); anything else, a dict that asks for nothing included, raises ValueError."""
-    if prefilter is None:
-        return None
-    if not isinstance(prefilter, dict):
-        raise ValueError(f"prefilter: None or a dict of {list(PREFILTER_KEYS)}, got {type(prefilter).__name__}")
-    unknown = sorted(set(prefilter) - set(PREFILTER_KEYS), key=str)
-    if unknown:
-        raise ValueError(f"prefilter: unknown key(s) {unknown}; known: {list(PREFILTER_KEYS)}")
-    kind, size, cap = prefilter.get("kind"), prefilter.get("size"), prefilter.get("cap")
-
-    def integer(x):
-        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
-    if kind is not None and (not isinstance(kind, str) or kind not in ("min", "mean")):
-        raise ValueError(f"prefilter: kind must be 'min', 'mean' or None, got {kind!r}")
-    if kind is None:
-        if size is not None and not (integer(size) and 3 <= size <= 63 and size % 2 == 1):
-            raise ValueError(f"prefilter: size must be an odd integer in 3..63, got {size!r}")
-        size = None
-    elif size is None:
-        raise ValueError(f"prefilter: kind {kind!r} needs a size (odd, 3..63)")
-    elif not (integer(size) and 3 <= size <= 63 and size % 2 == 1):
-        raise ValueError(f"prefilter: size must be an odd integer in 3..63, got {size!r}")
-    if cap is not None and not (integer(cap) and 1 <= cap <= 255):
-        raise ValueError(f"prefilter: cap must be an integer in 1..255, got {cap!r}")
-    if kind is None and cap is None:
-        raise ValueError("prefilter: the dict asks for nothing (no kind and no cap); pass None for no filter")
-    return {"kind": kind, "size": None if size is None else int(size), "cap": None if cap is None else int(cap)}
-
-
 def prefilter(frames, kind, size=None, cap=None, background=None, out=None):
     """Spatial pre-filter of uint8 frames [n, H, W] or [H, W] on the device, one launch (tpiv_prefilter): with g = max(f,
     background) - background (g = f without one, background uint8 [H, W]) and the size x size neighbourhood clipped to
@@ -1116,39 +746,6 @@ def prefilter(frames, kind, size=None, cap=None, background=None, out=None):
                                  _lib.PREFILTERS[par["kind"]], par["size"] or 0, par["cap"] or 255, out.data_ptr(),
                                  _stream()))
     return out
-
-
-EQUALIZE_KEYS = ("tile", "clip")
-EQUALIZE_DEFAULTS = {"tile": 64, "clip": 3.0}
-
-
-def equalize_arg(equalize):
-    """The equalize= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (no equalization),
-    "clahe" (tile 64, clip 3.0) or a dict with any of tile (integer, 8..256: the tile size aimed at, in pixels) and clip
-    (1..256: the clip limit in units of the uniform bin height; 256 never clips).  Returns None or {"tile": int, "clip":
-    float, "clip_q8": int} with clip_q8 = round(256 clip), what tpiv_equalize takes; anything else -- unknown strings or
-    keys, bools, a non-integer tile, values out of range, an empty dict -- raises ValueError."""
-    if equalize is None:
-        return None
-    if isinstance(equalize, str):
-        if equalize != "clahe":
-            raise ValueError(f"equalize: None, 'clahe' or a dict of {list(EQUALIZE_KEYS)}, got {equalize!r}")
-        equalize = dict(EQUALIZE_DEFAULTS)
-    if not isinstance(equalize, dict):
-        raise ValueError(f"equalize: None, 'clahe' or a dict of {list(EQUALIZE_KEYS)}, got {type(equalize).__name__}")
-    unknown = sorted(set(equalize) - set(EQUALIZE_KEYS), key=str)
-    if unknown:
-        raise ValueError(f"equalize: unknown key(s) {unknown}; known: {list(EQUALIZE_KEYS)}")
-    if not equalize:
-        raise ValueError("equalize: the dict names neither tile nor clip; pass 'clahe' for the defaults, None for no filter")
-    tile = equalize.get("tile", EQUALIZE_DEFAULTS["tile"])
-    clip = equalize.get("clip", EQUALIZE_DEFAULTS["clip"])
-    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or not 8 <= tile <= 256:
-        raise ValueError(f"equalize: tile must be an integer in 8..256, got {tile!r}")
-    if isinstance(clip, (bool, np.bool_)) or not isinstance(clip, (int, float, np.integer, np.floating)) \
-            or not 1 <= clip <= 256:                                    # (a NaN fails the comparison)
-        raise ValueError(f"equalize: clip must be a number in 1..256, got {clip!r}")
-    return {"tile": int(tile), "clip": float(clip), "clip_q8": int(round(float(clip) * 256))}
 
 
 def equalize_grid(H, W, tile):
@@ -1187,77 +784,6 @@ def equalize(frames, tile=EQUALIZE_DEFAULTS["tile"], clip=EQUALIZE_DEFAULTS["cli
     if return_luts:
         return out, work[:need].view(n, ky, kx, 256)
     return out
-
-
-DEPTH_BINS = 65536
-DEPTH_CURVES = ("linear", "sqrt")
-DEPTH_AUTO_DEFAULTS = {"clip_low": 0.0, "clip_high": 1e-4, "sample": 32}
-DEPTH_KEYS = ("lo", "hi", "curve", "auto", "clip_low", "clip_high", "sample", "lut")
-
-
-def depth_arg(depth):
-    """The depth= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved).  None: 8-bit frames as
-    before.  {"lo", "hi", "curve"}: uint16 frames through depth_lut(lo, hi, curve) (integers 0 <= lo < hi <= 65535; curve
-    "linear" by default, or "sqrt").  "auto" or {"auto": True, "clip_low", "clip_high", "sample", "curve"}: lo, hi from
-    depth_range of the histogram of `sample` pairs of the recording (clips: fractions in [0, 0.5), defaults 0 and 1e-4;
-    sample >= 1, default 32).  {"lut": table}: the caller's own uint8 [65536] table (numpy array or tensor).  Returns None
-    or the full dict of its form -- {"lo", "hi", "curve"}, {"auto": True, "clip_low", "clip_high", "sample", "curve"} or
-    {"lut": numpy uint8 [65536]}; anything else (unknown keys, mixed forms, a dict that asks for nothing) raises ValueError."""
-    if depth is None:
-        return None
-    if isinstance(depth, str):
-        if depth != "auto":
-            raise ValueError(f"depth: None, 'auto' or a dict of {list(DEPTH_KEYS)}, got {depth!r}")
-        depth = {"auto": True}
-    if not isinstance(depth, dict):
-        raise ValueError(f"depth: None, 'auto' or a dict of {list(DEPTH_KEYS)}, got {type(depth).__name__}")
-    unknown = sorted(set(depth) - set(DEPTH_KEYS), key=str)
-    if unknown:
-        raise ValueError(f"depth: unknown key(s) {unknown}; known: {list(DEPTH_KEYS)}")
-
-    def integer(x):
-        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
-
-    def only(form, allowed):
-        extra = sorted(set(depth) - set(allowed))
-        if extra:
-            raise ValueError(f"depth: key(s) {extra} do not go with {form} (that form takes {list(allowed)})")
-    if "lut" in depth:
-        only("'lut'", ("lut",))
-        lut = depth["lut"]
-        if isinstance(lut, torch.Tensor):
-            if lut.dtype != torch.uint8:
-                raise ValueError(f"depth: lut must be uint8 [{DEPTH_BINS}], got dtype {lut.dtype}")
-            lut = lut.detach().cpu().numpy()
-        if not isinstance(lut, np.ndarray) or lut.dtype != np.uint8 or lut.shape != (DEPTH_BINS,):
-            raise ValueError(f"depth: lut must be a uint8 array or tensor of shape ({DEPTH_BINS},), got "
-                             f"{getattr(lut, 'dtype', type(lut).__name__)} {getattr(lut, 'shape', '')}")
-        return {"lut": np.ascontiguousarray(lut)}
-    curve = depth.get("curve", "linear")
-    if not isinstance(curve, str) or curve not in DEPTH_CURVES:
-        raise ValueError(f"depth: curve must be one of {list(DEPTH_CURVES)}, got {curve!r}")
-    if "auto" in depth:
-        only("'auto'", ("auto", "clip_low", "clip_high", "sample", "curve"))
-        if depth["auto"] is not True:
-            raise ValueError(f"depth: auto must be True (leave the key out for a fixed range), got {depth['auto']!r}")
-        par = dict(DEPTH_AUTO_DEFAULTS, **{k: depth[k] for k in DEPTH_AUTO_DEFAULTS if k in depth})
-        for k in ("clip_low", "clip_high"):
-            c = par[k]
-            if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)) or not 0 <= c < 0.5:
-                raise ValueError(f"depth: {k} must be a fraction in [0, 0.5), got {c!r}")
-        if not integer(par["sample"]) or par["sample"] < 1:
-            raise ValueError(f"depth: sample must be an integer >= 1, got {par['sample']!r}")
-        return {"auto": True, "clip_low": float(par["clip_low"]), "clip_high": float(par["clip_high"]),
-                "sample": int(par["sample"]), "curve": curve}
-    if "lo" in depth or "hi" in depth:
-        only("a fixed range", ("lo", "hi", "curve"))
-        if "lo" not in depth or "hi" not in depth:
-            raise ValueError("depth: a fixed range needs both lo and hi")
-        lo, hi = depth["lo"], depth["hi"]
-        if not integer(lo) or not integer(hi) or not 0 <= lo < hi <= DEPTH_BINS - 1:
-            raise ValueError(f"depth: lo and hi must be integers with 0 <= lo < hi <= {DEPTH_BINS - 1}, got {lo!r}, {hi!r}")
-        return {"lo": int(lo), "hi": int(hi), "curve": curve}
-    raise ValueError("depth: the dict asks for nothing (no lo / hi, no auto, no lut); pass None for 8-bit frames")
 
 
 def depth_lut(lo, hi, curve="linear"):
@@ -1386,76 +912,6 @@ def depth_map(frames, lut, offsets=None, shape=None, out=None):
         check(lib.tpiv_depth_map(f.data_ptr(), None if off_d is None else off_d.data_ptr(), n, H, W, lut.data_ptr(),
                                  out.data_ptr(), _stream()))
     return out
-
-
-DEWARP_FORMS = ("homography", "poly", "map")
-DEWARP_KEYS = DEWARP_FORMS + ("interp", "fill")
-DEWARP_DEFAULTS = {"interp": "cubic", "fill": 0}
-DEWARP_POLY_ORDERS = {3: 1, 6: 2, 10: 3}            # coefficients per axis -> order
-
-
-def dewarp_arg(dewarp):
-    """The dewarp= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (frames as recorded)
-    or a dict that holds exactly one backward map -- where in the camera frame every pixel of the rectified frame comes
-    from; pixel centres at the integers, x along the columns, y along the rows, the rectified frame has the camera
-    frame's shape --
-      "homography": 3 x 3, (x, y, 1) of the output pixel -> the source pixel, homogeneous;
-      "poly": float [2, K], K = 3, 6 or 10 -- source x (row 0) and source y (row 1) in pixels as polynomials of order 1, 2
-        or 3 in the output coordinates normalised to [-1, 1], xn = 2 x / (W - 1) - 1, yn = 2 y / (H - 1) - 1, with the terms
-        in the order 1, xn, yn | xn^2, xn yn, yn^2 | xn^3, xn^2 yn, xn yn^2, yn^3;
-      "map": a pair (xs, ys) of float arrays [H, W], the source coordinates themselves (radial models, the output of a
-        calibration package); non-finite entries count as outside;
-    and optionally "interp" ("cubic", the default: Catmull-Rom; or "linear") and "fill" (integer 0..255, default 0: the
-    value of pixels whose source lies outside the camera frame).  Returns None or {form: float64 array(s), "interp": str,
-    "fill": int}; anything else raises ValueError."""
-    if dewarp is None:
-        return None
-    if not isinstance(dewarp, dict):
-        raise ValueError(f"dewarp: None or a dict with one of {list(DEWARP_FORMS)}, got {type(dewarp).__name__}")
-    unknown = sorted(set(dewarp) - set(DEWARP_KEYS), key=str)
-    if unknown:
-        raise ValueError(f"dewarp: unknown key(s) {unknown}; known: {list(DEWARP_KEYS)}")
-    forms = [k for k in DEWARP_FORMS if k in dewarp]
-    if len(forms) != 1:
-        raise ValueError(f"dewarp: exactly one of {list(DEWARP_FORMS)} is needed, got {forms}")
-    form = forms[0]
-
-    def array(x, what):
-        if isinstance(x, torch.Tensor):
-            x = x.detach().cpu().numpy()
-        try:
-            a = np.asarray(x)
-            if a.dtype.kind not in "fiu":
-                raise TypeError
-            return np.ascontiguousarray(a, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"dewarp: {what} must be an array of numbers") from None
-    if form == "homography":
-        val = array(dewarp[form], "the homography")
-        if val.shape != (3, 3) or not np.isfinite(val).all():
-            raise ValueError(f"dewarp: the homography must be a finite 3 x 3 matrix, got shape {val.shape}")
-        if not np.any(val[2] != 0):
-            raise ValueError("dewarp: the homography's last row is zero")
-    elif form == "poly":
-        val = array(dewarp[form], "the polynomial")
-        if val.ndim != 2 or val.shape[0] != 2 or val.shape[1] not in DEWARP_POLY_ORDERS or not np.isfinite(val).all():
-            raise ValueError(f"dewarp: the polynomial must be finite [2, K] with K in {sorted(DEWARP_POLY_ORDERS)}, got "
-                             f"shape {val.shape}")
-    else:
-        pair = dewarp[form]
-        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-            raise ValueError("dewarp: map must be a pair (xs, ys) of float arrays [H, W]")
-        xs, ys = array(pair[0], "map xs"), array(pair[1], "map ys")
-        if xs.ndim != 2 or xs.shape != ys.shape or xs.size == 0:
-            raise ValueError(f"dewarp: map must be a pair of arrays [H, W] of one shape, got {xs.shape} and {ys.shape}")
-        val = (xs, ys)
-    interp = dewarp.get("interp", DEWARP_DEFAULTS["interp"])
-    fill = dewarp.get("fill", DEWARP_DEFAULTS["fill"])
-    if not isinstance(interp, str) or interp not in _lib.DEWARP_INTERPS:
-        raise ValueError(f"dewarp: interp must be one of {sorted(_lib.DEWARP_INTERPS)}, got {interp!r}")
-    if isinstance(fill, (bool, np.bool_)) or not isinstance(fill, (int, np.integer)) or not 0 <= fill <= 255:
-        raise ValueError(f"dewarp: fill must be an integer in 0..255, got {fill!r}")
-    return {form: val, "interp": interp, "fill": int(fill)}
 
 
 def _dewarp_form(arg):
@@ -1655,40 +1111,6 @@ def dewarp(frames, map, interp="cubic", fill=0, offsets=None, shape=None, out=No
     return out
 
 
-DEFORM_DEFAULTS = {"iterations": 3, "interp": "cubic", "smooth": True}
-DEFORM_MAX_ITERATIONS = 8
-
-
-def deform_arg(deform):
-    """The deform= argument of Plan / OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None or 0 (off), an
-    integer 1..8 (that many rounds of image deformation behind the last pass at DEFORM_DEFAULTS) or a dict with any of
-    iterations (0..8), interp ("cubic" or "linear") and smooth (bool: the 3 x 3 binomial on the predictor).  Returns None
-    (off) or the full parameter dict; anything else raises ValueError."""
-    if deform is None:
-        return None
-    if isinstance(deform, (bool, np.bool_)):
-        raise ValueError(f"deform: None, an integer 0..{DEFORM_MAX_ITERATIONS} or a dict of {sorted(DEFORM_DEFAULTS)}, got {deform!r}")
-    if isinstance(deform, (int, np.integer)):
-        deform = {"iterations": deform}
-    if not isinstance(deform, dict):
-        raise ValueError(f"deform: None, an integer 0..{DEFORM_MAX_ITERATIONS} or a dict of {sorted(DEFORM_DEFAULTS)}, "
-                         f"got {type(deform).__name__}")
-    unknown = sorted(set(deform) - set(DEFORM_DEFAULTS), key=str)
-    if unknown:
-        raise ValueError(f"deform: unknown key(s) {unknown}; known: {sorted(DEFORM_DEFAULTS)}")
-    par = dict(DEFORM_DEFAULTS, **deform)
-    n = par["iterations"]
-    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 0 <= n <= DEFORM_MAX_ITERATIONS:
-        raise ValueError(f"deform: iterations must be an integer in 0..{DEFORM_MAX_ITERATIONS}, got {n!r}")
-    if not isinstance(par["interp"], str) or par["interp"] not in _lib.DEWARP_INTERPS:
-        raise ValueError(f"deform: interp must be one of {sorted(_lib.DEWARP_INTERPS)}, got {par['interp']!r}")
-    if not isinstance(par["smooth"], (bool, np.bool_)):
-        raise ValueError(f"deform: smooth must be a bool, got {par['smooth']!r}")
-    if n == 0:
-        return None
-    return {"iterations": int(n), "interp": par["interp"], "smooth": bool(par["smooth"])}
-
-
 def _fields3(who, u, v, inv):
     _need_cuda(u, v, inv)
     if u.dtype != torch.float64 or v.dtype != torch.float64 or inv.dtype != torch.uint8:
@@ -1830,32 +1252,26 @@ class Plan:
         # deform: None, an integer or a dict (deform_arg): that many rounds of image deformation behind the last pass -- the
         # frames warped by the dense field, the first pass on the warped frames, the residual added (tpiv_plan_set_deform);
         # deform_stage() and deform_ms() read what the last round left and what the rounds cost
-        self.outlier = outlier_arg(outlier)
-        self.mask = mask_arg(mask)
-        self.deform = deform_arg(deform)
-        self.uncertainty_par = uncertainty_arg(uncertainty)
         # ensemble: sum-of-correlation passes next to run() -- ensemble_begin / _add / _end, run_ensemble
         # (tpiv_plan_set_ensemble); window sizes 16, 32, 64 only, and neither uncertainty= nor deform=
-        self.ensemble = bool(ensemble)
-        if self.ensemble:
-            ensemble_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], self.uncertainty_par, self.deform)
         # correlation: None, "phase", "rpc" or a dict (correlation_arg): every pass takes its peak from the phase-only /
         # robust-phase-correlation map instead of the plain cross-correlation (tpiv_plan_set_correlation); window sizes 16,
         # 32, 64 only, neither uncertainty= nor deform= nor ensemble=, and `precision` has no effect on such a plan
-        self.correlation = correlation_arg(correlation)
-        if self.correlation is not None:
-            correlation_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], mode, self.uncertainty_par, self.deform,
-                              self.ensemble)
         # weighting: None, "gaussian", "uniform" or a dict (weighting_arg): every pass multiplies its windows by a separable
         # weight in front of the transform (tpiv_plan_set_weighting); window sizes 16, 32, 64 only, neither uncertainty= nor
         # ensemble= nor correlation=; combines with deform= (the residual passes are weighted too), and `precision` has no
         # effect on such a plan
+        self.outlier = outlier_arg(outlier)
+        self.mask = mask_arg(mask)
+        self.deform = deform_arg(deform)
+        self.uncertainty_par = uncertainty_arg(uncertainty)
+        self.ensemble = bool(ensemble)
+        self.correlation = correlation_arg(correlation)
         self.weighting = weighting_arg(weighting)
-        if self.weighting is not None:
-            weighting_check([w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], mode, self.uncertainty_par, self.ensemble,
-                            self.correlation)
-        if self.mask is not None and tuple(self.mask["image"].shape) != (H, W):
-            raise ValueError(f"mask of shape {tuple(self.mask['image'].shape)} for frames of shape {(H, W)}")
+        refuse_all(dict(uncertainty=self.uncertainty_par, deform=self.deform, ensemble=self.ensemble or None,
+                        correlation=self.correlation, weighting=self.weighting),
+                   [w for w, _ in pass_sizes(ws, ov, n_pass, pass_scale)], mode)
+        mask_shape(self.mask, (H, W))
         if not torch.cuda.is_available():
             raise RuntimeError("torchpiv_amd.Plan needs a ROCm device (there is no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None \
@@ -1915,37 +1331,32 @@ class Plan:
         """Switches the plan's passes to the filtered map (correlation_arg's forms; None: back to the plain
         cross-correlation).  The tables are built here and uploaded once (tpiv_plan_set_correlation)."""
         par = correlation_arg(correlation)
-        with torch.cuda.device(self.device):
-            if par is None:
-                check(lib.tpiv_plan_set_correlation(self._h, _lib.CORR_NONE, 0.0, 0.0, 0.0, None, 0))
-            else:
-                sizes = []
-                for p in range(lib.tpiv_plan_n_pass(self._h)):
-                    w = C.c_int()
-                    check(lib.tpiv_plan_pass_geometry(self._h, p, C.byref(w), None, None, None))
-                    sizes.append(w.value)
-                tab = correlation_tables(par, sizes)
-                check(lib.tpiv_plan_set_correlation(self._h, _lib.CORRELATIONS[par["kind"]], par["dx"], par["dy"], par["floor"],
-                                                    tab.ctypes.data, tab.size))
+        self._set_tables(lib.tpiv_plan_set_correlation, correlation_tables, par,
+                         (_lib.CORR_NONE, 0.0, 0.0, 0.0) if par is None else
+                         (_lib.CORRELATIONS[par["kind"]], par["dx"], par["dy"], par["floor"]))
         self.correlation = par
 
     def set_weighting(self, weighting):
         """Switches the plan's passes to weighted windows (weighting_arg's forms; None: back to the plain passes).  The
         tables are built here and uploaded once (tpiv_plan_set_weighting)."""
         par = weighting_arg(weighting)
+        self._set_tables(lib.tpiv_plan_set_weighting, weighting_tables, par,
+                         (_lib.WEIGHT_NONE, 0.0, 0.0) if par is None else (_lib.WEIGHTINGS[par["kind"]], par["sx"], par["sy"]))
+        self.weighting = par
+
+    def _set_tables(self, setter, tables, par, head):
+        """setter(plan, *head, table, length): the table of tables(par, the window size of every pass), or none for par None."""
         with torch.cuda.device(self.device):
             if par is None:
-                check(lib.tpiv_plan_set_weighting(self._h, _lib.WEIGHT_NONE, 0.0, 0.0, None, 0))
-            else:
-                sizes = []
-                for p in range(lib.tpiv_plan_n_pass(self._h)):
-                    w = C.c_int()
-                    check(lib.tpiv_plan_pass_geometry(self._h, p, C.byref(w), None, None, None))
-                    sizes.append(w.value)
-                tab = weighting_tables(par, sizes)
-                check(lib.tpiv_plan_set_weighting(self._h, _lib.WEIGHTINGS[par["kind"]], par["sx"], par["sy"],
-                                                  tab.ctypes.data, tab.size))
-        self.weighting = par
+                check(setter(self._h, *head, None, 0))
+                return
+            sizes = []
+            for p in range(lib.tpiv_plan_n_pass(self._h)):
+                w = C.c_int()
+                check(lib.tpiv_plan_pass_geometry(self._h, p, C.byref(w), None, None, None))
+                sizes.append(w.value)
+            tab = tables(par, sizes)
+            check(setter(self._h, *head, tab.ctypes.data, tab.size))
 
     @property
     def out_shape(self):
