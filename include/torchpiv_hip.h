@@ -196,6 +196,39 @@ int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double ep
  * run, [batch, n_rows, n_cols] of that pass.  TPIV_EINVAL when the test is off. */
 int tpiv_plan_pass_outliers(const tpiv_plan* plan, int pass, uint8_t** status_dev);
 
+/* ---- local least-squares fit: denoised vectors and derivatives (extension; the reference has none) ---------- */
+
+/* Local polynomial regression of fields u, v float64 [batch, n_rows, n_cols] (Raffel et al., "least-squares operators"):
+ * per cell the fit's constant term is the denoised vector and its linear terms are the derivatives per cell spacing.
+ * skip_dev uint8 of the same shape or NULL: non-zero = the cell is not data.  radius in {1, 2, 3}, order in {1, 2}.
+ *
+ * A cell is DATA when its skip byte is 0 and both u and v are finite.  Per cell (R, C): S = the data cells (R + j, C + i)
+ * with |i|, |j| <= radius inside the grid (the centre included when it is data).  Basis, in this order:
+ *   phi_0 .. phi_5 = 1, i, j, i*i, i*j, j*j     (i: column offset, j: row offset, integers); n = 3 at order 1, 6 at order 2.
+ * Moments: the integers sum_S i^a j^b, summed in int32, each converted to float64 once (exact); M[p][q] = sum_S phi_p phi_q.
+ * Right-hand sides, per component w of (u, v): b[q] starts at +0.0 and takes b[q] = b[q] + w * (double)phi_q(i, j) -- one
+ * product, one add -- for the cells of S in row-major order (j outer, i inner, both ascending).
+ * LDL^T of M without pivoting, the right-hand sides riding along, A = M, on the lower triangle:
+ *   for k = 0 .. n-1:  d[k] = A[k][k];   pivot k is accepted when d[k] > 2^-30 * M[k][k] (one product, one compare);
+ *     for q = k+1 .. n-1:  l = A[q][k] / d[k];   for s = k+1 .. q: A[q][s] = A[q][s] - l * A[s][k];
+ *                          b[q] = b[q] - l * b[k];   L[q][k] = l;
+ *   y[k] = b[k] / d[k];
+ *   back substitution over m unknowns, k = m-1 .. 0:  t = y[k];  for q = k+1 .. m-1: t = t - L[q][k] * c[q];  c[k] = t.
+ * The ladder: order 2 asked and pivots 0..5 all accepted -> m = 6, order_dev = 2; else pivots 0..2 all accepted -> m = 3 on
+ * the shared leading block, order_dev = 1; else |S| >= 1 -> c0 = b[0] / (double)|S| (b[0] as summed, one division), order_dev
+ * = 0; else order_dev = -1.  (Over 5 000 random validity patterns per radius a full-rank M keeps every d[k] / M[k][k]
+ * >= 7.7e-6 and a rank-deficient one has its first failing pivot <= 3.3e-14: the threshold sits in the gap)
+ * fit_dev float64 [6, batch, n_rows, n_cols] = the planes U, Ux, Uy, V, Vx, Vy = c0, c1, c2 of u, then of v; the slopes are
+ * NaN at order_dev <= 0 and everything is NaN at -1 (the NaN written is 0x7ff8000000000000).  count_dev uint8 = |S|.
+ * order_dev int8.  The fit is evaluated at every cell, skipped ones included (from their neighbours).
+ * Every floating-point operation is one IEEE float64 + - * / in the order written (no contraction, no square root), so a
+ * host model that does the same gives the same bits -- for data whose sums stay finite; beyond that nothing is promised
+ * except that nothing faults.  TPIV_EINVAL, nothing launched: a null u, v, fit, count or order pointer, n_rows or n_cols < 1,
+ * batch < 0, radius or order outside their sets, an output that overlaps an input or another output, batch * n_rows * n_cols
+ * >= 2^31.  batch == 0 succeeds and launches nothing.  Enqueues only; allocates nothing. */
+int tpiv_field_fit(const double* u_dev, const double* v_dev, const uint8_t* skip_dev, int batch, int n_rows, int n_cols,
+                   int radius, int order, double* fit_dev, uint8_t* count_dev, int8_t* order_dev, void* stream);
+
 /* ---- geometric mask (extension; the reference has none) ------------------------------------------ */
 
 /* Pixel step: out_dev[f][p] = mask_dev[p] != 0 ? 0 : frames_dev[f][p] for n frames [n, pixels] uint8 against one image

@@ -7,8 +7,8 @@ arrays as dtype, shape and a hash of their bytes, exceptions as class name and m
 import hashlib, inspect, itertools, json, os, re, sys, tempfile
 
 PARSERS = ("correlation_arg", "weighting_arg", "outlier_arg", "uncertainty_arg", "mask_arg", "dynamic_mask_arg", "prefilter_arg",
-           "equalize_arg", "depth_arg", "dewarp_arg", "deform_arg")
-HOST_TESTS = ("background", "deform", "depth", "dewarp", "dynmask", "ensemble", "equalize", "frame_chain", "mask", "outlier",
+           "equalize_arg", "depth_arg", "dewarp_arg", "deform_arg", "derive_arg")
+HOST_TESTS = ("background", "deform", "depth", "derive", "dewarp", "dynmask", "ensemble", "equalize", "frame_chain", "mask", "outlier",
               "phase", "prefilter", "uncertainty", "weighting")                 # tests/test_<name>_host.py
 FEATURES = {"uncertainty": "cs", "deform": 2, "ensemble": True, "correlation": "rpc", "weighting": "gaussian",
             "dynamic_mask": {"kind": "bright", "size": 5, "level": 200}}
@@ -122,8 +122,8 @@ def dump(path, tree):
 
     def resident(a=frames, b=frames, **kw):
         return backend.ResidentPIV(a, b, 32, 16, **kw)
-    bad = {"background": "x", "outlier": "x", "depth": "x", "mask": 5, "dewarp": "x", "uncertainty": "x", "deform": "x",
-           "correlation": "x", "weighting": "x", "dynamic_mask": "x", "equalize": "x", "prefilter": "x", "precision": "x"}
+    bad = {"background": "x", "outlier": "x", "depth": "x", "mask": 5, "dewarp": "x", "uncertainty": "x", "derive": "x",
+           "deform": "x", "correlation": "x", "weighting": "x", "dynamic_mask": "x", "equalize": "x", "prefilter": "x", "precision": "x"}
     small = np.zeros((8, 8), np.uint8)
     for k, v in bad.items():
         out[f"single/offline {k}"] = outcome(offline, **{k: v})

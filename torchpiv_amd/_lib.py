@@ -81,6 +81,7 @@ SIGNATURES = {
     "tpiv_plan_pass_fields": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p)]),
     "tpiv_median_test": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _dbl, _dbl, _int, _u8p, _f64p, _f64p, _vp]),
+    "tpiv_field_fit": (C.c_int, [_f64p, _f64p, _u8p, _int, _int, _int, _int, _int, _f64p, _u8p, _vp, _vp]),
     "tpiv_plan_set_outlier": (C.c_int, [C.c_void_p, _int, _dbl, _dbl, _int]),
     "tpiv_plan_pass_outliers": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p)]),
     "tpiv_apply_mask": (C.c_int, [_u8p, _int, C.c_longlong, _u8p, _u8p, _vp]),

@@ -341,8 +341,8 @@ class OfflinePIV:
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., folder_mode: str = "pairs", precision: str = "exact",
                  validation_ratio: float = 1.2, validation_window: int = 3, background=None, outlier=None,
-                 depth=None, mask=None, dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None,
-                 dynamic_mask=None, equalize=None, prefilter=None) -> None:
+                 depth=None, mask=None, dewarp=None, uncertainty=None, derive=None, deform=None, correlation=None,
+                 weighting=None, dynamic_mask=None, equalize=None, prefilter=None) -> None:
         # precision (extension, keyword after the reference's arguments).  "exact" (default): as "f64", with the map cells
         # that reach the result of a 64x64 first pass evaluated as exact integer correlation sums instead of through a
         # float64 FFT (csrc/xcorr_exact.hip: within 1e-14 px of the reference's float64 pass 1, about 1.5x the rate of
@@ -394,6 +394,15 @@ class OfflinePIV:
         # (i, x, y, u, v, su, sv): su, sv are flipped and scaled like u, v (no sign change), and NaN where the last pass's
         # vector was invalid (the delivered value is an interpolation), in mask-excluded cells and where the correlation
         # peak gives no estimate.
+        # derive (extension): None, one name of engine.DERIVE_QUANTITIES, a tuple or list of them, or a dict with
+        # "quantities" and any of radius (1..3) and order (1, 2) (engine.derive_arg) -- derivatives of every delivered field on
+        # the device: a least-squares polynomial fit over the (2 radius + 1)^2 neighbourhood of every cell that leaves out
+        # the excluded cells of mask= / dynamic_mask= and non-finite vectors (engine.field_fit, tpiv_field_fit), then the
+        # slopes dudx .. dvdy, vorticity, divergence, shear, q, swirl in 1/s (q: 1/s^2) and the fit's own value u_smooth,
+        # v_smooth (engine.derive).  The fit runs on the fields as delivered -- filled, flipped, signed, scaled -- with the
+        # steps of the delivered x, y.  When set, every delivered tuple gains ONE trailing element, a dict {name: float64
+        # [n_rows, n_cols]} in the order asked for: __call__ yields (x, y, u, v[, su, sv], d), batched() (i, x, y, u, v[, su,
+        # sv], d), ensemble() returns (x, y, u, v, d).  Every quantity is NaN in excluded cells (no fill value applies).
         # deform (extension): None, an integer 1..8 or a dict with any of iterations, interp ("cubic" / "linear") and smooth
         # -- that many rounds of iterative image deformation behind the last pass (engine.deform_arg, tpiv_plan_set_deform):
         # both frames are warped by the dense field of the last pass, the first pass measures the residual on the warped
@@ -433,7 +442,8 @@ class OfflinePIV:
                    validation_window=validation_window)
         opts = options.parse_options(run, stack=False, background=background, outlier=outlier, prefilter=prefilter,
                                      depth=depth, equalize=equalize, mask=mask, dewarp=dewarp, uncertainty=uncertainty,
-                                     deform=deform, correlation=correlation, weighting=weighting, dynamic_mask=dynamic_mask)
+                                     derive=derive, deform=deform, correlation=correlation, weighting=weighting,
+                                     dynamic_mask=dynamic_mask)
         device = DeviceMap.devicies[device]                             # KeyError like B:845
         dataset = PIVDataset(folder, file_fmt, folder_mode, deep=opts.depth is not None,
                              transform=ToTensor(dtype=torch.uint8 if opts.depth is None else torch.uint16))
@@ -452,7 +462,7 @@ class OfflinePIV:
     def _init_state(self, device, dataset, iter_function, run, opts):
         """Every attribute of an object, for both constructors: the run parameters (run: a dict of wind_size, overlap,
         multipass, multipass_mode, dt, scale, multipass_scale, precision, validation_ratio and validation_window), the
-        twelve keywords as options.parse_options checked them (opts: an options.Options record), and the state that the methods
+        thirteen keywords as options.parse_options checked them (opts: an options.Options record), and the state that the methods
         build up, empty."""
         self._device, self._dataset, self._iter_function = device, dataset, iter_function
         self._wind_size, self._overlap, self._dt = run["wind_size"], run["overlap"], run["dt"]
@@ -463,6 +473,7 @@ class OfflinePIV:
         self._outlier, self._prefilter, self._equalize = opts.outlier, opts.prefilter, opts.equalize
         self._mask, self._dewarp, self._uncertainty = opts.mask, opts.dewarp, opts.uncertainty
         self._depth = depth = opts.depth
+        self._derive = opts.derive            # the delivered tuples gain a dict of derived fields (_derived)
         self._deform = opts.deform            # handed to every plan
         self._correlation = opts.correlation  # handed to every plan but ensemble()'s
         self._weighting = opts.weighting      # handed to every plan but ensemble()'s
@@ -1233,12 +1244,46 @@ class OfflinePIV:
                 return out
         return Pipe()
 
+    def _derived(self, U, V, skip, xs, ys, plan=None):
+        """derive=: {name: field} of the finished fields U, V -- stacks [n, n_rows, n_cols] or one pair [n_rows, n_cols],
+        device tensors (read in place; the results stay on the device) or numpy arrays (one upload of the two stacks, one
+        copy down of all quantities).  skip: the excluded cells as delivered, a device tensor of the fields' shape or of
+        one grid, bool or uint8, or None; every quantity is NaN there.  xs, ys: the delivered coordinates, whose steps
+        scale the slopes (a grid of one column / row: the nominal step of the last pass)."""
+        par = self._derive
+        host = not isinstance(U, torch.Tensor)
+        if host:
+            UV = torch.from_numpy(np.stack([U, V])).to(self._device)
+            U, V = UV[0], UV[1]
+        one = U.dim() == 2
+        if one:
+            U, V = U[None], V[None]
+        if skip is not None:
+            skip = skip.to(torch.uint8).expand(U.shape[0], -1, -1).contiguous()
+        if plan is not None:
+            w, o = plan.geometry[-1][:2]
+        else:
+            w, o = options.pass_sizes(self._wind_size, self._overlap, self._iter, self._iter_scale)[-1]
+        nominal = (w - o) * self._scale
+        hx = float(xs[0, 1] - xs[0, 0]) if xs.shape[1] > 1 else nominal
+        hy = float(ys[1, 0] - ys[0, 0]) if ys.shape[0] > 1 else nominal
+        got = engine.derive(engine.field_fit(U, V, skip, par["radius"], par["order"]), hx, hy, par["quantities"])
+        stack = torch.stack([got[k] for k in par["quantities"]])
+        if skip is not None:
+            stack.masked_fill_(skip.bool()[None], float("nan"))
+        if one:
+            stack = stack[:, 0]
+        if host:
+            stack = stack.cpu().numpy()
+        return {k: stack[q] for q, k in enumerate(par["quantities"])}
+
     def _finish_batch(self, state, x, y, plan=None):
         """The finished tuples of a batch: the device has flipped and scaled the fields (_post_submit), the host stage has
         patched the filled cells (_post_complete); what is left is ONE copy of the two stacks out of the pinned staging
         memory (so that results a caller keeps do not pin pages) and the per-pair views.  Returns per pair None or
-        (x, y, u, v); x, y are one pair of read-only arrays per batch (the reference makes fresh copies per pair; a caller
-        that wants to write into them copies first)."""
+        (x, y, u, v), with uncertainty= followed by su, sv and with derive= closed by its dict; x, y are one pair of
+        read-only arrays per batch (the reference makes fresh copies per pair; a caller that wants to write into them
+        copies first)."""
         keep = state["keep_final"]
         if not keep.any():
             return [None] * keep.size
@@ -1269,6 +1314,19 @@ class OfflinePIV:
         xs, ys = x * self._scale, y * self._scale
         xs.flags.writeable = False
         ys.flags.writeable = False
+        if self._derive is not None:
+            # derive=: from the stacks as they are delivered, fills and fill values included; the excluded cells are read
+            # from their device copies (dynamic_mask=: every pair's own grid; mask=: the one grid)
+            skip = state["dev"].get("excluded")
+            if skip is None and self._mask is not None and plan is not None:
+                skip = self._fill_grid(plan)[1]
+            D = self._derived(U, V, skip, xs, ys, plan)
+            sig = ()
+            if "fsu" in state["host"]:
+                sig = (state["dev"]["fsu"], state["dev"]["fsv"]) if self.device_out else \
+                    (np.array(state["host"]["fsu"].numpy()), np.array(state["host"]["fsv"].numpy()))
+            return [(xs, ys, U[k], V[k]) + tuple(s_[k] for s_ in sig) + ({q: f[k] for q, f in D.items()},) if keep[k] else None
+                    for k in range(keep.size)]
         if "fsu" in state["host"]:
             # uncertainty=: beside the fields, NaN in the excluded cells too (the kernel wrote them; no fill value)
             if self.device_out:
@@ -1278,15 +1336,23 @@ class OfflinePIV:
             return [(xs, ys, U[k], V[k], SU[k], SV[k]) if keep[k] else None for k in range(keep.size)]
         return [(xs, ys, U[k], V[k]) if keep[k] else None for k in range(keep.size)]
 
-    def _finish(self, uv, x, y, plan=None, sigma=None, excluded=None):
+    def _finish(self, uv, x, y, plan=None, sigma=None, excluded=None, derive=True):
         """Flip and unit scaling of B:894-898 (numpy, the reference's own expressions); then, with mask=, the fill value
         into the excluded cells of the plan's last pass.  sigma: the raw (su, sv) of uncertainty=, which take the flip and
-        the scaling, no sign and no fill, and follow u, v in the tuple."""
+        the scaling, no sign and no fill, and follow u, v in the tuple.  derive=: its dict closes the tuple."""
         if uv is None:
             return None
+        if derive and self._derive is not None:
+            out = self._finish(uv, x, y, plan=plan, sigma=sigma, excluded=excluded, derive=False)
+            skip = None
+            if excluded is not None:
+                skip = torch.from_numpy(np.ascontiguousarray(excluded)).to(self._device)
+            elif self._mask is not None and plan is not None:
+                skip = self._fill_grid(plan)[1]
+            return out + (self._derived(out[2], out[3], skip, out[0], out[1], plan),)
         if sigma is not None:
             su, sv = (np.flip(s_, axis=0) * self._scale / self._dt * 1000 for s_ in sigma)
-            return self._finish(uv, x, y, plan=plan, excluded=excluded) + (su, sv)
+            return self._finish(uv, x, y, plan=plan, excluded=excluded, derive=False) + (su, sv)
         u, v = uv
         u = np.flip(u, axis=0)
         v = -np.flip(v, axis=0)
@@ -1392,7 +1458,10 @@ class OfflinePIV:
                     out = next(res) if staged else self._one(i)
                     if out is not None:
                         if self.device_out and not staged:      # the one-pair path finishes on the host
-                            out = out[:2] + tuple(torch.from_numpy(np.ascontiguousarray(f)).to(dev) for f in out[2:])
+                            def up(f):
+                                return torch.from_numpy(np.ascontiguousarray(f)).to(dev)
+                            out = out[:2] + tuple({k: up(q) for k, q in f.items()} if isinstance(f, dict) else up(f)
+                                                  for f in out[2:])
                         yield (i,) + out
 
         # uploads run on their own stream into a double-buffered device copy of the staging slots, so that the PCIe
@@ -1491,8 +1560,8 @@ class ResidentPIV(OfflinePIV):
                  multipass: int = 1, multipass_mode: str = "CWS", dt: int = 1, scale: float = 1.,
                  multipass_scale: float = 2., precision: str = "exact", validation_ratio: float = 1.2,
                  validation_window: int = 3, background=None, outlier=None, depth=None, mask=None,
-                 dewarp=None, uncertainty=None, deform=None, correlation=None, weighting=None, dynamic_mask=None,
-                 equalize=None, prefilter=None) -> None:
+                 dewarp=None, uncertainty=None, derive=None, deform=None, correlation=None, weighting=None,
+                 dynamic_mask=None, equalize=None, prefilter=None) -> None:
         # dewarp (see OfflinePIV): every launch rectifies its pairs into a reused buffer, addressed by their offsets in the
         # caller's stacks (nothing is gathered first, and the caller's frames are never written)
         # depth (see OfflinePIV): the frames are uint16 stacks if and only if it is given; they stay as they are and every
@@ -1515,7 +1584,8 @@ class ResidentPIV(OfflinePIV):
                    validation_window=validation_window)
         opts = options.parse_options(run, frames_a.shape, background=background, outlier=outlier, prefilter=prefilter,
                                      depth=depth, equalize=equalize, mask=mask, dewarp=dewarp, uncertainty=uncertainty,
-                                     deform=deform, correlation=correlation, weighting=weighting, dynamic_mask=dynamic_mask)
+                                     derive=derive, deform=deform, correlation=correlation, weighting=weighting,
+                                     dynamic_mask=dynamic_mask)
         device = _require_gpu(frames_a.device)
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], run, opts)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()

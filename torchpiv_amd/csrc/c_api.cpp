@@ -946,6 +946,37 @@ int tpiv_median_test(const double* u, const double* v, const uint8_t* invalid, i
                            nullptr, (hipStream_t)stream);
 }
 
+int tpiv_field_fit(const double* u, const double* v, const uint8_t* skip, int batch, int n_rows, int n_cols, int radius,
+                   int order, double* fit, uint8_t* count, int8_t* order_out, void* stream) {
+    if (batch < 0 || n_rows < 1 || n_cols < 1) return fail(TPIV_EINVAL, "tpiv_field_fit: empty grid");
+    if (radius < 1 || radius > 3) return fail(TPIV_EINVAL, "tpiv_field_fit: radius must be 1, 2 or 3");
+    if (order < 1 || order > 2) return fail(TPIV_EINVAL, "tpiv_field_fit: order must be 1 or 2");
+    if (!u || !v || !fit || !count || !order_out) return fail(TPIV_EINVAL, "tpiv_field_fit: null pointer");
+    if ((long long)batch * n_rows * n_cols >= (1LL << 31)) return fail(TPIV_EINVAL, "tpiv_field_fit: field stack too large");
+    if (batch == 0) return TPIV_OK;
+    const size_t cells = (size_t)batch * n_rows * n_cols;
+    const Span in[3] = {{u, cells * 8}, {v, cells * 8}, {skip, cells}};
+    const Span out[3] = {{fit, 6 * cells * 8}, {count, cells}, {order_out, cells}};
+    if (const int k = aliased(in, 3, out, 3))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_field_fit: an output aliases an input" : "tpiv_field_fit: two outputs overlap");
+    if (batch > 65535 || (n_rows + tpiv::FIELDFIT_TILE_ROWS - 1) / tpiv::FIELDFIT_TILE_ROWS > 65535)
+        return fail(TPIV_EUNSUPPORTED, "tpiv_field_fit: more than 65535 pairs or tile rows in one call");
+    tpiv::FieldFitParams q{};
+    q.u = u;
+    q.v = v;
+    q.skip = skip;
+    q.batch = batch;
+    q.n_rows = n_rows;
+    q.n_cols = n_cols;
+    q.radius = radius;
+    q.order_max = order;
+    q.fit = fit;
+    q.count = count;
+    q.order = order_out;
+    hipError_t he = tpiv::launch_field_fit(q, (hipStream_t)stream);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_field_fit");
+}
+
 int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double eps, int min_neighbours) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
     if (kind != 0 && kind != 1) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: kind must be 0 (off) or 1 (normalized median)");

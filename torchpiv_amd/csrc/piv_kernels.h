@@ -217,6 +217,22 @@ struct OutlierParams {
 };
 hipError_t launch_median_test(const OutlierParams& p, hipStream_t stream);
 
+// local least-squares fit of vector fields (fieldfit.hip, defined in include/torchpiv_hip.h: tpiv_field_fit): one lane per
+// cell, one workgroup per FIELDFIT_TILE_COLS x FIELDFIT_TILE_ROWS tile, the tile and its `radius` halo staged in LDS
+constexpr int FIELDFIT_TILE_COLS = 64, FIELDFIT_TILE_ROWS = 8;
+struct FieldFitParams {
+    const double* u;         // [batch, n_rows, n_cols]
+    const double* v;
+    const uint8_t* skip;     // optional: non-zero = not data
+    int batch, n_rows, n_cols;
+    int radius;              // 1..3
+    int order_max;           // 1 or 2: the order asked for
+    double* fit;             // out [6, batch, n_rows, n_cols]: U, Ux, Uy, V, Vx, Vy
+    uint8_t* count;          // out: data cells used
+    int8_t* order;           // out: the order fitted, 2 / 1 / 0 / -1; none of the outputs may alias an input
+};
+hipError_t launch_field_fit(const FieldFitParams& p, hipStream_t stream);
+
 // geometric mask (mask.hip, defined in include/torchpiv_hip.h).  apply: out = mask ? 0 : frames for n frames against one
 // image (out may be frames itself).  coverage: a wavefront per window of the (ws, ov) grid counts its masked pixels into count
 // (optional) and writes grid = count > limit (optional).  fields: u = v = +0.0, invalid = invalid_value, status = 2 (optional)

@@ -182,11 +182,14 @@ def shard_background(piv, indices, group=None):
 def run_sharded(piv, batch_size: int = 32, policy: str = "block", group=None):
     """Process an OfflinePIV dataset across all ranks.  Every rank runs its shard through
     piv.batched(); rank 0 returns (ids, x, y, uv[n, 2, R, S]) for the pairs that survived,
-    in dataset order; other ranks return None.  An object with uncertainty= yields longer tuples, which are not
-    gathered: ValueError."""
+    in dataset order; other ranks return None.  An object with uncertainty= or derive= yields longer tuples, which are
+    not gathered: ValueError."""
     import numpy as np
     if getattr(piv, "_uncertainty", None) is not None:
         raise ValueError("run_sharded: uncertainty= is not gathered across ranks; run without it, or use batched() per rank")
+    if getattr(piv, "_derive", None) is not None:
+        raise ValueError("run_sharded: derive= is not gathered across ranks (the gather carries two planes per pair); run "
+                         "without it, or use batched() per rank")
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     mine = shard_indices(len(piv), rank, world, policy)

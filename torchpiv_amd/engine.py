@@ -402,6 +402,85 @@ def median_test(u, v, inv, threshold=2.0, eps=0.1, min_neighbours=3, want_median
     return (status, mu, mv) if want_medians else status
 
 
+FIELD_FIT_TILE = (8, 64)         # rows, columns of the cells a workgroup of tpiv_field_fit covers (csrc/piv_kernels.h)
+
+
+def field_fit(u, v, skip=None, radius=2, order=2):
+    """Local least-squares polynomial fit (tpiv_field_fit) of fields u, v float64 [batch, n_rows, n_cols] (or [n_rows,
+    n_cols]) on the GPU over the (2 radius + 1)^2 neighbourhood of every cell, radius 1..3, order 1 or 2; skip (uint8,
+    optional, the same shape): non-zero = the cell is not data, as is a cell whose u or v is not finite.  Returns (fit,
+    count, order): fit float64 [6, batch, n_rows, n_cols] = the planes U, Ux, Uy, V, Vx, Vy (the denoised vector and its
+    slopes per cell spacing along the columns and the rows), count uint8 = the data cells used, order int8 = the order
+    fitted (2, 1, 0: the mean, -1: nothing, all NaN).  A 2-D input gives outputs without the batch axis.  The inputs are not
+    written."""
+    _need_cuda(u, v, skip)
+    if u.dtype != torch.float64 or v.dtype != torch.float64 or (skip is not None and skip.dtype != torch.uint8):
+        raise TypeError("field_fit: u, v float64 and skip uint8")
+    if u.dim() not in (2, 3) or u.shape != v.shape or (skip is not None and skip.shape != u.shape):
+        raise ValueError("field_fit: [batch, n_rows, n_cols] or [n_rows, n_cols] tensors of one shape")
+    par = derive_arg({"quantities": DERIVE_QUANTITIES[0], "radius": radius, "order": order})
+    flat = u.dim() == 2
+    if flat:
+        u, v = u[None], v[None]
+        skip = None if skip is None else skip[None]
+    u, v = u.contiguous(), v.contiguous()
+    skip = None if skip is None else skip.contiguous()
+    B, nr, nc = u.shape
+    fit = torch.empty(6, B, nr, nc, dtype=torch.float64, device=u.device)
+    count = torch.empty(B, nr, nc, dtype=torch.uint8, device=u.device)
+    fitted = torch.empty(B, nr, nc, dtype=torch.int8, device=u.device)
+    with torch.cuda.device(u.device):
+        check(lib.tpiv_field_fit(u.data_ptr(), v.data_ptr(), None if skip is None else skip.data_ptr(), B, nr, nc,
+                                 par["radius"], par["order"], fit.data_ptr(), count.data_ptr(), fitted.data_ptr(), _stream()))
+    return (fit[:, 0], count[0], fitted[0]) if flat else (fit, count, fitted)
+
+
+def derive(fit, hx, hy, quantities=DERIVE_QUANTITIES):
+    """The quantities of DERIVE_QUANTITIES named in `quantities` from field_fit's planes (fit, or the tuple field_fit
+    returns): {name: float64 tensor}, elementwise on fit's device.  hx, hy: the signed grid steps along the columns and the
+    rows in millimetres; with fields in m/s the slopes dudx = Ux / (hx / 1000), dudy = Uy / (hy / 1000), dvdx, dvdy come out
+    in 1/s.  vorticity = dvdx - dudy, divergence = dudx + dvdy, shear = dvdx + dudy, q = -0.5 (dudx dudx + 2 dudy dvdx + dvdy
+    dvdy), swirl = sqrt(max(0, dudx dvdy - dudy dvdx - 0.25 (dudx + dvdy)^2)) (the imaginary part of the complex eigenvalue
+    of the gradient tensor), u_smooth = U, v_smooth = V.  Every expression left to right as written, one float64 operation
+    each."""
+    if isinstance(fit, (tuple, list)):
+        fit = fit[0]
+    names = derive_arg({"quantities": tuple(quantities) if isinstance(quantities, list) else quantities})["quantities"]
+    if not isinstance(fit, torch.Tensor) or fit.dtype != torch.float64:
+        raise TypeError("derive: fit float64, the planes of field_fit")
+    if fit.dim() < 1 or fit.shape[0] != 6:
+        raise ValueError("derive: fit holds the six planes U, Ux, Uy, V, Vx, Vy")
+    if not is_real(hx) or not is_real(hy) or not hx or not hy or hx != hx or hy != hy:
+        raise ValueError(f"derive: hx, hy must be non-zero numbers (millimetres), got {hx!r}, {hy!r}")
+    U, Ux, Uy, V, Vx, Vy = fit.unbind(0)
+    # (the steps as tensors on fit's device: torch divides by a host scalar as a product with its reciprocal, which is not
+    #  the correctly rounded quotient)
+    sx = torch.full((), float(hx) / 1000, dtype=torch.float64, device=fit.device)
+    sy = torch.full((), float(hy) / 1000, dtype=torch.float64, device=fit.device)
+    made = {"u_smooth": U, "v_smooth": V}
+
+    def get(name):
+        if name in made:
+            return made[name]
+        if name in ("dudx", "dudy", "dvdx", "dvdy"):
+            out = {"dudx": Ux, "dudy": Uy, "dvdx": Vx, "dvdy": Vy}[name] / (sx if name[-1] == "x" else sy)
+        elif name == "vorticity":
+            out = get("dvdx") - get("dudy")
+        elif name == "divergence":
+            out = get("dudx") + get("dvdy")
+        elif name == "shear":
+            out = get("dvdx") + get("dudy")
+        elif name == "q":
+            out = (get("dudx") * get("dudx") + 2.0 * get("dudy") * get("dvdx") + get("dvdy") * get("dvdy")) * -0.5
+        else:
+            s = get("dudx") + get("dvdy")
+            disc = get("dudx") * get("dvdy") - get("dudy") * get("dvdx") - (s * s) * 0.25
+            out = torch.sqrt(torch.where(disc < 0, torch.zeros_like(disc), disc))     # (a NaN stays NaN)
+        made[name] = out
+        return out
+    return {name: get(name) for name in names}
+
+
 def uncertainty(a, b, u, v, ws, ov, invalid=None, radius=3, want_stats=False):
     """Correlation-statistics uncertainty (Wieneke 2015; tpiv_uncertainty) of fields u, v float64 [batch, n_rows, n_cols] (or
     [n_rows, n_cols]) at geometry (ws, ov) on frames a, b uint8 [batch, H, W] (or [H, W]) on the GPU: the 1-sigma random

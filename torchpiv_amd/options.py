@@ -2,7 +2,7 @@
 parsers on one front end (_front), the table of what does not combine (EXCLUSIONS) and the record of the parsed values.
 
 parse_options checks the keywords in one order for both constructors: depth, background, outlier, prefilter, equalize, mask,
-uncertainty, deform, correlation, weighting, what these refuse to combine, dynamic_mask, dewarp -- OfflinePIV checks
+uncertainty, derive, deform, correlation, weighting, what these refuse to combine, dynamic_mask, dewarp -- OfflinePIV checks
 precision in front of them and looks up its device and opens its dataset behind them; ResidentPIV checks depth against the
 frames' dtype and precision in front of them and asks for the GPU last.
 """
@@ -206,6 +206,43 @@ def uncertainty_arg(uncertainty):
     if not is_int(R) or not 0 <= R <= UNCERTAINTY_MAX_RADIUS:
         raise ValueError(f"uncertainty: radius must be an integer in 0..{UNCERTAINTY_MAX_RADIUS}, got {R!r}")
     return {"kind": "cs", "radius": int(R)}
+
+
+DERIVE_QUANTITIES = ("dudx", "dudy", "dvdx", "dvdy", "vorticity", "divergence", "shear", "q", "swirl", "u_smooth", "v_smooth")
+DERIVE_DEFAULTS = {"radius": 2, "order": 2}
+DERIVE_RADII, DERIVE_ORDERS = (1, 2, 3), (1, 2)
+_DERIVE = dict(name="derive", keys=["order", "quantities", "radius"], defaults=DERIVE_DEFAULTS, wrap="quantities")
+
+
+def derive_arg(derive):
+    """The derive= argument of OfflinePIV / ResidentPIV / run_folder, checked (no GPU involved): None (nothing derived), one
+    name of DERIVE_QUANTITIES, a tuple or list of them (each once), or a dict with "quantities" (a name or a tuple / list)
+    and any of radius (1, 2 or 3: the fit takes the (2 radius + 1)^2 neighbourhood) and order (1 or 2: the polynomial),
+    defaults DERIVE_DEFAULTS (include/torchpiv_hip.h: tpiv_field_fit has the operator).  Returns None or {"quantities":
+    tuple, "radius": int, "order": int}; anything else raises ValueError."""
+    _, par = _front(derive, **_DERIVE)
+    if par is None:
+        return None
+    if "quantities" not in par:
+        raise ValueError(f"derive: the dict needs 'quantities' (names out of {list(DERIVE_QUANTITIES)})")
+    names = par["quantities"]
+    if isinstance(names, str):
+        names = (names,)
+    if not isinstance(names, (tuple, list)) or not names:
+        raise ValueError(f"derive: None, a name, a tuple or list of names or a dict of {_DERIVE['keys']}, got "
+                         f"{par['quantities']!r}")
+    for q in names:
+        if not isinstance(q, str) or q not in DERIVE_QUANTITIES:
+            raise ValueError(f"derive: unknown quantity {q!r}; known: {list(DERIVE_QUANTITIES)}")
+    twice = sorted({q for q in names if list(names).count(q) > 1})
+    if twice:
+        raise ValueError(f"derive: {twice} named more than once")
+    radius, order = par["radius"], par["order"]
+    if not is_int(radius) or radius not in DERIVE_RADII:
+        raise ValueError(f"derive: radius must be 1, 2 or 3, got {radius!r}")
+    if not is_int(order) or order not in DERIVE_ORDERS:
+        raise ValueError(f"derive: order must be 1 or 2, got {order!r}")
+    return {"quantities": tuple(names), "radius": int(radius), "order": int(order)}
 
 
 DEFORM_DEFAULTS = {"iterations": 3, "interp": "cubic", "smooth": True}
@@ -603,9 +640,9 @@ def weighting_check(sizes, mode=None, uncertainty=None, ensemble=False, correlat
     refuse("weighting", dict(uncertainty=uncertainty, ensemble=ensemble or None, correlation=correlation), sizes, mode)
 
 
-KEYWORDS = ("background", "outlier", "prefilter", "depth", "equalize", "mask", "dewarp", "uncertainty", "deform", "correlation",
-            "weighting", "dynamic_mask")
-# The twelve keywords of OfflinePIV / ResidentPIV, as given or as their parsers returned them (None: not given).
+KEYWORDS = ("background", "outlier", "prefilter", "depth", "equalize", "mask", "dewarp", "uncertainty", "derive", "deform",
+            "correlation", "weighting", "dynamic_mask")
+# The thirteen keywords of OfflinePIV / ResidentPIV, as given or as their parsers returned them (None: not given).
 Options = namedtuple("Options", KEYWORDS, defaults=(None,) * len(KEYWORDS))
 
 
@@ -634,7 +671,7 @@ def parse_options(run, frames_shape=None, stack=True, **given):
     mask = mask_arg(raw.mask)
     mask_shape(mask, shape)
     opts = Options(background=background, outlier=outlier, prefilter=prefilter, depth=depth, equalize=equalize, mask=mask,
-                   uncertainty=uncertainty_arg(raw.uncertainty), deform=deform_arg(raw.deform),
+                   uncertainty=uncertainty_arg(raw.uncertainty), derive=derive_arg(raw.derive), deform=deform_arg(raw.deform),
                    correlation=correlation_arg(raw.correlation), weighting=weighting_arg(raw.weighting))
     sizes = [w for w, _ in pass_sizes(run["wind_size"], run["overlap"], run["multipass"], run["multipass_scale"])]
     refuse_all(opts._asdict(), sizes, run["multipass_mode"])

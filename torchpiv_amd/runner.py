@@ -22,6 +22,13 @@ from .backend import OfflinePIV
 KEYS_PAIR = ("x[mm]", "y[mm]", "Vx[m/s]", "Vy[m/s]")
 
 
+def derive_key(name: str) -> str:
+    """The column of a quantity of derive= in the per-pair output: its name and unit."""
+    if name in ("u_smooth", "v_smooth"):
+        return f"{name}[m/s]"
+    return "q[1/s^2]" if name == "q" else f"{name}[1/s]"
+
+
 def _numbered(path: str):
     """path, then 'stem (1).ext', 'stem (2).ext', ... -- the naming scheme of PlotterFunctions.py:16-24."""
     stem, ext = os.path.splitext(path)
@@ -237,8 +244,8 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
                folder_mode: str = "pairs", save_opt: str = "Dont save", save_dir: str = "Out",
                batch_size: int = 32, on_pair=None, distributed: bool = False, stats_on_device: bool = True,
                precision: str = "exact", streaming_stats: bool = False, background=None, outlier=None, depth=None,
-               mask=None, dewarp=None, deform=None, correlation=None, weighting=None, dynamic_mask=None, equalize=None,
-               prefilter=None):
+               mask=None, dewarp=None, derive=None, deform=None, correlation=None, weighting=None, dynamic_mask=None,
+               equalize=None, prefilter=None):
     """Process a folder like PIVWorker.run.  save_opt: "Dont save" | "Save all binary" |
     "Save all text" | "Save statistics" (anything but "Dont save" also writes the statistics table).
     streaming_stats: running accumulators instead of the stacked fields (EnsembleStats(streaming=True): O(1) memory in
@@ -265,6 +272,12 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
     dynamic_mask: the per-pair masks of OfflinePIV, segmented on the device from every pair's own frames (None or a dict with
     kind, size, level and optionally grow, threshold, pixels, fill; engine.dynamic_mask_arg); per pair, so sharded runs need
     nothing more.  The statistics take the delivered fields as they are, as for mask=.
+    derive: derivatives of every pair's field from a local least-squares fit on the device (None, a name or a tuple of names out
+    of engine.DERIVE_QUANTITIES, or a dict with quantities, radius and order; engine.derive_arg): the per-pair output gets one
+    more column per quantity, in the order asked for -- "<name>[1/s]" for the slopes, vorticity, divergence, shear and swirl,
+    "q[1/s^2]", "u_smooth[m/s]" and "v_smooth[m/s]" -- written by save_binary / save_table and handed to on_pair; NaN in the
+    cells mask= / dynamic_mask= exclude.  The statistics table stays as it is.  Per pair, so sharded runs need nothing
+    more (dist.run_sharded, whose gather carries two planes per pair, refuses the keyword).
     depth: the tone map of deep (10..16-bit) files of OfflinePIV (None, "auto" or a dict, engine.depth_arg); with
     distributed=True every rank takes "auto"'s histogram over the sample of the whole dataset, not of its shard, so all
     ranks use the same range.
@@ -273,7 +286,7 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
     piv = OfflinePIV(folder, device, file_fmt, wind_size, overlap, multipass=multipass,
                      multipass_mode=multipass_mode, dt=dt, scale=scale, multipass_scale=multipass_scale,
                      folder_mode=folder_mode, precision=precision, background=background, outlier=outlier, prefilter=prefilter,
-                     depth=depth, equalize=equalize, mask=mask, dewarp=dewarp, deform=deform,
+                     depth=depth, equalize=equalize, mask=mask, dewarp=dewarp, derive=derive, deform=deform,
                      correlation=correlation, weighting=weighting, dynamic_mask=dynamic_mask)
     if len(piv) == 0:
         return None, 0
@@ -292,11 +305,14 @@ def run_folder(folder: str, device: str, file_fmt: str, wind_size: int, overlap:
         pdist.shard_background(piv, indices)
     x = y = None
     done = 0
-    for i, xx, yy, u, v in piv.batched(batch_size, indices=indices):
+    for out in piv.batched(batch_size, indices=indices):
+        i, xx, yy, u, v = out[:5]
         x, y = xx, yy
         stats.add(u, v, index=i)
         done += 1
         output = dict(zip(KEYS_PAIR, (x, y, u, v)))
+        if derive is not None:
+            output.update((derive_key(k), f) for k, f in out[5].items())
         # single process: the reference's names (numbered in processing order); several ranks: the
         # dataset index goes into the name, so that files map to pairs whatever the interleaving
         tag = f"_pair_{i:06d}" if world > 1 else "_pair"
