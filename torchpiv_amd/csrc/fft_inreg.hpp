@@ -2,10 +2,12 @@
 //
 // One lane holds a whole line of N complex samples in registers (N = 8..128)
 // and transforms it with compile-time-unrolled radix-4 (first stage radix-2
-// when log2 N is odd) decimation-in-frequency butterflies.  All array indices
+// when log2 N is odd) butterflies, in one of two forms: butterfly-first
+// (decimation in frequency, fft_dif) or twiddle-first (decimation in time,
+// fft_twf; fewer instructions).  All array indices
 // and twiddles are compile-time constants, so the array lives in VGPRs and the
 // trivial twiddles (1, -i, -1, i) cost nothing.  The output is left in
-// digit-reversed order: output bin k sits at fft_pos(k, N).
+// digit-reversed order: output bin k sits at fft_pos(k, N), in either form.
 //
 // The header also compiles as plain host C++ (tests/test_host_logic.py::test_fft_codelets_on_host builds
 // it with g++ and checks it against numpy.fft).
@@ -119,11 +121,17 @@ struct TwRegs {
     }
 };
 
+// the constants of w = exp(-DIR * 2*pi*i * K / N) = C + i S (non-trivial K only) and -S, from either twiddle source
 template <int K, int N, int DIR, typename TW>
-TPIV_HD cf twmul_t(cf a, const TW& tw) {
+TPIV_HD void tw_consts(const TW& tw, float& C, float& S, float& nS) {
     constexpr int idx = ((K % N) * (128 / N)) % 128;
-    if constexpr (std::is_same<TW, TwLiteral>::value || idx % 32 == 0) {
-        return twmul<K, N, DIR>(a);
+    static_assert(idx % 32 != 0, "trivial twiddles take no constants");
+    if constexpr (std::is_same<TW, TwLiteral>::value) {
+        constexpr float c = TW_COS[idx] * mut_tw<K, N>();
+        constexpr float s = (DIR > 0 ? -TW_SIN[idx] : TW_SIN[idx]) * mut_tw<K, N>();
+        C = c;
+        S = s;
+        nS = -s;
     } else {
         // cos = (+-) M[rc], sin = (+-) M[rs] with M[r] = cos(2 pi r / 128) = sin(2 pi (32 - r) / 128)
         constexpr int q = idx / 32, r = idx % 32;
@@ -132,19 +140,46 @@ TPIV_HD cf twmul_t(cf a, const TW& tw) {
         constexpr bool cneg = (q == 1 || q == 2);
         constexpr bool sneg0 = (q == 2 || q == 3);
         constexpr bool sneg = DIR > 0 ? !sneg0 : sneg0;   // multiply by exp(-DIR * i * theta)
-        float C = tw.template m<rc, cneg>();
-        float S = tw.template m<rs, sneg>();
-        float nS = tw.template m<rs, !sneg>();
+        C = tw.template m<rc, cneg>();
+        S = tw.template m<rs, sneg>();
+        nS = tw.template m<rs, !sneg>();
         if constexpr (MUT_TW_ON && mut_tw<K, N>() != 1.0f) {
             C *= MUT_TW;
             S *= MUT_TW;
             nS *= MUT_TW;
         }
+    }
+}
+
+TPIV_HD float fma_f(float a, float b, float c) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        return cf{__builtin_fmaf(a.y, nS, a.x * C), __builtin_fmaf(a.y, C, a.x * S)};
+    return __builtin_fmaf(a, b, c);
 #else
-        return cf{a.x * C + a.y * nS, a.x * S + a.y * C};
+    return a * b + c;
 #endif
+}
+
+// w b with its fma written out, either twiddle source
+template <int K, int N, int DIR, typename TW>
+TPIV_HD cf twmul_f(cf b, const TW& tw) {
+    constexpr int idx = ((K % N) * (128 / N)) % 128;
+    if constexpr (idx % 32 == 0) {
+        return twmul<K, N, DIR>(b);
+    } else {
+        float C, S, nS;
+        tw_consts<K, N, DIR>(tw, C, S, nS);
+        return cf{fma_f(b.y, nS, b.x * C), fma_f(b.y, C, b.x * S)};
+    }
+}
+
+// the twiddle product of the butterfly-first form: literals go through twmul, whose multiply-adds the backend contracts (kept as
+// it is: the units on that form stay instruction for instruction what they were), register constants through twmul_f
+template <int K, int N, int DIR, typename TW>
+TPIV_HD cf twmul_t(cf a, const TW& tw) {
+    if constexpr (std::is_same<TW, TwLiteral>::value) {
+        return twmul<K, N, DIR>(a);
+    } else {
+        return twmul_f<K, N, DIR>(a, tw);
     }
 }
 
@@ -187,15 +222,113 @@ struct FFTStage {
     }
 };
 
+// The butterfly-first (decimation-in-frequency) form above: additions, then the twiddle products of the outputs.
+template <int N, int DIR, typename TW>
+TPIV_HD void fft_dif(cf (&x)[N], const TW& tw) {
+    FFTStage<N, 0, DIR, N, TW>::run(x, tw);
+}
+
+// ---- twiddle-first (decimation-in-time) form ---------------------------------------------------------
+// The same radix plan read from the other end: the N-point transform of x is combined from the N/4-point (N/2-point at a
+// radix-2 level) transforms Y_m of the samples x[4n + m], with the twiddles w = w_N^k IN FRONT of the butterfly, where the
+// butterfly's additions ride on the multiply-adds:
+//   a + w b                   two nested fma per component
+//   a - w b = 2a - (a + w b)  one fma per component (2.0f is an inline constant)
+// A twiddled radix-2 butterfly is 6 instructions instead of 8, a radix-4 one 24 instead of 28.  Every fma is written out
+// (__builtin_fmaf; a plain expression of the same order on the host), so the form does not depend on what the backend
+// contracts.  Trivial twiddles (1, -+i, -1) keep the plain addition and subtraction.  Rounding: DESIGN.md 3.4b.
+//
+// The sub-transforms come back in natural order and each level writes its results where it likes -- after unrolling every
+// value is its own SSA name -- so the top level puts bin k into x[FFT_POS<k, N>], the register the form above leaves it in.
+
+// p = a + w b,  q = a - w b,  w = exp(-DIR * 2*pi*i * K / N)
+template <int K, int N, int DIR, typename TW>
+TPIV_HD void tw_butterfly(cf a, cf b, const TW& tw, cf& p, cf& q) {
+    constexpr int idx = ((K % N) * (128 / N)) % 128;
+    if constexpr (idx % 32 == 0) {
+        const cf wb = twmul<K, N, DIR>(b);
+        p = cadd(a, wb);
+        q = csub(a, wb);
+    } else {
+        float C, S, nS;
+        tw_consts<K, N, DIR>(tw, C, S, nS);
+        p = cf{fma_f(b.x, C, fma_f(b.y, nS, a.x)), fma_f(b.x, S, fma_f(b.y, C, a.y))};
+        q = cf{fma_f(2.0f, a.x, -p.x), fma_f(2.0f, a.y, -p.y)};
+    }
+}
+
+// y[k] = bin k (natural order) of the N-point transform of x[OFF + STRIDE * n], n = 0 .. N-1; x is only read
+template <int N, int OFF, int STRIDE, int DIR, int TOTAL, typename TW>
+struct FFTTwFirst {
+    static TPIV_HD void run(const cf (&x)[TOTAL], cf (&y)[N], const TW& tw) {
+        if constexpr (N == 1) {
+            y[0] = x[OFF];
+        } else if constexpr (N == 2) {
+            const cf a = x[OFF], b = x[OFF + STRIDE];
+            y[0] = cadd(a, b);
+            y[1] = csub(a, b);
+        } else if constexpr (radix2_first(N)) {
+            cf y0[N / 2], y1[N / 2];
+            FFTTwFirst<N / 2, OFF, 2 * STRIDE, DIR, TOTAL, TW>::run(x, y0, tw);
+            FFTTwFirst<N / 2, OFF + STRIDE, 2 * STRIDE, DIR, TOTAL, TW>::run(x, y1, tw);
+            static_for<0, N / 2>([&](auto kc) TPIV_LAMBDA_INLINE {
+                constexpr int k = decltype(kc)::value;
+                tw_butterfly<k, N, DIR>(y0[k], y1[k], tw, y[k], y[k + N / 2]);
+            });
+        } else {
+            cf y0[N / 4], y1[N / 4], y2[N / 4], y3[N / 4];
+            // sub-transform by sub-transform in the order of m, so that inputs die early.  (Measured on the 64x64 unit's
+            // register allocation: the order 0, 2, 1, 3 and asm pins behind each sub-transform both spill more.)
+            FFTTwFirst<N / 4, OFF, 4 * STRIDE, DIR, TOTAL, TW>::run(x, y0, tw);
+            FFTTwFirst<N / 4, OFF + STRIDE, 4 * STRIDE, DIR, TOTAL, TW>::run(x, y1, tw);
+            FFTTwFirst<N / 4, OFF + 2 * STRIDE, 4 * STRIDE, DIR, TOTAL, TW>::run(x, y2, tw);
+            FFTTwFirst<N / 4, OFF + 3 * STRIDE, 4 * STRIDE, DIR, TOTAL, TW>::run(x, y3, tw);
+            static_for<0, N / 4>([&](auto kc) TPIV_LAMBDA_INLINE {
+                constexpr int k = decltype(kc)::value;
+                cf t0, t1, t2, t3;
+                tw_butterfly<2 * k, N, DIR>(y0[k], y2[k], tw, t0, t1);                               // Y0 +- w^2k Y2
+                tw_butterfly<3 * k, N, DIR>(twmul_f<k, N, DIR>(y1[k], tw), y3[k], tw, t2, t3);      // w^k Y1 +- w^3k Y3
+                // forward: -i t3; inverse: +i t3
+                const cf r3 = DIR > 0 ? cf{t3.y, -t3.x} : cf{-t3.y, t3.x};
+                y[k] = cadd(t0, t2);
+                y[k + N / 4] = cadd(t1, r3);
+                y[k + N / 2] = csub(t0, t2);
+                y[k + 3 * N / 4] = csub(t1, r3);
+            });
+        }
+    }
+};
+
+template <int N, int DIR, typename TW>
+TPIV_HD void fft_twf(cf (&x)[N], const TW& tw) {
+    cf y[N];
+    FFTTwFirst<N, 0, 1, DIR, N, TW>::run(x, y, tw);
+    static_for<0, N>([&](auto kc) TPIV_LAMBDA_INLINE {
+        constexpr int k = decltype(kc)::value;
+        x[FFT_POS<k, N>] = y[k];
+    });
+}
+
+// Which form a translation unit's fft_inreg / c2r_inreg calls run: the 64x64 and 32x32 tile units (xcorr_ws64, xcorr_ws32,
+// xcorr_ws32c) define TPIV_FFT_TWIDDLE_FIRST in front of their includes; every other unit keeps the butterfly-first form
+// (DESIGN.md 3.1).  A template argument, not a second body under one name: the two choices are two functions.
+#ifdef TPIV_FFT_TWIDDLE_FIRST
+constexpr bool FFT_TWIDDLE_FIRST = true;
+#else
+constexpr bool FFT_TWIDDLE_FIRST = false;
+#endif
+
 // Unnormalised N-point transform of x[0..N) in place; bin k ends at x[fft_pos(k, N)].
-template <int N, int DIR>
+template <int N, int DIR, bool TWF = FFT_TWIDDLE_FIRST>
 TPIV_HD void fft_inreg(cf (&x)[N]) {
-    FFTStage<N, 0, DIR, N>::run(x);
+    if constexpr (TWF) fft_twf<N, DIR>(x, TwLiteral{});
+    else FFTStage<N, 0, DIR, N>::run(x);
 }
 // the same with the twiddle constants taken from `tw` (TwRegs<N>, or TwLiteral{} for the form above)
-template <int N, int DIR, typename TW>
+template <int N, int DIR, typename TW, bool TWF = FFT_TWIDDLE_FIRST>
 TPIV_HD void fft_inreg(cf (&x)[N], const TW& tw) {
-    FFTStage<N, 0, DIR, N, TW>::run(x, tw);
+    if constexpr (TWF) fft_twf<N, DIR>(x, tw);
+    else FFTStage<N, 0, DIR, N, TW>::run(x, tw);
 }
 
 // (Used by the tile kernels for WS <= 32: same-box A/B 2.4 % (32x32 CWS pass) to 5.8 % (32x32 pass 1)
@@ -207,7 +340,7 @@ TPIV_HD void fft_inreg(cf (&x)[N], const TW& tw) {
 // With z[m] = r[2m] + i r[2m+1]:  z = IDFT_{N/2}(G),  G[k] = (Y[k] + conj Y[M-k]) + i w^k (Y[k] - conj Y[M-k]),
 // w = exp(2 pi i / N), M = N/2; the pair (k, M-k) shares S = Y[k] + conj Y[M-k], T = w^k (Y[k] - conj Y[M-k]):
 // G[k] = S + i T,  G[M-k] = conj(S) + i conj(T).
-template <int N>
+template <int N, bool TWF = FFT_TWIDDLE_FIRST>
 TPIV_HD void c2r_inreg(const cf (&Y)[N / 2 + 1], cf (&h)[N / 2]) {
     constexpr int M = N / 2;
     static_assert(M >= 2, "N >= 4");
@@ -221,7 +354,7 @@ TPIV_HD void c2r_inreg(const cf (&Y)[N / 2 + 1], cf (&h)[N / 2]) {
         h[M - k] = cf{S.x + T.y, T.x - S.y};
     });
     h[M / 2] = cf{2.0f * Y[M / 2].x, -2.0f * Y[M / 2].y};
-    fft_inreg<M, -1>(h);
+    fft_inreg<M, -1, TWF>(h);
 }
 
 }  // namespace tpiv

@@ -1443,6 +1443,10 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
     using TW = std::conditional_t<WS == 16, TwRegs<WS>, TwLiteral>;
     TW tw;
     if constexpr (!std::is_same<TW, TwLiteral>::value) tw.init();
+    // Units that run the twiddle-first codelets (FFT_TWIDDLE_FIRST, fft_inreg.hpp) run them in every transform but one: the
+    // forward column transform of the 64x64 first-pass instances.  Those sit at the 168 registers of three wavefronts per
+    // SIMD, and with that one transform twiddle-first the allocation spills two registers (locating kernel 0 -> 2).
+    constexpr bool TWF_COL = FFT_TWIDDLE_FIRST && !(WS == 64 && MODE == MODE_PASS1);
 
     const int N = p.n_rows * p.n_cols;
     const int groups = (N + G::WPW - 1) / G::WPW;
@@ -1708,7 +1712,7 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
         // lane = kx, x[y] natural (NOSWAP, lanes 32..63: x[y] = row y + 32)
         transpose_tile<WS, PLANAR, NOSWAP>(x, tile, fresh_lane());
         TPIV_STAMP(4);      // transposition 1
-        fft_inreg<WS, 1>(x, tw);                          // over y; Z(ky, kx = lane) at x[FFT_POS<ky>]
+        fft_inreg<WS, 1, TW, TWF_COL>(x, tw);             // over y; Z(ky, kx = lane) at x[FFT_POS<ky>]
         TPIV_STAMP(5);      // forward column FFT
 
         // ---- paired half inverse (DESIGN.md 3.1 "Cross-spectrum and inverse columns in mirror pairs").  P(-ky, -kx) =

@@ -1,4 +1,5 @@
 // Tile kernels for 64x64 interrogation windows (see xcorr_tile.hpp).
+#define TPIV_FFT_TWIDDLE_FIRST      // this unit runs the twiddle-first codelets (fft_inreg.hpp)
 #include "xcorr_tile.hpp"
 namespace tpiv {
 hipError_t launch_xcorr_ws64(const PassParams& p, int mode, int n_cu, hipStream_t stream) {
