@@ -229,6 +229,49 @@ int tpiv_plan_pass_outliers(const tpiv_plan* plan, int pass, uint8_t** status_de
 int tpiv_field_fit(const double* u_dev, const double* v_dev, const uint8_t* skip_dev, int batch, int n_rows, int n_cols,
                    int radius, int order, double* fit_dev, uint8_t* count_dev, int8_t* order_dev, void* stream);
 
+/* ---- stereoscopic reconstruction: three components from two cameras (extension; the reference has none) ------ */
+
+/* Two cameras look at the light sheet z = 0 from different sides; each delivers an in-plane field on the SAME grid of
+ * cells, in the same unit: u1, v1 and u2, v2 float64 [batch, cells].  To first order a particle that moves by (U, V, W)
+ * is seen by camera c moving by (U + a_c W, V + b_c W), a_c, b_c the viewing tangents of that camera at the cell (a1, b1,
+ * a2, b2 float64 [cells], the same for every pair).  Per cell, the least-squares solution of the four equations and the
+ * root of the sum of their squared residuals, in float64, every operation rounded once, left to right as written:
+ *   du = u1 - u2;  dv = v1 - v2;  da = a1 - a2;  db = b1 - b2;  g = da*da + db*db
+ *   W  = (da*du + db*dv) / g
+ *   U  = ((u1 + u2) - (a1 + a2)*W) * 0.5
+ *   V  = ((v1 + v2) - (b1 + b2)*W) * 0.5
+ *   eu = du - da*W;  ev = dv - db*W;  res = sqrt((eu*eu + ev*ev) * 0.5)
+ * With the four 1-sigma fields su1, sv1, su2, sv2 [batch, cells] (all four or none), the propagated 1-sigma errors, the
+ * four components' errors taken as independent:
+ *   q1 = su1*su1;  q2 = su2*su2;  r1 = sv1*sv1;  r2 = sv2*sv2;  qs = q1 + q2;  rs = r1 + r2
+ *   sW = sqrt(((da*da)*qs + (db*db)*rs) / (g*g))
+ *   ma = (a1 + a2)*0.5;  mb = (b1 + b2)*0.5
+ *   ka = ma*da/g;  kb = ma*db/g;  la = mb*db/g;  lb = mb*da/g                       (product, then quotient)
+ *   cu1 = 0.5 - ka;  cu2 = 0.5 + ka;  cv1 = 0.5 - la;  cv2 = 0.5 + la
+ *   sU = sqrt((cu1*cu1)*q1 + (cu2*cu2)*q2 + (kb*kb)*rs)
+ *   sV = sqrt((cv1*cv1)*r1 + (cv2*cv2)*r2 + (lb*lb)*qs)
+ * status_dev uint8 [batch, cells], the tests in this order:
+ *   1  skip_dev (uint8 [cells] or NULL) is non-zero: U = V = W = fill; res and the sigmas NaN
+ *   3  a1, b1, a2 or b2 is not finite, or g == 0 (the two views cannot tell W from U): everything NaN
+ *   2  u1, v1, u2 or v2 is not finite: everything NaN
+ *   0  otherwise: the reconstruction; a non-finite input sigma makes sU, sV, sW of that cell NaN and nothing else.
+ * The NaN written is 0x7ff8000000000000.  Per pair: pair_count_dev int32 [batch] = the status-0 cells; pair_rms_dev
+ * float64 [batch] = sqrt(S / (double)count), NaN at count 0, with S = the sum of res*res over the status-0 cells in a
+ * fixed order: lane t of 1024 sums the cells t, t + 1024, ... in ascending order from +0.0, then acc[t] = acc[t] +
+ * acc[t + s] for s = 512, 256, ..., 1.  No floating-point atomics: the same call gives the same bytes.
+ * A host model that does the same operations gives the same bits in U, V, W, res, the sigmas and the status -- for data
+ * whose intermediate values stay finite; beyond that nothing is promised except that nothing faults.
+ * TPIV_EINVAL, nothing launched: a null field, tangent or output pointer (sU, sV, sW are needed only with the sigmas),
+ * batch < 0, cells < 1, a partial set of sigmas, an output that overlaps an input or another output, batch * cells >= 2^31.
+ * TPIV_EUNSUPPORTED: more than 524 280 pairs.  batch == 0 succeeds and launches nothing.  The inputs are not written.
+ * Enqueues only (two launches); allocates nothing and needs no work memory. */
+int tpiv_stereo_reconstruct(const double* u1_dev, const double* v1_dev, const double* u2_dev, const double* v2_dev,
+                            const double* su1_dev, const double* sv1_dev, const double* su2_dev, const double* sv2_dev,
+                            const uint8_t* skip_dev, const double* a1_dev, const double* b1_dev, const double* a2_dev,
+                            const double* b2_dev, int batch, long long cells, double fill, double* U_dev, double* V_dev,
+                            double* W_dev, double* res_dev, double* sU_dev, double* sV_dev, double* sW_dev,
+                            uint8_t* status_dev, double* pair_rms_dev, int32_t* pair_count_dev, void* stream);
+
 /* ---- geometric mask (extension; the reference has none) ------------------------------------------ */
 
 /* Pixel step: out_dev[f][p] = mask_dev[p] != 0 ? 0 : frames_dev[f][p] for n frames [n, pixels] uint8 against one image

@@ -18,6 +18,7 @@ _API = {
     "get_field_shape", "get_coordinates", "moving_window_array",
     "interpolate_boarders", "fillMissingValues", "getPixelsForInterp", "nan_helper",
     "post_validate", "free_cuda_memory", "ResidentPIV", "fill_holes_host", "piv_iteration_CWS_Fast", "OnlinePIV",
+    "StereoPIV",
 }
 
 

@@ -1765,3 +1765,302 @@ class OnlinePIV:
         self._resize = resize
         self._scale = scale
         self._device = DeviceMap.devicies[device]           # KeyError like B:927
+
+
+class StereoPIV:
+    """Stereoscopic PIV: two cameras that look at the light sheet z = 0 from different sides, run in lockstep, and the
+    three components (U, V, W) of every vector from their two in-plane fields (engine.stereo_reconstruct,
+    tpiv_stereo_reconstruct).
+
+        piv = StereoPIV(cam1=(a1, b1), cam2=(a2, b2), P=(P1, P2), wind_size=32, overlap=16, scale=0.1, origin=(X0, Y0))
+        for i, x, y, U, V, W, res in piv.batched(): ...
+
+    cam1, cam2: the frames a and b of each camera, uint8 tensors [n, H, W] on the GPU (ResidentPIV's); from_folders()
+    takes two folders instead (OfflinePIV's).  P = (P1, P2): the cameras, float64 [3, 4] each, (x_cam, y_cam, 1) ~ P (X, Y,
+    Z, 1) in camera pixels -- engine.stereo_fit makes one from a calibration target.  scale: mm per pixel of the rectified
+    frames, origin = (X0, Y0): the world position of their pixel (0, 0); pixel (x, y) is the world point (X0 + scale x, Y0 -
+    scale y, 0).  World frame: right-handed, mm, X to the right, Y up, Z towards the cameras.
+
+    Both cameras are rectified onto the sheet with dewarp={"homography": engine.stereo_homography(P_c, scale, origin),
+    "interp": interp, "fill": dewarp_fill} and get the same mask=: the caller's image, if any, OR-ed with the pixels that
+    either camera does not see (dewarp_outside() of both), with the caller's threshold / pixels / fill.  Both then exclude
+    the same cells; those carry `fill` in U, V, W.  Every other run parameter and keyword goes to both objects unchanged;
+    uncertainty= adds sU, sV, sW to what is yielded.  Refused (ValueError, before any GPU call): dewarp=, dynamic_mask=
+    (per-camera masks), derive= (two-component derivatives of a three-component field), cameras of different frame shapes
+    or pair counts, a scale that is not finite and positive, a P that is not a finite [3, 4] matrix or whose centre does
+    not lie in front of the sheet (C_z > 0).
+
+    A pair is delivered when BOTH cameras deliver it: each camera drops pairs by the reference's rules, unchanged (stats
+    counts them).  U, V, W are in the unit of the cameras' u, v (scale / dt * 1000), res is the root of the summed squared
+    residuals of the four equations in that unit -- a measure of how well the two views agree, dominated by calibration
+    and registration errors when it is large everywhere."""
+
+    device_out = False       # True: U, V, W, res (and the sigmas) are yielded as tensors on the device
+
+    _REFUSED = ("dewarp", "dynamic_mask", "derive")
+
+    def __init__(self, cam1, cam2, P, wind_size: int, overlap: int, *, scale: float, origin=(0.0, 0.0), interp="cubic",
+                 dewarp_fill=0, mask=None, **keywords) -> None:
+        try:
+            (a1, b1), (a2, b2) = cam1, cam2
+        except (TypeError, ValueError):
+            raise ValueError("StereoPIV: cam1 and cam2 are the pairs (frames_a, frames_b) of the two cameras") from None
+        frames = (a1, b1, a2, b2)
+        if any(not isinstance(t, torch.Tensor) or t.dim() != 3 for t in frames):
+            raise ValueError("StereoPIV: every camera takes two tensors [n, H, W]")
+        if tuple(a1.shape[1:]) != tuple(a2.shape[1:]):
+            raise ValueError(f"StereoPIV: the cameras' frame shapes differ, {tuple(a1.shape[1:])} and {tuple(a2.shape[1:])}")
+        if a1.shape[0] != a2.shape[0]:
+            raise ValueError(f"StereoPIV: the cameras' pair counts differ, {a1.shape[0]} and {a2.shape[0]}")
+        shape = (int(a1.shape[1]), int(a1.shape[2]))
+        dw, mask = self._geometry(P, scale, origin, interp, dewarp_fill, mask, keywords, shape)
+        self._resident = True
+        self._frames_a = (a1, a2)
+        self._cams = tuple(ResidentPIV(a, b, wind_size, overlap, scale=scale, mask=mask, dewarp=dw[c], **keywords)
+                           for c, (a, b) in enumerate(((a1, b1), (a2, b2))))
+        self._after()
+
+    @classmethod
+    def from_folders(cls, folder1: str, folder2: str, device: str, file_fmt: str, P, wind_size: int, overlap: int, *,
+                     scale: float, origin=(0.0, 0.0), interp="cubic", dewarp_fill=0, mask=None, **keywords):
+        """The same over two folders of image files, one per camera (OfflinePIV's folder, device, file_fmt, folder_mode)."""
+        self = cls.__new__(cls)
+        cls._check(P, scale, origin, keywords)
+        # the frame shapes and pair counts, from objects that read the folders and touch nothing else
+        probe = [OfflinePIV(f, device, file_fmt, wind_size, overlap, scale=scale, **keywords) for f in (folder1, folder2)]
+        shapes, counts = [p.frame_shape() for p in probe], [len(p) for p in probe]
+        for p in probe:
+            p.close()
+        if counts[0] != counts[1]:
+            raise ValueError(f"StereoPIV: the cameras' pair counts differ, {counts[0]} and {counts[1]}")
+        if shapes[0] is None or shapes[1] is None:
+            raise ValueError("StereoPIV: a folder without a decodable pair")
+        if tuple(shapes[0]) != tuple(shapes[1]):
+            raise ValueError(f"StereoPIV: the cameras' frame shapes differ, {tuple(shapes[0])} and {tuple(shapes[1])}")
+        shape = (int(shapes[0][0]), int(shapes[0][1]))
+        dw, mask = self._geometry(P, scale, origin, interp, dewarp_fill, mask, keywords, shape)
+        self._resident = False
+        self._frames_a = None
+        self._cams = tuple(OfflinePIV(f, device, file_fmt, wind_size, overlap, scale=scale, mask=mask, dewarp=dw[c], **keywords)
+                           for c, f in enumerate((folder1, folder2)))
+        self._after()
+        return self
+
+    @classmethod
+    def _check(cls, P, scale, origin, keywords):
+        """The refusals that need no frame: keywords, scale, origin, cameras.  Returns the cameras."""
+        for k in cls._REFUSED:
+            if keywords.get(k) is not None:
+                raise ValueError(f"StereoPIV: {k}= does not combine with a stereo run" + {
+                    "dewarp": " (the rectification is the cameras' own: stereo_homography)",
+                    "dynamic_mask": " (both cameras must exclude the same cells)",
+                    "derive": " (its derivatives are those of a two-component field)"}[k])
+        engine.stereo_homography(np.eye(3, 4), scale, origin)           # (scale and origin, checked where they are used)
+        try:
+            P1, P2 = P
+        except (TypeError, ValueError):
+            raise ValueError("StereoPIV: P = (P1, P2), one float64 [3, 4] matrix per camera") from None
+        cams = []
+        for c, Pc in enumerate((P1, P2)):
+            try:
+                engine.stereo_tangents(Pc, 0.0, 0.0)                     # finite [3, 4], C_z > 0
+            except ValueError as e:
+                raise ValueError(f"StereoPIV: camera {c + 1}: {e}") from None
+            cams.append(np.array(Pc, dtype=np.float64))
+        return tuple(cams)
+
+    def _geometry(self, P, scale, origin, interp, dewarp_fill, mask, keywords, shape):
+        """Checks; then the two dewarp= dicts and the one mask= dict of the cameras, for frames of `shape`."""
+        self._P = self._check(P, scale, origin, keywords)
+        self._scale, self._origin, self._shape = float(scale), (float(origin[0]), float(origin[1])), shape
+        dw = tuple(engine.dewarp_arg({"homography": engine.stereo_homography(Pc, scale, origin), "interp": interp,
+                                      "fill": dewarp_fill}) for Pc in self._P)
+        par = engine.mask_arg(mask)
+        unseen = np.zeros(shape, dtype=bool)
+        for d in dw:
+            unseen |= engine.dewarp_outside(engine.dewarp_map(d, shape[0], shape[1]))
+        if par is not None:
+            image = par["image"].cpu().numpy()
+            if image.shape != shape:
+                raise ValueError(f"mask: image of shape {image.shape} for frames of shape {shape}")
+            unseen |= image != 0
+        par = dict(par or {}, image=unseen)
+        self._fill = float(par.get("fill", engine.MASK_DEFAULTS["fill"]))
+        self._unseen = unseen
+        return dw, par
+
+    def _after(self):
+        for cam in self._cams:
+            cam.device_out = True
+        self._uncertainty = self._cams[0]._uncertainty is not None
+        self._planes = None
+        self._skip = None
+        self.reset_stats()
+
+    def __len__(self) -> int:
+        return len(self._cams[0])
+
+    def reset_stats(self):
+        """stats: pairs delivered, pairs dropped by camera 1 only / camera 2 only / both (undecodable ones included), and
+        pair_rms: {pair index: the rms of res over the pair's reconstructed cells}."""
+        self._counts = {"delivered": 0, "dropped_camera1_only": 0, "dropped_camera2_only": 0, "dropped_both": 0}
+        self._rms = []               # (pair indices, device tensor) per batch, read when stats is
+
+    @property
+    def stats(self):
+        rms = {}
+        for ids, t in self._rms:
+            rms.update(zip(ids, t.cpu().numpy().tolist()))
+        return dict(self._counts, pair_rms=rms)
+
+    def cameras(self):
+        """The two per-camera objects (ResidentPIV / OfflinePIV), for their own stats, mask_grid() and dewarp_outside()."""
+        return self._cams
+
+    def _last_pass(self):
+        plan = self._cams[0]._single_plan(self._shape)
+        w, o, _, _ = plan.geometry[-1]
+        return get_coordinates(self._shape, w, o)
+
+    def planes(self):
+        """((a1, b1), (a2, b2)): the tangent planes of the two cameras at the cells of the delivered fields, float64 numpy
+        [n_rows, n_cols] (engine.stereo_planes at the window centres of the last pass)."""
+        if self._planes is None:
+            x, y = self._last_pass()
+            self._planes = tuple(engine.stereo_planes(Pc, x, y, self._scale, self._origin) for Pc in self._P)
+        return self._planes
+
+    def _device_geometry(self):
+        """The tangent planes and the excluded cells on the device, made once."""
+        if self._skip is None:
+            dev = self._cams[0]._device
+            grid = self._cams[0].mask_grid()
+            planes = [torch.from_numpy(q).to(dev) for cam in self.planes() for q in cam]
+            self._skip = (planes, torch.from_numpy(np.ascontiguousarray(grid).view(np.uint8)).to(dev))
+        return self._skip
+
+    def batched(self, batch_size: int = 32, indices=None) -> Generator:
+        """Runs both cameras' batched() over the same pairs and joins what they deliver on the pair index; the stacks of one
+        batch go through ONE engine.stereo_reconstruct call.  Yields (i, x, y, U, V, W, res), with uncertainty= followed by
+        sU, sV, sW: x, y as the classes deliver them, the fields float64 [n_rows, n_cols] -- numpy arrays, or tensors on
+        the device with device_out.  A pair that either camera drops or cannot decode yields nothing."""
+        idx = list(range(len(self))) if indices is None else list(indices)
+        if not idx:
+            return
+        batch_size = int(batch_size)
+        (a1, b1, a2, b2), skip = self._device_geometry()
+
+        def stream(cam):
+            """(position in idx, tuple) of what the camera delivers, in its order (idx's)."""
+            pos = -1
+            for out in cam.batched(batch_size, idx):
+                pos += 1
+                while idx[pos] != out[0]:
+                    pos += 1
+                yield pos, out
+        streams = [stream(cam) for cam in self._cams]
+        got = [{}, {}]
+        ahead = [None, None]
+
+        def pull(c, hi):
+            """Everything camera c delivers below position hi into got[c]; the first tuple past it waits in ahead[c]."""
+            while True:
+                if ahead[c] is None:
+                    ahead[c] = next(streams[c], None)
+                    if ahead[c] is None:
+                        return
+                if ahead[c][0] >= hi:
+                    return
+                got[c][ahead[c][0]] = ahead[c][1]
+                ahead[c] = None
+
+        try:
+            for lo in range(0, len(idx), batch_size):
+                hi = min(lo + batch_size, len(idx))
+                pull(0, hi)
+                pull(1, hi)
+                both = [p for p in range(lo, hi) if p in got[0] and p in got[1]]
+                n1 = sum(1 for p in range(lo, hi) if p in got[0])
+                n2 = sum(1 for p in range(lo, hi) if p in got[1])
+                st = self._counts
+                st["delivered"] += len(both)
+                st["dropped_camera1_only"] += n2 - len(both)
+                st["dropped_camera2_only"] += n1 - len(both)
+                st["dropped_both"] += (hi - lo) - n1 - n2 + len(both)
+                if both:
+                    one = [got[0][p] for p in both]
+                    two = [got[1][p] for p in both]
+                    x, y = one[0][1], one[0][2]
+                    fields = [torch.stack([t[k] for t in cam]) for cam in (one, two) for k in (3, 4)]
+                    sigma = None
+                    if self._uncertainty:
+                        sigma = [torch.stack([t[k] for t in cam]) for cam in (one, two) for k in (5, 6)]
+                    rec = engine.stereo_reconstruct(*fields, a1, b1, a2, b2, sigma=sigma, skip=skip, fill=self._fill)
+                    self._rms.append(([idx[p] for p in both], rec.pair_rms))
+                    out = [rec.U, rec.V, rec.W, rec.res] + ([rec.sU, rec.sV, rec.sW] if self._uncertainty else [])
+                    if not self.device_out:
+                        out = [t.cpu().numpy() for t in out]
+                    for k, p in enumerate(both):
+                        yield (idx[p], x, y) + tuple(t[k] for t in out)
+                for c in (0, 1):
+                    for p in range(lo, hi):
+                        got[c].pop(p, None)
+        finally:
+            for s in streams:
+                s.close()
+
+    def __call__(self) -> Generator:
+        for out in self.batched():
+            yield (out[1].copy(), out[2].copy()) + out[3:]
+
+    def disparity(self, indices=None, batch_size: int = 32):
+        """Whether the sheet lies where the calibration target stood: the displacement between what the two cameras see AT
+        THE SAME INSTANT.  Frame a of camera 1 and frame a of camera 2 of the pairs `indices` (None: all) are rectified,
+        each through its own map (engine.dewarp), and correlated as one ensemble -- ResidentPIV(rect1, rect2, ...).ensemble()
+        with this object's window sizes, passes and mask, dt = 1.  Returns (x, y, dx, dy) in millimetres, dx along X, dy
+        along Y (up), laid out like the delivered fields; None where ensemble() returns None.
+
+        The sign: camera c's rectification puts a particle at (X, Y, z0) where its line of sight meets z = 0, at (X + a_c
+        z0, Y + b_c z0) to first order -- the viewing tangents' own definition with dZ = z0.  Camera 2's position minus camera
+        1's is what the correlation of rect1 with rect2 measures: a sheet at z = z0 instead of 0 shows as dx = (a2 - a1) z0
+        and dy = (b2 - b1) z0; a sheet that is tilted shows a z0 that varies across the field.  The peak is as wide as the
+        sheet is thick, (a2 - a1) times the thickness.  This only measures: correcting the calibration from it (Wieneke
+        2005) is left to the caller.  Resident frames only (NotImplementedError for from_folders objects and with depth=);
+        window sizes 16, 32, 64 (ensemble()'s)."""
+        if not self._resident:
+            raise NotImplementedError("StereoPIV.disparity: resident frames only (build the object from tensors)")
+        one = self._cams[0]
+        if one._depth is not None:
+            raise NotImplementedError("StereoPIV.disparity: 8-bit frames only")
+        idx = list(range(len(self))) if indices is None else list(indices)
+        if not idx:
+            return None
+        H, W = self._shape
+        batch_size = int(batch_size)
+        rect = []
+        for cam, frames in zip(self._cams, self._frames_a):
+            frames = frames.contiguous()
+            m = cam._dewarp_map((H, W), frames.device)
+            out = torch.empty(len(idx), H, W, dtype=torch.uint8, device=frames.device)
+            for s in range(0, len(idx), batch_size):
+                chunk = idx[s:s + batch_size]
+                off = torch.tensor(chunk, dtype=torch.int64) * (H * W)
+                engine.dewarp(frames.view(-1), m, cam._dewarp["interp"], cam._dewarp["fill"], offsets=off, shape=(H, W),
+                              out=out[s:s + len(chunk)])
+            rect.append(out)
+        piv = ResidentPIV(rect[0], rect[1], one._wind_size, one._overlap, multipass=one._iter, multipass_mode=one._mode,
+                          dt=1, scale=self._scale, multipass_scale=one._iter_scale, precision=one._precision,
+                          validation_ratio=one._val_ratio, validation_window=one._val_win, outlier=one._outlier,
+                          mask=one._mask)
+        try:
+            got = piv.ensemble(batch_size=batch_size)
+        finally:
+            piv.close()
+        if got is None:
+            return None
+        x, y, u, v = got[:4]
+        return x, y, u / 1000.0, v / 1000.0          # scale / dt * 1000 with dt = 1: micrometres -> millimetres
+
+    def close(self):
+        for cam in self._cams:
+            cam.close()

@@ -977,6 +977,71 @@ int tpiv_field_fit(const double* u, const double* v, const uint8_t* skip, int ba
     return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_field_fit");
 }
 
+int tpiv_stereo_reconstruct(const double* u1, const double* v1, const double* u2, const double* v2, const double* su1,
+                            const double* sv1, const double* su2, const double* sv2, const uint8_t* skip, const double* a1,
+                            const double* b1, const double* a2, const double* b2, int batch, long long cells, double fill,
+                            double* U, double* V, double* W, double* res, double* sU, double* sV, double* sW, uint8_t* status,
+                            double* pair_rms, int32_t* pair_count, void* stream) {
+    if (batch < 0 || cells < 1) return fail(TPIV_EINVAL, "tpiv_stereo_reconstruct: empty grid");
+    if (!u1 || !v1 || !u2 || !v2 || !a1 || !b1 || !a2 || !b2 || !U || !V || !W || !res || !status || !pair_rms || !pair_count)
+        return fail(TPIV_EINVAL, "tpiv_stereo_reconstruct: null pointer");
+    const int n_sigma = (su1 != nullptr) + (sv1 != nullptr) + (su2 != nullptr) + (sv2 != nullptr);
+    if (n_sigma != 0 && n_sigma != 4)
+        return fail(TPIV_EINVAL, "tpiv_stereo_reconstruct: the sigmas su1, sv1, su2, sv2 come all four or not at all");
+    if (n_sigma == 4 && (!sU || !sV || !sW)) return fail(TPIV_EINVAL, "tpiv_stereo_reconstruct: null pointer");
+    if (cells >= (1LL << 31) || (long long)batch * cells >= (1LL << 31))
+        return fail(TPIV_EINVAL, "tpiv_stereo_reconstruct: field stack too large");
+    if (batch == 0) return TPIV_OK;
+    const size_t n = (size_t)batch * cells, one = (size_t)cells;
+    const bool sig = n_sigma == 4;
+    const Span in[13] = {{u1, n * 8},  {v1, n * 8},  {u2, n * 8},  {v2, n * 8},  {su1, n * 8},  {sv1, n * 8}, {su2, n * 8},
+                         {sv2, n * 8}, {skip, one},  {a1, one * 8}, {b1, one * 8}, {a2, one * 8}, {b2, one * 8}};
+    const Span out[10] = {{U, n * 8},
+                          {V, n * 8},
+                          {W, n * 8},
+                          {res, n * 8},
+                          {sig ? sU : nullptr, n * 8},
+                          {sig ? sV : nullptr, n * 8},
+                          {sig ? sW : nullptr, n * 8},
+                          {status, n},
+                          {pair_rms, (size_t)batch * 8},
+                          {pair_count, (size_t)batch * 4}};
+    if (const int k = aliased(in, 13, out, 10))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_stereo_reconstruct: an output aliases an input"
+                                        : "tpiv_stereo_reconstruct: two outputs overlap");
+    if ((batch + tpiv::STEREO_BLOCK_PAIRS - 1) / tpiv::STEREO_BLOCK_PAIRS > 65535)
+        return fail(TPIV_EUNSUPPORTED, "tpiv_stereo_reconstruct: too many pairs in one call");
+    tpiv::StereoParams q{};
+    q.u1 = u1;
+    q.v1 = v1;
+    q.u2 = u2;
+    q.v2 = v2;
+    q.su1 = su1;
+    q.sv1 = sv1;
+    q.su2 = su2;
+    q.sv2 = sv2;
+    q.skip = skip;
+    q.a1 = a1;
+    q.b1 = b1;
+    q.a2 = a2;
+    q.b2 = b2;
+    q.batch = batch;
+    q.cells = cells;
+    q.fill = fill;
+    q.U = U;
+    q.V = V;
+    q.W = W;
+    q.res = res;
+    q.sU = sig ? sU : nullptr;
+    q.sV = sig ? sV : nullptr;
+    q.sW = sig ? sW : nullptr;
+    q.status = status;
+    q.pair_rms = pair_rms;
+    q.pair_count = pair_count;
+    hipError_t he = tpiv::launch_stereo_reconstruct(q, (hipStream_t)stream);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_stereo_reconstruct");
+}
+
 int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double eps, int min_neighbours) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
     if (kind != 0 && kind != 1) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: kind must be 0 (off) or 1 (normalized median)");

@@ -233,6 +233,27 @@ struct FieldFitParams {
 };
 hipError_t launch_field_fit(const FieldFitParams& p, hipStream_t stream);
 
+// stereoscopic reconstruction (stereo.hip, defined in include/torchpiv_hip.h: tpiv_stereo_reconstruct): a workgroup of
+// STEREO_BLOCK_THREADS lanes keeps the geometry of its cells in registers and walks STEREO_BLOCK_PAIRS pairs of the
+// stack; a lane owns one cell (8-byte accesses) or, where every plane allows it, two adjacent ones (16-byte accesses).
+// The per-pair summary is a second launch, one workgroup of STEREO_SUM_THREADS lanes per pair.
+constexpr int STEREO_BLOCK_THREADS = 256, STEREO_BLOCK_PAIRS = 8, STEREO_SUM_THREADS = 1024;
+struct StereoParams {
+    const double *u1, *v1, *u2, *v2;         // [batch, cells]
+    const double *su1, *sv1, *su2, *sv2;     // optional, all four or none
+    const uint8_t* skip;                     // optional [cells]
+    const double *a1, *b1, *a2, *b2;         // [cells]
+    int batch;
+    long long cells;
+    double fill;
+    double *U, *V, *W, *res;                 // out [batch, cells]
+    double *sU, *sV, *sW;                    // out with the sigmas
+    uint8_t* status;                         // out [batch, cells]
+    double* pair_rms;                        // out [batch]
+    int32_t* pair_count;                     // out [batch]; none of the outputs may alias an input
+};
+hipError_t launch_stereo_reconstruct(const StereoParams& p, hipStream_t stream);
+
 // geometric mask (mask.hip, defined in include/torchpiv_hip.h).  apply: out = mask ? 0 : frames for n frames against one
 // image (out may be frames itself).  coverage: a wavefront per window of the (ws, ov) grid counts its masked pixels into count
 // (optional) and writes grid = count > limit (optional).  fields: u = v = +0.0, invalid = invalid_value, status = 2 (optional)

@@ -1312,6 +1312,199 @@ def dewarp_fit(target_px, image_px, kind="homography", shape=None):
     return {"poly": np.ascontiguousarray(coef.T)}
 
 
+# ---- stereoscopic PIV: camera geometry on the host (numpy float64, no GPU) and the reconstruction (tpiv_stereo_reconstruct).
+# World frame: right-handed, millimetres, the light sheet is z = 0, X to the right, Y up, Z towards the cameras.  Rectified
+# frame: the camera frames' shape, pixel (x, y) -- x along the columns, y along the rows, downwards -- is the world point
+# (X0 + p x, Y0 - p y, 0) with p = scale (mm per pixel) and origin = (X0, Y0).  Camera: P float64 [3, 4], (x_cam, y_cam, 1) ~
+# P (X, Y, Z, 1) in camera pixels, y down.
+
+def _stereo_camera(P, who):
+    try:
+        P = np.array(P, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: P must be a finite float64 [3, 4] matrix") from None
+    if P.shape != (3, 4) or not np.isfinite(P).all():
+        raise ValueError(f"{who}: P must be a finite float64 [3, 4] matrix, got shape {P.shape}")
+    return P
+
+
+def _stereo_scale(scale, origin, who):
+    if not is_real(scale) or not np.isfinite(scale) or not scale > 0:
+        raise ValueError(f"{who}: scale must be a finite positive number (mm per pixel), got {scale!r}")
+    try:
+        X0, Y0 = (float(q) for q in origin)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: origin must be two numbers (X0, Y0) in mm, got {origin!r}") from None
+    if not (np.isfinite(X0) and np.isfinite(Y0)):
+        raise ValueError(f"{who}: origin must be finite, got {origin!r}")
+    return float(scale), X0, Y0
+
+
+def stereo_fit(world_mm, image_px):
+    """The camera matrix P [3, 4] from a calibration target (numpy, no GPU): world_mm [N, 3] the dots' world positions in
+    mm, image_px [N, 2] where they were found in the camera frame, (x, y) in pixels.  Normalised DLT: the world points
+    shifted to their centroid and scaled to a mean distance of sqrt 3, the image points to sqrt 2 (as dewarp_fit
+    normalises), the matrix from the SVD of the [2 N, 12] design matrix.  P is scaled to |P[2, :3]| = 1 and signed so that
+    the target points have positive depth P[2] . (X, Y, Z, 1).  ValueError for fewer than 6 points, non-finite input and
+    points that do not determine a camera: the normalised design matrix must have rank 11, tested as s[10] > 1e-8 s[0] on
+    its singular values (a target whose dots all lie in one plane has rank 8: calibrate on two planes or more)."""
+    try:
+        w, s = np.asarray(world_mm, dtype=np.float64), np.asarray(image_px, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("stereo_fit: world_mm must be an array [N, 3] and image_px [N, 2]") from None
+    if w.ndim != 2 or s.ndim != 2 or w.shape[1:] != (3,) or s.shape[1:] != (2,) or w.shape[0] != s.shape[0] \
+            or not (np.isfinite(w).all() and np.isfinite(s).all()):
+        raise ValueError(f"stereo_fit: world_mm must be a finite array [N, 3] and image_px [N, 2], got {w.shape} and {s.shape}")
+    if w.shape[0] < 6:
+        raise ValueError(f"stereo_fit: a camera matrix needs at least 6 points, got {w.shape[0]}")
+
+    def norm(p):
+        c = p.mean(axis=0)
+        d = np.sqrt(((p - c) ** 2).sum(axis=1)).mean()
+        if not d > 0:
+            raise ValueError("stereo_fit: the points coincide")
+        k = np.sqrt(float(p.shape[1])) / d
+        N = np.eye(p.shape[1] + 1)
+        N[:-1, :-1] *= k
+        N[:-1, -1] = -k * c
+        return N
+    Nw, Ns = norm(w), norm(s)
+    wn = (Nw @ np.column_stack([w, np.ones(len(w))]).T).T
+    sn = (Ns @ np.column_stack([s, np.ones(len(s))]).T).T
+    A = np.zeros((2 * len(w), 12))
+    A[0::2, 0:4], A[0::2, 8:12] = wn, -sn[:, 0:1] * wn
+    A[1::2, 4:8], A[1::2, 8:12] = wn, -sn[:, 1:2] * wn
+    _, sv, vt = np.linalg.svd(A)
+    if not sv[10] > 1e-8 * sv[0]:
+        raise ValueError("stereo_fit: the points do not determine a camera matrix (all in one plane?)")
+    P = np.linalg.inv(Ns) @ vt[-1].reshape(3, 4) @ Nw
+    k = np.sqrt((P[2, :3] ** 2).sum())
+    if not k > 0:
+        raise ValueError("stereo_fit: the points do not determine a camera matrix")
+    P = P / k
+    depth = P[2, :3] @ w.T + P[2, 3]
+    return -P if depth.mean() < 0 else P
+
+
+def stereo_centre(P):
+    """The centre of projection C [3] of the camera P [3, 4], in mm: C = -P[:, :3]^-1 P[:, 3]."""
+    P = _stereo_camera(P, "stereo_centre")
+    try:
+        return -np.linalg.solve(P[:, :3], P[:, 3])
+    except np.linalg.LinAlgError:
+        raise ValueError("stereo_centre: P[:, :3] is singular (a camera at infinity)") from None
+
+
+def stereo_homography(P, scale, origin=(0.0, 0.0)):
+    """The backward map of the camera P for dewarp= -- {"homography": stereo_homography(P, scale, origin)} --: the 3 x 3
+    matrix that takes the rectified pixel (x, y, 1) to the camera pixel, P @ [[p, 0, X0], [0, -p, Y0], [0, 0, 0], [0, 0, 1]]
+    with p = scale in mm per pixel and origin = (X0, Y0) the world position of pixel (0, 0); exact for a pinhole."""
+    P = _stereo_camera(P, "stereo_homography")
+    p, X0, Y0 = _stereo_scale(scale, origin, "stereo_homography")
+    return P @ np.array([[p, 0.0, X0], [0.0, -p, Y0], [0.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+
+
+def stereo_tangents(P, X, Y):
+    """The viewing tangents (a, b) of the camera P at the world points (X, Y, 0), arrays of one shape in mm: a = (X - C_x) /
+    C_z, b = (Y - C_y) / C_z with C = stereo_centre(P).  To first order a particle at (X, Y, 0) that moves by (dX, dY, dZ) is
+    seen in the rectified frame of that camera moving by (dX + a dZ, dY + b dZ).  ValueError unless C_z > 0 (a camera in
+    or behind the sheet)."""
+    C_ = stereo_centre(P)
+    if not (np.isfinite(C_).all() and C_[2] > 0):
+        raise ValueError(f"stereo_tangents: the camera centre {tuple(C_)} does not lie in front of the sheet (C_z > 0)")
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    return (X - C_[0]) / C_[2], (Y - C_[1]) / C_[2]
+
+
+def stereo_planes(P, x, y, scale, origin=(0.0, 0.0)):
+    """The tangent planes (a, b) of the camera P for the fields the classes deliver: x, y [n_rows, n_cols] are the pixel
+    coordinates of the window centres as get_coordinates returns them (not scaled).  Delivered fields are flipped along
+    axis 0 and x, y are not, so cell [r, c] of a delivered field belongs to the window centre (x[r, c], y[n_rows - 1 - r,
+    c]) = the world point (X0 + p x, Y0 - p y, 0).  Returns contiguous float64 [n_rows, n_cols] planes in the delivered
+    orientation -- what stereo_reconstruct takes."""
+    p, X0, Y0 = _stereo_scale(scale, origin, "stereo_planes")
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError(f"stereo_planes: x, y must be [n_rows, n_cols] arrays of one shape, got {x.shape} and {y.shape}")
+    a, b = stereo_tangents(P, X0 + p * x, Y0 - p * np.flip(y, axis=0))
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+# the cells a workgroup of tpiv_stereo_reconstruct covers at one cell per lane (twice as many at two) and the pairs it
+# walks; the lanes of the per-pair summary's workgroup (csrc/piv_kernels.h)
+STEREO_BLOCK = (256, 8)
+STEREO_SUM_THREADS = 1024
+
+
+class StereoFields(tuple):
+    """What stereo_reconstruct returns: a tuple (U, V, W, res, status, pair_rms, pair_count) -- with sigma followed by sU, sV,
+    sW -- whose elements also answer to these names."""
+    _names = ("U", "V", "W", "res", "status", "pair_rms", "pair_count", "sU", "sV", "sW")
+
+    def __getattr__(self, name):
+        names = StereoFields._names
+        if name in names and names.index(name) < len(self):
+            return self[names.index(name)]
+        raise AttributeError(name)
+
+
+def stereo_reconstruct(u1, v1, u2, v2, a1, b1, a2, b2, sigma=None, skip=None, fill=0.0):
+    """The three components of every cell from the fields of two cameras (tpiv_stereo_reconstruct; include/torchpiv_hip.h
+    has the arithmetic).  u1, v1, u2, v2: float64 tensors [batch, n_rows, n_cols] (or [n_rows, n_cols]) on the GPU, the
+    fields as the classes deliver them, both cameras with the same scale and dt; a1, b1, a2, b2: float64 [n_rows, n_cols],
+    the tangent planes in the same orientation (stereo_planes); sigma: None or the four fields (su1, sv1, su2, sv2) of
+    uncertainty=, shaped like u1; skip: None or uint8 / bool [n_rows, n_cols], non-zero = excluded in every pair (U, V, W =
+    fill there).  Returns a StereoFields record: U, V, W, res float64 and status uint8 shaped like u1 (0: reconstructed, 1:
+    skipped, 2: a non-finite input vector, 3: no geometry), pair_rms float64 and pair_count int32 [batch] (scalars for a 2-D
+    input) and, with sigma, sU, sV, sW.  The inputs are not written."""
+    fields = (u1, v1, u2, v2)
+    planes = (a1, b1, a2, b2)
+    sig = () if sigma is None else tuple(sigma)
+    if len(sig) not in (0, 4):
+        raise ValueError("stereo_reconstruct: sigma takes the four fields (su1, sv1, su2, sv2) or None")
+    every = fields + planes + sig
+    if any(not isinstance(t, torch.Tensor) for t in every) or (skip is not None and not isinstance(skip, torch.Tensor)):
+        raise TypeError("stereo_reconstruct: tensors on the GPU")
+    _need_cuda(*every, skip)
+    if any(t.dtype != torch.float64 for t in every) or (skip is not None and skip.dtype not in (torch.uint8, torch.bool)):
+        raise TypeError("stereo_reconstruct: fields, tangent planes and sigmas float64, skip uint8 or bool")
+    if u1.dim() not in (2, 3) or any(t.shape != u1.shape for t in fields + sig):
+        raise ValueError("stereo_reconstruct: [batch, n_rows, n_cols] or [n_rows, n_cols] fields of one shape")
+    grid = tuple(u1.shape[-2:])
+    if any(tuple(t.shape) != grid for t in planes) or (skip is not None and tuple(skip.shape) != grid):
+        raise ValueError(f"stereo_reconstruct: the tangent planes and skip must be [{grid[0]}, {grid[1]}]")
+    if any(t.device != u1.device for t in every) or (skip is not None and skip.device != u1.device):
+        raise ValueError("stereo_reconstruct: every tensor on one device")
+    if grid[0] < 1 or grid[1] < 1:
+        raise ValueError("stereo_reconstruct: empty grid")
+    if not is_real(fill):
+        raise ValueError(f"stereo_reconstruct: fill must be a number, got {fill!r}")
+    flat = u1.dim() == 2
+    B = 1 if flat else u1.shape[0]
+    fields = tuple(t.contiguous() for t in fields)
+    planes = tuple(t.contiguous() for t in planes)
+    sig = tuple(t.contiguous() for t in sig)
+    if skip is not None:
+        skip = skip.contiguous()
+        skip = skip.view(torch.uint8) if skip.dtype == torch.bool else skip
+    dev = u1.device
+    shape = (B,) + grid
+    out = [torch.empty(shape, dtype=torch.float64, device=dev) for _ in range(4 + (3 if sig else 0))]
+    status = torch.empty(shape, dtype=torch.uint8, device=dev)
+    rms = torch.empty(B, dtype=torch.float64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    ptr_s = [t.data_ptr() for t in sig] if sig else [None] * 4
+    ptr_o = [t.data_ptr() for t in out] + ([] if sig else [None] * 3)
+    with torch.cuda.device(dev):
+        check(lib.tpiv_stereo_reconstruct(*[t.data_ptr() for t in fields], *ptr_s, None if skip is None else skip.data_ptr(),
+                                          *[t.data_ptr() for t in planes], B, grid[0] * grid[1], float(fill), *ptr_o,
+                                          status.data_ptr(), rms.data_ptr(), count.data_ptr(), _stream()))
+    got = out[:4] + [status, rms, count] + out[4:]
+    if flat:
+        got = [t[0] for t in got]
+    return StereoFields(got)
+
+
 class Plan:
     """The multipass pipeline of OfflinePIV.__call__ (PIVbackend.py:873-882) for batches of
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
