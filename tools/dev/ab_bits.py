@@ -1,7 +1,10 @@
 """Do two builds of the library produce the same BITS?  (development aid for changes that must not move a result)
    python tools/dev/ab_bits.py dump out.npz     (with TPIV_LIB=<build>)      -> fields of a fixed set of plans on seeded frames
-   python tools/dev/ab_bits.py cmp a.npz b.npz                               -> per-array count of differing bytes"""
-import os, sys
+   python tools/dev/ab_bits.py cmp a.npz b.npz                               -> per-array count of differing bytes
+The dump holds the SHA-256 of every frame set it rendered ("in<tag>"); cmp first compares those and says INPUTS DIFFER for a
+plan whose frames were not the same in the two runs -- its field counts then say nothing about the builds
+(profiles/exact_offsets/)."""
+import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 
@@ -28,6 +31,12 @@ if sys.argv[1] == "dump":
     def put(tag, u, v, inv):
         out["u" + tag], out["v" + tag], out["m" + tag] = u.cpu().numpy(), v.cpu().numpy(), inv.cpu().numpy()
 
+    def put_inputs(tag, *frames):
+        h = hashlib.sha256()
+        for f in frames:
+            h.update(f.contiguous().cpu().numpy().tobytes())
+        out["in" + tag] = np.frombuffer(h.digest(), np.uint8)
+
     for i, (H, W, ws, n_pass, mode, prec, kind, noise) in enumerate(CASES):
         try:
             A, B = synth.make_batch(3, H, W, device="cuda", kind=kind, noise=noise)
@@ -35,6 +44,7 @@ if sys.argv[1] == "dump":
             g = torch.Generator(device="cuda").manual_seed(7 + i)
             A = torch.randint(0, 256, (3, H, W), dtype=torch.uint8, device="cuda", generator=g)
             B = torch.randint(0, 256, (3, H, W), dtype=torch.uint8, device="cuda", generator=g)
+        put_inputs(str(i), A, B)
         plan = engine.Plan(H, W, ws, ws // 2, n_pass=n_pass, mode=mode, max_batch=3, precision=prec)
         put(str(i), *plan.run(A, B))
         torch.cuda.synchronize()
@@ -44,6 +54,7 @@ if sys.argv[1] == "dump":
     A[0, :96, :96] = 0                                              # empty windows: zeroed in one frame, constant in both
     A[1, 128:224, 128:224] = 9
     B[1, 128:224, 128:224] = 9
+    put_inputs("_variants", A, B, A2, B2)                           # one frame set for every variant chain
     n_plans = len(CASES)
     for name, kw in VARIANTS.items():
         for ws, n_pass, scale in CHAINS:
@@ -72,7 +83,18 @@ else:
     bad = sorted(set(a.files) ^ set(b.files))
     if bad:
         print("arrays in one dump only:", bad)
-    for k in sorted(set(a.files) & set(b.files)):
+    common = sorted(set(a.files) & set(b.files))
+    inputs = [k for k in common if k.startswith("in")]
+    if not inputs:
+        print("no frame hashes in these dumps: whether the inputs were the same is not known")
+    for k in inputs:                                                # before any field count
+        if not np.array_equal(a[k], b[k]):
+            bad.append(k)
+            which = "every variant chain" if k == "in_variants" else "plan " + k[2:]
+            print(f"INPUTS DIFFER for {which}: sha256 {a[k].tobytes().hex()} against {b[k].tobytes().hex()}")
+    for k in common:
+        if k in inputs:
+            continue
         x, y = a[k], b[k]
         d = x.size if x.shape != y.shape or x.dtype != y.dtype else int((x.view(np.uint8) != y.view(np.uint8)).sum())
         if d:

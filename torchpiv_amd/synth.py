@@ -4,6 +4,12 @@ Used by bench.py (generated on the GPU so decode/H2D stay outside the timed
 region) and by the tests.  Particle positions are displaced by a smooth field
 (frame b = particles of frame a moved by (dx, dy)), not by image warping, so
 both frames are band-limited alike.
+
+A pair is the same in every run on one device: _render sums the particles into
+the pixels under torch's deterministic algorithms, so the float32 sums have one
+order (an unordered atomic sum that lands near .5 rounds to another grey level
+now and then; profiles/exact_offsets/).  The CPU and a GPU may still differ in
+single pixels, by the rounding of exp.
 """
 from __future__ import annotations
 
@@ -43,16 +49,24 @@ def _render(px, py, amp, H, W, sigma, device):
     img = torch.zeros(H * W, dtype=torch.float32, device=device)
     cx = torch.round(px)
     cy = torch.round(py)
-    for oy in range(-3, 4):
-        yy = cy + oy
-        wy = torch.exp(-((yy - py) ** 2) / (2 * sigma * sigma))
-        oky = (yy >= 0) & (yy < H)
-        for ox in range(-3, 4):
-            xx = cx + ox
-            w = wy * torch.exp(-((xx - px) ** 2) / (2 * sigma * sigma))
-            ok = oky & (xx >= 0) & (xx < W)
-            idx = yy.long() * W + xx.long()          # (in float32 the flat index is inexact beyond 2^24 pixels)
-            img.index_add_(0, idx[ok], (amp * w)[ok])
+    # index_add_ on a GPU is a float32 atomic add in whatever order the wavefronts arrive; under deterministic algorithms
+    # it sums in one order, so the image has the same bits in every run (the CPU's is ordered either way)
+    det = torch.are_deterministic_algorithms_enabled()
+    warn_only = torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        for oy in range(-3, 4):
+            yy = cy + oy
+            wy = torch.exp(-((yy - py) ** 2) / (2 * sigma * sigma))
+            oky = (yy >= 0) & (yy < H)
+            for ox in range(-3, 4):
+                xx = cx + ox
+                w = wy * torch.exp(-((xx - px) ** 2) / (2 * sigma * sigma))
+                ok = oky & (xx >= 0) & (xx < W)
+                idx = yy.long() * W + xx.long()          # (in float32 the flat index is inexact beyond 2^24 pixels)
+                img.index_add_(0, idx[ok], (amp * w)[ok])
+    finally:
+        torch.use_deterministic_algorithms(det, warn_only=warn_only)
     return img.view(H, W)
 
 
@@ -60,9 +74,10 @@ def make_pair(H: int, W: int, index: int = 0, kind: str = "wavy", density: float
               sigma: float = 1.0, noise: float = 0.0, offset: float = 8.0,
               device="cpu"):
     """One (frame_a, frame_b) pair of uint8 [H, W] tensors on `device`.
-    Random draws are made on the CPU generator (seed = 1234 + index) so that a
-    pair is identical whichever device renders it (up to float32 rounding of
-    the accumulation order)."""
+    Random draws are made on the CPU generator (seed = 1234 + index) and the
+    particles are summed in one order, so a pair is the same in every run on one
+    device; the CPU's and a GPU's pair may differ in single pixels by the
+    rounding of exp."""
     g = torch.Generator(device="cpu")
     g.manual_seed(BASE_SEED + int(index))
     pad = 10.0
