@@ -272,6 +272,51 @@ int tpiv_stereo_reconstruct(const double* u1_dev, const double* v1_dev, const do
                             double* W_dev, double* res_dev, double* sU_dev, double* sV_dev, double* sW_dev,
                             uint8_t* status_dev, double* pair_rms_dev, int32_t* pair_count_dev, void* stream);
 
+/* Self-calibration: where the light sheet really lies, from the disparity between the two rectified views of the SAME
+ * instant.  dx, dy float64 [batch, cells], in mm: camera 2's rectified position of a particle minus camera 1's, along X and
+ * along Y (up).  X, Y float64 [cells]: the world position of each cell on z = 0.  The disparity belongs to the midpoint of
+ * the two rectified positions (symmetric assignment), so camera 1 saw the particle at q1 and camera 2 at q2 below; the
+ * point of the sheet is the midpoint M of the shortest segment between the two lines of sight, gap its length.  Host
+ * values, read during the call: cameras_host[6] = the centres C1, C2; plane_host[3] = (c0, c1, c2) of a plane Z = c0 + c1 X +
+ * c2 Y with the tolerance tol; centre_host[3] = (Xm, Ym, Zm), subtracted before the sums.  Per cell, in float64, every
+ * operation rounded once, left to right as written, a dot product its x, then y, then z term:
+ *   hx = dx*0.5;  hy = dy*0.5
+ *   q1 = (X - hx, Y - hy, 0);  q2 = (X + hx, Y + hy, 0)
+ *   d1 = q1 - C1;  d2 = q2 - C2  (their z: 0.0 - C.z);  w = C1 - C2
+ *   a = d1.d1;  b = d1.d2;  c = d2.d2;  d = d1.w;  e = d2.w
+ *   den = a*c - b*b
+ *   s = (b*e - c*d)/den;  t = (a*e - b*d)/den
+ *   p1 = C1 + s*d1;  p2 = C2 + t*d2
+ *   M = (p1 + p2)*0.5;  g = p1 - p2;  gap = sqrt(g.g)
+ *   r = M.z - ((c0 + c1*M.x) + c2*M.y)
+ * status_dev uint8 [batch, cells], the tests in this order:
+ *   1  skip_dev (uint8 [cells] or NULL) is non-zero
+ *   3  one of the six centre coordinates is not finite
+ *   2  dx or dy is not finite
+ *   3  den is not finite or den <= 0 (parallel lines of sight; a non-finite X or Y) -- tested behind 2 because a
+ *      non-finite dx or dy makes den a NaN: with the centres' test before it, 3 precedes 2 wherever both can be told apart
+ *   4  gap > gap_max
+ *   5  |r| > tol
+ *   0  otherwise.
+ * An infinite gap_max or tol switches its test off (the comparison is false).  Mx, My, Mz, gap float64 [batch, cells] --
+ * all four or all four NULL -- hold M and gap at status 0, 4 and 5 and NaN (0x7ff8000000000000) at 1, 2 and 3.
+ * Per item of the batch, over its status-0 cells: count_dev int32 [batch]; sums_dev float64 [batch, 9] = the sums of
+ *   x, y, z, x*x, x*y, y*y, x*z, y*z, z*z    with x = M.x - Xm, y = M.y - Ym, z = M.z - Zm  (one subtraction, one product),
+ * each in pair_rms's fixed order: lane t of 1024 sums the cells t, t + 1024, ... in ascending order from +0.0, then acc[t] =
+ * acc[t] + acc[t + s] for s = 512, 256, ..., 1.  No floating-point atomics, no contraction: the same call gives the same
+ * bytes, and a host model that does the same operations gives the same bits in the points, the status, the count and the
+ * sums -- for data whose intermediate values stay finite; beyond that nothing is promised except that nothing faults.
+ * TPIV_EINVAL, nothing launched: a null dx, dy, X, Y, host array, status, count or sums pointer, a partial set of Mx, My,
+ * Mz, gap, batch < 0, cells < 1, an output that overlaps an input or another output, batch * cells >= 2^31, a gap_max or tol
+ * that is negative or NaN.  TPIV_EUNSUPPORTED: more than 524 280 items.  batch == 0 succeeds and launches nothing.  The
+ * inputs are not written.  Enqueues only (two launches; the second, one workgroup per item, triangulates again and reads
+ * no output of the first); allocates nothing and needs no work memory. */
+int tpiv_stereo_triangulate(const double* dx_dev, const double* dy_dev, const double* X_dev, const double* Y_dev,
+                            const uint8_t* skip_dev, int batch, long long cells, const double* cameras_host,
+                            double gap_max, const double* plane_host, double tol, const double* centre_host,
+                            double* Mx_dev, double* My_dev, double* Mz_dev, double* gap_dev, uint8_t* status_dev,
+                            int32_t* count_dev, double* sums_dev, void* stream);
+
 /* ---- geometric mask (extension; the reference has none) ------------------------------------------ */
 
 /* Pixel step: out_dev[f][p] = mask_dev[p] != 0 ? 0 : frames_dev[f][p] for n frames [n, pixels] uint8 against one image

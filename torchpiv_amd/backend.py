@@ -1813,10 +1813,20 @@ class StereoPIV:
         if a1.shape[0] != a2.shape[0]:
             raise ValueError(f"StereoPIV: the cameras' pair counts differ, {a1.shape[0]} and {a2.shape[0]}")
         shape = (int(a1.shape[1]), int(a1.shape[2]))
-        dw, mask = self._geometry(P, scale, origin, interp, dewarp_fill, mask, keywords, shape)
         self._resident = True
+        # what self_calibrate() needs to build the same object over the same frames with other cameras
+        self._made_from = dict(cam1=(a1, b1), cam2=(a2, b2), wind_size=wind_size, overlap=overlap, scale=scale, origin=origin,
+                               interp=interp, dewarp_fill=dewarp_fill, mask=mask, **keywords)
+        self._build(P, shape)
+
+    def _build(self, P, shape):
+        """The two per-camera objects and everything derived from the cameras P, for the resident frames of this object."""
+        m = dict(self._made_from)
+        (a1, b1), (a2, b2) = m.pop("cam1"), m.pop("cam2")
+        wind_size, overlap, scale, origin = m.pop("wind_size"), m.pop("overlap"), m.pop("scale"), m.pop("origin")
+        dw, mask = self._geometry(P, scale, origin, m.pop("interp"), m.pop("dewarp_fill"), m.pop("mask"), m, shape)
         self._frames_a = (a1, a2)
-        self._cams = tuple(ResidentPIV(a, b, wind_size, overlap, scale=scale, mask=mask, dewarp=dw[c], **keywords)
+        self._cams = tuple(ResidentPIV(a, b, wind_size, overlap, scale=scale, mask=mask, dewarp=dw[c], **m)
                            for c, (a, b) in enumerate(((a1, b1), (a2, b2))))
         self._after()
 
@@ -2013,7 +2023,12 @@ class StereoPIV:
         for out in self.batched():
             yield (out[1].copy(), out[2].copy()) + out[3:]
 
-    def disparity(self, indices=None, batch_size: int = 32):
+    def projections(self):
+        """(P1, P2): copies of the cameras this object works with -- the constructor's, or the corrected ones after
+        self_calibrate()."""
+        return tuple(Pc.copy() for Pc in self._P)
+
+    def disparity(self, indices=None, batch_size: int = 32, *, wind_size=None, overlap=None, multipass=None):
         """Whether the sheet lies where the calibration target stood: the displacement between what the two cameras see AT
         THE SAME INSTANT.  Frame a of camera 1 and frame a of camera 2 of the pairs `indices` (None: all) are rectified,
         each through its own map (engine.dewarp), and correlated as one ensemble -- ResidentPIV(rect1, rect2, ...).ensemble()
@@ -2024,17 +2039,34 @@ class StereoPIV:
         z0, Y + b_c z0) to first order -- the viewing tangents' own definition with dZ = z0.  Camera 2's position minus camera
         1's is what the correlation of rect1 with rect2 measures: a sheet at z = z0 instead of 0 shows as dx = (a2 - a1) z0
         and dy = (b2 - b1) z0; a sheet that is tilted shows a z0 that varies across the field.  The peak is as wide as the
-        sheet is thick, (a2 - a1) times the thickness.  This only measures: correcting the calibration from it (Wieneke
-        2005) is left to the caller.  Resident frames only (NotImplementedError for from_folders objects and with depth=);
-        window sizes 16, 32, 64 (ensemble()'s)."""
+        sheet is thick, (a2 - a1) times the thickness.  This only measures; self_calibrate() corrects the cameras from it.
+        wind_size, overlap, multipass: the grid of this measurement, None: the object's own -- a sheet offset is often
+        several times the flow's displacement and wants larger windows; the returned x, y describe the grid used.  Resident
+        frames only (NotImplementedError for from_folders objects and with depth=); window sizes 16, 32, 64 (ensemble()'s)."""
+        got = self._measure(indices, batch_size, wind_size, overlap, multipass, "disparity")
+        return None if got is None else got[:4]
+
+    @staticmethod
+    def _grid_arg(who, wind_size, overlap, multipass):
+        for name, v, low in (("wind_size", wind_size, 1), ("overlap", overlap, 0), ("multipass", multipass, 1)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < low):
+                raise ValueError(f"StereoPIV.{who}: {name} must be an integer >= {low} or None, got {v!r}")
+
+    def _measure(self, indices, batch_size, wind_size, overlap, multipass, who):
+        """disparity()'s (x, y, dx, dy) followed by the excluded cells of the grid it used (bool, as delivered) and that
+        grid's window centres in pixels (get_coordinates: x, y above are scaled as the classes deliver them)."""
+        self._grid_arg(who, wind_size, overlap, multipass)
         if not self._resident:
-            raise NotImplementedError("StereoPIV.disparity: resident frames only (build the object from tensors)")
+            raise NotImplementedError(f"StereoPIV.{who}: resident frames only (build the object from tensors)")
         one = self._cams[0]
         if one._depth is not None:
-            raise NotImplementedError("StereoPIV.disparity: 8-bit frames only")
+            raise NotImplementedError(f"StereoPIV.{who}: 8-bit frames only")
         idx = list(range(len(self))) if indices is None else list(indices)
         if not idx:
             return None
+        ws = one._wind_size if wind_size is None else int(wind_size)
+        ov = one._overlap if overlap is None else int(overlap)
+        n_pass = one._iter if multipass is None else int(multipass)
         H, W = self._shape
         batch_size = int(batch_size)
         rect = []
@@ -2048,18 +2080,115 @@ class StereoPIV:
                 engine.dewarp(frames.view(-1), m, cam._dewarp["interp"], cam._dewarp["fill"], offsets=off, shape=(H, W),
                               out=out[s:s + len(chunk)])
             rect.append(out)
-        piv = ResidentPIV(rect[0], rect[1], one._wind_size, one._overlap, multipass=one._iter, multipass_mode=one._mode,
+        piv = ResidentPIV(rect[0], rect[1], ws, ov, multipass=n_pass, multipass_mode=one._mode,
                           dt=1, scale=self._scale, multipass_scale=one._iter_scale, precision=one._precision,
                           validation_ratio=one._val_ratio, validation_window=one._val_win, outlier=one._outlier,
                           mask=one._mask)
         try:
             got = piv.ensemble(batch_size=batch_size)
+            grid = None if got is None else piv.mask_grid()
         finally:
             piv.close()
         if got is None:
             return None
         x, y, u, v = got[:4]
-        return x, y, u / 1000.0, v / 1000.0          # scale / dt * 1000 with dt = 1: micrometres -> millimetres
+        w, o = engine.pass_sizes(ws, ov, n_pass, one._iter_scale)[-1]
+        # scale / dt * 1000 with dt = 1: micrometres -> millimetres
+        return x, y, u / 1000.0, v / 1000.0, grid, get_coordinates((H, W), w, o)
+
+    def self_calibrate(self, indices=None, batch_size: int = 32, *, iterations: int = 4, tol=None, trim: float = 3.0,
+                       gap_max=None, min_cells=None, apply: bool = True, wind_size=None, overlap=None, multipass=None):
+        """Corrects both cameras from the disparity map (Wieneke 2005): the light sheet never lies exactly where the
+        calibration target stood.  Every round (at most `iterations`):
+          1. disparity() of the pairs `indices` with the current cameras, on the grid wind_size / overlap / multipass (None:
+             the object's own), its excluded cells skipped;
+          2. every cell's disparity triangulated between the two cameras' lines of sight (engine.stereo_triangulate: the
+             disparity belongs to the MIDPOINT of the two rectified positions) and a least-squares plane Z = c0 + c1 X + c2 Y
+             through the points (engine.stereo_plane); then, at most twice more and until the count stops changing, cells
+             further than trim x the rms residual from the plane are left out and the plane is fitted again; cells whose
+             lines of sight pass further than gap_max mm from each other (None: no test) are left out from the start;
+          3. both cameras expressed in the frame of that plane (engine.stereo_correct): the sheet becomes z = 0.
+        The run stops with the round whose measured plane stays within tol mm of z = 0 at every non-excluded cell, max |c0 +
+        c1 X + c2 Y| <= tol; that round's correction is still applied.  tol = None: 0.05 x scale, a twentieth of a pixel of
+        sheet height -- about what the disparity pass resolves; a convention, not a measured bound.  RuntimeError when fewer
+        than min_cells cells survive a round (None: a quarter of the non-excluded cells, at least 3).
+        Returns {"P": (P1, P2) corrected, "T": [4, 4] taking the corrected world frame to the constructor's (the product of
+        the rounds' transforms), "rounds": [{"plane": (c0, c1, c2), "rms", "count", "height", "gap": the median distance of
+        the lines of sight, "d": the median |disparity|, all in mm}], "converged"}.  apply=True: the object continues with
+        the corrected cameras over the same resident frames -- homographies, unseen-pixel mask, tangent planes and skip grid
+        are made anew as the constructor makes them, stats is reset; apply=False: the object is left as it was.  Resident
+        8-bit frames only (NotImplementedError for from_folders objects and with depth=, before any GPU call)."""
+        who = "self_calibrate"
+        self._grid_arg(who, wind_size, overlap, multipass)
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
+            raise ValueError(f"StereoPIV.{who}: iterations must be an integer >= 1, got {iterations!r}")
+        if not engine.is_real(trim) or not np.isfinite(trim) or not trim > 0:
+            raise ValueError(f"StereoPIV.{who}: trim must be a finite number > 0, got {trim!r}")
+        for name, v in (("tol", tol), ("gap_max", gap_max)):
+            if v is not None and (not engine.is_real(v) or not np.isfinite(v) or v < 0):
+                raise ValueError(f"StereoPIV.{who}: {name} must be a finite number >= 0 or None, got {v!r}")
+        if min_cells is not None and (isinstance(min_cells, bool) or not isinstance(min_cells, (int, np.integer)) or min_cells < 3):
+            raise ValueError(f"StereoPIV.{who}: min_cells must be an integer >= 3 or None, got {min_cells!r}")
+        if not self._resident:
+            raise NotImplementedError(f"StereoPIV.{who}: resident frames only (build the object from tensors)")
+        if self._cams[0]._depth is not None:
+            raise NotImplementedError(f"StereoPIV.{who}: 8-bit frames only")
+        tol = 0.05 * self._scale if tol is None else float(tol)
+        gap_max = float("inf") if gap_max is None else float(gap_max)
+        dev = self._cams[0]._device
+        P, T, rounds, converged = self.projections(), np.eye(4), [], False
+        for k in range(int(iterations)):
+            # round 1 measures with this object; a later round with one built from the same frames and the corrected cameras
+            piv = self if k == 0 else StereoPIV(**self._made_from, P=P)
+            try:
+                got = piv._measure(indices, batch_size, wind_size, overlap, multipass, who)
+            finally:
+                if piv is not self:
+                    piv.close()
+            if got is None:
+                if indices is not None and not list(indices):
+                    raise ValueError(f"StereoPIV.{who}: no pairs to measure the disparity on")
+                raise RuntimeError(f"StereoPIV.{who}: round {k + 1}: the disparity pass delivered no field (too many invalid "
+                                   "vectors: larger windows may reach the offset)")
+            _, _, dx, dy, grid, (x, y) = got
+            X, Y = engine.stereo_cells(x, y, self._scale, self._origin)
+            free = np.ones(X.shape, dtype=bool) if grid is None else ~grid
+            need = max(3, (int(free.sum()) + 3) // 4) if min_cells is None else int(min_cells)
+            centre = (float(X.mean()), float(Y.mean()), 0.0)
+            C1, C2 = engine.stereo_centre(P[0]), engine.stereo_centre(P[1])
+            on = [torch.from_numpy(np.ascontiguousarray(q, dtype=np.float64)).to(dev) for q in (dx, dy, X, Y)]
+            skip = torch.from_numpy(np.ascontiguousarray(~free).view(np.uint8)).to(dev)
+            first = engine.stereo_triangulate(*on, C1, C2, skip=skip, gap_max=gap_max, centre=centre)
+            count = int(first.count)
+
+            def fit(rec):
+                if int(rec.count) < need:
+                    raise RuntimeError(f"StereoPIV.{who}: round {k + 1}: {int(rec.count)} of {int(free.sum())} non-excluded "
+                                       f"cells survive, fewer than min_cells = {need}")
+                return engine.stereo_plane(int(rec.count), rec.sums, centre)
+            c0, c1, c2, rms = fit(first)
+            for _ in range(2):
+                rec = engine.stereo_triangulate(*on, C1, C2, skip=skip, gap_max=gap_max, plane=(c0, c1, c2), tol=float(trim) * rms,
+                                                centre=centre, points=False)
+                if int(rec.count) == count:
+                    break
+                count = int(rec.count)
+                c0, c1, c2, rms = fit(rec)
+            used = (first.status == 0).cpu().numpy()
+            height = float(np.abs(c0 + c1 * X + c2 * Y)[free].max())
+            rounds.append({"plane": (c0, c1, c2), "rms": rms, "count": count, "height": height,
+                           "gap": float(np.median(first.gap.cpu().numpy()[used])),
+                           "d": float(np.median(np.sqrt(dx * dx + dy * dy)[free]))})
+            (P1, T1), (P2, _) = engine.stereo_correct(P[0], (c0, c1, c2)), engine.stereo_correct(P[1], (c0, c1, c2))
+            P, T = (P1, P2), T @ T1
+            if height <= tol:
+                converged = True
+                break
+        if apply:
+            for cam in self._cams:
+                cam.close()
+            self._build(P, self._shape)
+        return {"P": tuple(Pc.copy() for Pc in P), "T": T, "rounds": rounds, "converged": converged}
 
     def close(self):
         for cam in self._cams:

@@ -1042,6 +1042,57 @@ int tpiv_stereo_reconstruct(const double* u1, const double* v1, const double* u2
     return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_stereo_reconstruct");
 }
 
+int tpiv_stereo_triangulate(const double* dx, const double* dy, const double* X, const double* Y, const uint8_t* skip,
+                            int batch, long long cells, const double* cameras_host, double gap_max, const double* plane_host,
+                            double tol, const double* centre_host, double* Mx, double* My, double* Mz, double* gap,
+                            uint8_t* status, int32_t* count, double* sums, void* stream) {
+    if (batch < 0 || cells < 1) return fail(TPIV_EINVAL, "tpiv_stereo_triangulate: empty grid");
+    if (!dx || !dy || !X || !Y || !cameras_host || !plane_host || !centre_host || !status || !count || !sums)
+        return fail(TPIV_EINVAL, "tpiv_stereo_triangulate: null pointer");
+    const int n_points = (Mx != nullptr) + (My != nullptr) + (Mz != nullptr) + (gap != nullptr);
+    if (n_points != 0 && n_points != 4)
+        return fail(TPIV_EINVAL, "tpiv_stereo_triangulate: the points Mx, My, Mz, gap come all four or not at all");
+    if (!(gap_max >= 0)) return fail(TPIV_EINVAL, "tpiv_stereo_triangulate: gap_max must be >= 0 (infinity: no test)");
+    if (!(tol >= 0)) return fail(TPIV_EINVAL, "tpiv_stereo_triangulate: tol must be >= 0 (infinity: no test)");
+    if (cells >= (1LL << 31) || (long long)batch * cells >= (1LL << 31))
+        return fail(TPIV_EINVAL, "tpiv_stereo_triangulate: field stack too large");
+    if (batch == 0) return TPIV_OK;
+    const size_t n = (size_t)batch * cells, one = (size_t)cells;
+    const Span in[5] = {{dx, n * 8}, {dy, n * 8}, {X, one * 8}, {Y, one * 8}, {skip, one}};
+    const Span out[7] = {{Mx, n * 8}, {My, n * 8}, {Mz, n * 8}, {gap, n * 8}, {status, n}, {count, (size_t)batch * 4},
+                         {sums, (size_t)batch * 9 * 8}};
+    if (const int k = aliased(in, 5, out, 7))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_stereo_triangulate: an output aliases an input"
+                                        : "tpiv_stereo_triangulate: two outputs overlap");
+    if ((batch + tpiv::STEREO_BLOCK_PAIRS - 1) / tpiv::STEREO_BLOCK_PAIRS > 65535)
+        return fail(TPIV_EUNSUPPORTED, "tpiv_stereo_triangulate: too many items in one call");
+    tpiv::TriangulateParams q{};
+    q.dx = dx;
+    q.dy = dy;
+    q.X = X;
+    q.Y = Y;
+    q.skip = skip;
+    q.batch = batch;
+    q.cells = cells;
+    for (int k = 0; k < 3; ++k) {
+        q.C1[k] = cameras_host[k];
+        q.C2[k] = cameras_host[3 + k];
+        q.plane[k] = plane_host[k];
+        q.centre[k] = centre_host[k];
+    }
+    q.gap_max = gap_max;
+    q.tol = tol;
+    q.Mx = Mx;
+    q.My = My;
+    q.Mz = Mz;
+    q.gap = gap;
+    q.status = status;
+    q.count = count;
+    q.sums = sums;
+    hipError_t he = tpiv::launch_stereo_triangulate(q, (hipStream_t)stream);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_stereo_triangulate");
+}
+
 int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double eps, int min_neighbours) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
     if (kind != 0 && kind != 1) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: kind must be 0 (off) or 1 (normalized median)");

@@ -254,6 +254,27 @@ struct StereoParams {
 };
 hipError_t launch_stereo_reconstruct(const StereoParams& p, hipStream_t stream);
 
+// stereo self-calibration (stereo.hip, defined in include/torchpiv_hip.h: tpiv_stereo_triangulate): the same streaming
+// layout -- STEREO_BLOCK_THREADS lanes, one or two cells per lane, STEREO_BLOCK_PAIRS items of the stack per workgroup --
+// writes the points and the status; the sums of the plane fit are a second launch, one workgroup of STEREO_SUM_THREADS
+// lanes per item, that triangulates its cells again instead of reading the points back (they are optional).
+struct TriangulateParams {
+    const double *dx, *dy;                   // [batch, cells]
+    const double *X, *Y;                     // [cells]
+    const uint8_t* skip;                     // optional [cells]
+    int batch;
+    long long cells;
+    double C1[3], C2[3];                     // the camera centres
+    double gap_max;
+    double plane[3], tol;                    // c0, c1, c2
+    double centre[3];                        // Xm, Ym, Zm of the sums
+    double *Mx, *My, *Mz, *gap;              // out [batch, cells], all four or none
+    uint8_t* status;                         // out [batch, cells]
+    int32_t* count;                          // out [batch]
+    double* sums;                            // out [batch, 9]; none of the outputs may alias an input
+};
+hipError_t launch_stereo_triangulate(const TriangulateParams& p, hipStream_t stream);
+
 // geometric mask (mask.hip, defined in include/torchpiv_hip.h).  apply: out = mask ? 0 : frames for n frames against one
 // image (out may be frames itself).  coverage: a wavefront per window of the (ws, ov) grid counts its masked pixels into count
 // (optional) and writes grid = count > limit (optional).  fields: u = v = +0.0, invalid = invalid_value, status = 2 (optional)

@@ -11,6 +11,7 @@
 // The per-pair summary is a second launch that reads res and status back, one workgroup per pair, every lane summing its
 // cells in ascending order and the lanes combined by a fixed tree: no floating-point atomics, the same bytes every time.
 // Every floating-point operation is one IEEE float64 operation, contraction is off for this unit.
+// Below it, the self-calibration's triangulation (tpiv_stereo_triangulate) in the same layout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -205,6 +206,162 @@ hipError_t launch_stereo_reconstruct(const StereoParams& p, hipStream_t stream) 
     hipError_t he = hipGetLastError();
     if (he != hipSuccess) return he;
     hipLaunchKernelGGL(stereo_summary_kernel, dim3((unsigned)p.batch), dim3(kSum), 0, stream, p);
+    return hipGetLastError();
+}
+
+// ---- self-calibration: the point between the two cameras' lines of sight per cell of a disparity field, and the sums of a
+// plane fit through those points (include/torchpiv_hip.h: tpiv_stereo_triangulate has the definition and the operation
+// order).  The streaming kernel has stereo_kernel's layout -- a lane keeps X, Y and skip of its VEC cells and walks kPairs
+// items of the stack: 2 planes in and up to 4 planes and a byte out per item.  The sums are a second launch, one workgroup
+// of kSum lanes per item: lane t walks the cells t, t + kSum, ... and triangulates them AGAIN (about 60 operations, two
+// divisions and a root per cell: the same function, so the same bits) instead of reading Mx, My, Mz back, which the caller
+// may not have asked for; it reads dx, dy, X, Y and skip only.  Nine accumulators per lane, folded one after the other
+// through one 8 KiB LDS array by pair_rms's tree.  One workgroup per item is what the fixed order costs without work
+// memory: a large grid at a small batch leaves most of the device idle in this second launch (profiles/selfcal).
+namespace {
+
+struct TriPoint {
+    double x, y, z, gap;
+    int st;
+};
+
+__device__ __forceinline__ TriPoint triangulate(const TriangulateParams& p, bool centres, double dx, double dy, double X,
+                                                double Y, bool skipped) {
+    const double hx = dx * 0.5, hy = dy * 0.5;
+    const double q1x = X - hx, q1y = Y - hy, q2x = X + hx, q2y = Y + hy;
+    const double d1x = q1x - p.C1[0], d1y = q1y - p.C1[1], d1z = 0.0 - p.C1[2];
+    const double d2x = q2x - p.C2[0], d2y = q2y - p.C2[1], d2z = 0.0 - p.C2[2];
+    const double wx = p.C1[0] - p.C2[0], wy = p.C1[1] - p.C2[1], wz = p.C1[2] - p.C2[2];
+    const double a = d1x * d1x + d1y * d1y + d1z * d1z;
+    const double b = d1x * d2x + d1y * d2y + d1z * d2z;
+    const double c = d2x * d2x + d2y * d2y + d2z * d2z;
+    const double d = d1x * wx + d1y * wy + d1z * wz;
+    const double e = d2x * wx + d2y * wy + d2z * wz;
+    const double den = a * c - b * b;
+    const double s = (b * e - c * d) / den, t = (a * e - b * d) / den;
+    const double p1x = p.C1[0] + s * d1x, p1y = p.C1[1] + s * d1y, p1z = p.C1[2] + s * d1z;
+    const double p2x = p.C2[0] + t * d2x, p2y = p.C2[1] + t * d2y, p2z = p.C2[2] + t * d2z;
+    const double gx = p1x - p2x, gy = p1y - p2y, gz = p1z - p2z;
+    TriPoint o;
+    o.x = (p1x + p2x) * 0.5;
+    o.y = (p1y + p2y) * 0.5;
+    o.z = (p1z + p2z) * 0.5;
+    o.gap = __dsqrt_rn(gx * gx + gy * gy + gz * gz);
+    const double r = o.z - ((p.plane[0] + p.plane[1] * o.x) + p.plane[2] * o.y);
+    const bool data = is_finite(dx) && is_finite(dy);
+    const bool lines = is_finite(den) && den > 0.0;
+    o.st = skipped ? 1 : !centres ? 3 : !data ? 2 : !lines ? 3 : o.gap > p.gap_max ? 4 : __builtin_fabs(r) > p.tol ? 5 : 0;
+    return o;
+}
+
+__device__ __forceinline__ bool centres_finite(const TriangulateParams& p) {
+    return is_finite(p.C1[0]) && is_finite(p.C1[1]) && is_finite(p.C1[2]) && is_finite(p.C2[0]) && is_finite(p.C2[1]) &&
+           is_finite(p.C2[2]);
+}
+
+template <int VEC, bool PTS>
+__global__ __launch_bounds__(kThreads) void triangulate_kernel(TriangulateParams p) {
+    const size_t cells = (size_t)p.cells;
+    const size_t c0 = ((size_t)blockIdx.x * kThreads + threadIdx.x) * VEC;
+    if (c0 >= cells) return;                          // (VEC == 2: cells is even, both cells are inside)
+    const double nan = __longlong_as_double(kNaN);
+    const bool centres = centres_finite(p);
+    const DV<VEC> X = load<VEC>(p.X, c0), Y = load<VEC>(p.Y, c0);
+    BV<VEC> sk{};
+    if (p.skip != nullptr) sk = *reinterpret_cast<const BV<VEC>*>(p.skip + c0);
+    const int item0 = blockIdx.y * kPairs;
+    const int item1 = item0 + kPairs < p.batch ? item0 + kPairs : p.batch;
+    for (int item = item0; item < item1; ++item) {
+        const size_t at = (size_t)item * cells + c0;
+        const DV<VEC> dx = load<VEC>(p.dx, at), dy = load<VEC>(p.dy, at);
+        DV<VEC> oX, oY, oZ, oG;
+        BV<VEC> oS;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const TriPoint m = triangulate(p, centres, dx.x[k], dy.x[k], X.x[k], Y.x[k], sk.x[k] != 0);
+            const bool blank = m.st >= 1 && m.st <= 3;
+            oX.x[k] = blank ? nan : m.x;
+            oY.x[k] = blank ? nan : m.y;
+            oZ.x[k] = blank ? nan : m.z;
+            oG.x[k] = blank ? nan : m.gap;
+            oS.x[k] = (uint8_t)m.st;
+        }
+        if (PTS) {
+            store<VEC>(p.Mx, at, oX);
+            store<VEC>(p.My, at, oY);
+            store<VEC>(p.Mz, at, oZ);
+            store<VEC>(p.gap, at, oG);
+        }
+        *reinterpret_cast<BV<VEC>*>(p.status + at) = oS;
+    }
+}
+
+// count = the status-0 cells of the item; sums[0..8] = the sums of x, y, z, xx, xy, yy, xz, yz, zz over them with (x, y, z) =
+// M - centre: lane t sums its cells t, t + kSum, ... in ascending order from +0.0, then the lanes fold in halves.
+__global__ __launch_bounds__(kSum) void triangulate_sums_kernel(TriangulateParams p) {
+    __shared__ double acc[kSum];
+    __shared__ int cnt[kSum];
+    const int t = threadIdx.x;
+    const size_t cells = (size_t)p.cells, base = (size_t)blockIdx.x * cells;
+    const bool centres = centres_finite(p);
+    double sum[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sum[k] = 0.0;
+    int n = 0;
+#pragma unroll 2
+    for (size_t c = t; c < cells; c += kSum) {
+        const bool skipped = p.skip != nullptr && p.skip[c] != 0;
+        const TriPoint m = triangulate(p, centres, p.dx[base + c], p.dy[base + c], p.X[c], p.Y[c], skipped);
+        const bool ok = m.st == 0;
+        const double x = m.x - p.centre[0], y = m.y - p.centre[1], z = m.z - p.centre[2];
+        const double q[9] = {x, y, z, x * x, x * y, y * y, x * z, y * z, z * z};
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sum[k] = ok ? sum[k] + q[k] : sum[k];
+        n += ok ? 1 : 0;
+    }
+    cnt[t] = n;
+#pragma unroll                                        // (sum[] stays in registers)
+    for (int k = 0; k < 9; ++k) {
+        __syncthreads();                              // (the fold before has been read out)
+        acc[t] = sum[k];
+        __syncthreads();
+        for (int s = kSum / 2; s >= 1; s >>= 1) {
+            if (t < s) {
+                acc[t] = acc[t] + acc[t + s];
+                if (k == 0) cnt[t] += cnt[t + s];
+            }
+            __syncthreads();
+        }
+        if (t == 0) p.sums[(size_t)blockIdx.x * 9 + k] = acc[0];
+    }
+    if (t == 0) p.count[blockIdx.x] = cnt[0];
+}
+
+template <int VEC>
+void launch_triangulate_vec(const TriangulateParams& p, hipStream_t stream) {
+    const long long per_block = (long long)kThreads * VEC;
+    const dim3 grid((unsigned)((p.cells + per_block - 1) / per_block), (unsigned)((p.batch + kPairs - 1) / kPairs));
+    if (p.Mx != nullptr)
+        hipLaunchKernelGGL((triangulate_kernel<VEC, true>), grid, dim3(kThreads), 0, stream, p);
+    else
+        hipLaunchKernelGGL((triangulate_kernel<VEC, false>), grid, dim3(kThreads), 0, stream, p);
+}
+
+}  // namespace
+
+hipError_t launch_stereo_triangulate(const TriangulateParams& p, hipStream_t stream) {
+    if (p.batch <= 0) return hipSuccess;
+    if (p.cells < 1 || (p.batch + kPairs - 1) / kPairs > 65535) return hipErrorInvalidValue;
+    bool wide = p.cells % 2 == 0 && (p.skip == nullptr || ((uintptr_t)p.skip & 1) == 0) && ((uintptr_t)p.status & 1) == 0;
+    const void* planes[] = {p.dx, p.dy, p.X, p.Y, p.Mx, p.My, p.Mz, p.gap};
+    for (const void* q : planes) wide = wide && aligned16(q);       // (an absent plane is null: aligned)
+    if (wide)
+        launch_triangulate_vec<2>(p, stream);
+    else
+        launch_triangulate_vec<1>(p, stream);
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return he;
+    hipLaunchKernelGGL(triangulate_sums_kernel, dim3((unsigned)p.batch), dim3(kSum), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -1505,6 +1505,163 @@ def stereo_reconstruct(u1, v1, u2, v2, a1, b1, a2, b2, sigma=None, skip=None, fi
     return StereoFields(got)
 
 
+# ---- stereo self-calibration (Wieneke 2005): the sheet's plane from the disparity of the two rectified views, and the
+# cameras expressed in the frame of that plane.  The triangulation is the device's (tpiv_stereo_triangulate); the plane and
+# the corrected cameras are host geometry (numpy float64, no GPU).
+
+def stereo_cells(x, y, scale, origin=(0.0, 0.0)):
+    """The world positions (X, Y) of the cells in the orientation of the delivered fields: x, y [n_rows, n_cols] are the
+    window centres as get_coordinates returns them; cell [r, c] of a delivered field is the world point (X0 + p x[r, c], Y0 -
+    p y[n_rows - 1 - r, c], 0) -- the flip stereo_planes applies.  Returns contiguous float64 arrays."""
+    p, X0, Y0 = _stereo_scale(scale, origin, "stereo_cells")
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError(f"stereo_cells: x, y must be [n_rows, n_cols] arrays of one shape, got {x.shape} and {y.shape}")
+    return np.ascontiguousarray(X0 + p * x), np.ascontiguousarray(Y0 - p * np.flip(y, axis=0))
+
+
+class StereoPoints(tuple):
+    """What stereo_triangulate returns: a tuple (X, Y, Z, gap, status, count, sums) -- (status, count, sums) with
+    points=False -- whose elements also answer to these names."""
+
+    def __new__(cls, values, names):
+        self = super().__new__(cls, values)
+        self._names = tuple(names)
+        return self
+
+    def __getattr__(self, name):
+        names = self.__dict__.get("_names", ())
+        if name in names:
+            return self[names.index(name)]
+        raise AttributeError(name)
+
+    @property
+    def count(self):                                  # (tuple.count would answer first)
+        return self[self._names.index("count")]
+
+
+def stereo_triangulate(dx, dy, X, Y, C1, C2, skip=None, gap_max=float("inf"), plane=None, tol=float("inf"),
+                       centre=(0.0, 0.0, 0.0), points=True):
+    """The points of the light sheet from a disparity field (tpiv_stereo_triangulate; include/torchpiv_hip.h has the
+    arithmetic).  dx, dy: float64 tensors [batch, n_rows, n_cols] (or without the batch axis; any cell shape, [cells]
+    included) on the GPU, in mm, camera 2's rectified position minus camera 1's along X and Y (up) -- what
+    StereoPIV.disparity() returns; X, Y: float64 tensors of the cell shape, the cells on z = 0 (stereo_cells); C1, C2: the
+    camera centres (stereo_centre), three numbers each; skip: None or uint8 / bool of the cell shape; gap_max: the longest
+    accepted distance between the two lines of sight (status 4 beyond it); plane = (c0, c1, c2) and tol: cells further than
+    tol from the plane get status 5 (None: the plane 0 -- give tol with a plane); centre = (Xm, Ym, Zm): subtracted before
+    the sums.  Returns a StereoPoints record: X, Y, Z, gap float64 (left out with points=False) and status uint8 shaped
+    like dx, count int32 and sums float64 [batch] and [batch, 9] (a scalar and [9] for an input without the batch axis):
+    the sums of x, y, z, xx, xy, yy, xz, yz, zz over the status-0 cells -- what stereo_plane takes."""
+    every = (dx, dy, X, Y)
+    if any(not isinstance(t, torch.Tensor) for t in every) or (skip is not None and not isinstance(skip, torch.Tensor)):
+        raise TypeError("stereo_triangulate: tensors on the GPU")
+    _need_cuda(*every, skip)
+    if any(t.dtype != torch.float64 for t in every) or (skip is not None and skip.dtype not in (torch.uint8, torch.bool)):
+        raise TypeError("stereo_triangulate: dx, dy, X, Y float64, skip uint8 or bool")
+    grid = tuple(X.shape)
+    if X.dim() < 1 or Y.shape != X.shape or dx.shape != dy.shape or dx.dim() not in (X.dim(), X.dim() + 1) \
+            or tuple(dx.shape[dx.dim() - X.dim():]) != grid:
+        raise ValueError("stereo_triangulate: dx, dy of one shape, [batch] + the shape of X, Y or that shape itself")
+    if skip is not None and tuple(skip.shape) != grid:
+        raise ValueError(f"stereo_triangulate: skip must have the cells' shape {grid}")
+    if any(t.device != dx.device for t in every) or (skip is not None and skip.device != dx.device):
+        raise ValueError("stereo_triangulate: every tensor on one device")
+    cells = int(np.prod(grid))
+    if cells < 1:
+        raise ValueError("stereo_triangulate: empty grid")
+
+    def triple(v, what):
+        try:
+            out = [float(q) for q in v]
+        except (TypeError, ValueError):
+            out = []
+        if len(out) != 3:
+            raise ValueError(f"stereo_triangulate: {what} takes three numbers, got {v!r}")
+        return out
+    cams = triple(C1, "C1") + triple(C2, "C2")
+    pl = [0.0, 0.0, 0.0] if plane is None else triple(plane, "plane")
+    mid = triple(centre, "centre")
+    for name, v in (("gap_max", gap_max), ("tol", tol)):
+        if not is_real(v) or not float(v) >= 0:
+            raise ValueError(f"stereo_triangulate: {name} must be a number >= 0 (infinity: no test), got {v!r}")
+    flat = dx.dim() == X.dim()
+    B = 1 if flat else dx.shape[0]
+    dx, dy, X, Y = (t.contiguous() for t in every)
+    if skip is not None:
+        skip = skip.contiguous()
+        skip = skip.view(torch.uint8) if skip.dtype == torch.bool else skip
+    dev = dx.device
+    shape = (B,) + grid
+    out = [torch.empty(shape, dtype=torch.float64, device=dev) for _ in range(4)] if points else []
+    status = torch.empty(shape, dtype=torch.uint8, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    sums = torch.empty((B, 9), dtype=torch.float64, device=dev)
+    host = lambda v: (C.c_double * len(v))(*v)                          # noqa: E731
+    with torch.cuda.device(dev):
+        check(lib.tpiv_stereo_triangulate(dx.data_ptr(), dy.data_ptr(), X.data_ptr(), Y.data_ptr(),
+                                          None if skip is None else skip.data_ptr(), B, cells, host(cams), float(gap_max),
+                                          host(pl), float(tol), host(mid), *([t.data_ptr() for t in out] or [None] * 4),
+                                          status.data_ptr(), count.data_ptr(), sums.data_ptr(), _stream()))
+    got = out + [status, count, sums]
+    if flat:
+        got = [t[0] for t in got]
+    return StereoPoints(got, (("X", "Y", "Z", "gap") if points else ()) + ("status", "count", "sums"))
+
+
+def stereo_plane(count, sums, centre=(0.0, 0.0, 0.0)):
+    """(c0, c1, c2, rms): the least-squares plane Z = c0 + c1 X + c2 Y through the points whose centred sums
+    stereo_triangulate returns -- count and sums [9] of ONE item (numbers, arrays or tensors), centre the point the sums
+    were taken about -- from the normal equations of the centred moments: Sxx = sum xx - (sum x)^2 / n and so on, (c1, c2)
+    from the 2 x 2 block, c0 from the means; rms = the root of the mean squared residual.  ValueError for fewer than 3
+    points, non-finite sums, and points on one line: the block's determinant must exceed 1e-12 Sxx Syy."""
+    n = int(count)
+    s = np.asarray(sums.cpu() if isinstance(sums, torch.Tensor) else sums, dtype=np.float64).reshape(-1)
+    Xm, Ym, Zm = (float(q) for q in centre)
+    if s.shape != (9,) or not np.isfinite(s).all():
+        raise ValueError("stereo_plane: sums takes the nine finite sums of one item")
+    if n < 3:
+        raise ValueError(f"stereo_plane: a plane needs at least 3 cells, got {n}")
+    mx, my, mz = s[0] / n, s[1] / n, s[2] / n
+    Sxx, Sxy, Syy = s[3] - s[0] * mx, s[4] - s[0] * my, s[5] - s[1] * my
+    Sxz, Syz, Szz = s[6] - s[0] * mz, s[7] - s[1] * mz, s[8] - s[2] * mz
+    det = Sxx * Syy - Sxy * Sxy
+    if not (Sxx > 0 and Syy > 0 and det > 1e-12 * Sxx * Syy):
+        raise ValueError("stereo_plane: the cells lie on one line and do not determine a plane")
+    c1 = (Sxz * Syy - Syz * Sxy) / det
+    c2 = (Syz * Sxx - Sxz * Sxy) / det
+    k = mz - c1 * mx - c2 * my                                         # the plane in centred coordinates: z = k + c1 x + c2 y
+    c0 = Zm + k - c1 * Xm - c2 * Ym
+    ss = Szz - c1 * Sxz - c2 * Syz
+    return float(c0), float(c1), float(c2), float(np.sqrt(max(ss, 0.0) / n))
+
+
+def stereo_correct(P, plane):
+    """(P_new, T): the camera P [3, 4] expressed in the world frame of the measured sheet.  plane = (c0, c1, c2): the sheet
+    is Z = c0 + c1 X + c2 Y in the OLD frame.  T [4, 4] is the rigid transform that takes NEW world coordinates to old ones:
+    its z axis is the plane's normal n = (-c1, -c2, 1) / |.|, its x axis the old X axis projected into the plane and
+    normalised, y = n x x, its origin (0, 0, c0), the plane's point above the old origin.  P_new = P @ T projects a point
+    given in the new frame to where P projects the same point given in the old one; the sheet is z = 0 in the new frame.
+    ValueError for a non-finite plane and when the corrected centre does not lie in front of the sheet (C_z > 0)."""
+    P = _stereo_camera(P, "stereo_correct")
+    try:
+        c0, c1, c2 = (float(q) for q in plane)
+    except (TypeError, ValueError):
+        raise ValueError(f"stereo_correct: plane takes three numbers (c0, c1, c2), got {plane!r}") from None
+    if not (np.isfinite(c0) and np.isfinite(c1) and np.isfinite(c2)):
+        raise ValueError(f"stereo_correct: the plane must be finite, got {(c0, c1, c2)}")
+    n = np.array([-c1, -c2, 1.0])
+    n /= np.sqrt(n @ n)
+    ex = np.array([1.0, 0.0, 0.0]) - n[0] * n
+    ex /= np.sqrt(ex @ ex)
+    T = np.eye(4)
+    T[:3, 0], T[:3, 1], T[:3, 2], T[:3, 3] = ex, np.cross(n, ex), n, (0.0, 0.0, c0)
+    P_new = P @ T
+    C_ = stereo_centre(P_new)
+    if not (np.isfinite(C_).all() and C_[2] > 0):
+        raise ValueError(f"stereo_correct: the corrected camera centre {tuple(C_)} does not lie in front of the sheet (C_z > 0)")
+    return P_new, T
+
+
 class Plan:
     """The multipass pipeline of OfflinePIV.__call__ (PIVbackend.py:873-882) for batches of
     pairs resident on one GPU.  Owns the device workspace; `run` only enqueues kernels."""
