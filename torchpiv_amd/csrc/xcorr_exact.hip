@@ -15,6 +15,8 @@
 //      span; W / 4 v_dot4_u32_u8 per lane and cell --, re-checks the decisions on the exact values (no neighbour or second
 //      candidate above the arg-max, no evaluated cell below the minimum) and writes the 8-double record of
 //      finalize_kernel<true>.  Undecided windows are appended to a list.
+//      64x64 swaps the frames' roles: frame b's row in the lane's registers, ROTATED THERE (dx is wave-uniform: one window
+//      per wavefront), frame a in an LDS tile read by rows -- rot_cells; the same integers.
 //      xcorr_exact_refine_any_kernel<G> (here): the same for any even W <= 128 (8, the generic sizes 12 ... 126) with lane =
 //      CELL: both windows in LDS, the lane of a cell walks all rows of its rotation;
 //   3. xcorr_f64_list_kernel<W> / xcorr_f64_tile_list_kernel<W> (xcorr_f64.hip) / the float64 generic kernel run the float64
@@ -39,8 +41,8 @@ struct XGeo {
     static constexpr int GROUP = W < 64 ? W : 64;            // lanes of one window inside a wavefront
     static constexpr int WPW = 64 / GROUP;                   // windows per wavefront (32x32: two)
     static constexpr int PARTS = W / GROUP;                  // wavefronts per window (128x128: two)
-    // wavefronts per workgroup.  64x64 (one window per wavefront): 2 -> 16.9 KB of LDS per workgroup, 9 workgroups = 18
-    // wavefronts per CU against 4 x 4 = 16 with 4 (1.10 -> 1.06 ms per 1 016 064 windows; profiles/exact_neighbourhood)
+    // wavefronts per workgroup.  64x64 (one window per wavefront, 5 KB of LDS and 64 registers each: 8 wavefronts per SIMD
+    // either way): 1 and 2 measure alike (0.945 / 0.93 ms per 1 016 064 windows; profiles/exact_rotation)
     static constexpr int WAVES = W == 128 || W == 64 ? 2 : 4;
     static constexpr int WINS = WAVES * WPW / PARTS;         // windows per workgroup: 8 / 2 / 1
     static constexpr int KD = W * W;
@@ -51,6 +53,12 @@ struct XGeo {
     static constexpr int LW = GROUP * PARTS;                 // lanes per window
     static constexpr int AP = NDW + 4;                       // dwords per row of the frame-a hand-over tile (16-byte reads, all banks)
     static_assert(!COOP || (W * AP <= W * XP && (LW * P16) == W * P16), "the hand-over tile lives in the parked rows' memory");
+    // 64x64 (one window per wavefront, so dx is wave-uniform): frame b is NOT parked.  It passes through a hand-over tile and
+    // comes back as the lane's own row in registers, where it is rotated; frame a's chunks follow through the SAME tile and
+    // stay there (rot_cells below).  One tile of W x AP dwords per window: with a tile for each frame (one wave_sync less)
+    // LDS holds 16 wavefronts per CU instead of 32, and the wavefront count is what this kernel's time follows
+    static constexpr bool ROT = W == 64;
+    static constexpr int LDS_DW = ROT ? W * AP : W * XP;     // dwords of LDS per window
 };
 constexpr int XCELLS = 5 + EXACT_MAX_SECOND + EXACT_MAX_MIN;      // cells a window can ask for
 
@@ -134,6 +142,155 @@ __device__ __forceinline__ void decide_and_store(const PassParams& p, const uint
     if (go && !redo && r0 < 8 && writer) out[r0] = v;
 }
 
+// ---- 64x64 (XGeo<W>::ROT): the cells' partial sums with frame b ROTATED IN REGISTERS.  The parked form below does the
+// rotation by addressing LDS: every frame-b chunk is scattered twice over into odd-pitch rows (32 bank-conflicted ds_write_b32
+// per lane) and comes back as spans of single dwords.  Here the two frames swap roles: lane y keeps b[y][0..W) in NDW
+// registers (through a hand-over tile: 16-byte accesses, pitch AP; the reads are conflict-free, the stores conflict two-way:
+// 8 lanes = two rows against 32 banks), frame a stays in a tile of the same kind,
+// and for a cell (dy, dx) lane y reads row (y - dy) & (W - 1) of frame a and forms
+//     sum_x a[y - dy][x] b[y][(x + dx) & (W - 1)];
+// summed over the lanes that is the integer sum_y a[y] . b[y + dy] of the parked form (y -> y - dy): every S is the same.
+// One window per wavefront makes dx wave-uniform: the dword part of the rotation is a uniform choice among NDW bodies
+// with static register indices (indices mod NDW: the circular wrap is free), the byte part a scalar operand of v_alignbyte.
+// f(integral constant s) for the wave-uniform s in 0 ... 15: the uniform choice among 16 statically indexed bodies
+template <typename F>
+__device__ __forceinline__ void rot_choice(int s, F&& f) {
+    switch (__builtin_amdgcn_readfirstlane(s)) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 7: f(std::integral_constant<int, 7>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 9: f(std::integral_constant<int, 9>{}); break;
+        case 10: f(std::integral_constant<int, 10>{}); break;
+        case 11: f(std::integral_constant<int, 11>{}); break;
+        case 12: f(std::integral_constant<int, 12>{}); break;
+        case 13: f(std::integral_constant<int, 13>{}); break;
+        case 14: f(std::integral_constant<int, 14>{}); break;
+        default: f(std::integral_constant<int, 15>{}); break;
+    }
+}
+// dword i of row b rotated by 4 S + sh bytes (byte x of the rotated row is b's byte (x + 4 S + sh) mod 64)
+template <int S>
+__device__ __forceinline__ uint32_t rot_dword(const uint32_t (&b)[16], int i, unsigned sh) {
+    return __builtin_amdgcn_alignbyte(b[(i + S + 1) & 15], b[(i + S) & 15], sh);
+}
+// u = row b rotated by bx bytes.  bx is the same in every lane.
+__device__ __forceinline__ void rotate_row(const uint32_t (&b)[16], int bx, uint32_t (&u)[16]) {
+    const unsigned sh = (unsigned)__builtin_amdgcn_readfirstlane(bx & 3);
+    rot_choice(bx >> 2, [&](auto sc) TPIV_LAMBDA_INLINE {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) u[i] = rot_dword<decltype(sc)::value>(b, i, sh);
+    });
+}
+// sum_i a[i] . (row b rotated by bx bytes)[i]: the rotated dwords go straight into the dot products (no second row of
+// registers); two chains, because a dot product straight into the last one's sum waits a state
+__device__ __forceinline__ unsigned rotate_dot(const uint32_t (&a)[16], const uint32_t (&b)[16], int bx) {
+    const unsigned sh = (unsigned)__builtin_amdgcn_readfirstlane(bx & 3);
+    unsigned acc[2] = {0u, 0u};
+    rot_choice(bx >> 2, [&](auto sc) TPIV_LAMBDA_INLINE {
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            acc[i & 1] = __builtin_amdgcn_udot4(a[i], rot_dword<decltype(sc)::value>(b, i, sh), acc[i & 1], false);
+    });
+    return acc[0] + acc[1];
+}
+
+// tile: the window's LDS; ca / cb: the lane's 16-byte chunks of the two frames (chunk ci = lane + 64 k: row ci / 4, piece
+// ci % 4); q: the cell of lane j < XCELLS or -1.  Fills P[0 .. XCELLS) and the window sums P[12], P[13].
+template <int W>
+__device__ __forceinline__ void rot_cells(uint32_t* tile, int lane, const uint32_t (&ca)[XGeo<W>::P16][4],
+                                          const uint32_t (&cb)[XGeo<W>::P16][4], bool go, int m, bool nb_fast, int q,
+                                          unsigned (&P)[16]) {
+    using G = XGeo<W>;
+    constexpr int NDW = G::NDW, KD = G::KD, RP = G::AP / 4;  // (RP: tile row pitch in 16-byte pieces)
+    static_assert(NDW == 16 && G::WPW == 1 && G::PARTS == 1, "one window per wavefront, 16 dwords per row");
+    uint4* const ta = reinterpret_cast<uint4*>(tile);       // (first frame b's chunks, then frame a's)
+    auto put = [&](uint4* t, const uint32_t (&ch)[G::P16][4]) TPIV_LAMBDA_INLINE {
+#pragma unroll
+        for (int k = 0; k < G::P16; ++k) {
+            const int ci = lane + 64 * k;
+            t[(ci / G::P16) * RP + ci % G::P16] = make_uint4(ch[k][0], ch[k][1], ch[k][2], ch[k][3]);
+        }
+    };
+    auto get_row = [&](const uint4* t, int r, uint32_t (&d)[NDW]) TPIV_LAMBDA_INLINE {
+#pragma unroll
+        for (int k = 0; k < NDW / 4; ++k) {
+            const uint4 v = t[r * RP + k];
+            d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
+        }
+    };
+    // the window sums from the chunks: no lane needs its own frame-a row
+#pragma unroll
+    for (int k = 0; k < G::P16; ++k) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            P[12] = __builtin_amdgcn_sad_u8(ca[k][c], 0u, P[12]);
+            P[13] = __builtin_amdgcn_sad_u8(cb[k][c], 0u, P[13]);
+        }
+    }
+    uint32_t b[NDW];
+    put(ta, cb);
+    wave_sync();
+    get_row(ta, lane, b);
+    wave_sync();                                        // (b's reads are issued: LDS serves a wavefront in order)
+    put(ta, ca);
+    wave_sync();
+
+    // ---- S at every other requested cell (all of them for an irregular arg-max): one loop, one rotation choice inside
+#pragma nounroll
+    for (int c = nb_fast ? 5 : 0; c < XCELLS; ++c) {
+        const int qc = __builtin_amdgcn_readlane(q, c);
+        if (qc < 0) continue;                           // (wave-uniform)
+        const int dy = qc / W - W / 2, bx = (qc % W - W / 2) & (W - 1);
+        uint32_t a[NDW];
+        get_row(ta, (lane - dy) & (W - 1), a);
+        P[c] = rotate_dot(a, b, bx);
+    }
+    // ---- S at m and its four neighbours, shared (regular arg-max): ONE rotation to byte (dx - 1) mod W gives m - 1 (u), and
+    //      m / m + 1 one and two bytes on (u[NDW] = u[0]: circular); m +- W are m's rotation against the frame-a rows
+    //      (y - dy -+ 1).  LAST, so that the rotated row takes frame b's registers (nothing needs b after it)
+    if (nb_fast) {
+        const int mm = go ? m : KD / 2 + W / 2;         // (a window that does not go: any cell, discarded)
+        const int dy = mm / W - W / 2, s = (mm % W - W / 2 - 1) & (W - 1);
+        const int r0 = (lane - dy) & (W - 1), ru = (r0 - 1) & (W - 1), rd = (r0 + 1) & (W - 1);
+        uint32_t u[NDW];
+        rotate_row(b, s, u);
+        unsigned s_m = 0u, s_l = 0u, s_r = 0u, s_t = 0u, s_b = 0u;
+        // (16 bytes of a row at a time, the rows above and below in a second sweep that forms m's rotation again: whole rows,
+        //  or three rows at once, would cost the registers that the eighth wavefront per SIMD lives on)
+#pragma unroll
+        for (int k = 0; k < NDW / 4; ++k) {
+            const uint4 va = ta[r0 * RP + k];
+            const uint32_t a[4] = {va.x, va.y, va.z, va.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t lo = u[4 * k + j], nx = u[(4 * k + j + 1) % NDW];
+                s_r = __builtin_amdgcn_udot4(a[j], lo, s_r, false);
+                s_m = __builtin_amdgcn_udot4(a[j], __builtin_amdgcn_alignbyte(nx, lo, 1u), s_m, false);
+                s_l = __builtin_amdgcn_udot4(a[j], __builtin_amdgcn_alignbyte(nx, lo, 2u), s_l, false);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NDW / 4; ++k) {
+            const uint4 vu = ta[ru * RP + k], vd = ta[rd * RP + k];
+            const uint32_t au[4] = {vu.x, vu.y, vu.z, vu.w}, ad[4] = {vd.x, vd.y, vd.z, vd.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t c = __builtin_amdgcn_alignbyte(u[(4 * k + j + 1) % NDW], u[4 * k + j], 1u);
+                s_t = __builtin_amdgcn_udot4(au[j], c, s_t, false);
+                s_b = __builtin_amdgcn_udot4(ad[j], c, s_b, false);
+            }
+            if (k & 1) __builtin_amdgcn_sched_barrier(0);        // (at most four reads ahead: the scheduler would hoist all eight)
+        }
+        P[0] = go ? s_m : 0u, P[1] = go ? s_l : 0u, P[2] = go ? s_r : 0u, P[3] = go ? s_t : 0u, P[4] = go ? s_b : 0u;
+    }
+}
+
 // Everything below is per-lane data with predicated control flow: for 32x32 the two windows of a wavefront take their
 // decisions independently.  (64x64: one window per wavefront; 128x128: one window per workgroup of two wavefronts, partial
 // sums joined through LDS behind ONE barrier that both wavefronts reach or neither does.)
@@ -141,7 +298,7 @@ template <int W>
 __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel(PassParams p) {
     using G = XGeo<W>;
     constexpr int NDW = G::NDW, XP = G::XP, KD = G::KD;
-    __shared__ __attribute__((aligned(16))) uint32_t parked[G::WINS][W * XP];
+    __shared__ __attribute__((aligned(16))) uint32_t parked[G::WINS][G::LDS_DW];
     __shared__ unsigned joined[2][16];                       // 128x128: per wavefront the partial S of 12 cells + 4 window sums
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
@@ -244,7 +401,9 @@ __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel
         else wave_sync();
     };
     uint32_t au[NDW], ad[NDW];                               // frame-a rows (row - 1), (row + 1): the shared neighbourhood only
-    if constexpr (G::COOP) {
+    if constexpr (G::ROT) {
+        rot_cells<W>(rows_b, lane, ca, cb, go, m, nb_fast, q, P);        // (64x64: every cell, frame b rotated in registers)
+    } else if constexpr (G::COOP) {
         // frame a: chunks -> hand-over tile (pitch AP dwords: 16-byte reads of 16 lanes cover all banks) -> the lane's row
         uint4* const ta = reinterpret_cast<uint4*>(rows_b);
 #pragma unroll
@@ -290,12 +449,12 @@ __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel
             rows_b[row * XP + NDW + i] = b[i];
         }
     }
-    lds_sync();                                         // the rows are parked
+    if constexpr (!G::ROT) lds_sync();                  // the rows are parked
 
     // ---- S at m and its four neighbours, shared (regular arg-max, see above): ONE span of NDW + 2 dwords from byte s =
     //      (dx - 1) mod W of m's frame-b row, aligned to s once (u), then the rotations s / s + 1 / s + 2 (m - 1 / m / m + 1)
     //      and m's span against the frame-a rows above and below (m + W / m - W)
-    if constexpr (G::COOP) {
+    if constexpr (G::COOP && !G::ROT) {
         if (nb_fast) {
             const int mm = go ? m : KD / 2 + W / 2;     // (windows that do not go: any cell, discarded)
             const int dy = mm / W - W / 2, s = (mm % W - W / 2 - 1) & (W - 1);
@@ -321,7 +480,7 @@ __global__ __launch_bounds__(64 * XGeo<W>::WAVES) void xcorr_exact_refine_kernel
         }
     }
     // ---- S at every other requested cell (all of them when the wavefront does not take the shared neighbourhood)
-    static_for<0, XCELLS>([&](auto cc) TPIV_LAMBDA_INLINE {
+    static_for<0, G::ROT ? 0 : XCELLS>([&](auto cc) TPIV_LAMBDA_INLINE {
         constexpr int c = decltype(cc)::value;
         if (c < 5 && nb_fast) return;                   // (done above)
         int qc = __builtin_amdgcn_readlane(q, c);
