@@ -317,6 +317,74 @@ int tpiv_stereo_triangulate(const double* dx_dev, const double* dy_dev, const do
                             double* Mx_dev, double* My_dev, double* Mz_dev, double* gap_dev, uint8_t* status_dev,
                             int32_t* count_dev, double* sums_dev, void* stream);
 
+/* ---- particle images and their pairing: hybrid PIV / PTV (extension; the reference has none) ------- */
+
+/* Particle images of n frames frames_dev uint8 [n, H, W], H, W >= 3.  Pixel (r, c) with 1 <= r <= H - 2 and 1 <= c <= W - 2
+ * and intensity I is a particle image iff
+ *   I >= level (0..255),
+ *   mask_dev (uint8 [H, W] or NULL, one image for every frame) is zero there,
+ *   I >  the pixels (r-1, c-1), (r-1, c), (r-1, c+1), (r, c-1)   -- the four neighbours before it in raster order,
+ *   I >= the pixels (r, c+1), (r+1, c-1), (r+1, c), (r+1, c+1)   -- the four behind it;
+ * so a plateau of equal pixels gives its raster-first pixel alone, and two horizontally, vertically or diagonally
+ * adjacent pixels are never both reported.  Border pixels are never reported, however bright.
+ * tpiv_particle_count writes, per frame f, row_start_dev int32 [n, H + 1]: entry r = how many particle images lie in the
+ * rows before r (entry 0 = 0, entry H = the total), and count_dev int32 [n] = that total.  Enqueues only (two launches);
+ * allocates nothing.
+ * tpiv_particle_detect takes row_start_dev as tpiv_particle_count (same frames, level, mask) left it and writes the list of
+ * each frame in RASTER ORDER of the peak pixel -- list index = row_start[r] + the particle images of row r left of c; the
+ * order is a property of the index, not of scheduling, and no atomic operation takes part -- into x_dev, y_dev float64
+ * [n, capacity] and peak_dev uint8 [n, capacity]: peak = I, and with T = table_dev float64 [256] (the caller's table of
+ * ln(max(i, 1))), per axis in float64, every operation rounded once, as written:
+ *   den = (L - 2*C) + R;  off = den < 0 ? (L - R) / (2*den) : 0
+ *   x = c + off   with L = T[I(r, c-1)], C = T[I], R = T[I(r, c+1)]
+ *   y = r + off   with L = T[I(r-1, c)], C = T[I], R = T[I(r+1, c)]
+ * (image coordinates: x along the columns, y along the rows downward, pixel (0, 0) centred at the origin; |off| <= 1/2 up
+ * to rounding).  A host model that does the same operations on the same table gives the same bits.  Capacity: the
+ * first `capacity` particle images of a frame are stored; entries at list index >= capacity are not written, nor are the
+ * entries of a frame behind its last particle image; row_start and count stay those of the whole list.  capacity == 0
+ * writes nothing (x_dev, y_dev, peak_dev may be NULL).  Enqueues only (one launch); allocates nothing.
+ * TPIV_EINVAL, nothing launched: a null frames, row_start, count, table or (capacity > 0) list pointer, n < 0, H or W < 3,
+ * level outside 0..255, capacity < 0, H * W >= 2^31, n * (H + 1) or n * capacity >= 2^31, an output that overlaps an input
+ * or another output.  TPIV_EUNSUPPORTED: more than 65535 frames.  n == 0 succeeds and launches nothing.  The frames, the
+ * mask and the table are not written. */
+int tpiv_particle_count(const uint8_t* frames_dev, int n, int H, int W, int level, const uint8_t* mask_dev,
+                        int32_t* row_start_dev, int32_t* count_dev, void* stream);
+int tpiv_particle_detect(const uint8_t* frames_dev, int n, int H, int W, int level, const uint8_t* mask_dev,
+                         const double* table_dev, const int32_t* row_start_dev, int capacity, double* x_dev, double* y_dev,
+                         uint8_t* peak_dev, void* stream);
+
+/* Pairs the particle images of frame a with those of frame b, for n pairs of frames [H, W].  xa_dev, ya_dev float64
+ * [n, cap_a] and rsa_dev int32 [n, H + 1], xb_dev, yb_dev [n, cap_b] and rsb_dev: lists as tpiv_particle_detect writes them
+ * (raster order; the stored length of a list is min(row_start[H], capacity)).  up_dev, vp_dev float64 [n, n_rows, n_cols]:
+ * the predicted displacement in pixels in image orientation (u along the columns, v along the rows downward, row 0 the
+ * top row of windows) at the window centres xc_dev float64 [n_cols], yc_dev [n_rows] (image coordinates, strictly
+ * ascending).  radius: R > 0, finite.  For particle i of a at (x, y), in float64, every operation rounded once, as written:
+ *   per axis, with k = how many centres are <= the coordinate:  j0 = max(k - 1, 0);  j1 = min(k, n - 1);
+ *     t = j1 > j0 ? (coordinate - c[j0]) / (c[j1] - c[j0]) : 0          -- constant outside the centres; a 1-wide grid works
+ *   g(x, y) = a + ty*(b - a)   with a = g[y0][x0] + tx*(g[y0][x1] - g[y0][x0]),  b = g[y1][x0] + tx*(g[y1][x1] - g[y1][x0])
+ *   px = x + up(x, y);  py = y + vp(x, y)
+ *   status 3 unless 0 <= px <= W - 1 and 0 <= py <= H - 1  (a NaN is outside)
+ *   candidates: the stored particles j of b in the rows max(ceil(py - R - 0.5), 0) .. min(floor(py + R + 0.5), H - 1) (through
+ *     rsb) with  d2 = dx*dx + dy*dy <= R*R,  dx = px - xb[j],  dy = py - yb[j]  (the bound inclusive)
+ *   fwd = the candidate of smallest d2, of equal ones the lowest j;  status 1 without a candidate
+ *   one-to-one: j goes to the claimant (i with fwd = j) of smallest d2, of equal ones the lowest i; the others get status 2.
+ * match_dev int32 [n, cap_a]: j at status 0, else -1.  status_dev uint8 [n, cap_a]: 0 matched, 1 no candidate, 2 lost
+ * the candidate to a nearer claimant, 3 predicted outside the frame, 255 for the entries behind the stored list.  d2_dev
+ * float64 [n, cap_a]: the d2 to fwd at status 0 and 2, NaN (0x7ff8000000000000) otherwise.  matched_dev int32 [n]: how
+ * many have status 0.  The claims are decided by unsigned integer atomic minima (on the bit pattern of d2, which orders
+ * like d2 >= +0.0, then on i) between launches, the count by integer atomic adds: nothing depends on scheduling, and a host
+ * model that does the same operations gives the same bits.  work_dev: work_bytes >= 16 * n * cap_b bytes, 8-byte aligned,
+ * contents ignored and overwritten.  TPIV_EINVAL, nothing launched: a null pointer (lists of capacity 0 and their work
+ * memory may be NULL), n < 0, H, W, n_rows or n_cols < 1, a negative capacity, a radius that is not a positive finite
+ * number, work memory too small or misaligned, n * (H + 1), n * cap_a, n * cap_b or n * n_rows * n_cols >= 2^31, an output that
+ * overlaps an input, the work memory or another output.  TPIV_EUNSUPPORTED: more than 65535 pairs.  n == 0 succeeds and
+ * launches nothing.  The inputs are not written.  Enqueues only (two memsets, three launches); allocates nothing. */
+int tpiv_particle_match(const double* xa_dev, const double* ya_dev, const int32_t* rsa_dev, int cap_a, const double* xb_dev,
+                        const double* yb_dev, const int32_t* rsb_dev, int cap_b, int n, int H, int W, const double* up_dev,
+                        const double* vp_dev, int n_rows, int n_cols, const double* xc_dev, const double* yc_dev,
+                        double radius, int32_t* match_dev, uint8_t* status_dev, double* d2_dev, int32_t* matched_dev,
+                        void* work_dev, size_t work_bytes, void* stream);
+
 /* ---- geometric mask (extension; the reference has none) ------------------------------------------ */
 
 /* Pixel step: out_dev[f][p] = mask_dev[p] != 0 ? 0 : frames_dev[f][p] for n frames [n, pixels] uint8 against one image

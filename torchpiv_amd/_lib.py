@@ -87,6 +87,10 @@ SIGNATURES = {
     "tpiv_stereo_triangulate": (C.c_int, [_f64p] * 4 + [_u8p, _int, C.c_longlong, C.POINTER(C.c_double), _dbl,
                                           C.POINTER(C.c_double), _dbl, C.POINTER(C.c_double)] + [_f64p] * 4
                                 + [_u8p, _vp, _f64p, _vp]),
+    "tpiv_particle_count": (C.c_int, [_u8p, _int, _int, _int, _int, _u8p, _vp, _vp, _vp]),
+    "tpiv_particle_detect": (C.c_int, [_u8p, _int, _int, _int, _int, _u8p, _f64p, _vp, _int, _f64p, _f64p, _u8p, _vp]),
+    "tpiv_particle_match": (C.c_int, [_f64p, _f64p, _vp, _int, _f64p, _f64p, _vp, _int, _int, _int, _int, _f64p, _f64p, _int,
+                                      _int, _f64p, _f64p, _dbl, _vp, _u8p, _f64p, _vp, _vp, C.c_size_t, _vp]),
     "tpiv_plan_set_outlier": (C.c_int, [C.c_void_p, _int, _dbl, _dbl, _int]),
     "tpiv_plan_pass_outliers": (C.c_int, [C.c_void_p, _int, C.POINTER(C.c_void_p)]),
     "tpiv_apply_mask": (C.c_int, [_u8p, _int, C.c_longlong, _u8p, _u8p, _vp]),

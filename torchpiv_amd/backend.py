@@ -18,6 +18,7 @@ There is no CPU compute path: device="cpu" raises.
 """
 from __future__ import annotations
 
+import collections
 from time import time
 from typing import Generator
 
@@ -326,6 +327,10 @@ def free_cuda_memory():
 # ----------------------------------------------------------------------------------------
 # the generator API (B:824-903)
 # ----------------------------------------------------------------------------------------
+Tracks = collections.namedtuple("Tracks", "x y u v residual peak_a peak_b count_a count_b matched")
+Tracks.__doc__ = "The particle tracks of one pair (OfflinePIV.tracks has the fields' definitions)."
+
+
 class OfflinePIV:
     """for x, y, u, v in OfflinePIV(folder, device, file_fmt, wind_size, overlap, ...)(): ...
 
@@ -900,13 +905,13 @@ class OfflinePIV:
                                         uncertainty=self._uncertainty, deform=self._deform),
                        [w for w, _ in engine.pass_sizes(self._wind_size, self._overlap, self._iter, self._iter_scale)])
 
-    def _frame_batches(self, idx, batch_size, H, W):
+    def _frame_batches(self, idx, batch_size, H, W, ids=None):
         """The prepared frames of the pairs idx, batch_size at a time, as (A, B) uint8 [n, H, W] on the device: read through
         the native read-ahead ring, unpacked on the device and taken through the preparation steps exactly as batched()
         takes them (tone map, rectification, background, pre-filter, equalize, mask pixels).  Pairs that cannot be decoded
         or have another frame shape are left out, as compute_background() leaves them out.  The stacks live in buffers
         of this object that the next batch overwrites: the consumer enqueues its work on the current stream before it
-        asks for the next one."""
+        asks for the next one.  ids: a list that holds, while a batch is out, the pair ids of its n pairs."""
         dev = self._device
         lut = self._depth_table()
         deep = lut is not None
@@ -946,6 +951,8 @@ class OfflinePIV:
                     else:
                         frames = self._filtered(frames, None, out=dst)
                     frames = self._finished(frames, True)
+                    if ids is not None:
+                        ids[:] = st.chunk
                     yield frames[:n], frames[n:]
                     cur.synchronize()           # upload and consumer are through: staging and frame buffers may be refilled
                 batches.release()
@@ -984,6 +991,86 @@ class OfflinePIV:
         else:
             uv = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)[0]
         return self._finish(uv, x, y, plan=plan)
+
+    def tracks(self, level, radius=engine.TRACKS_RADIUS, indices=None, batch_size: int = 32) -> Generator:
+        """Hybrid PIV / PTV ("super-resolution" PIV: Keane, Adrian & Zhang 1995; Cowen & Monismith 1997) over the pairs
+        `indices` (None: all): the converged field of a pair predicts where each particle image of frame a lies in frame b,
+        and each is paired with the nearest particle image there -- one unbinned vector per particle, at the particle's
+        own position.  level: the intensity a particle image's peak pixel must reach, an integer in 1..255, required;
+        radius: the search radius around the predicted position in pixels, in (0, 8] (engine.tracks_arg).
+
+        Yields (i, x, y, u, v, t) for every pair the post-validation keeps, batch_size pairs per launch: x, y, u, v are what
+        batched() delivers for that pair (numpy arrays; uncertainty= and derive= do not apply to tracks() and add nothing
+        to its tuples), t is a Tracks record of numpy arrays over the matched particles only, in raster order of frame a:
+          x, y         the position in frame a: image coordinates (x along the columns, y along the rows DOWNWARD, pixel
+                       (0, 0) centred at the origin) times scale, millimetres
+          u, v         (x_b - x_a) * scale / dt * 1000 and -(y_b - y_a) * scale / dt * 1000: the units and signs of the
+                       delivered fields, v positive upward in the image
+          residual     the distance between the predicted and the found position in frame b, pixels
+          peak_a, peak_b    the peak pixels' intensities
+          count_a, count_b, matched    particle images found in either frame, and pairs made (= len(t.x))
+        How this relates to the delivered grid: its rows are flipped -- cell [r, c] of the delivered u, v was measured by the
+        window whose centre lies at column x[r, c] and image row y[n_rows - 1 - r, c] of the coordinates get_coordinates
+        returns (engine.stereo_cells applies the same flip) -- while t.y is the image row itself times scale and is never
+        flipped; t.v has the delivered sign, positive toward smaller t.y.
+        The frames are prepared as batched() prepares them (pairs that cannot be decoded, or have another frame shape than
+        the first, are left out); the particle images are detected on the prepared frames (engine.particle_detect), mask=
+        hands its image to the detection (no particle under it), and the predictor is the pair's raw field after the
+        post-validation has filled it, interpolated bilinearly between the centres of the last pass's windows
+        (engine.particle_match).  deform=, correlation=, weighting= and outlier= act through the plan as in batched().
+        ValueError with dynamic_mask=; the arguments are checked at the call, the work starts at the first next()."""
+        par = self._tracks_check(level, radius)
+        idx = list(range(len(self._dataset))) if indices is None else list(indices)
+        first = self._first_decodable(idx) if idx else None
+        return self._tracks(par, idx, first[1], int(batch_size)) if first is not None else iter(())
+
+    def _tracks_check(self, level, radius):
+        """The checked arguments of tracks(); ValueError with dynamic_mask=."""
+        par = engine.tracks_arg(level, radius)
+        if self._dynmask is not None:
+            raise ValueError("tracks: dynamic_mask= is not supported (the detection takes one mask image for every pair); "
+                             "use mask=, or run without it")
+        return par
+
+    def _tracks(self, par, idx, shape, batch_size):
+        """tracks() over the pairs idx of frame shape `shape`, with the checked arguments par."""
+        H, W = shape
+        plan = self._get_plan(H, W, max_batch=batch_size)
+        w, o, _, _ = plan.geometry[-1]
+        x, y = get_coordinates((H, W), w, o)
+        nr, nc = x.shape
+        # the centres of the windows in image coordinates: window k covers the pixels k (w - o) .. k (w - o) + w - 1
+        xc, yc = np.arange(nc) * float(w - o) + (w - 1) / 2, np.arange(nr) * float(w - o) + (w - 1) / 2
+        dev = self._device
+        image = self._static_image((H, W), dev)
+        ids = []
+        for A, B in self._frame_batches(idx, batch_size, H, W, ids=ids):
+            chunk = list(ids)
+            u, v, inv = plan.run(A, B)
+            pa = engine.particle_detect(A, par["level"], mask=image)      # on the frame buffers, before the next batch
+            pb = engine.particle_detect(B, par["level"], mask=image)
+            raw = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)
+            kept = [k for k, uv in enumerate(raw) if uv is not None]
+            if not kept:
+                continue
+            pred = np.zeros((2, len(chunk), nr, nc))
+            for k in kept:
+                pred[0, k], pred[1, k] = raw[k]
+            pred = torch.from_numpy(pred).to(dev)
+            m = engine.particle_match(pa, pb, pred[0], pred[1], xc, yc, par["radius"], (H, W))
+            host = [t.cpu().numpy() for t in (pa.x, pa.y, pa.peak, pa.count, pb.x, pb.y, pb.peak, pb.count) + tuple(m)]
+            for k in kept:
+                t = self._tracks_of(*(a[k] for a in host))
+                yield (chunk[k],) + self._finish(raw[k], x, y, plan=plan, derive=False) + (t,)
+
+    def _tracks_of(self, xa, ya, peak_a, count_a, xb, yb, peak_b, count_b, match, status, d2, matched):
+        """The Tracks of one pair from its two lists and engine.particle_match's verdicts (numpy): the matched particles in
+        frame a's order, positions and displacements in the delivered units and signs."""
+        ia = np.flatnonzero(status == engine.PARTICLE_STATUS["matched"])
+        ib = match[ia]
+        return Tracks(xa[ia] * self._scale, ya[ia] * self._scale,
+                      (xb[ib] - xa[ia]) * self._scale / self._dt * 1000, -(yb[ib] - ya[ia]) * self._scale / self._dt * 1000,
+                      np.sqrt(d2[ia]), peak_a[ia], peak_b[ib], int(count_a), int(count_b), int(matched))
 
     def reset_stats(self):
         """Counters of the post-validation: pairs seen, dropped for 'no invalid vector' / 'too many
@@ -1711,9 +1798,10 @@ class ResidentPIV(OfflinePIV):
             yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan)))
         yield from emit(pipe.flush())
 
-    def _frame_batches(self, idx, batch_size, H, W):
+    def _frame_batches(self, idx, batch_size, H, W, ids=None):
         """The prepared frames of the pairs idx, batch_size at a time, as (A, B) uint8 [n, H, W]: the steps of batched(),
-        into the same reused buffers (the consumer enqueues its work before it asks for the next batch)."""
+        into the same reused buffers (the consumer enqueues its work before it asks for the next batch).  ids: a list that
+        holds, while a batch is out, the pair ids of its n pairs."""
         lut = self._depth_table()
         dbuf = None if lut is None else self._scratch("_depth_frames", (2, batch_size), H, W, self._A.device)
         bg = self._background((H, W))
@@ -1730,6 +1818,8 @@ class ResidentPIV(OfflinePIV):
             out_a, out_b = (None, None) if buf is None else (buf[0, :n], buf[1, :n])
             fa, fb = self._filtered(A, bg_a, out=out_a), self._filtered(B, bg_b, out=out_b)
             owned |= fa is not A
+            if ids is not None:
+                ids[:] = chunk
             yield self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b)
 
     def ensemble(self, indices=None, batch_size: int = 32):
@@ -1744,6 +1834,13 @@ class ResidentPIV(OfflinePIV):
         plan = self._ensemble_plan(H, W, batch_size)
         u, v, inv = plan.run_ensemble(lambda: self._frame_batches(idx, batch_size, H, W))
         return self._ensemble_finish(plan, (H, W), u, v, inv)
+
+    def tracks(self, level, radius=engine.TRACKS_RADIUS, indices=None, batch_size: int = 32) -> Generator:
+        """OfflinePIV.tracks over the resident pairs: (i, x, y, u, v, t) per kept pair of `indices` (None: all), t the
+        Tracks of its matched particle images."""
+        par = self._tracks_check(level, radius)
+        idx = list(range(len(self))) if indices is None else list(indices)
+        return self._tracks(par, idx, tuple(int(s_) for s_ in self._A.shape[1:]), int(batch_size)) if idx else iter(())
 
     def __call__(self) -> Generator:
         for out in self.batched(1):

@@ -1093,6 +1093,126 @@ int tpiv_stereo_triangulate(const double* dx, const double* dy, const double* X,
     return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_stereo_triangulate");
 }
 
+static int particle_frames(const char* who, const uint8_t* frames, int n, int H, int W, int level, int capacity) {
+    const std::string w(who);
+    if (n < 0 || H < 3 || W < 3) return fail(TPIV_EINVAL, w + ": frames of at least 3 x 3 pixels");
+    if (level < 0 || level > 255) return fail(TPIV_EINVAL, w + ": level must be in 0..255");
+    if (capacity < 0) return fail(TPIV_EINVAL, w + ": negative capacity");
+    if (!frames) return fail(TPIV_EINVAL, w + ": null pointer");
+    if ((long long)H * W >= (1LL << 31) || (long long)n * (H + 1) >= (1LL << 31) || (long long)n * capacity >= (1LL << 31))
+        return fail(TPIV_EINVAL, w + ": frames or lists too large");
+    if (n > 65535) return fail(TPIV_EUNSUPPORTED, w + ": more than 65535 frames in one call");
+    return TPIV_OK;
+}
+
+int tpiv_particle_count(const uint8_t* frames, int n, int H, int W, int level, const uint8_t* mask, int32_t* row_start,
+                        int32_t* count, void* stream) {
+    if (const int rc = particle_frames("tpiv_particle_count", frames, n, H, W, level, 0)) return rc;
+    if (!row_start || !count) return fail(TPIV_EINVAL, "tpiv_particle_count: null pointer");
+    if (n == 0) return TPIV_OK;
+    const size_t px = (size_t)H * W;
+    const Span in[2] = {{frames, n * px}, {mask, px}};
+    const Span out[2] = {{row_start, (size_t)n * (H + 1) * 4}, {count, (size_t)n * 4}};
+    if (const int k = aliased(in, 2, out, 2))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_particle_count: an output aliases an input" : "tpiv_particle_count: two outputs overlap");
+    tpiv::ParticleParams q{};
+    q.frames = frames;
+    q.n = n;
+    q.H = H;
+    q.W = W;
+    q.level = level;
+    q.mask = mask;
+    q.row_start = row_start;
+    q.count = count;
+    hipError_t he = tpiv::launch_particle_count(q, (hipStream_t)stream);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_particle_count");
+}
+
+int tpiv_particle_detect(const uint8_t* frames, int n, int H, int W, int level, const uint8_t* mask, const double* table,
+                         const int32_t* row_start, int capacity, double* x, double* y, uint8_t* peak, void* stream) {
+    if (const int rc = particle_frames("tpiv_particle_detect", frames, n, H, W, level, capacity)) return rc;
+    if (!row_start || !table || (capacity > 0 && (!x || !y || !peak)))
+        return fail(TPIV_EINVAL, "tpiv_particle_detect: null pointer");
+    if (n == 0 || capacity == 0) return TPIV_OK;
+    const size_t px = (size_t)H * W, cells = (size_t)n * capacity;
+    const Span in[4] = {{frames, n * px}, {mask, px}, {table, 256 * 8}, {row_start, (size_t)n * (H + 1) * 4}};
+    const Span out[3] = {{x, cells * 8}, {y, cells * 8}, {peak, cells}};
+    if (const int k = aliased(in, 4, out, 3))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_particle_detect: an output aliases an input" : "tpiv_particle_detect: two outputs overlap");
+    tpiv::ParticleParams q{};
+    q.frames = frames;
+    q.n = n;
+    q.H = H;
+    q.W = W;
+    q.level = level;
+    q.mask = mask;
+    q.table = table;
+    q.row_start = const_cast<int32_t*>(row_start);      // (read only by the writing launch)
+    q.capacity = capacity;
+    q.x = x;
+    q.y = y;
+    q.peak = peak;
+    hipError_t he = tpiv::launch_particle_detect(q, (hipStream_t)stream);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_particle_detect");
+}
+
+int tpiv_particle_match(const double* xa, const double* ya, const int32_t* rsa, int cap_a, const double* xb, const double* yb,
+                        const int32_t* rsb, int cap_b, int n, int H, int W, const double* up, const double* vp, int n_rows,
+                        int n_cols, const double* xc, const double* yc, double radius, int32_t* match, uint8_t* status,
+                        double* d2, int32_t* matched, void* work, size_t work_bytes, void* stream) {
+    if (n < 0 || H < 1 || W < 1 || n_rows < 1 || n_cols < 1) return fail(TPIV_EINVAL, "tpiv_particle_match: empty frame or grid");
+    if (cap_a < 0 || cap_b < 0) return fail(TPIV_EINVAL, "tpiv_particle_match: negative capacity");
+    if (!(radius > 0) || !std::isfinite(radius)) return fail(TPIV_EINVAL, "tpiv_particle_match: radius must be a positive finite number");
+    if (!rsa || !rsb || !up || !vp || !xc || !yc || !matched || (cap_a > 0 && (!xa || !ya || !match || !status || !d2))
+        || (cap_b > 0 && (!xb || !yb)))
+        return fail(TPIV_EINVAL, "tpiv_particle_match: null pointer");
+    const long long lim = 1LL << 31;
+    if ((long long)n * (H + 1) >= lim || (long long)n * cap_a >= lim || (long long)n * cap_b >= lim
+        || (long long)n * n_rows * n_cols >= lim)
+        return fail(TPIV_EINVAL, "tpiv_particle_match: lists or field stack too large");
+    if (n > 65535) return fail(TPIV_EUNSUPPORTED, "tpiv_particle_match: more than 65535 pairs in one call");
+    if (n == 0) return TPIV_OK;
+    const size_t na = (size_t)n * cap_a, nb = (size_t)n * cap_b, need = 16 * nb;
+    if (need > 0 && (!work || work_bytes < need || ((uintptr_t)work & 7) != 0))
+        return fail(TPIV_EINVAL, "tpiv_particle_match: work memory of 16 * n * cap_b bytes, 8-byte aligned");
+    const size_t rs = (size_t)n * (H + 1) * 4, cells = (size_t)n * n_rows * n_cols * 8;
+    const Span in[10] = {{xa, na * 8}, {ya, na * 8}, {rsa, rs}, {xb, nb * 8}, {yb, nb * 8}, {rsb, rs}, {up, cells}, {vp, cells},
+                         {xc, (size_t)n_cols * 8}, {yc, (size_t)n_rows * 8}};
+    const Span out[5] = {{match, na * 4}, {status, na}, {d2, na * 8}, {matched, (size_t)n * 4}, {work, need}};
+    if (const int k = aliased(in, 10, out, 5))
+        return fail(TPIV_EINVAL, k == 1 ? "tpiv_particle_match: an output aliases an input" : "tpiv_particle_match: two outputs overlap");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(matched, 0, (size_t)n * 4, st));
+    if (need > 0) HIP_TRY(hipMemsetAsync(work, 0xff, need, st));
+    tpiv::ParticleMatchParams q{};
+    q.xa = xa;
+    q.ya = ya;
+    q.rsa = rsa;
+    q.cap_a = cap_a;
+    q.xb = xb;
+    q.yb = yb;
+    q.rsb = rsb;
+    q.cap_b = cap_b;
+    q.n = n;
+    q.H = H;
+    q.W = W;
+    q.up = up;
+    q.vp = vp;
+    q.n_rows = n_rows;
+    q.n_cols = n_cols;
+    q.xc = xc;
+    q.yc = yc;
+    q.radius = radius;
+    q.match = match;
+    q.status = status;
+    q.d2 = d2;
+    q.matched = matched;
+    q.claim_d2 = (unsigned long long*)work;
+    q.claim_i = (unsigned*)((char*)work + 8 * nb);
+    hipError_t he = tpiv::launch_particle_match(q, st);
+    return he == hipSuccess ? TPIV_OK : hip_fail(he, "launch_particle_match");
+}
+
 int tpiv_plan_set_outlier(tpiv_plan* plan, int kind, double threshold, double eps, int min_neighbours) {
     if (!plan) return fail(TPIV_EINVAL, "null plan");
     if (kind != 0 && kind != 1) return fail(TPIV_EINVAL, "tpiv_plan_set_outlier: kind must be 0 (off) or 1 (normalized median)");

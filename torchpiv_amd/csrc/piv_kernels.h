@@ -233,6 +233,47 @@ struct FieldFitParams {
 };
 hipError_t launch_field_fit(const FieldFitParams& p, hipStream_t stream);
 
+// particle images and their pairing (particles.hip, defined in include/torchpiv_hip.h: tpiv_particle_count / _detect /
+// _match).  Detection: a wavefront per image row, PARTICLE_BLOCK_ROWS adjacent rows per workgroup, a lane per
+// PARTICLE_LANE_PIXELS adjacent pixels of a 256-pixel step along the row; launch_particle_count leaves the per-row counts
+// scanned in row_start, launch_particle_detect walks the rows again and writes the list in raster order.  Matching: a
+// lane per particle of frame a, three launches (nearest candidate, claim by distance, claim by index and verdict).
+constexpr int PARTICLE_BLOCK_ROWS = 4, PARTICLE_LANE_PIXELS = 4;
+struct ParticleParams {
+    const uint8_t* frames;   // [n, H, W]
+    int n, H, W;
+    int level;               // 0..255
+    const uint8_t* mask;     // optional [H, W]: non-zero = no particle image here
+    const double* table;     // [256] ln(max(i, 1)) (detect only)
+    int32_t* row_start;      // [n, H + 1]: out of count, in of detect
+    int32_t* count;          // out of count [n]
+    int capacity;            // detect: entries per frame of x, y, peak
+    double *x, *y;           // out of detect [n, capacity]
+    uint8_t* peak;           // out of detect [n, capacity]
+};
+hipError_t launch_particle_count(const ParticleParams& p, hipStream_t stream);
+hipError_t launch_particle_detect(const ParticleParams& p, hipStream_t stream);
+struct ParticleMatchParams {
+    const double *xa, *ya;   // [n, cap_a]
+    const int32_t* rsa;      // [n, H + 1]
+    int cap_a;
+    const double *xb, *yb;   // [n, cap_b]
+    const int32_t* rsb;      // [n, H + 1]
+    int cap_b;
+    int n, H, W;
+    const double *up, *vp;   // [n, n_rows, n_cols]
+    int n_rows, n_cols;
+    const double *xc, *yc;   // [n_cols], [n_rows], ascending
+    double radius;
+    int32_t* match;          // out [n, cap_a]
+    uint8_t* status;         // out [n, cap_a]
+    double* d2;              // out [n, cap_a]
+    int32_t* matched;        // out [n], zero on entry
+    unsigned long long* claim_d2;    // work [n, cap_b], all bits set on entry
+    unsigned* claim_i;               // work [n, cap_b], all bits set on entry
+};
+hipError_t launch_particle_match(const ParticleMatchParams& p, hipStream_t stream);
+
 // stereoscopic reconstruction (stereo.hip, defined in include/torchpiv_hip.h: tpiv_stereo_reconstruct): a workgroup of
 // STEREO_BLOCK_THREADS lanes keeps the geometry of its cells in registers and walks STEREO_BLOCK_PAIRS pairs of the
 // stack; a lane owns one cell (8-byte accesses) or, where every plane allows it, two adjacent ones (16-byte accesses).

@@ -6,6 +6,7 @@ otherwise -- there is no CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import functools
 
@@ -479,6 +480,150 @@ def derive(fit, hx, hy, quantities=DERIVE_QUANTITIES):
         made[name] = out
         return out
     return {name: get(name) for name in names}
+
+
+TRACKS_RADIUS = 1.5              # pixels: generous for the predictor error of a multipass field, about half the 2.9 px mean
+TRACKS_RADIUS_MAX = 8.0          # nearest-neighbour spacing at 0.03 particles per pixel
+PARTICLE_STATUS = {"matched": 0, "no_candidate": 1, "lost_claim": 2, "outside": 3, "no_particle": 255}
+
+Particles = collections.namedtuple("Particles", "x y peak row_start count")
+Matches = collections.namedtuple("Matches", "match status d2 matched")
+
+
+def tracks_arg(level=None, radius=TRACKS_RADIUS):
+    """The arguments of tracks(), checked (no GPU involved): level, the intensity threshold of a particle image, an integer
+    in 1..255 and required -- there is no honest default for an intensity threshold; radius, the search radius around the
+    predicted position in pixels, a number in (0, 8].  Returns {"level": int, "radius": float}."""
+    if level is None:
+        raise ValueError("tracks: level is required (the intensity threshold of a particle image, an integer in 1..255)")
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 1 <= level <= 255:
+        raise ValueError(f"tracks: level must be an integer in 1..255, got {level!r}")
+    if not is_real(radius) or not 0 < radius <= TRACKS_RADIUS_MAX:      # (a NaN fails the comparison)
+        raise ValueError(f"tracks: radius must be a number in (0, {TRACKS_RADIUS_MAX:g}] (pixels), got {radius!r}")
+    return {"level": int(level), "radius": float(radius)}
+
+
+def particle_table():
+    """The table of the sub-pixel fit of particle_detect: float64 [256], ln(max(i, 1)), made on the host (the device and
+    a host model read the same numbers, so the fit is the same bits whatever logarithm made them)."""
+    return np.log(np.maximum(np.arange(256), 1).astype(np.float64))
+
+
+@functools.lru_cache(maxsize=None)
+def _particle_table_on(device):
+    return torch.from_numpy(particle_table()).to(device)
+
+
+def particle_detect(frames, level, mask=None, capacity=None):
+    """Particle images (tpiv_particle_count / tpiv_particle_detect) of uint8 frames [n, H, W] (or [H, W]) on the GPU, H, W >=
+    3: the interior pixels that reach `level` (integer 0..255), are not under mask (uint8 [H, W], optional, non-zero =
+    masked), exceed their four 8-neighbours before them in raster order and are not below the four behind them, each with
+    a three-point log-Gaussian sub-pixel fit per axis.  Returns Particles(x, y, peak, row_start, count): x, y float64
+    [n, capacity] in image coordinates (x along the columns, y along the rows downward, pixel (0, 0) centred at the origin),
+    peak uint8 [n, capacity], row_start int32 [n, H + 1] (list index of the first particle of each row; entry H = the
+    total), count int32 [n] -- every list in raster order of the peak pixel, in every run.  capacity=None counts first, reads
+    the totals once on the host and stores exactly the longest list; a given capacity needs no host read and stores the
+    first `capacity` particles of each frame, with count and row_start still those of the whole list.  Entries behind a
+    frame's last particle are unspecified.  A 2-D input gives outputs without the frame axis.  The inputs are not
+    written."""
+    _need_cuda(frames, mask)
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or (mask is not None and mask.dtype != torch.uint8):
+        raise TypeError("particle_detect: frames uint8 and mask uint8")
+    if frames.dim() not in (2, 3):
+        raise ValueError("particle_detect: frames must be [n, H, W] or [H, W]")
+    flat = frames.dim() == 2
+    f = (frames[None] if flat else frames).contiguous()
+    n, H, W = f.shape
+    if H < 3 or W < 3:
+        raise ValueError(f"particle_detect: frames of at least 3 x 3 pixels, got {H} x {W}")
+    if mask is not None and tuple(mask.shape) != (H, W):
+        raise ValueError(f"particle_detect: mask must be [{H}, {W}], got {tuple(mask.shape)}")
+    if mask is not None and mask.device != f.device:
+        raise ValueError("particle_detect: frames and mask on one device")
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level <= 255:
+        raise ValueError(f"particle_detect: level must be an integer in 0..255, got {level!r}")
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0):
+        raise ValueError(f"particle_detect: capacity must be None or an integer >= 0, got {capacity!r}")
+    mask = None if mask is None else mask.contiguous()
+    mp = None if mask is None else mask.data_ptr()
+    row_start = torch.empty(n, H + 1, dtype=torch.int32, device=f.device)
+    count = torch.empty(n, dtype=torch.int32, device=f.device)
+    with torch.cuda.device(f.device):
+        check(lib.tpiv_particle_count(f.data_ptr(), n, H, W, int(level), mp, row_start.data_ptr(), count.data_ptr(), _stream()))
+        cap = int(count.max()) if capacity is None and n else int(capacity or 0)      # (the one host read)
+        x = torch.empty(n, cap, dtype=torch.float64, device=f.device)
+        y = torch.empty_like(x)
+        peak = torch.empty(n, cap, dtype=torch.uint8, device=f.device)
+        if n and cap:
+            check(lib.tpiv_particle_detect(f.data_ptr(), n, H, W, int(level), mp, _particle_table_on(f.device).data_ptr(),
+                                           row_start.data_ptr(), cap, x.data_ptr(), y.data_ptr(), peak.data_ptr(), _stream()))
+    return Particles(x[0], y[0], peak[0], row_start[0], count[0]) if flat else Particles(x, y, peak, row_start, count)
+
+
+def particle_match(pa, pb, up, vp, xc, yc, radius, shape):
+    """Pairs the particle images pa of frame a with pb of frame b (Particles of particle_detect, of n frames each or of
+    one) through a predictor (tpiv_particle_match).  up, vp float64 [n, n_rows, n_cols] (or [n_rows, n_cols]) on the GPU: the
+    predicted displacement in pixels in image orientation -- u along the columns, v along the rows downward, row 0 the top
+    row of windows: a plan's raw field, before the delivered flip and sign -- at the window centres xc [n_cols], yc [n_rows]
+    (host sequences, image coordinates, strictly ascending); between the centres it is interpolated bilinearly, outside
+    them held constant.  radius: pixels, > 0.  shape: (H, W) of the frames.  A particle of a is matched to the particle of b
+    nearest to its predicted position within the radius (the bound inclusive; ties to the lower index), one-to-one: a
+    particle of b goes to its nearest claimant (ties to the lower index).  Returns Matches(match, status, d2, matched):
+    match int32 [n, capacity of pa] (index into pb's list, -1 unmatched), status uint8 (PARTICLE_STATUS: 0 matched, 1 no
+    candidate, 2 lost the candidate to a nearer claimant, 3 predicted outside the frame, 255 behind the list's end), d2
+    float64 (squared distance to the nearest candidate at status 0 and 2, NaN otherwise), matched int32 [n].  The result
+    does not depend on scheduling.  The inputs are not written."""
+    if not isinstance(pa, Particles) or not isinstance(pb, Particles):
+        raise TypeError("particle_match: pa, pb are the Particles of particle_detect")
+    _need_cuda(pa.x, pb.x, up, vp)
+    if not isinstance(up, torch.Tensor) or not isinstance(vp, torch.Tensor) or up.dtype != torch.float64 or vp.dtype != torch.float64:
+        raise TypeError("particle_match: up, vp float64")
+    flat = pa.x.dim() == 1
+    if (pb.x.dim() == 1) != flat or up.dim() != (2 if flat else 3) or up.shape != vp.shape:
+        raise ValueError("particle_match: lists of n frames with up, vp [n, n_rows, n_cols], or of one frame with [n_rows, n_cols]")
+    if flat:
+        pa, pb = Particles(*(t[None] for t in pa)), Particles(*(t[None] for t in pb))
+        up, vp = up[None], vp[None]
+    H, W = (int(s) for s in shape)
+    n, cap_a = pa.x.shape
+    cap_b = pb.x.shape[1]
+    for p in (pa, pb):
+        if p.x.dtype != torch.float64 or p.y.dtype != torch.float64 or p.row_start.dtype != torch.int32:
+            raise TypeError("particle_match: x, y float64 and row_start int32")
+        if p.x.shape != p.y.shape or p.x.shape[0] != n or tuple(p.row_start.shape) != (n, H + 1):
+            raise ValueError(f"particle_match: lists of {n} frames of shape ({H}, {W}): x, y [n, capacity], row_start [n, {H + 1}]")
+    if up.shape[0] != n:
+        raise ValueError(f"particle_match: up, vp must hold {n} fields, got {up.shape[0]}")
+    xc = np.ascontiguousarray(xc, dtype=np.float64).reshape(-1)
+    yc = np.ascontiguousarray(yc, dtype=np.float64).reshape(-1)
+    if (yc.size, xc.size) != tuple(up.shape[1:]):
+        raise ValueError(f"particle_match: {yc.size} x {xc.size} window centres for fields {tuple(up.shape[1:])}")
+    if not (np.all(np.diff(xc) > 0) and np.all(np.diff(yc) > 0) and np.isfinite(xc).all() and np.isfinite(yc).all()):
+        raise ValueError("particle_match: xc, yc must be finite and strictly ascending")
+    if not is_real(radius) or not radius > 0 or radius == float("inf"):
+        raise ValueError(f"particle_match: radius must be a positive number (pixels), got {radius!r}")
+    dev = pa.x.device
+    if any(t.device != dev for t in (pa.y, pa.row_start, pb.x, pb.y, pb.row_start, up, vp)):
+        raise ValueError("particle_match: every tensor on one device")
+    xa, ya, rsa = pa.x.contiguous(), pa.y.contiguous(), pa.row_start.contiguous()
+    xb, yb, rsb = pb.x.contiguous(), pb.y.contiguous(), pb.row_start.contiguous()
+    up, vp = up.contiguous(), vp.contiguous()
+    centres = torch.from_numpy(np.concatenate([xc, yc])).to(dev)
+    match = torch.empty(n, cap_a, dtype=torch.int32, device=dev)
+    status = torch.empty(n, cap_a, dtype=torch.uint8, device=dev)
+    d2 = torch.empty(n, cap_a, dtype=torch.float64, device=dev)
+    matched = torch.empty(n, dtype=torch.int32, device=dev)
+    work = torch.empty(2 * n * cap_b, dtype=torch.int64, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t.numel() else None
+    with torch.cuda.device(dev):
+        if n:
+            check(lib.tpiv_particle_match(ptr(xa), ptr(ya), rsa.data_ptr(), cap_a, ptr(xb), ptr(yb), rsb.data_ptr(), cap_b, n,
+                                          H, W, up.data_ptr(), vp.data_ptr(), yc.size, xc.size, centres.data_ptr(),
+                                          centres[xc.size:].data_ptr(), float(radius), ptr(match), ptr(status), ptr(d2),
+                                          ptr(matched), ptr(work), work.numel() * 8, _stream()))
+    return Matches(match[0], status[0], d2[0], matched[0]) if flat else Matches(match, status, d2, matched)
 
 
 def uncertainty(a, b, u, v, ws, ov, invalid=None, radius=3, want_stats=False):
