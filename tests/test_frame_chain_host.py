@@ -1,7 +1,8 @@
 """The ownership rule of the frame chain, without a GPU: OfflinePIV._filtered (background and pre-filter) and _finished
 (equalize, then mask pixels) on CPU tensors, with the four engine calls replaced by stand-ins that apply the numpy models
-and honour out; and _scratch, the one reuse-if-big-enough rule of the reused frame buffers.  A step may write in place only
-into memory the object made -- never into a caller's tensor."""
+and honour out; _scratch, the one reuse-if-big-enough rule of the reused frame buffers; and the prepared frame source over
+resident stacks (_frame_batches): its chunks, views and copies.  A step may write in place only into memory the object
+made -- never into a caller's tensor."""
 import itertools
 
 import numpy as np
@@ -158,3 +159,73 @@ def test_scratch_reuses_what_is_big_enough():
     meta = piv._scratch("_pf_frames", (4,), H, W, torch.device("meta"))     # another device
     assert piv._scratch("_pf_frames", (4,), H, W, torch.device("meta")) is meta
     assert piv._scratch("_pf_frames", (4,), H, W, CPU) is not meta and piv._pf_frames.device == CPU
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# the prepared frame source over resident stacks (ResidentPIV._raw_batches under OfflinePIV._frame_batches)
+# --------------------------------------------------------------------------------------------------------------------
+RAGGED, GATHERED = ([0, 1, 2], [[0, 1], [2]]), ([2, 0, 1], [[2, 0], [1]])          # (idx, its chunks at batch size 2)
+
+
+def _resident(seed, background=None, **steps):
+    """A ResidentPIV over N random CPU pairs (and the pairs as numpy); background: a pair of images, as given by a caller."""
+    rng = np.random.default_rng(seed)
+    A_h, B_h = (rng.integers(0, 256, (N, H, W), dtype=np.uint8) for _ in range(2))
+    piv = _object(**steps)
+    piv._A, piv._B = torch.from_numpy(A_h.copy()), torch.from_numpy(B_h.copy())
+    if background is not None:
+        piv._bg_arg = tuple(torch.from_numpy(b_) for b_ in background)
+    return piv, A_h, B_h
+
+
+@pytest.mark.parametrize("idx,chunks", [RAGGED, GATHERED], ids=["ragged", "gathered"])
+def test_resident_frame_batches_plain(stand_ins, idx, chunks):
+    """No step on: the chunks idx[s:s + 2] with their ids, every pair staged, no masks, no step launched; a run of
+    consecutive pairs is a view of the caller's stacks, anything else a gathered copy."""
+    piv, A_h, B_h = _resident(2)
+    got = list(piv._frame_batches(idx, 2, H, W, idx[0]))
+    assert [raw.chunk for raw, _, _, _ in got] == chunks and stand_ins == []
+    assert [raw.last for raw, _, _, _ in got] == [False, True]
+    for raw, fa, fb, masks in got:
+        c = raw.chunk
+        assert raw.order == [(i, True) for i in c] and masks is None and raw.stack is None
+        assert fa is raw.A and fb is raw.B and (raw.bg_a, raw.bg_b) == (None, None)
+        assert np.array_equal(fa.numpy(), A_h[c]) and np.array_equal(fb.numpy(), B_h[c])
+        consecutive = c == list(range(c[0], c[0] + len(c)))
+        assert raw.owned == (not consecutive)
+        assert _aliases(fa, piv._A) == consecutive and _aliases(fb, piv._B) == consecutive
+        if consecutive:
+            assert fa.data_ptr() == piv._A[c[0]].data_ptr() and fb.data_ptr() == piv._B[c[0]].data_ptr()
+    assert piv._bg_frames is None and piv._depth_frames is None and piv._dw_frames is None
+
+
+@pytest.mark.parametrize("idx,chunks", [RAGGED, GATHERED], ids=["ragged", "gathered"])
+@pytest.mark.parametrize("with_bg,with_pf,with_eq,with_mask",
+                         [c for c in itertools.product((False, True), repeat=4) if any(c)])
+def test_resident_frame_batches_steps(stand_ins, with_bg, with_pf, with_eq, with_mask, idx, chunks):
+    """Any step on: every batch equals the model chain of its pairs (frame a minus bg_a, frame b minus bg_b), in memory
+    that is not the caller's, and the caller's stacks are never written."""
+    rng = np.random.default_rng(5)
+    bgs = tuple(rng.integers(0, 90, (H, W), dtype=np.uint8) for _ in range(2)) if with_bg else None
+    m = _mask()
+    piv, A_h, B_h = _resident(3, background=bgs, prefilter=PF if with_pf else None, equalize=EQ if with_eq else None,
+                              mask=m if with_mask else None)
+    want = []
+    for f, bg in ((A_h, bgs[0] if with_bg else None), (B_h, bgs[1] if with_bg else None)):
+        f = PM.prefilter(f, PF["kind"], PF["size"], PF["cap"], background=bg) if with_pf else \
+            (np.maximum(f, bg) - bg) if with_bg else f
+        f = EM.equalize(f, EQ["tile"], EM.clip_q8_of(EQ["clip"])) if with_eq else f
+        want.append(MM.apply(f, m) if with_mask else f)
+    seen = []
+    for raw, fa, fb, masks in piv._frame_batches(idx, 2, H, W, idx[0]):       # (the buffers are reused: compare batch by batch)
+        c = raw.chunk
+        seen.append(c)
+        assert masks is None and tuple(fa.shape) == tuple(fb.shape) == (len(c), H, W)
+        assert np.array_equal(fa.numpy(), want[0][c]) and np.array_equal(fb.numpy(), want[1][c]), c
+        assert not _aliases(fa, piv._A) and not _aliases(fb, piv._B)
+        assert np.array_equal(piv._A.numpy(), A_h) and np.array_equal(piv._B.numpy(), B_h)
+    assert seen == chunks
+    per_stack = [k for k, on in (("prefilter", with_pf), ("subtract_background", with_bg and not with_pf),
+                                 ("equalize", with_eq), ("apply_mask", with_mask)) if on]
+    assert sorted(stand_ins) == sorted(per_stack * 2 * len(chunks))              # one launch per step, stack and batch
+    assert tuple(piv._bg_frames.shape) == (2, 2, H, W)

@@ -255,14 +255,10 @@ def test_offline_background_equals_presubtracted_frames(tmp_path, frames, precis
     pg.close()
 
 
-def test_file_staging_with_unstageable_pairs_and_a_stale_reader(tmp_path):
-    """The file staging that batched() and compute_background() share, over 6 pairs of 96 x 128 BMPs of which pair 2 has
-    a truncated a file (undecodable) and pair 4 another frame shape: the minimum leaves both out at any batch size; the
-    fields of the good pairs are those of ResidentPIV on frames subtracted in torch; pair 4 reaches the one-pair path
-    when its turn comes, where the dataset's background does not fit its shape (ValueError, after the pairs before it);
-    a generator abandoned without close() leaves a live reader behind, which the next run -- of either kind -- stops."""
+def _folder_with_unstageable_pairs(tmp_path):
+    """6 pairs of 96 x 128 BMPs of which pair 2 has a truncated a file (undecodable) and pair 4 another frame shape;
+    (A, B, H, W, the good pairs)."""
     from PIL import Image
-    import torchpiv_amd as T
     from torchpiv_amd import synth
     H, W, good = 96, 128, [0, 1, 3, 5]
     A, B = synth.make_batch(6, H, W, kind="wavy", noise=1.5)
@@ -278,6 +274,17 @@ def test_file_staging_with_unstageable_pairs_and_a_stale_reader(tmp_path):
     (tmp_path / "image2_a.bmp").write_bytes(blob[:len(blob) // 2])
     for s_, F in (("a", A), ("b", B)):
         Image.fromarray(F[4, :80].numpy(), "L").save(tmp_path / f"image4_{s_}.bmp")
+    return A, B, H, W, good
+
+
+def test_file_staging_with_unstageable_pairs_and_a_stale_reader(tmp_path):
+    """The file staging that batched() and compute_background() share, over 6 pairs of 96 x 128 BMPs of which pair 2 has
+    a truncated a file (undecodable) and pair 4 another frame shape: the minimum leaves both out at any batch size; the
+    fields of the good pairs are those of ResidentPIV on frames subtracted in torch; pair 4 reaches the one-pair path
+    when its turn comes, where the dataset's background does not fit its shape (ValueError, after the pairs before it);
+    a generator abandoned without close() leaves a live reader behind, which the next run -- of either kind -- stops."""
+    import torchpiv_amd as T
+    A, B, H, W, good = _folder_with_unstageable_pairs(tmp_path)
     kw = dict(multipass=2, multipass_mode="CWS")
     min_a, min_b = A[good].amin(0), B[good].amin(0)
     res = _fields(T.ResidentPIV(_sub(A[good], min_a).cuda(), _sub(B[good], min_b).cuda(), 32, 16, **kw).batched(4))
@@ -315,6 +322,36 @@ def test_file_staging_with_unstageable_pairs_and_a_stale_reader(tmp_path):
     assert rd2._h is None and piv._reader._h is None
     gen1.close()
     gen2.close()
+    piv.close()
+
+
+def test_ensemble_and_tracks_over_unstageable_pairs_and_a_stale_reader(tmp_path):
+    """The same folder under ensemble() and tracks(), which read through the staging of batched(): the pairs that cannot be
+    staged are left out -- ensemble() over the whole folder is ensemble() over the good pairs, tracks() yields no id of
+    the others --, and a tracks() generator abandoned after its first tuple leaves a live reader behind that the next
+    batched() stops, to deliver what a fresh object delivers."""
+    import torchpiv_amd as T
+    _, _, H, W, good = _folder_with_unstageable_pairs(tmp_path)
+    kw = dict(multipass=2, multipass_mode="CWS", background="min")
+    piv = T.OfflinePIV(str(tmp_path), "cuda:0", "bmp", 32, 16, **kw)
+    whole, picked = piv.ensemble(batch_size=2), piv.ensemble(indices=good, batch_size=4)
+    assert whole is not None and len(whole) == 4
+    assert all(np.array_equal(f, g, equal_nan=True) for f, g in zip(whole, picked))
+    ids = [t[0] for t in piv.tracks(60, batch_size=2)]
+    assert ids and set(ids) <= set(good) and ids == [t[0] for t in piv.tracks(60, indices=good, batch_size=4)]
+    every = [0, 1, 2, 3, 5]
+    gen = piv.tracks(60, batch_size=2)
+    assert next(gen)[0] == ids[0]
+    rd = piv._reader
+    assert rd._h is not None                      # abandoned, still referenced: its finally has not run
+    got = _fields(piv.batched(2, indices=every))
+    assert rd._h is None and piv._reader._h is None
+    fresh = T.OfflinePIV(str(tmp_path), "cuda:0", "bmp", 32, 16, **kw)
+    want = _fields(fresh.batched(2, indices=every))
+    assert len(want) >= 2
+    _same(got, want)
+    gen.close()
+    fresh.close()
     piv.close()
 
 

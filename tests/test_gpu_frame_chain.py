@@ -1,9 +1,11 @@
 """What enters the passes: the frames every path hands to engine.Plan.run -- ResidentPIV.batched over consecutive and over
-gathered pairs, OfflinePIV.batched over files and the one-pair loop -- against the numpy models of the frame chain in chain
+gathered pairs, OfflinePIV.batched over files and the one-pair loop, tracks() of both classes -- and to
+engine.Plan.ensemble_add (ensemble() of both classes), against the numpy models of the frame chain in chain
 order (tone map, background, pre-filter and cap, equalize, mask pixels), bit for bit, for every combination of steps that
 is a branch of its own in the backend.  The expectation comes from the models alone, never from a run of the library with
 the steps off.  Also pinned: the caller's resident frames are never written, the plain consecutive resident path hands out
-views of them, and the reused buffers exist exactly when a path needs them."""
+views of them, the reused buffers exist exactly when a path needs them, compute_background() of both classes is the
+models' minimum, and the file path launches each step once per batch over both stacks."""
 import numpy as np
 import pytest
 import torch
@@ -45,7 +47,9 @@ SETS = {
     "depth+background+prefilter+equalize+mask": {"depth": R16, "background": "min", "prefilter": PF, "equalize": EQ,
                                                  "mask": MASK},
 }
-PATHS = ["resident", "resident_gathered", "files", "one_pair"]
+PATHS = ["resident", "resident_gathered", "files", "one_pair",
+         "resident_ensemble", "files_ensemble", "resident_tracks", "files_tracks"]
+LEVEL = 60                                      # tracks(): any level does, the frames are captured in front of the detection
 
 
 @pytest.fixture(scope="module")
@@ -118,15 +122,14 @@ def test_the_models_chain_does_something(frames):
 
 @pytest.fixture
 def launches(monkeypatch):
-    """[(data_ptr of a, clone of a, clone of b)] of every engine.Plan.run from here on."""
+    """[(data_ptr of a, clone of a, clone of b)] of every engine.Plan.run and engine.Plan.ensemble_add from here on."""
     from torchpiv_amd import engine
     seen = []
-    run = engine.Plan.run
-
-    def capture(self, a, b, *args, **kw):
-        seen.append((a.data_ptr(), a.clone(), b.clone()))
-        return run(self, a, b, *args, **kw)
-    monkeypatch.setattr(engine.Plan, "run", capture)
+    for name in ("run", "ensemble_add"):
+        def capture(self, a, b, *args, _inner=getattr(engine.Plan, name), **kw):
+            seen.append((a.data_ptr(), a.clone(), b.clone()))
+            return _inner(self, a, b, *args, **kw)
+        monkeypatch.setattr(engine.Plan, name, capture)
     return seen
 
 
@@ -154,6 +157,8 @@ def test_frames_that_enter_the_passes(frames, folders, launches, name, path):
     want_a, want_b = _expected(name, frames)
     kw = dict(multipass=1, **opts)
     keep = None
+    consume = {"ensemble": lambda piv, **kw: piv.ensemble(**kw),
+               "tracks": lambda piv, **kw: list(piv.tracks(LEVEL, **kw))}.get(path.split("_")[-1])
     if path.startswith("resident"):
         src = frames[2:] if deep else frames[:2]
         Ad, Bd = (torch.from_numpy(f).cuda() for f in src)
@@ -163,6 +168,10 @@ def test_frames_that_enter_the_passes(frames, folders, launches, name, path):
         if path == "resident":
             list(piv.batched(3))
             chunks = [[0, 1, 2], [3]]                    # idx[s:s + bs]: a ragged last chunk
+        elif consume is not None:                        # both in one object: consecutive pairs, then gathered ones
+            consume(piv, batch_size=3)
+            consume(piv, indices=[3, 0, 2], batch_size=2)
+            chunks = [[0, 1, 2], [3], [3, 0], [2]]
         else:
             list(piv.batched(2, indices=[3, 0, 2]))
             chunks = [[3, 0], [2]]
@@ -170,6 +179,9 @@ def test_frames_that_enter_the_passes(frames, folders, launches, name, path):
         piv = T.OfflinePIV(folders[1] if deep else folders[0], "cuda:0", "png" if deep else "bmp", WS, OV, **kw)
         if path == "files":
             list(piv.batched(3))
+            chunks = [[0, 1, 2], [3]]
+        elif consume is not None:
+            consume(piv, batch_size=3)
             chunks = [[0, 1, 2], [3]]
         else:
             piv.call_batch = 1
@@ -187,5 +199,47 @@ def test_frames_that_enter_the_passes(frames, folders, launches, name, path):
         if name == "plain" and path == "resident":
             assert launches[0][0] == Ad.data_ptr()                                         # ... and are not copied
     got = {k: getattr(piv, k) is not None for k in ("_depth_frames", "_bg_frames", "_pf_frames", "_eq_work")}
-    assert got == _allocated(path, opts)
+    assert got == _allocated("files" if path.startswith("files") else path, opts)
+    piv.close()
+
+
+@pytest.mark.parametrize("indices", [None, [3, 0, 2]], ids=["all", "indices"])
+@pytest.mark.parametrize("deep", [False, True], ids=["uint8", "depth"])
+@pytest.mark.parametrize("path", ["resident", "files"])
+def test_compute_background_is_the_models_minimum(frames, folders, path, deep, indices):
+    """compute_background() folds the raw frame source: the minimum over the pairs asked for of the frames behind the
+    tone map (R16 maps the deep frames onto the uint8 ones), two pairs per batch."""
+    import torchpiv_amd as T
+    pairs = list(range(N)) if indices is None else indices
+    want_a, want_b = (f[pairs].min(axis=0) for f in _expected("depth" if deep else "plain", frames))
+    kw = dict(multipass=1, depth=R16) if deep else dict(multipass=1)
+    if path == "resident":
+        Ad, Bd = (torch.from_numpy(f).cuda() for f in (frames[2:] if deep else frames[:2]))
+        piv = T.ResidentPIV(Ad, Bd, WS, OV, **kw)
+    else:
+        piv = T.OfflinePIV(folders[1] if deep else folders[0], "cuda:0", "png" if deep else "bmp", WS, OV, **kw)
+    bg_a, bg_b = piv.compute_background(indices=indices, batch_size=2)
+    assert bg_a.dtype == torch.uint8 and tuple(bg_a.shape) == tuple(bg_b.shape) == (H, W)
+    assert np.array_equal(bg_a.cpu().numpy(), want_a) and np.array_equal(bg_b.cpu().numpy(), want_b)
+    piv.close()
+
+
+@pytest.mark.parametrize("name,per_batch", [("prefilter+equalize+mask", (1, 1, 1)),
+                                            ("depth+background+prefilter+equalize+mask", (2, 1, 1))])
+def test_file_path_launches_each_step_once_per_batch(frames, folders, monkeypatch, name, per_batch):
+    """Over files both stacks of a batch are one tensor: the pre-filter, equalize and the mask pixels run once over it --
+    only a background that the unpack could not fuse (here: behind the tone map) makes the filter, which subtracts it,
+    run per stack.  Two batches (3 + 1 pairs)."""
+    import torchpiv_amd as T
+    from torchpiv_amd import engine
+    calls = {"prefilter": 0, "equalize": 0, "apply_mask": 0}
+    for step in calls:
+        def counted(*args, _inner=getattr(engine, step), _step=step, **kw):
+            calls[_step] += 1
+            return _inner(*args, **kw)
+        monkeypatch.setattr(engine, step, counted)
+    deep = "depth" in SETS[name]
+    piv = T.OfflinePIV(folders[1] if deep else folders[0], "cuda:0", "png" if deep else "bmp", WS, OV, multipass=1, **SETS[name])
+    list(piv.batched(3))
+    assert calls == {step: 2 * k for step, k in zip(("prefilter", "equalize", "apply_mask"), per_batch)}
     piv.close()

@@ -19,6 +19,7 @@ There is no CPU compute path: device="cpu" raises.
 from __future__ import annotations
 
 import collections
+import contextlib
 from time import time
 from typing import Generator
 
@@ -330,6 +331,13 @@ def free_cuda_memory():
 Tracks = collections.namedtuple("Tracks", "x y u v residual peak_a peak_b count_a count_b matched")
 Tracks.__doc__ = "The particle tracks of one pair (OfflinePIV.tracks has the fields' definitions)."
 
+# What a raw frame source (_raw_batches, _load_pair) hands out: [(pair id, staged)] of a batch's pairs in order and the ids of
+# the n staged ones; their uint8 frames A, B [n, H, W] on the device behind tone map and rectification (None: none staged)
+# and whether they are memory of the object; the background still to be subtracted from each stack (None: none, or the
+# unpack fused it); whether the batch is the run's last (asking for more ends the run: a consumer with results in flight
+# collects them first); and, where A and B are the halves of ONE tensor [2n, H, W] of the object's, that tensor
+Raw = collections.namedtuple("Raw", "order chunk A B owned bg_a bg_b last stack", defaults=(True, None))
+
 
 class OfflinePIV:
     """for x, y, u, v in OfflinePIV(folder, device, file_fmt, wind_size, overlap, ...)(): ...
@@ -494,17 +502,18 @@ class OfflinePIV:
         self._depth_range = (depth["lo"], depth["hi"]) if depth is not None and "lo" in depth else None
         self._depth_lut = None           # the tone-map table in use: uint8 [65536] on the device, once resolved
         self._depth_frames = None        # the mapped frames of a launch, uint8 [2 * batch, H, W] (ResidentPIV: [2, batch, H, W]), reused
-        self._pf_frames = None           # batched(): the filtered frames of a launch, uint8 [2 * batch, H, W], reused
+        self._pf_frames = None           # over files (_prep_out): the filtered frames of a launch, uint8 [2 * batch, H, W], reused
         self._bg = None                  # the background in use: uint8 [2, H, W] on the device, once resolved
-        self._bg_frames = None           # ResidentPIV: the frames of a launch minus the background / filtered, uint8 [2, batch, H, W], reused
+        self._bg_frames = None           # ResidentPIV (_prep_out): the frames of a launch minus the background / filtered, uint8 [2, batch, H, W], reused
         self._plan = None
         self._ens_plan = None            # the plan of ensemble(), made on first use
         self._single_plans = {}          # plans of the one-pair path, per frame shape
-        self._reader = None              # the ReadAhead of the latest run over files (closed when that run ended)
-        self._stage, self._stage_key = None, None            # pinned staging buffers, kept from call to call
+        self._reader = None              # the ReadAhead of the latest run over files (_raw_batches; closed when that run ended)
+        self._stage, self._stage_key = None, None            # pinned staging buffers of _raw_batches, kept from call to call
         self._raw_dev, self._raw_dev_key = None, None        # their device copies
         self._pool, self._pool_size = None, 0                # fill-worker processes
         self._down_stream = None         # the stream of _post_submit's copies
+        self._up_stream = None           # the stream of _raw_batches' uploads
         self.reset_stats()
 
     def __len__(self) -> int:
@@ -577,6 +586,14 @@ class OfflinePIV:
             a, b = self._dataset[int(i)]
             if a is not None and b is not None and tuple(a.shape) == tuple(b.shape) == tuple(shape):
                 yield a.to(self._device), b.to(self._device)
+
+    def _side_stream(self, name, device):
+        """The stream kept in attribute `name` for `device`, made on first use."""
+        stream = getattr(self, name)
+        if stream is None or stream.device != device:
+            stream = torch.cuda.Stream(device)
+            setattr(self, name, stream)
+        return stream
 
     def _scratch(self, name, lead, H, W, device):
         """The reused uint8 buffer of attribute `name`, at least lead + (H, W) large: the one kept there if it has that
@@ -695,6 +712,30 @@ class OfflinePIV:
             fb = engine.apply_mask_pairs(fb, masks, out=fb if owned else out_b)
         return fa, fb, masks
 
+    def _prepared(self, raw, out=None):
+        """(fa, fb, masks): the frames of a Raw record through the preparation steps -- background, pre-filter and cap,
+        equalize, mask pixels (_filtered, _finished), with masks None; under dynamic_mask= the chain with the segmentation
+        in it and the pairs' masks (_pair_chain).  out: where a step that may not write in place writes, uint8
+        [2, n, H, W] (None: fresh tensors).  One launch per step and frame stack; where both stacks are one tensor of this
+        object's (raw.stack, with out as contiguous), one launch per step over it -- only a pending background, one per
+        stack, takes the two halves one by one."""
+        out_a, out_b = (None, None) if out is None else (out[0], out[1])
+        if self._dynmask is not None:
+            return self._pair_chain(raw.A, raw.B, raw.bg_a, raw.bg_b, raw.owned, out_a, out_b, ids=raw.chunk)
+        if raw.stack is not None:
+            n, dst = len(raw.chunk), out.flatten(0, 1)
+            if raw.bg_a is None:
+                frames = self._filtered(raw.stack, None, out=dst)
+            else:
+                self._filtered(raw.A, raw.bg_a, out=out_a)
+                self._filtered(raw.B, raw.bg_b, out=out_b)
+                frames = dst
+            frames = self._finished(frames, True)
+            return frames[:n], frames[n:], None
+        fa, fb = self._filtered(raw.A, raw.bg_a, out=out_a), self._filtered(raw.B, raw.bg_b, out=out_b)
+        owned = raw.owned or fa is not raw.A
+        return self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b), None
+
     def _run_masked(self, plan, fa, fb, masks):
         """dynamic_mask=: the passes on prepared frames with their masks; (u, v, inv, excluded) with excluded bool
         [n, n_rows, n_cols], the excluded cells of every pair in the orientation of the delivered fields (a copy, enqueued
@@ -704,8 +745,8 @@ class OfflinePIV:
         return u, v, inv, excluded
 
     def _load_pair(self, i):
-        """(a, b, bg_a, bg_b, owned) for pair i alone: its uint8 frames on the device behind tone map and rectification,
-        what is to be subtracted from them, and whether they are memory of this object.  None for an undecodable pair."""
+        """The Raw record of pair i alone: its uint8 frames on the device behind tone map and rectification, what is to be
+        subtracted from them, and whether they are memory of this object.  None for an undecodable pair."""
         a, b = self._dataset[i]
         if a is None or b is None:
             return None
@@ -721,18 +762,17 @@ class OfflinePIV:
             a, b = self._dewarped(a, buf[0]), self._dewarped(b, buf[1])
         bg = self._background(shape)
         bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
-        return a, b, bg_a, bg_b, True
+        return Raw([(i, True)], [i], a, b, True, bg_a, bg_b)
 
     def pair_mask(self, i):
         """uint8 [H, W] numpy, 0 / 1: the mask pair i gets under dynamic_mask=, mask='s image included -- for tuning size
         and level.  None without the keyword or for a pair that cannot be decoded."""
         if self._dynmask is None:
             return None
-        got = self._load_pair(int(i))
-        if got is None:
+        raw = self._load_pair(int(i))
+        if raw is None:
             return None
-        a, b, bg_a, bg_b, owned = got
-        return self._pair_chain(a, b, bg_a, bg_b, owned, ids=[int(i)], masks_only=True)[2][0].cpu().numpy()
+        return self._pair_chain(raw.A, raw.B, raw.bg_a, raw.bg_b, raw.owned, ids=raw.chunk, masks_only=True)[2][0].cpu().numpy()
 
     def _masked(self, frames, out=None):
         """uint8 frames [n, H, W] or [H, W] through the pixel step of mask= (one tpiv_apply_mask call), into out (None: a
@@ -845,50 +885,25 @@ class OfflinePIV:
         """(bg_a, bg_b): the per-pixel minimum over the a frames and over the b frames of the pairs `indices` (None: every
         pair of the dataset) as uint8 [H, W] tensors on the device -- what background="min" subtracts.  Pairs that cannot
         be decoded or whose frame shape differs from the dataset's (frame_shape()) are left out; with none left both
-        images are 255 everywhere (the identity of the minimum: a rank's empty shard).  The files go through the native
-        read-ahead ring and the device unpack, like batched() (whose staging buffers they share when batch_size and the
-        file size agree), and each batch is folded in with tpiv_frame_min.  With depth= the minimum is taken over the
-        tone-mapped frames (depth="auto" resolves here first), with dewarp= over the rectified frames."""
+        images are 255 everywhere (the identity of the minimum: a rank's empty shard).  The frames come from the raw
+        source of batched() (_raw_batches: over files the native read-ahead ring and the device unpack, whose staging
+        buffers the two share when batch_size and the file size agree), and each batch is folded in with tpiv_frame_min.
+        With depth= the minimum is taken over the tone-mapped frames (depth="auto" resolves here first), with dewarp=
+        over the rectified frames."""
         shape = self.frame_shape()
         if shape is None:
             raise ValueError("compute_background: the dataset holds no decodable pair")
         H, W = shape
-        dev = self._device
-        acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=dev)
+        acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=self._device)
         idx = list(range(len(self._dataset))) if indices is None else list(indices)
-        if not idx:
-            return acc[0], acc[1]
-        bs = int(batch_size or self.bg_batch)
-        lut = self._depth_table()
-        deep = lut is not None
-        pairs = self._dataset.img_pairs
-        first = self._first_decodable(idx)
-        cap = slot_bytes(H, W, pairs[first[0]] if first is not None else (), deep=deep)
-        stage, raw_dev = self._staging(bs, cap)
-        raw_d = raw_dev[0]
-        cur = torch.cuda.current_stream(dev)
-        batches = StagedBatches(idx, pairs, bs, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads, deep=deep)
-        self._reader = batches.reader
-        try:
-            for st in batches:
-                n = len(st.chunk)       # (pairs that are not staged are left out, as batched() leaves them to the one-pair path)
-                if n:
-                    raw_d[:st.n_files].copy_(stage[st.buf][:st.n_files], non_blocking=True)
-                    if deep:
-                        frames = self._map_staged(raw_d[:st.n_files], st, H, W, lut, bs)
-                    else:
-                        desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
-                        lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
-                        frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W)      # [2n, H, W]: a_0..a_n-1, b_0..b_n-1
-                    if self._dewarp is not None:
-                        frames = self._dewarped(frames, self._scratch("_dw_frames", (2 * bs,), H, W, dev)[:2 * n])
-                    engine.frame_min(frames[:n], acc[0])
-                    engine.frame_min(frames[n:], acc[1])
-                    cur.synchronize()           # the upload is through: the readers may refill the staging buffer
-                batches.release()
-        finally:
-            batches.close()
-            torch.cuda.synchronize(dev)
+        if idx:
+            first = self._first_decodable(idx)
+            with contextlib.closing(self._raw_batches(idx, int(batch_size or self.bg_batch), H, W, None,
+                                                      None if first is None else first[0])) as source:
+                for raw in source:
+                    if raw.chunk:           # (pairs that are not staged are left out, as batched() leaves them to the one-pair path)
+                        engine.frame_min(raw.A, acc[0])
+                        engine.frame_min(raw.B, acc[1])
         return acc[0], acc[1]
 
     def _ensemble_plan(self, H, W, max_batch):
@@ -905,60 +920,110 @@ class OfflinePIV:
                                         uncertainty=self._uncertainty, deform=self._deform),
                        [w for w, _ in engine.pass_sizes(self._wind_size, self._overlap, self._iter, self._iter_scale)])
 
-    def _frame_batches(self, idx, batch_size, H, W, ids=None):
-        """The prepared frames of the pairs idx, batch_size at a time, as (A, B) uint8 [n, H, W] on the device: read through
-        the native read-ahead ring, unpacked on the device and taken through the preparation steps exactly as batched()
-        takes them (tone map, rectification, background, pre-filter, equalize, mask pixels).  Pairs that cannot be decoded
-        or have another frame shape are left out, as compute_background() leaves them out.  The stacks live in buffers
-        of this object that the next batch overwrites: the consumer enqueues its work on the current stream before it
-        asks for the next one.  ids: a list that holds, while a batch is out, the pair ids of its n pairs."""
+    def _raw_batches(self, idx, batch_size, H, W, bg, like=None):
+        """The raw frame source over files: one Raw record per batch_size pairs of idx -- read by the native reader threads
+        (io.ReadAhead) into pinned staging memory, uploaded, and unpacked (uncompressed BMPs, with the background bg
+        [2, H, W] subtracted in the same kernel) or tone-mapped (depth=) and rectified (dewarp=) on the device; these two
+        leave bg to the consumer.  A batch none of whose pairs is staged comes with frames None; its order tells the
+        consumer which pairs to run one by one.  The frames live in memory that a later batch overwrites: the consumer
+        enqueues its work on the current stream before it asks for the next batch, and stream order protects them; the
+        events below protect the device copies of the staging slots and the staging memory.  The one place that stages
+        files: closing the generator (also mid-run) stops the reader threads and waits for the device.  like: a decodable
+        pair of idx, whose files size the staging slots."""
         dev = self._device
-        lut = self._depth_table()
-        deep = lut is not None
-        dewarp = self._dewarp is not None
-        if dewarp:
-            self._dewarp_shape((H, W))
-        bg = self._background((H, W), batch_size)
+        lut = self._depth_table()                     # (depth="auto": the histogram prepass runs here, once, before _staging)
+        deep, dewarp = lut is not None, self._dewarp is not None
+        fused = None if deep or dewarp else bg        # (a background is in rectified coordinates and mapped units)
+        bg_a, bg_b = (None, None) if bg is None or fused is not None else (bg[0], bg[1])
         pairs = self._dataset.img_pairs
-        first = self._first_decodable(idx)
-        cap = slot_bytes(H, W, pairs[first[0]] if first is not None else (), deep=deep)
+        cap = slot_bytes(H, W, pairs[like] if like is not None else (), deep=deep)
         stage, raw_dev = self._staging(batch_size, cap)
-        raw_all = raw_dev[0]
-        cur = torch.cuda.current_stream(dev)
+        # the host side of the loop below: read-ahead ring, header sweep, host decode of other formats, descriptor tables
         batches = StagedBatches(idx, pairs, batch_size, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads,
                                 deep=deep)
         self._reader = batches.reader
+        # uploads run on their own stream into a double-buffered device copy of the staging slots, so that the PCIe
+        # transfer of batch n + 1 (4 MP: 268 MB, ~5 ms) overlaps the passes of batch n (~3 ms) instead of preceding them
+        cur = torch.cuda.current_stream(dev)
+        up_stream = self._side_stream("_up_stream", dev)     # (kept: a stream's first use costs milliseconds)
+        consumed = [None, None]             # event: the unpack kernel that read raw_dev[k] has run
+        release = None                      # upload event of the batch before (its staging buffer is still held)
+        n_up = 0
+
+        def let_go(rel):
+            if rel is not None:
+                if rel[0] is not None:
+                    rel[0].synchronize()              # its upload is through: the readers may refill the staging buffer
+                batches.release()
+
         try:
-            for st in batches:
-                n = len(st.chunk)
+            for k, st in enumerate(batches):
+                up, frames, n = None, None, len(st.chunk)
                 if n:
-                    raw_d = raw_all[:st.n_files]
-                    raw_d.copy_(stage[st.buf][:st.n_files], non_blocking=True)
-                    if deep:
-                        frames = self._map_staged(raw_d, st, H, W, lut, batch_size)
-                    else:
+                    dbuf, n_up = n_up % 2, n_up + 1
+                    with torch.cuda.stream(up_stream):
+                        if consumed[dbuf] is not None:
+                            up_stream.wait_event(consumed[dbuf])
+                        raw_d = raw_dev[dbuf][:st.n_files]
+                        raw_d.copy_(stage[st.buf][:st.n_files], non_blocking=True)
+                        up = torch.cuda.Event()
+                        up.record(up_stream)
+                    # unpacked frame order: every a of the batch, then every b (two contiguous stacks)
+                    if not deep:
                         desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
                         lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
-                        frames = engine.bmp_unpack(raw_all.view(-1), desc_d, lut_d, H, W, background=None if dewarp else bg)
-                    if dewarp:
-                        frames = self._dewarped(frames, self._scratch("_dw_frames", (2 * batch_size,), H, W, frames.device)[:2 * n])
-                    dst = frames if self._prefilter is None else \
-                        self._scratch("_pf_frames", (2 * batch_size,), H, W, frames.device)[:2 * n]
-                    if (deep or dewarp) and bg is not None:
-                        self._filtered(frames[:n], bg[0], out=dst[:n])
-                        self._filtered(frames[n:], bg[1], out=dst[n:])
-                        frames = dst
+                    cur.wait_event(up)
+                    if deep:
+                        # the tone map where the unpack sits: one launch, slots a0 b0 a1 b1 .. -> stacks a_0..a_n-1, b_0..b_n-1
+                        frames = self._map_staged(raw_d, st, H, W, lut, batch_size)
                     else:
-                        frames = self._filtered(frames, None, out=dst)
-                    frames = self._finished(frames, True)
-                    if ids is not None:
-                        ids[:] = st.chunk
-                    yield frames[:n], frames[n:]
-                    cur.synchronize()           # upload and consumer are through: staging and frame buffers may be refilled
-                batches.release()
+                        frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=fused)
+                    consumed[dbuf] = torch.cuda.Event()
+                    consumed[dbuf].record(cur)
+                    if dewarp:
+                        # one launch over both stacks, into a buffer kept from batch to batch
+                        frames = self._dewarped(frames, self._scratch("_dw_frames", (2 * batch_size,), H, W, dev)[:2 * n])
+                # the staging buffer of the batch before goes back now, with this batch's upload and unpack enqueued -- not
+                # when the consumer resumes this generator: that is behind its host work, and the readers, which bound the
+                # file path, then wait for a buffer (measured: 6.3 k -> 4.3 k pairs/s in half of the runs)
+                let_go(release)
+                release = (up,)
+                yield Raw(st.order, st.chunk, frames[:n] if n else None, frames[n:] if n else None, True, bg_a, bg_b,
+                          (k + 1) * batch_size >= len(idx), frames)
+            let_go(release)
         finally:
+            # consumer finished, raised, or abandoned the run (GeneratorExit lands here): stop the reader threads, then wait
+            # for every upload / unpack still queued (they read the staging buffers and write raw_dev, which the next run
+            # over files on this object reuses with no events to order itself behind)
             batches.close()
             torch.cuda.synchronize(dev)
+
+    def _prep_out(self, raw, batch_size, H, W):
+        """Where _prepared writes what it may not write in place, uint8 [2, n, H, W]: over files the uploaded stacks
+        themselves; only the pre-filter, a stencil, writes a buffer kept from batch to batch (stream order keeps a
+        batch's passes ahead of the next batch's filter)."""
+        n = len(raw.chunk)
+        dst = raw.stack if self._prefilter is None else \
+            self._scratch("_pf_frames", (2 * batch_size,), H, W, raw.stack.device)[:2 * n]
+        return dst.view(2, n, H, W)
+
+    def _frame_batches(self, idx, batch_size, H, W, like):
+        """The prepared frame source of batched(), ensemble() and tracks(): (raw, fa, fb, masks) per batch_size pairs of idx
+        -- the Raw record of _raw_batches, and its frames through the preparation steps (_prepared: background,
+        pre-filter, equalize, mask pixels; masks under dynamic_mask= only) as uint8 [n, H, W] on the device; fa None for
+        a batch without a staged pair.  The stacks live in buffers of this object that the next batch overwrites: the
+        consumer enqueues its work on the current stream before it asks for the next one.  Closing this generator closes
+        the raw source."""
+        self._depth_table()                           # depth="auto" and background="min" run their own pass over the
+        if self._dewarp is not None:                  # dataset: here, before the raw source stages anything
+            self._dewarp_shape((H, W))
+        bg = self._background((H, W), batch_size)
+        with contextlib.closing(self._raw_batches(idx, batch_size, H, W, bg, like)) as source:
+            for raw in source:
+                if raw.chunk:
+                    yield (raw,) + self._prepared(raw, self._prep_out(raw, batch_size, H, W))
+                else:
+                    yield raw, None, None, None
 
     def ensemble(self, indices=None, batch_size: int = 32):
         """Ensemble (sum-of-correlation) PIV over the pairs `indices` (None: all): ONE field (x, y, u, v) from the summed
@@ -980,7 +1045,13 @@ class OfflinePIV:
         H, W = first[1]
         batch_size = int(batch_size)
         plan = self._ensemble_plan(H, W, batch_size)
-        u, v, inv = plan.run_ensemble(lambda: self._frame_batches(idx, batch_size, H, W))
+
+        def chunks():                           # one pass over the recording; unstaged pairs are left out
+            with contextlib.closing(self._frame_batches(idx, batch_size, H, W, first[0])) as batches:
+                for raw, fa, fb, _ in batches:
+                    if raw.chunk:
+                        yield fa, fb
+        u, v, inv = plan.run_ensemble(chunks)
         return self._ensemble_finish(plan, (H, W), u, v, inv)
 
     def _ensemble_finish(self, plan, shape, u, v, inv):
@@ -1022,7 +1093,7 @@ class OfflinePIV:
         par = self._tracks_check(level, radius)
         idx = list(range(len(self._dataset))) if indices is None else list(indices)
         first = self._first_decodable(idx) if idx else None
-        return self._tracks(par, idx, first[1], int(batch_size)) if first is not None else iter(())
+        return self._tracks(par, idx, first, int(batch_size)) if first is not None else iter(())
 
     def _tracks_check(self, level, radius):
         """The checked arguments of tracks(); ValueError with dynamic_mask=."""
@@ -1032,9 +1103,9 @@ class OfflinePIV:
                              "use mask=, or run without it")
         return par
 
-    def _tracks(self, par, idx, shape, batch_size):
-        """tracks() over the pairs idx of frame shape `shape`, with the checked arguments par."""
-        H, W = shape
+    def _tracks(self, par, idx, first, batch_size):
+        """tracks() over the pairs idx, whose first decodable pair and frame shape are `first`, with the checked arguments par."""
+        like, (H, W) = first
         plan = self._get_plan(H, W, max_batch=batch_size)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
@@ -1043,25 +1114,27 @@ class OfflinePIV:
         xc, yc = np.arange(nc) * float(w - o) + (w - 1) / 2, np.arange(nr) * float(w - o) + (w - 1) / 2
         dev = self._device
         image = self._static_image((H, W), dev)
-        ids = []
-        for A, B in self._frame_batches(idx, batch_size, H, W, ids=ids):
-            chunk = list(ids)
-            u, v, inv = plan.run(A, B)
-            pa = engine.particle_detect(A, par["level"], mask=image)      # on the frame buffers, before the next batch
-            pb = engine.particle_detect(B, par["level"], mask=image)
-            raw = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)
-            kept = [k for k, uv in enumerate(raw) if uv is not None]
-            if not kept:
-                continue
-            pred = np.zeros((2, len(chunk), nr, nc))
-            for k in kept:
-                pred[0, k], pred[1, k] = raw[k]
-            pred = torch.from_numpy(pred).to(dev)
-            m = engine.particle_match(pa, pb, pred[0], pred[1], xc, yc, par["radius"], (H, W))
-            host = [t.cpu().numpy() for t in (pa.x, pa.y, pa.peak, pa.count, pb.x, pb.y, pb.peak, pb.count) + tuple(m)]
-            for k in kept:
-                t = self._tracks_of(*(a[k] for a in host))
-                yield (chunk[k],) + self._finish(raw[k], x, y, plan=plan, derive=False) + (t,)
+        with contextlib.closing(self._frame_batches(idx, batch_size, H, W, like)) as batches:
+            for src, A, B, _ in batches:
+                chunk = src.chunk
+                if not chunk:           # (none of the batch's pairs is staged: left out)
+                    continue
+                u, v, inv = plan.run(A, B)
+                pa = engine.particle_detect(A, par["level"], mask=image)      # on the frame buffers, before the next batch
+                pb = engine.particle_detect(B, par["level"], mask=image)
+                raw = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)
+                kept = [k for k, uv in enumerate(raw) if uv is not None]
+                if not kept:
+                    continue
+                pred = np.zeros((2, len(chunk), nr, nc))
+                for k in kept:
+                    pred[0, k], pred[1, k] = raw[k]
+                pred = torch.from_numpy(pred).to(dev)
+                m = engine.particle_match(pa, pb, pred[0], pred[1], xc, yc, par["radius"], (H, W))
+                host = [t.cpu().numpy() for t in (pa.x, pa.y, pa.peak, pa.count, pb.x, pb.y, pb.peak, pb.count) + tuple(m)]
+                for k in kept:
+                    t = self._tracks_of(*(a[k] for a in host))
+                    yield (chunk[k],) + self._finish(raw[k], x, y, plan=plan, derive=False) + (t,)
 
     def _tracks_of(self, xa, ya, peak_a, count_a, xb, yb, peak_b, count_b, match, status, d2, matched):
         """The Tracks of one pair from its two lists and engine.particle_match's verdicts (numpy): the matched particles in
@@ -1090,6 +1163,10 @@ class OfflinePIV:
     device_out = False       # batched(): yield u, v as float64 tensors ON THE DEVICE (the finished fields of B:894-898, hole
                              # fills scattered in from the host) instead of numpy arrays -- for callers that go on with them
                              # on the GPU (dist.run_sharded: the end-of-run gather over xGMI)
+
+    def _in_flight(self):
+        """Launches of batched() in flight before a batch's results are collected."""
+        return self.pipeline_depth
 
     def auto_host_config(self, ranks_on_node=None):
         """Size the reader threads and the fill-worker processes from the cores this rank really has (affinity mask and
@@ -1170,9 +1247,7 @@ class OfflinePIV:
         # start while they run.  (The small kernels above stay on the compute stream: on the side stream too they made
         # the whole generator slower -- 9.1 -> 8.2 k pairs/s, same box.)
         cur = torch.cuda.current_stream(u.device)
-        down = self._down_stream
-        if down is None or down.device != u.device:
-            down = self._down_stream = torch.cuda.Stream(u.device)
+        down = self._side_stream("_down_stream", u.device)
         ready = torch.cuda.Event()
         ready.record(cur)
         with torch.cuda.stream(down):
@@ -1462,21 +1537,19 @@ class OfflinePIV:
     def _one(self, i):
         """Pair i alone: decode on the host, one launch per pass, post-validation, flip / scale (B:868-898).
         None for an undecodable or dropped pair.  Plans of this path are kept per frame shape."""
-        got = self._load_pair(i)
-        if got is None:
+        raw = self._load_pair(i)
+        if raw is None:
             return None
-        a, b, bg_a, bg_b, _ = got
-        shape = (int(a.shape[-2]), int(a.shape[-1]))
+        shape = (int(raw.A.shape[-2]), int(raw.A.shape[-1]))
         plan = self._single_plan(shape)
+        # one launch per frame and step; in place from equalize on: the upload and what the steps made are this object's
+        fa, fb, masks = self._prepared(raw)
         excluded = None
-        if self._dynmask is not None:
-            fa, fb, masks = self._pair_chain(a, b, bg_a, bg_b, True, ids=[i])
+        if masks is not None:
             u, v, inv, excluded = self._run_masked(plan, fa, fb, masks)
             excluded = excluded[0].cpu().numpy()
         else:
-            # one launch per frame and step; in place from equalize on: the upload and what the steps made are this object's
-            a, b = self._filtered(a, bg_a), self._filtered(b, bg_b)
-            u, v, inv = plan.run(self._finished(a, True), self._finished(b, True))
+            u, v, inv = plan.run(fa, fb)
         sigma = None if self._uncertainty is None else plan.uncertainty(1)
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates(shape, w, o)
@@ -1510,36 +1583,21 @@ class OfflinePIV:
         threads (io.ReadAhead) put the next batches' files into pinned staging memory -- uncompressed BMPs as their RAW
         FILE BYTES (no host decode: header skip, row flip, padding strip and palette / gray conversion
         run on the device, tpiv_bmp_unpack), other formats decoded on the host -- while the GPU works on
-        the current batch (triple-buffered staging, uploads on their own stream).  Yields (pair_index, x, y, u, v); dropped pairs yield nothing."""
+        the current batch (triple-buffered staging, uploads on their own stream: _raw_batches).  Yields (pair_index, x, y, u, v); dropped pairs yield nothing."""
         idx = list(range(len(self._dataset))) if indices is None else list(indices)
-        if not idx:
-            return
-        first = self._first_decodable(idx)       # the frame shape is the first decodable pair's
+        first = self._first_decodable(idx) if idx else None       # the frame shape is the first decodable pair's
         if first is None:
             return
         H, W = first[1]
-        lut = self._depth_table()                     # (depth="auto": the histogram prepass runs here, once, before ...)
-        deep = lut is not None
-        dewarp = self._dewarp is not None
-        if dewarp:
-            self._dewarp_shape((H, W))
-        bg = self._background((H, W), batch_size)     # (background="min": the prepass over the files runs here, once)
         plan = self._get_plan(H, W, max_batch=batch_size)
-        pairs = self._dataset.img_pairs
-        cap = slot_bytes(H, W, pairs[first[0]], deep=deep)
-        stage, raw_dev = self._staging(batch_size, cap)
-        # the host side of the loop below: read-ahead ring, header sweep, host decode of other formats, descriptor tables
-        batches = StagedBatches(idx, pairs, batch_size, H, W, [t.numpy() for t in stage], cap, threads=self.read_threads,
-                                deep=deep)
-        self._reader = batches.reader
         w, o, _, _ = plan.geometry[-1]
         x, y = get_coordinates((H, W), w, o)
         dev = self._device
-        pipe = self._post_pipeline(x, y, depth=self.pipeline_depth, plan=plan)
+        pipe = self._post_pipeline(x, y, depth=self._in_flight(), plan=plan)
 
         def emit(finished):
             """Results of finished batches in dataset order; the pairs that were not staged run now."""
-            for (order, chunk), res in finished:
+            for order, res in finished:
                 res = iter(res)
                 for i, staged in order:
                     out = next(res) if staged else self._one(i)
@@ -1551,91 +1609,25 @@ class OfflinePIV:
                                                   for f in out[2:])
                         yield (i,) + out
 
-        # uploads run on their own stream into a double-buffered device copy of the staging slots, so that the PCIe
-        # transfer of batch n + 1 (4 MP: 268 MB, ~5 ms) overlaps the passes of batch n (~3 ms) instead of preceding them
-        cur = torch.cuda.current_stream(dev)
-        up_stream = torch.cuda.Stream(dev)
-        consumed = [None, None]             # event: the unpack kernel that read raw_dev[k] has run
-        release = None                      # upload event of the batch before (its staging buffer is still held)
-        n_up = 0
-
-        def let_go(rel):
-            if rel is not None:
-                if rel[0] is not None:
-                    rel[0].synchronize()              # its upload is through: the readers may refill the staging buffer
-                batches.release()
-
-        try:
-            for st in batches:
+        with contextlib.closing(self._frame_batches(idx, batch_size, H, W, first[0])) as batches:
+            for raw, fa, fb, masks in batches:
                 # (a pair that is not staged -- undecodable, or a frame shape other than the batch's -- takes the one-pair
                 #  path when its turn comes, in emit: that skips an undecodable pair like B:138-139 and gives another
                 #  shape its own plan)
-                ticket, up = None, None
-                if st.chunk:
-                    n = len(st.chunk)
-                    dbuf, n_up = n_up % 2, n_up + 1
-                    with torch.cuda.stream(up_stream):
-                        if consumed[dbuf] is not None:
-                            up_stream.wait_event(consumed[dbuf])
-                        raw_d = raw_dev[dbuf][:st.n_files]
-                        raw_d.copy_(stage[st.buf][:st.n_files], non_blocking=True)
-                        up = torch.cuda.Event()
-                        up.record(up_stream)
-                    # unpacked frame order: every a of the batch, then every b (two contiguous stacks)
-                    if not deep:
-                        desc_d = torch.from_numpy(st.desc).to(dev, non_blocking=True)
-                        lut_d = torch.from_numpy(st.lut).to(dev, non_blocking=True)
-                    cur.wait_event(up)
-                    if deep:
-                        # the tone map where the unpack sits: one launch, slots a0 b0 a1 b1 .. -> stacks a_0..a_n-1, b_0..b_n-1
-                        frames = self._map_staged(raw_d, st, H, W, lut, batch_size)
-                    else:
-                        # [2n, H, W]: a_0..a_n-1, b_0..b_n-1 (with a background: minus bg_a / bg_b, in the same kernel --
-                        # unless the frames are rectified first: the background is in rectified coordinates)
-                        frames = engine.bmp_unpack(raw_d.view(-1), desc_d, lut_d, H, W, background=None if dewarp else bg)
-                    consumed[dbuf] = torch.cuda.Event()
-                    consumed[dbuf].record(cur)
-                    if dewarp:
-                        # one launch over both stacks, into a buffer kept from batch to batch
-                        frames = self._dewarped(frames, self._scratch("_dw_frames", (2 * batch_size,), H, W, frames.device)[:2 * n])
-                    # the filter writes a buffer kept from batch to batch (stream order keeps a batch's passes ahead of the
-                    # next batch's filter), the subtraction alone goes in place
-                    dst = frames if self._prefilter is None else \
-                        self._scratch("_pf_frames", (2 * batch_size,), H, W, frames.device)[:2 * n]
-                    if self._dynmask is not None:
-                        # per stack, with the segmentation between the background and the filter
-                        todo = bg if (deep or dewarp) and bg is not None else (None, None)
-                        fa, fb, masks = self._pair_chain(frames[:n], frames[n:], todo[0], todo[1], True, dst[:n], dst[n:],
-                                                         ids=st.chunk)
-                        u, v, inv, excluded = self._run_masked(plan, fa, fb, masks)
-                        ticket = self._post_submit(u, v, inv, plan=plan, excluded=excluded)
-                    else:
-                        if (deep or dewarp) and bg is not None:
-                            # per stack: the tone map subtracted nothing, and neither did an unpack in front of dewarp=
-                            self._filtered(frames[:n], bg[0], out=dst[:n])
-                            self._filtered(frames[n:], bg[1], out=dst[n:])
-                            frames = dst
-                        else:
-                            # one launch over the stack (the unpack subtracted already)
-                            frames = self._filtered(frames, None, out=dst)
-                        # one call per step over the stack, in place: the unpack, the tone map or the filter wrote it into
-                        # memory of this object
-                        frames = self._finished(frames, True)
-                        u, v, inv = plan.run(frames[:n], frames[n:])
-                        ticket = self._post_submit(u, v, inv, plan=plan)
-                let_go(release)
-                release = (up,)
+                ticket = None
+                if masks is not None:
+                    u, v, inv, excluded = self._run_masked(plan, fa, fb, masks)
+                    ticket = self._post_submit(u, v, inv, plan=plan, excluded=excluded)
+                elif fa is not None:
+                    u, v, inv = plan.run(fa, fb)
+                    ticket = self._post_submit(u, v, inv, plan=plan)
                 # the host work of the PREVIOUS batches runs while the GPU works on this one
-                yield from emit(pipe.push((st.order, st.chunk), ticket))
-            let_go(release)
-            release = None
-            yield from emit(pipe.flush())
-        finally:
-            # consumer finished, raised, or abandoned the generator (GeneratorExit lands here): stop the reader threads,
-            # then wait for every upload / unpack still queued (they read the staging buffers and write raw_dev, which the
-            # next run over files on this object reuses with a fresh upload stream and no events to order itself behind)
-            batches.close()
-            torch.cuda.synchronize(dev)
+                yield from emit(pipe.push(raw.order, ticket))
+                if raw.last:
+                    # drained while the source is open: asking it for more ends the run (over files: reader threads
+                    # stopped, device synchronised), which the batches in flight need not wait for
+                    yield from emit(pipe.flush())
+            yield from emit(pipe.flush())         # (nothing left, unless the source ended early: its reader was closed under it)
 
 
 class ResidentPIV(OfflinePIV):
@@ -1677,8 +1669,8 @@ class ResidentPIV(OfflinePIV):
         self._init_state(device, range(frames_a.shape[0]), IterModMap.functions[multipass_mode], run, opts)
         self._A, self._B = frames_a.contiguous(), frames_b.contiguous()
 
-    def frame_shape(self):
-        return tuple(self._A.shape[1:]) if len(self) else None
+    def _first_decodable(self, idx):
+        return (idx[0], tuple(int(s_) for s_ in self._A.shape[1:])) if len(idx) else None
 
     def _depth_pairs(self, sample):
         for i in engine.depth_sample(len(self), sample):
@@ -1722,27 +1714,20 @@ class ResidentPIV(OfflinePIV):
         A, B, owned = self._select([i], self._depth_table(), dw=dw)
         bg = self._background((H, W))
         bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
-        return A, B, bg_a, bg_b, owned
+        return Raw([(i, True)], [i], A, B, owned, bg_a, bg_b)
 
     def compute_background(self, indices=None, batch_size=None):
         """(bg_a, bg_b): the per-pixel minimum of the resident a frames and of the b frames (of the pairs `indices`;
-        None: all), uint8 [H, W] on the device (tpiv_frame_min; 255 everywhere for no pair).  batch_size: pairs gathered
-        at a time for `indices` (default bg_batch).  With depth= the minimum is taken over the tone-mapped frames, with
-        dewarp= over the rectified frames, batch_size pairs at a time."""
-        H, W = self._A.shape[1:]
-        acc = torch.full((2, H, W), 255, dtype=torch.uint8, device=self._device)
+        None: all), uint8 [H, W] on the device (tpiv_frame_min; 255 everywhere for no pair).  batch_size: pairs mapped,
+        rectified or gathered at a time (default bg_batch).  With depth= the minimum is taken over the tone-mapped
+        frames, with dewarp= over the rectified frames, batch_size pairs at a time."""
         lut = self._depth_table()
-        dewarp = self._dewarp is not None
-        if lut is None and not dewarp and indices is None:   # the resident stacks as they are: one launch each
+        if len(self) and (lut is not None or self._dewarp is not None or indices is not None):
+            return super().compute_background(indices, batch_size)
+        acc = torch.full((2,) + tuple(self._A.shape[1:]), 255, dtype=torch.uint8, device=self._device)
+        if len(self):                                        # the resident stacks as they are: one launch each
             engine.frame_min(self._A, acc[0])
             engine.frame_min(self._B, acc[1])
-            return acc[0], acc[1]
-        idx, bs = list(range(len(self))) if indices is None else list(indices), int(batch_size or self.bg_batch)
-        dw = self._scratch("_dw_frames", (2, min(bs, max(len(idx), 1))), H, W, self._A.device) if dewarp else None
-        for s in range(0, len(idx), bs):                     # mapped, rectified, viewed or gathered in bounded chunks
-            A, B, _ = self._select(idx[s:s + bs], lut, dw=dw)
-            engine.frame_min(A, acc[0])
-            engine.frame_min(B, acc[1])
         return acc[0], acc[1]
 
     # launches in flight before a batch's census is read.  Two: the copies of a batch's results run on a stream of their own,
@@ -1751,96 +1736,32 @@ class ResidentPIV(OfflinePIV):
     # timeline of the 'isolated spots' case, 0.8 ms idle per 64 pairs)
     resident_depth = 2
 
-    def batched(self, batch_size: int = 32, indices=None) -> Generator:
-        idx = list(range(len(self))) if indices is None else list(indices)
-        if not idx:
-            return
-        H, W = self._A.shape[1:]
-        lut = self._depth_table()                     # (depth="auto": the histogram of the sampled pairs, once, before ...)
-        # the reused buffers: the mapped frames of a launch (uint16 -> uint8; stream order keeps a launch's passes ahead of the
-        # next launch's map into the same memory), and what the later steps make of frames they may not write in place
-        dbuf = None if lut is None else self._scratch("_depth_frames", (2, batch_size), H, W, self._A.device)
-        bg = self._background((H, W))                 # (background="min" with dewarp=: its prepass uses the buffer below first)
-        dw = None if self._dewarp is None else self._scratch("_dw_frames", (2, batch_size), H, W, self._A.device)
+    def _in_flight(self):
+        return self.resident_depth
+
+    def _raw_batches(self, idx, batch_size, H, W, bg, like=None):
+        """The raw frame source over the resident stacks: one Raw record per batch_size pairs of idx, every pair staged --
+        _select's frames, mapped and rectified into reused buffers (stream order keeps a launch's passes ahead of the next
+        launch's writes into the same memory).  bg [2, H, W] is all left to the consumer."""
+        lut = self._depth_table()                     # (depth="auto": the histogram of the sampled pairs, once)
+        lead = (2, min(batch_size, len(idx)))         # (no larger than the run needs)
+        dbuf = None if lut is None else self._scratch("_depth_frames", lead, H, W, self._A.device)
+        dw = None if self._dewarp is None else self._scratch("_dw_frames", lead, H, W, self._A.device)
         bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
-        buf = None
-        if bg is not None or self._prefilter is not None \
-                or ((self._equalize is not None or self._zeroes_pixels()) and lut is None and dw is None):
-            buf = self._scratch("_bg_frames", (2, batch_size), H, W, self._A.device)
-        plan = self._get_plan(H, W, max_batch=batch_size)
-        w, o, _, _ = plan.geometry[-1]
-        x, y = get_coordinates((H, W), w, o)
-        pipe = self._post_pipeline(x, y, depth=self.resident_depth, plan=plan)
-
-        def emit(finished):
-            for chunk_ids, res in finished:
-                for i, out in zip(chunk_ids, res):
-                    if out is not None:
-                        yield (i,) + out
-
         for s in range(0, len(idx), batch_size):
             chunk = idx[s:s + batch_size]
             n = len(chunk)
             A, B, owned = self._select(chunk, lut, out=None if dbuf is None else (dbuf[0, :n], dbuf[1, :n]), dw=dw)
-            out_a, out_b = (None, None) if buf is None else (buf[0, :n], buf[1, :n])
-            # one launch per frame stack and step.  The background and the filter write the reused buffer (stream order
-            # keeps a launch's passes ahead of the next launch's writes into the same memory), and so does the first later
-            # step that meets the caller's frames; everything else goes in place
-            if self._dynmask is not None:
-                fa, fb, masks = self._pair_chain(A, B, bg_a, bg_b, owned, out_a, out_b, ids=chunk)
-                u, v, inv, excluded = self._run_masked(plan, fa, fb, masks)
-                yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan, excluded=excluded)))
-                continue
-            fa, fb = self._filtered(A, bg_a, out=out_a), self._filtered(B, bg_b, out=out_b)
-            owned |= fa is not A
-            u, v, inv = plan.run(self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b))
-            # host work of the previous batches overlaps this batch's kernels
-            yield from emit(pipe.push(chunk, self._post_submit(u, v, inv, plan=plan)))
-        yield from emit(pipe.flush())
+            yield Raw([(i, True) for i in chunk], chunk, A, B, owned, bg_a, bg_b, s + batch_size >= len(idx))
 
-    def _frame_batches(self, idx, batch_size, H, W, ids=None):
-        """The prepared frames of the pairs idx, batch_size at a time, as (A, B) uint8 [n, H, W]: the steps of batched(),
-        into the same reused buffers (the consumer enqueues its work before it asks for the next batch).  ids: a list that
-        holds, while a batch is out, the pair ids of its n pairs."""
-        lut = self._depth_table()
-        dbuf = None if lut is None else self._scratch("_depth_frames", (2, batch_size), H, W, self._A.device)
-        bg = self._background((H, W))
-        dw = None if self._dewarp is None else self._scratch("_dw_frames", (2, batch_size), H, W, self._A.device)
-        bg_a, bg_b = (None, None) if bg is None else (bg[0], bg[1])
-        buf = None
-        if bg is not None or self._prefilter is not None \
-                or ((self._equalize is not None or self._zeroes_pixels()) and lut is None and dw is None):
-            buf = self._scratch("_bg_frames", (2, batch_size), H, W, self._A.device)
-        for s in range(0, len(idx), batch_size):
-            chunk = idx[s:s + batch_size]
-            n = len(chunk)
-            A, B, owned = self._select(chunk, lut, out=None if dbuf is None else (dbuf[0, :n], dbuf[1, :n]), dw=dw)
-            out_a, out_b = (None, None) if buf is None else (buf[0, :n], buf[1, :n])
-            fa, fb = self._filtered(A, bg_a, out=out_a), self._filtered(B, bg_b, out=out_b)
-            owned |= fa is not A
-            if ids is not None:
-                ids[:] = chunk
-            yield self._finished(fa, owned, out=out_a), self._finished(fb, owned, out=out_b)
-
-    def ensemble(self, indices=None, batch_size: int = 32):
-        """OfflinePIV.ensemble over the resident pairs: one (x, y, u, v) from the summed correlation maps of the pairs
-        `indices` (None: all)."""
-        self._ensemble_check()
-        idx = list(range(len(self))) if indices is None else list(indices)
-        if not idx:
-            return None
-        H, W = self._A.shape[1:]
-        batch_size = int(batch_size)
-        plan = self._ensemble_plan(H, W, batch_size)
-        u, v, inv = plan.run_ensemble(lambda: self._frame_batches(idx, batch_size, H, W))
-        return self._ensemble_finish(plan, (H, W), u, v, inv)
-
-    def tracks(self, level, radius=engine.TRACKS_RADIUS, indices=None, batch_size: int = 32) -> Generator:
-        """OfflinePIV.tracks over the resident pairs: (i, x, y, u, v, t) per kept pair of `indices` (None: all), t the
-        Tracks of its matched particle images."""
-        par = self._tracks_check(level, radius)
-        idx = list(range(len(self))) if indices is None else list(indices)
-        return self._tracks(par, idx, tuple(int(s_) for s_ in self._A.shape[1:]), int(batch_size)) if idx else iter(())
+    def _prep_out(self, raw, batch_size, H, W):
+        """The background and the filter write a reused buffer, and so does the first later step that meets the caller's
+        frames (the tone map and the rectification have buffers of their own that equalize and mask go on in); None where
+        every step goes in place."""
+        if raw.bg_a is not None or self._prefilter is not None \
+                or ((self._equalize is not None or self._zeroes_pixels()) and self._depth is None and self._dewarp is None):
+            return self._scratch("_bg_frames", (2, batch_size), H, W, raw.A.device)[:, :len(raw.chunk)]
+        return None
 
     def __call__(self) -> Generator:
         for out in self.batched(1):

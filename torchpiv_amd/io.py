@@ -243,7 +243,8 @@ Staged = collections.namedtuple("Staged", "buf n_files order chunk desc lut")
 
 
 class StagedBatches:
-    """The host side of a run over files (OfflinePIV.batched, compute_background): iterating gives one Staged per `batch`
+    """The host side of a run over files (OfflinePIV._raw_batches, the frame source of batched(), ensemble(), tracks() and
+    compute_background()): iterating gives one Staged per `batch`
     pairs of `idx`.  pairs[i][0] / pairs[i][-1] are pair i's files; slot 2k of a batch is frame a of its pair k, slot
     2k + 1 frame b.  The files arrive through the read-ahead ring (`reader`) in `bufs`, uint8 numpy views [2 * batch, cap] of
     page-locked memory; the sweep over a batch's headers (parse_bmp_headers) hands the files it cannot place -- and every
