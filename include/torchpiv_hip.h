@@ -100,6 +100,23 @@ int tpiv_spline_matrix(int nc, const double* xc, int nf, const double* xf, doubl
 
 /* ---- function-level seam (device pointers) ---------------------------------- */
 
+/* Memory contract of every entry point that takes device pointers (tests/test_gpu_memory_contract.py holds each of them
+ * to it under guard bands and three fill patterns):
+ *   - frames (uint8, and the uint16 samples of tpiv_depth_*) may sit at ANY byte address a multiple of their element size:
+ *     the staging's wide loads take any alignment, and no entry point of the correlation seam (tpiv_pass1, tpiv_iter,
+ *     tpiv_debug_*, tpiv_ensemble_add, tpiv_uncertainty, tpiv_plan_run*) asks more of a frame than that.  A buffer that needs
+ *     more says so at its entry point (the accumulator of tpiv_ensemble_*, the nodes of tpiv_deform_warp, the map of
+ *     tpiv_dewarp, the work memory of tpiv_particle_match): a misaligned one is TPIV_EINVAL and nothing is written;
+ *   - typed inputs and outputs (double, float, int32, int16, ...) sit at their natural alignment, the work buffer at 256 bytes;
+ *   - the prior contents of a work buffer and of every pure output are irrelevant: the library zeroes what it needs zeroed,
+ *     and the same call gives the same bits whatever the buffers held;
+ *   - every cell of every output is written -- those of masked, dead, invalid and listed windows and of the partial last
+ *     wavefront too -- except where an entry point names a part it leaves alone (list entries behind a count or a total,
+ *     rows >= batch of a larger output array);
+ *   - nothing outside [0, bytes) of any buffer is written, and nothing outside an input reaches a result: a call reads
+ *     frame bytes of the pair it works on only, a work buffer of exactly the documented size suffices for every precision
+ *     and mode, and a refused call (TPIV_EINVAL: a NULL or short work buffer included) writes nothing at all. */
+
 /* Tensor part of extended_search_area_piv(frame_a, frame_b, window_size, overlap,
  * validate=True, validation_ratio), B:459-520 (+ correalte_fft B:249-257,
  * correlation_to_displacement B:360-422, peak2peak_secondpeak B:346-358).

@@ -2036,12 +2036,16 @@ static int ensemble_peaks_impl(int mode, const float* acc, long long n_pairs, in
 
 int tpiv_ensemble_add(int mode, const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ws, int ov, const double* u2,
                       const double* v2, float* acc, void* work, size_t work_bytes, void* stream) {
+    // the documented size (a plan hands its own buffer to the _impl, sized by ensemble_work_bytes)
+    if (batch > 0)
+        if (int rc = check_work(work, work_bytes, tpiv_work_bytes(H, W, ws, ov, 1))) return rc;
     return ensemble_add_impl(mode, a, b, batch, H, W, ws, ov, nullptr, nullptr, u2, v2, nullptr, acc, work, work_bytes, stream);
 }
 
 int tpiv_ensemble_peaks(int mode, const float* acc, long long n_pairs, int H, int W, int ws, int ov, const double* u0,
                         const double* v0, const double* u2, const double* v2, double val_ratio, int val_win, double* u, double* v,
                         uint8_t* invalid, double* du, double* dv, void* work, size_t work_bytes, void* stream) {
+    if (int rc = check_work(work, work_bytes, tpiv_work_bytes(H, W, ws, ov, 1))) return rc;      // the documented size
     return ensemble_peaks_impl(mode, acc, n_pairs, H, W, ws, ov, u0, v0, u2, v2, nullptr, val_ratio, val_win, u, v, invalid, du,
                                dv, work, work_bytes, stream);
 }
