@@ -21,7 +21,9 @@
 //     blocks first: 64 swaps per window at 8-14 issue cycles each, see "Swap-free first transposition" in xcorr_tile_body).
 //     The last transform is a c2r one: only spectrum
 //     columns 0..WS/2 cross the LDS the second time (transpose_half).  Kernels at three wavefronts per SIMD move one
-//     float plane at a time (8.4 KB per wavefront), the others complex elements (16.9 KB).
+//     float plane at a time (8.4 KB per wavefront), the others complex elements (16.9 KB).  The planar 32x32 and swap-free
+//     64x64 instances turn the first transposition's tile round (32 rows of 64 lanes, pitch 68 dwords, 8.7 KB): add-TID
+//     stores without an address register, 16-byte reads (transpose_tile<.., ROWS>).
 //   * the k <-> -k partner of the packed spectrum is fetched with ds_bpermute (no LDS memory).  The planar 32x32 / 64x64
 //     kernels split each spectrum column between the lanes of columns c and -c: half the cross-spectrum products, one
 //     radix-2 level and a WS/2-point inverse column transform per lane (transpose_half_pairs).
@@ -49,7 +51,11 @@ struct TileGeo {
     static constexpr bool PLANAR = PLANAR_;
     static constexpr int HROWS = WS / 2 + 1;            // spectrum columns 0..WS/2 (c2r last transform)
     static constexpr int HTILE = HROWS * PITCH;         // elements per half-transposition tile (WS <= 32)
-    static constexpr int LDS_FLOATS = NT * TILE * (PLANAR ? 1 : 2);
+    // Lane-contiguous first transposition of the planar 32x32 and 64x64 tiles (transpose_tile<.., ROWS>): 32 rows of 64
+    // lanes at a pitch of 68 dwords, row k = element k of every lane (8.7 KB per wavefront).
+    static constexpr int ROW_PITCH = 68;
+    static constexpr int ROW_FLOATS = (PLANAR && WS >= 32) ? 32 * ROW_PITCH : 0;
+    static constexpr int LDS_FLOATS = NT * TILE * (PLANAR ? 1 : 2) > ROW_FLOATS ? NT * TILE * (PLANAR ? 1 : 2) : ROW_FLOATS;
     static constexpr int MAP_PITCH = WS + 1;            // floats per row of the correlation map
     static constexpr int NDW = WS / 4;                  // dwords per window row
 };
@@ -245,6 +251,60 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// ---- rows R0 .. R0 + 15 of the lane-contiguous tile (TileGeo::ROW_PITCH): row k takes element E0 + k of every lane's line,
+// component Y.  ds_write_addtid_b32 stores to M0 + offset + 4 * lane: no address register travels to the LDS, so a store costs
+// 2 cycles of the store path where ds_write_b32 costs 4 and ds_write2_b32 6, and the 64 lanes of a row are 64 consecutive dwords
+// (conflict-free).  M0 belongs to the compiler: it is saved, written, used and restored inside ONE statement (s_nop 0: one
+// wait state between an SALU write of M0 and an add-TID LDS instruction).  The compiler does not count these stores in
+// lgkmcnt.  That is safe: the LDS serves a wavefront's instructions in order, a store returns no register, and an uncounted
+// older or younger store can only make a counted wait of the compiler's longer, never shorter.
+template <int WS, int E0, int R0, bool Y>
+__device__ __forceinline__ void store_rows16(const cf (&a)[WS], float* lds) {
+    constexpr int P = TileGeo<WS, true>::ROW_PITCH;
+    static_assert(P == 68, "the offsets below are 272 * row");
+    const unsigned m0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds) + 4u * P * R0;      // low dword of a flat LDS address
+    unsigned keep;
+#define TPIV_ROW(q) "v"(Y ? a[FFT_POS<E0 + R0 + q, WS>].y : a[FFT_POS<E0 + R0 + q, WS>].x)
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %1\n\t"
+        "s_nop 0\n\t"
+        "ds_write_addtid_b32 %2 offset:0\n\t"
+        "ds_write_addtid_b32 %3 offset:272\n\t"
+        "ds_write_addtid_b32 %4 offset:544\n\t"
+        "ds_write_addtid_b32 %5 offset:816\n\t"
+        "ds_write_addtid_b32 %6 offset:1088\n\t"
+        "ds_write_addtid_b32 %7 offset:1360\n\t"
+        "ds_write_addtid_b32 %8 offset:1632\n\t"
+        "ds_write_addtid_b32 %9 offset:1904\n\t"
+        "ds_write_addtid_b32 %10 offset:2176\n\t"
+        "ds_write_addtid_b32 %11 offset:2448\n\t"
+        "ds_write_addtid_b32 %12 offset:2720\n\t"
+        "ds_write_addtid_b32 %13 offset:2992\n\t"
+        "ds_write_addtid_b32 %14 offset:3264\n\t"
+        "ds_write_addtid_b32 %15 offset:3536\n\t"
+        "ds_write_addtid_b32 %16 offset:3808\n\t"
+        "ds_write_addtid_b32 %17 offset:4080\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "s"(m0), TPIV_ROW(0), TPIV_ROW(1), TPIV_ROW(2), TPIV_ROW(3), TPIV_ROW(4), TPIV_ROW(5), TPIV_ROW(6), TPIV_ROW(7),
+          TPIV_ROW(8), TPIV_ROW(9), TPIV_ROW(10), TPIV_ROW(11), TPIV_ROW(12), TPIV_ROW(13), TPIV_ROW(14), TPIV_ROW(15)
+        : "memory");
+#undef TPIV_ROW
+}
+// the 32 consecutive dwords at src (16-byte aligned) as 8 ds_read_b128
+__device__ __forceinline__ void read_row32(const float* src, float (&v)[32]) {
+    const float4* s4 = reinterpret_cast<const float4*>(src);
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+        const float4 q = s4[n];
+        v[4 * n] = q.x;
+        v[4 * n + 1] = q.y;
+        v[4 * n + 2] = q.z;
+        v[4 * n + 3] = q.w;
+    }
+}
+
 // ---- transposition of the wavefront's tile(s) through LDS ---------------------------------
 // in:  lane (w, i) holds line i of its window, element k at in[FFT_POS<k>] (the digit-reversed position the codelets leave it at)
 // out: lane (w, j) holds element j of every line: out[i] = element (line i, position j)
@@ -259,13 +319,55 @@ __device__ __forceinline__ void wave_sync() {
 // lines, out[i] = (line (i + 32) mod 64, position j) -- which the caller undoes as a sign of the odd bins of the next
 // transform (xcorr_tile_body, "Swap-free first transposition").
 // !NOSWAP at 64x64 (the fast-order DWS instance, planar): the off-diagonal 32x32 blocks change lane halves first.
-template <int WS, bool PLANAR, bool NOSWAP = false>
+// ROWS (planar 32x32, planar swap-free 64x64): the lane-contiguous tile.  Row k of the tile holds element k (64x64, phase 2:
+// element k + 32) of all 64 lanes, pitch 68 dwords; the stores are add-TID ones (store_rows16, two blocks of 16 rows that
+// meet at k = 15 | 16) and lane (h, j) reads its 32 values -- position j of the lines (h, 0 .. 31) -- as the 32 consecutive
+// dwords at 68 j + 32 h: 8 ds_read_b128.  h is the lane half: at 32x32 the lane's own window, in phase 1 of 64x64 the lane
+// half's own columns (the diagonal blocks), in phase 2 the OTHER half's (h ^ 1, the off-diagonal blocks, as NOSWAP above).
+// Banks: a 16-byte read of lane j covers the banks (4 j + 32 h + 4 q + 0 .. 3) mod 64, and each of the LDS's four 16-lane
+// service groups of ds_read_b128 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and their upper-half twins) holds 16 distinct
+// j mod 16: 16 disjoint runs of 4 banks, conflict-free (tests/test_lds_rows_host.py walks the layout).
+template <int WS, bool PLANAR, bool NOSWAP = false, bool ROWS = false>
 __device__ __forceinline__ void transpose_tile(cf (&a)[WS], float* lds, int lane) {
     using G = TileGeo<WS, PLANAR>;
     constexpr int P = G::PITCH;
     static_assert(!NOSWAP || WS == 64, "the swap-free form is a 64x64 one");
+    static_assert(!ROWS || (PLANAR && (WS == 32 || (WS == 64 && NOSWAP))), "lane-contiguous tiles: planar 32x32 and swap-free 64x64");
     cf* tile = reinterpret_cast<cf*>(lds);
-    if constexpr (PLANAR && WS > 32) {
+    if constexpr (ROWS) {
+        static_assert(32 * G::ROW_PITCH <= G::LDS_FLOATS, "the lane-contiguous tile fits");
+        const float* rd1 = lds + (lane & 31) * G::ROW_PITCH + 32 * (lane >> 5);
+        auto plane = [&](auto comp) TPIV_LAMBDA_INLINE {
+            constexpr bool Y = decltype(comp)::value;
+            float got[32];
+            wave_sync();
+            store_rows16<WS, 0, 0, Y>(a, lds);
+            store_rows16<WS, 0, 16, Y>(a, lds);
+            wave_sync();
+            read_row32(rd1, got);
+            if constexpr (WS == 64) {
+                const float* rd2 = lds + (lane & 31) * G::ROW_PITCH + 32 * ((lane >> 5) ^ 1);
+                float high[32];
+                wave_sync();
+                store_rows16<WS, 32, 0, Y>(a, lds);
+                store_rows16<WS, 32, 16, Y>(a, lds);
+                wave_sync();
+                read_row32(rd2, high);
+#pragma unroll
+                for (int r = 0; r < 32; ++r) {
+                    if constexpr (Y) a[32 + r].y = high[r];
+                    else a[32 + r].x = high[r];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                if constexpr (Y) a[r].y = got[r];
+                else a[r].x = got[r];
+            }
+        };
+        plane(std::false_type{});
+        plane(std::true_type{});
+    } else if constexpr (PLANAR && WS > 32) {
         // 64x64, one float plane at a time through two 32x33 float tiles (8.4 KB per wavefront, which
         // is what lets three wavefronts per SIMD fit in the LDS): the four blocks of each plane, two at a time
         // (after the swap of the off-diagonal blocks between the lane halves, or in the NOSWAP order)
@@ -1710,7 +1812,10 @@ __device__ __forceinline__ void xcorr_tile_body(const PassParams& p) {
         }
         TPIV_STAMP(3);      // forward row FFT
         // lane = kx, x[y] natural (NOSWAP, lanes 32..63: x[y] = row y + 32)
-        transpose_tile<WS, PLANAR, NOSWAP>(x, tile, fresh_lane());
+        // (the planar 32x32 and swap-free 64x64 instances take the lane-contiguous tile; the fast-order 64x64 DWS instance,
+        //  which swaps lane halves, and the complex tiles keep theirs)
+        constexpr bool ROWS = PLANAR && (WS == 32 || NOSWAP);
+        transpose_tile<WS, PLANAR, NOSWAP, ROWS>(x, tile, fresh_lane());
         TPIV_STAMP(4);      // transposition 1
         fft_inreg<WS, 1, TW, TWF_COL>(x, tw);             // over y; Z(ky, kx = lane) at x[FFT_POS<ky>]
         TPIV_STAMP(5);      // forward column FFT
