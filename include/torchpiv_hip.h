@@ -690,6 +690,55 @@ int tpiv_plan_ensemble_add(tpiv_plan* plan, const uint8_t* a_dev, const uint8_t*
 int tpiv_plan_ensemble_end(tpiv_plan* plan, double* u_dev, double* v_dev, uint8_t* invalid_dev, void* stream);
 int tpiv_plan_ensemble_maps(tpiv_plan* plan, float** acc_dev, long long* n_pairs);
 
+/* ---- single-pixel ensemble correlation (extension; the reference has none) ------------------------------ */
+
+/* Single-pixel ensemble correlation (Westerweel, Geelhoed & Lindken, Exp. Fluids 37 (2004) 375; Kaehler, Scholz & Ortmanns,
+ * Exp. Fluids 41 (2006) 327; Scharnowski, Hain & Kaehler, Exp. Fluids 52 (2012) 985): the correlation at one pixel, or at a
+ * small rectangular bin of pixels, is summed over the pairs of a recording instead of over an interrogation window.
+ * Everything up to the coefficient is exact integer arithmetic.
+ *   Inputs: prepared frames a_i, b_i, uint8 [H, W] (H * W < 2^31), i = 0 .. N - 1, N <= 65536 pairs in all.
+ *   Parameters: search radius R in 3..16, D = 2 R + 1; bin (bin_y, bin_x) = (k_y, k_x), both >= 1, k_y * k_x <= 256, k_y <= H,
+ *     k_x <= W; ONE integer pre-shift s = (shift_y, shift_x) for every bin, |s| <= 64 on each axis.
+ *   Bins: n_by = H / k_y by n_bx = W / k_x (integer division; the rows and columns left over belong to no bin); bin (r, c)
+ *     holds the pixels p = (y, x) with r k_y <= y < (r + 1) k_y and c k_x <= x < (c + 1) k_x.  b counts as 0 outside the frame.
+ *   Accumulated, all int64:
+ *     acc[r, c, j, i] = sum_i sum_{p in bin} a_i(p) b_i(p + s + d), d = (j - R, i - R)          [n_by, n_bx, D, D]
+ *     mom[0..3, y, x] = sum_i a_i, sum_i a_i^2, sum_i b_i, sum_i b_i^2 per pixel, each frame's own coordinates  [4, H, W]
+ *   Exact int64 numerators (N <= 2^16, a bin <= 2^8 pixels and bytes < 2^8 keep N acc < 2^56 and every sum of products of
+ *   two moments < 2^56, so each of these is below 2^57 in magnitude):
+ *     num[d] = N acc[d] - sum_{p in bin} mom0[p] mom2[p + s + d]
+ *     va     = N sum_p mom1[p] - sum_p mom0[p]^2
+ *     vb[d]  = N sum_p mom3[p + s + d] - sum_p mom2[p + s + d]^2
+ *   Coefficient: C[d] = double(num[d]) / sqrt(double(va) * double(vb[d])) -- each conversion and each operation ONE IEEE
+ *     float64 operation, in this order, no contraction.
+ *   Peak: M = (C - min C) + 1e-7 (the peak stage's recipe); the first arg-max (j, i) in raster order; three-point
+ *     log-Gaussian fit per axis, dx = (ln M[j, i-1] - ln M[j, i+1]) / (2 (ln M[j, i+1] + ln M[j, i-1]) - 4 ln M[j, i]), dy
+ *     alike along j; u = shift_x + i - R + dx, v = shift_y + j - R + dy; peak = C at the arg-max; ratio = M(peak) / (the
+ *     largest M outside the 5 x 5 cells around the peak, clipped to the plane).
+ *   Status, uint8, the first that applies: 1 border -- some p + s + d of the bin, d over the whole D x D plane, leaves the
+ *     frame; 2 flat -- va = 0 or some vb[d] = 0; 3 range -- the first arg-max over the whole plane lies on its outer ring
+ *     (|d_y| = R or |d_x| = R; otherwise it is the first arg-max of the interior); 4 fit -- dx or dy not finite, or |dx| > 1 or
+ *     |dy| > 1; 0 valid.  A bin with a non-zero status gets u = v = peak = ratio = NaN; border and flat bins also get an
+ *     all-zero plane.  Every output cell is written in every case.
+ * tpiv_pixel_corr_bytes: the bytes of acc, n_by n_bx D^2 8; 0 for a refused geometry.  mom is 4 H W 8 bytes.
+ * tpiv_pixel_corr_add: acc += and mom += over the pairs a_dev, b_dev uint8 [batch, H, W] (any alignment; 4-byte aligned
+ *   frames of a width divisible by 4 load fastest).  The caller zeroes both accumulators before the first call.  One int64
+ *   read-modify-write of every cell per call, by the one workgroup that owns the bin: no atomics, and integer sums, so any
+ *   split of a recording into calls gives the same bits.  batch <= 256: inside one call a bin's sum is kept in 32 bits, and
+ *   256 pixels x 256 pairs x 255^2 = 4 261 478 400 < 2^32.  batch == 0 succeeds and launches nothing.  The frames are not
+ *   written; acc and mom may overlap neither each other nor the frames.
+ * tpiv_pixel_corr_peaks: u_dev, v_dev, peak_dev, ratio_dev float64 and status_dev uint8 [n_by, n_bx]; corr_dev (optional,
+ *   may be NULL) float64 [n_by, n_bx, D, D]: the planes C.  acc_dev and mom_dev are not written.
+ * All three enqueue only, allocate nothing and keep no state.  TPIV_EINVAL, with nothing launched and nothing written: a null
+ * or not 8-byte aligned accumulator, a null frame pointer (batch > 0) or output pointer, a parameter outside the ranges
+ * above, n_pairs outside 1..65536, batch outside 0..256. */
+size_t tpiv_pixel_corr_bytes(int H, int W, int bin_y, int bin_x, int radius);
+int tpiv_pixel_corr_add(const uint8_t* a_dev, const uint8_t* b_dev, int batch, int H, int W, int bin_y, int bin_x, int radius,
+                        int shift_y, int shift_x, int64_t* acc_dev, int64_t* mom_dev, void* stream);
+int tpiv_pixel_corr_peaks(const int64_t* acc_dev, const int64_t* mom_dev, int n_pairs, int H, int W, int bin_y, int bin_x,
+                          int radius, int shift_y, int shift_x, double* u_dev, double* v_dev, double* peak_dev,
+                          double* ratio_dev, uint8_t* status_dev, double* corr_dev, void* stream);
+
 /* ---- spectrally filtered passes: phase-only and robust phase correlation ----------------------------------------------
  * (A. Eckstein, P. Vlachos, Digital particle image velocimetry (DPIV) robust phase correlation, Meas. Sci. Technol. 20
  * (2009) 055401.)  Every pass of a plan with this on takes its peak from a filtered map instead of the plain

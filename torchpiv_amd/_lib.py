@@ -124,6 +124,9 @@ SIGNATURES = {
     "tpiv_plan_ensemble_add": (C.c_int, [C.c_void_p, _u8p, _u8p, _int, _vp]),
     "tpiv_plan_ensemble_end": (C.c_int, [C.c_void_p, _f64p, _f64p, _u8p, _vp]),
     "tpiv_plan_ensemble_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
+    "tpiv_pixel_corr_bytes": (C.c_size_t, [_int] * 5),
+    "tpiv_pixel_corr_add": (C.c_int, [_u8p, _u8p] + [_int] * 8 + [_vp, _vp, _vp]),
+    "tpiv_pixel_corr_peaks": (C.c_int, [_vp, _vp] + [_int] * 8 + [_f64p] * 4 + [_u8p, _f64p, _vp]),
     "tpiv_plan_set_correlation": (C.c_int, [C.c_void_p, _int, _dbl, _dbl, _dbl, _vp, C.c_size_t]),
     "tpiv_debug_pass_spec": (C.c_int, [_int, _int, _dbl, _f32p, _u8p, _u8p, _int, _int, _int, _int, _int, _f64p, _f64p, _f64p,
                                        _f64p, _f64p, _u8p, _f32p, _f32p, _vp, C.c_size_t, _vp]),

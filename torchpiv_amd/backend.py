@@ -330,6 +330,8 @@ def free_cuda_memory():
 # ----------------------------------------------------------------------------------------
 Tracks = collections.namedtuple("Tracks", "x y u v residual peak_a peak_b count_a count_b matched")
 Tracks.__doc__ = "The particle tracks of one pair (OfflinePIV.tracks has the fields' definitions)."
+SinglePixel = collections.namedtuple("SinglePixel", "peak ratio status pairs corr", defaults=(None,))
+SinglePixel.__doc__ = "The quality record of OfflinePIV.single_pixel, which has the fields' definitions."
 
 # What a raw frame source (_raw_batches, _load_pair) hands out: [(pair id, staged)] of a batch's pairs in order and the ids of
 # the n staged ones; their uint8 frames A, B [n, H, W] on the device behind tone map and rectification (None: none staged)
@@ -1062,6 +1064,80 @@ class OfflinePIV:
         else:
             uv = self._post_validate_batch(u, v, inv, plan=plan, sigma=False)[0]
         return self._finish(uv, x, y, plan=plan)
+
+    def single_pixel(self, radius: int = 4, bin=1, shift=(0, 0), min_ratio=None, indices=None, batch_size: int = 32,
+                     planes: bool = False):
+        """Single-pixel ensemble correlation (Westerweel, Geelhoed & Lindken 2004; Kaehler, Scholz & Ortmanns 2006;
+        Scharnowski, Hain & Kaehler 2012) over the pairs `indices` (None: all): ONE field (x, y, u, v, q) whose cells are
+        bins of bin = k or (k_y, k_x) pixels, k_y * k_x <= 256 -- a single pixel, or e.g. one image row (1, W) of a
+        channel flow -- from the correlation summed over the recording instead of over a window, for steady flows
+        recorded with many pairs.  radius: the search radius R in 3..16 pixels around shift = (s_y, s_x), ONE integer
+        pre-shift (|s| <= 64) for every bin: a displacement is found within (-R, R) of it.  At most 65536 pairs.
+        The frames go through the preparation steps of batched() (pairs that cannot be staged are left out) and the
+        recording is read once.  x, y: the bin centres times scale (get_coordinates' geometry at window = bin, overlap
+        0, per axis); u, v: flip, sign and scale / dt * 1000 as in every delivered field; q: a SinglePixel record, flipped
+        like the field, of peak (the correlation coefficient at the peak), ratio (peak to second peak), status (uint8:
+        engine.PIXEL_CORR_STATUS) and pairs (the pairs summed), plus corr [n_by, n_bx, D, D], the coefficient planes, with
+        planes=True.  A bin whose status is not 0 carries NaN: 1 within reach of the frame edge, 2 constant pixels, 3
+        peak on the rim of the search area, 4 no sub-pixel fit, 5 ratio below min_ratio (None: no such test); with mask=
+        a bin whose masked share exceeds the mask's threshold has status 6 and the mask's fill value.  None when no pair
+        could be read.  ValueError with dynamic_mask=; MemoryError when the accumulator does not fit the free device
+        memory.  The window size, the passes, precision=, outlier=, deform=, correlation=, weighting= and uncertainty=
+        play no part here; there is no per-bin predictor."""
+        idx = list(range(len(self._dataset))) if indices is None else list(indices)
+        par = engine.single_pixel_arg(radius, bin, shift, min_ratio)
+        if self._dynmask is not None:
+            raise ValueError("single_pixel: dynamic_mask= is not supported (one sum over all pairs has no per-pair mask); "
+                             "use mask=, or run without it")
+        if len(idx) > engine.PIXEL_CORR_PAIRS:
+            raise ValueError(f"single_pixel: at most {engine.PIXEL_CORR_PAIRS} pairs, got {len(idx)}")
+        first = self._first_decodable(idx) if idx else None
+        if first is None:
+            return None
+        H, W = first[1]
+        engine.single_pixel_arg(radius, bin, shift, min_ratio, shape=(H, W))
+        (ky, kx), R = par["bin"], par["radius"]
+        dev = self._device
+        need = engine.pixel_corr_bytes(H, W, (ky, kx), R) + 4 * H * W * 8
+        free = torch.cuda.mem_get_info(dev)[0]
+        if need > free:
+            raise MemoryError(f"single_pixel: the accumulators of bin {(ky, kx)} at radius {R} take {need} bytes, the device "
+                              f"has {free} free: use a larger bin or a smaller radius")
+        if self._mask is not None:
+            self._mask_shape((H, W))
+        acc = mom = None
+        n = 0
+        with contextlib.closing(self._frame_batches(idx, int(batch_size), H, W, first[0])) as batches:
+            for raw, fa, fb, _ in batches:
+                if raw.chunk:                   # (unstaged pairs are left out)
+                    acc, mom = engine.pixel_corr_add(fa, fb, (ky, kx), R, par["shift"], acc=acc, mom=mom)
+                    n += len(raw.chunk)
+        if not n:
+            return None
+        out = engine.pixel_corr_peaks(acc, mom, n, (H, W), (ky, kx), R, par["shift"], planes=planes)
+        u, v, peak, ratio, status = (t.cpu().numpy() for t in out[:5])
+        if par["min_ratio"] is not None:
+            low = (status == 0) & (ratio < par["min_ratio"])
+            status[low] = engine.PIXEL_CORR_STATUS["ratio"]
+            for t in (u, v, peak, ratio):
+                t[low] = np.nan
+        if self._mask is not None:              # the coverage of every bin, counted once on the host
+            img = (self._mask["image"].cpu().numpy() != 0)[:H // ky * ky, :W // kx * kx]
+            share = img.reshape(H // ky, ky, W // kx, kx).sum(axis=(1, 3)) / float(ky * kx)
+            out_ = share > self._mask["threshold"]
+            status[out_] = engine.PIXEL_CORR_STATUS["masked"]
+            peak[out_] = ratio[out_] = np.nan
+            u[out_] = v[out_] = np.nan          # (the fill goes in below, behind sign and scale)
+        xs, ys = engine.pixel_corr_coordinates(H, W, (ky, kx))
+        x, y = np.meshgrid(xs, ys)
+        u = np.flip(u, axis=0) * self._scale / self._dt * 1000
+        v = -np.flip(v, axis=0) * self._scale / self._dt * 1000
+        peak, ratio, status = (np.flip(t, axis=0).copy() for t in (peak, ratio, status))
+        if self._mask is not None:
+            u[status == engine.PIXEL_CORR_STATUS["masked"]] = self._mask["fill"]
+            v[status == engine.PIXEL_CORR_STATUS["masked"]] = self._mask["fill"]
+        q = SinglePixel(peak, ratio, status, n, np.flip(out.corr.cpu().numpy(), axis=0).copy() if planes else None)
+        return x * self._scale, y * self._scale, u, v, q
 
     def tracks(self, level, radius=engine.TRACKS_RADIUS, indices=None, batch_size: int = 32) -> Generator:
         """Hybrid PIV / PTV ("super-resolution" PIV: Keane, Adrian & Zhang 1995; Cowen & Monismith 1997) over the pairs

@@ -2246,6 +2246,55 @@ int tpiv_frame_min(const uint8_t* frames, int n, long long pixels, uint8_t* acc,
     return TPIV_OK;
 }
 
+// single-pixel ensemble correlation: the geometry every entry refuses alike (bins, radius, shift)
+static bool pixel_corr_geometry(int H, int W, int bin_y, int bin_x, int radius, int shift_y, int shift_x) {
+    return H >= 1 && W >= 1 && bin_y >= 1 && bin_x >= 1 && (long long)bin_y * bin_x <= tpiv::kPixelCorrMaxBin && bin_y <= H &&
+           bin_x <= W && radius >= tpiv::kPixelCorrMinRadius && radius <= tpiv::kPixelCorrMaxRadius &&
+           std::abs(shift_y) <= tpiv::kPixelCorrMaxShift && std::abs(shift_x) <= tpiv::kPixelCorrMaxShift &&
+           (long long)H * W <= 0x7fffffffLL;
+}
+
+size_t tpiv_pixel_corr_bytes(int H, int W, int bin_y, int bin_x, int radius) {
+    if (!pixel_corr_geometry(H, W, bin_y, bin_x, radius, 0, 0)) return 0;
+    const size_t D = 2 * (size_t)radius + 1;
+    return (size_t)(H / bin_y) * (size_t)(W / bin_x) * D * D * sizeof(int64_t);
+}
+
+int tpiv_pixel_corr_add(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int bin_y, int bin_x, int radius,
+                        int shift_y, int shift_x, int64_t* acc, int64_t* mom, void* stream) {
+    if (!pixel_corr_geometry(H, W, bin_y, bin_x, radius, shift_y, shift_x))
+        return fail(TPIV_EINVAL, "tpiv_pixel_corr_add: bin_y, bin_x >= 1 with bin_y * bin_x <= 256 inside the frame, radius in "
+                                 "3..16, |shift| <= 64");
+    if (batch < 0 || batch > tpiv::kPixelCorrMaxBatch)
+        return fail(TPIV_EINVAL, "tpiv_pixel_corr_add: batch must be in 0..256 (the 32-bit partial sums of one call)");
+    if (!acc || !mom || ((uintptr_t)acc & 7u) || ((uintptr_t)mom & 7u))
+        return fail(TPIV_EINVAL, "tpiv_pixel_corr_add: acc and mom must be 8-byte aligned device pointers");
+    if (batch == 0) return TPIV_OK;
+    if (!a || !b) return fail(TPIV_EINVAL, "tpiv_pixel_corr_add: null pointer");
+    HIP_TRY(tpiv::launch_pixel_corr_add(a, b, batch, H, W, bin_y, bin_x, radius, shift_y, shift_x,
+                                        reinterpret_cast<long long*>(acc), reinterpret_cast<long long*>(mom), (hipStream_t)stream));
+    return TPIV_OK;
+}
+
+int tpiv_pixel_corr_peaks(const int64_t* acc, const int64_t* mom, int n_pairs, int H, int W, int bin_y, int bin_x, int radius,
+                          int shift_y, int shift_x, double* u, double* v, double* peak, double* ratio, uint8_t* status,
+                          double* corr, void* stream) {
+    if (!pixel_corr_geometry(H, W, bin_y, bin_x, radius, shift_y, shift_x))
+        return fail(TPIV_EINVAL, "tpiv_pixel_corr_peaks: bin_y, bin_x >= 1 with bin_y * bin_x <= 256 inside the frame, radius "
+                                 "in 3..16, |shift| <= 64");
+    if (n_pairs < 1 || n_pairs > tpiv::kPixelCorrMaxPairs)
+        return fail(TPIV_EINVAL, "tpiv_pixel_corr_peaks: n_pairs must be in 1..65536");
+    if (!acc || !mom || ((uintptr_t)acc & 7u) || ((uintptr_t)mom & 7u))
+        return fail(TPIV_EINVAL, "tpiv_pixel_corr_peaks: acc and mom must be 8-byte aligned device pointers");
+    if (!u || !v || !peak || !ratio || !status) return fail(TPIV_EINVAL, "tpiv_pixel_corr_peaks: null output pointer");
+    if (((uintptr_t)u | (uintptr_t)v | (uintptr_t)peak | (uintptr_t)ratio | (uintptr_t)corr) & 7u)
+        return fail(TPIV_EINVAL, "tpiv_pixel_corr_peaks: float64 outputs must be 8-byte aligned");
+    HIP_TRY(tpiv::launch_pixel_corr_peaks(reinterpret_cast<const long long*>(acc), reinterpret_cast<const long long*>(mom),
+                                          n_pairs, H, W, bin_y, bin_x, radius, shift_y, shift_x, u, v, peak, ratio, status, corr,
+                                          (hipStream_t)stream));
+    return TPIV_OK;
+}
+
 int tpiv_subtract_background(const uint8_t* frames, int n, long long pixels, const uint8_t* bg, uint8_t* out,
                              void* stream) {
     if (n < 0 || pixels <= 0) return fail(TPIV_EINVAL, "tpiv_subtract_background: bad shape");

@@ -484,6 +484,15 @@ bool win_size(int ws);
 // the pass with its finalize step; p.peak_raw: peak_raw_bytes(ws, batch, n_windows, 0)
 hipError_t launch_xcorr_win(const PassParams& p, int mode, const WinParams& s, int n_cu, hipStream_t stream);
 const char* xcorr_win_kernel_name(int ws, int mode, char* buf, int len);
+// single-pixel ensemble correlation (pixelcorr.hip, defined in include/torchpiv_hip.h: tpiv_pixel_corr_add / _peaks).  The
+// add kernel keeps a bin's sum of one call in 32 bits: 256 pixels x 256 pairs x 255^2 < 2^32, hence the batch bound.
+constexpr int kPixelCorrMinRadius = 3, kPixelCorrMaxRadius = 16, kPixelCorrMaxBin = 256, kPixelCorrMaxShift = 64;
+constexpr int kPixelCorrMaxBatch = 256, kPixelCorrMaxPairs = 65536;
+hipError_t launch_pixel_corr_add(const uint8_t* a, const uint8_t* b, int batch, int H, int W, int ky, int kx, int radius,
+                                 int sy, int sx, long long* acc, long long* mom, hipStream_t stream);
+hipError_t launch_pixel_corr_peaks(const long long* acc, const long long* mom, int n_pairs, int H, int W, int ky, int kx,
+                                   int radius, int sy, int sx, double* u, double* v, double* peak, double* ratio,
+                                   uint8_t* status, double* corr, hipStream_t stream);
 hipError_t launch_predict_mfma(const BandedPredictParams& q, hipStream_t stream);
 hipError_t launch_predict(const PredictParams& q, hipStream_t stream);
 

@@ -381,6 +381,118 @@ def ensemble_peaks(mode, acc, n_pairs, H, W, ws, ov, u0=None, v0=None, u2=None, 
     return (u, v, inv, du, dv) if raw else (u, v, inv)
 
 
+PIXEL_CORR_RADIUS = (3, 16)      # search radius R; the plane is D x D, D = 2 R + 1
+PIXEL_CORR_BIN = 256             # pixels of a bin at most
+PIXEL_CORR_SHIFT = 64            # |pre-shift| per axis at most
+PIXEL_CORR_BATCH = 256           # pairs per tpiv_pixel_corr_add call (32-bit partial sums)
+PIXEL_CORR_PAIRS = 65536         # pairs of a recording (the int64 numerators stay below 2^57)
+PIXEL_CORR_STATUS = {"valid": 0, "border": 1, "flat": 2, "range": 3, "fit": 4, "ratio": 5, "masked": 6}
+
+PixelCorr = collections.namedtuple("PixelCorr", "u v peak ratio status corr")
+
+
+def single_pixel_arg(radius=4, bin=1, shift=(0, 0), min_ratio=None, shape=None):
+    """The arguments of single-pixel ensemble correlation, checked (no GPU involved): radius, an integer in 3..16; bin, an
+    integer k (k x k pixels) or a pair (k_y, k_x) of integers >= 1 with k_y * k_x <= 256; shift, a pair of integers
+    (s_y, s_x) with |s| <= 64, the one pre-shift of every bin; min_ratio, None or a finite number >= 1; shape, None or the
+    frame shape (H, W), which a bin must fit.  Returns {"radius", "bin": (k_y, k_x), "shift": (s_y, s_x), "min_ratio"}."""
+    if not is_int(radius) or not PIXEL_CORR_RADIUS[0] <= radius <= PIXEL_CORR_RADIUS[1]:
+        raise ValueError(f"single_pixel: radius must be an integer in {PIXEL_CORR_RADIUS[0]}..{PIXEL_CORR_RADIUS[1]}, got {radius!r}")
+    ky_kx = (bin, bin) if is_int(bin) else bin
+    if (not isinstance(ky_kx, (tuple, list)) or len(ky_kx) != 2 or not all(is_int(k) for k in ky_kx)
+            or min(ky_kx) < 1 or ky_kx[0] * ky_kx[1] > PIXEL_CORR_BIN):
+        raise ValueError(f"single_pixel: bin must be an integer or a pair (k_y, k_x) of integers >= 1 with k_y * k_x <= "
+                         f"{PIXEL_CORR_BIN}, got {bin!r}")
+    if (not isinstance(shift, (tuple, list)) or len(shift) != 2 or not all(is_int(s) for s in shift)
+            or max(abs(int(s)) for s in shift) > PIXEL_CORR_SHIFT):
+        raise ValueError(f"single_pixel: shift must be a pair (s_y, s_x) of integers with |s| <= {PIXEL_CORR_SHIFT}, got {shift!r}")
+    if min_ratio is not None and (not is_real(min_ratio) or not np.isfinite(min_ratio) or min_ratio < 1):
+        raise ValueError(f"single_pixel: min_ratio must be None or a finite number >= 1, got {min_ratio!r}")
+    if shape is not None:
+        H, W = int(shape[0]), int(shape[1])
+        if ky_kx[0] > H or ky_kx[1] > W:
+            raise ValueError(f"single_pixel: a bin of {tuple(ky_kx)} pixels does not fit frames of {(H, W)}")
+    return {"radius": int(radius), "bin": (int(ky_kx[0]), int(ky_kx[1])), "shift": (int(shift[0]), int(shift[1])),
+            "min_ratio": None if min_ratio is None else float(min_ratio)}
+
+
+def pixel_corr_bytes(H, W, bin, radius):
+    """Bytes of the accumulator acc int64 [n_by, n_bx, D, D] of bins `bin` at search radius `radius` on H x W frames
+    (tpiv_pixel_corr_bytes; 0: a geometry the library refuses)."""
+    ky, kx = (bin, bin) if is_int(bin) else bin
+    return int(lib.tpiv_pixel_corr_bytes(int(H), int(W), int(ky), int(kx), int(radius)))
+
+
+def pixel_corr_coordinates(H, W, bin):
+    """(x [n_bx], y [n_by]): the bin centres in pixels -- the axis vectors of get_coordinates at window = bin, overlap 0,
+    each axis with its own bin edge."""
+    ky, kx = (bin, bin) if is_int(bin) else bin
+    return coordinates_1d(W, W, kx, 0)[0], coordinates_1d(H, H, ky, 0)[1]
+
+
+def _pixel_corr_acc(who, t, shape, dev):
+    _need_cuda(t)
+    if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or (dev is not None and t.device != dev):
+        raise ValueError(f"{who} must be a contiguous int64 {list(shape)} tensor on the device")
+
+
+def pixel_corr_add(a, b, bin, radius, shift=(0, 0), acc=None, mom=None):
+    """Adds the pairs a, b uint8 [batch, H, W] (or [H, W]) to the accumulators of single-pixel ensemble correlation and
+    returns (acc, mom) (tpiv_pixel_corr_add): acc int64 [n_by, n_bx, D, D], the products a(p) b(p + shift + d) summed over
+    the pixels of a bin and over the pairs; mom int64 [4, H, W], the per-pixel sums of a, a^2, b, b^2.  None: fresh zeroed
+    ones.  Exact integer sums without atomics: any split of a recording into calls gives the same bits.  At most 256 pairs
+    per library call: a larger batch goes in several."""
+    par = single_pixel_arg(radius, bin, shift)
+    a, b = _frames(a, b)
+    B, H, W = (int(s) for s in a.shape)
+    (ky, kx), R, (sy, sx) = par["bin"], par["radius"], par["shift"]
+    single_pixel_arg(radius, bin, shift, shape=(H, W))
+    D = 2 * R + 1
+    dev = a.device
+    if acc is None:
+        acc = torch.zeros(H // ky, W // kx, D, D, dtype=torch.int64, device=dev)
+    else:
+        _pixel_corr_acc("pixel_corr_add: acc", acc, (H // ky, W // kx, D, D), dev)
+    if mom is None:
+        mom = torch.zeros(4, H, W, dtype=torch.int64, device=dev)
+    else:
+        _pixel_corr_acc("pixel_corr_add: mom", mom, (4, H, W), dev)
+    with torch.cuda.device(dev):
+        for k in range(0, B, PIXEL_CORR_BATCH):
+            n = min(PIXEL_CORR_BATCH, B - k)
+            check(lib.tpiv_pixel_corr_add(a[k:k + n].data_ptr(), b[k:k + n].data_ptr(), n, H, W, ky, kx, R, sy, sx,
+                                          acc.data_ptr(), mom.data_ptr(), _stream()))
+    return acc, mom
+
+
+def pixel_corr_peaks(acc, mom, n_pairs, shape, bin, radius, shift=(0, 0), planes=False):
+    """The field of the accumulators of n_pairs pairs (tpiv_pixel_corr_peaks): a PixelCorr record of u, v (pixels, the
+    pre-shift included), peak (the correlation coefficient at the peak), ratio (peak to second peak) float64 and status
+    uint8 [n_by, n_bx] (PIXEL_CORR_STATUS), and corr float64 [n_by, n_bx, D, D], the planes of coefficients (planes=True;
+    else None).  A bin with a non-zero status carries NaN."""
+    H, W = int(shape[0]), int(shape[1])
+    par = single_pixel_arg(radius, bin, shift, shape=(H, W))
+    (ky, kx), R, (sy, sx) = par["bin"], par["radius"], par["shift"]
+    D = 2 * R + 1
+    nby, nbx = H // ky, W // kx
+    _pixel_corr_acc("pixel_corr_peaks: acc", acc, (nby, nbx, D, D), None)
+    _pixel_corr_acc("pixel_corr_peaks: mom", mom, (4, H, W), acc.device)
+    if not is_int(n_pairs) or not 1 <= n_pairs <= PIXEL_CORR_PAIRS:
+        raise ValueError(f"pixel_corr_peaks: n_pairs must be an integer in 1..{PIXEL_CORR_PAIRS}, got {n_pairs!r}")
+    dev = acc.device
+    u = torch.empty(nby, nbx, dtype=torch.float64, device=dev)
+    v = torch.empty_like(u)
+    peak = torch.empty_like(u)
+    ratio = torch.empty_like(u)
+    status = torch.empty(nby, nbx, dtype=torch.uint8, device=dev)
+    corr = torch.empty(nby, nbx, D, D, dtype=torch.float64, device=dev) if planes else None
+    with torch.cuda.device(dev):
+        check(lib.tpiv_pixel_corr_peaks(acc.data_ptr(), mom.data_ptr(), int(n_pairs), H, W, ky, kx, R, sy, sx, u.data_ptr(),
+                                        v.data_ptr(), peak.data_ptr(), ratio.data_ptr(), status.data_ptr(),
+                                        corr.data_ptr() if planes else None, _stream()))
+    return PixelCorr(u, v, peak, ratio, status, corr)
+
+
 def median_test(u, v, inv, threshold=2.0, eps=0.1, min_neighbours=3, want_medians=False):
     """Normalized median test (Westerweel & Scarano 2005; tpiv_median_test) on fields u, v float64 and the mask inv uint8,
     [batch, n_rows, n_cols] on the GPU.  Returns status uint8 (bit 0: flagged, bit 1: invalid on input), with
